@@ -6,9 +6,13 @@ A "step" is one pass of the hot path (kvz_hip_intra_frames: search + reconstruct
 1080p frames that is already resident in HBM.  N GPUs = N processes (torch.distributed.run), each with its own batch
 (frames are independent pictures with -p 1: weak scaling, no data-path collective).
 
-After the timed region the batch is CHECKED: frames of the batch that hold the picture of tests/golden/encoder_recon.json
+A plain run (`--gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps and prints the headline.  With --full
+it also CHECKS the batch after the timed region: frames of the batch that hold the picture of tests/golden/encoder_recon.json
 (the reference encoder's own reconstruction of the first frame of the clip) are downloaded and hashed, and the device
-checksums of all frames of the batch must agree between copies of the same picture -> "verified" (false => exit code 1).
+checksums of all frames of the batch must agree between copies of the same picture -> "verified" (false => exit code 1);
+and it runs the auxiliary legs (chain, entropy coder, 4K and other presets, the reference exchange) and the CPU baselines.
+
+--dump-outputs DIR writes what the timed path computed in its last step as DIR/<name>.npy (dump_outputs()).
 
 Prints ONE JSON line on rank 0; see DESIGN.md "Measurement" for every field.
 """
@@ -20,6 +24,7 @@ import os
 import subprocess
 import sys
 import time
+import zlib
 
 import numpy as np
 
@@ -78,6 +83,42 @@ def golden_digest(w, h, seed, qp, deblock, tiles=None, wpp=False, no_wpp=False, 
         return None
     v = g.get(key + suffix)
     return v[0] if v else None
+
+
+DUMP_BYTES = 60_000_000      # --dump-outputs: the .npy files of a run hold at most this much data (64 MB with room for their headers)
+DUMP_PICTURES = 4            # ... of at most this many pictures (sequences) of a batch: the first, the last and two drawn with a fixed seed
+
+
+def dump_indices(n, k=DUMP_PICTURES):
+    """a fixed choice of k of n items: the first and the last, the others drawn with seed 0 (sorted)"""
+    if n <= k:
+        return list(range(n))
+    rest = np.random.default_rng(0).choice(np.arange(1, n - 1), k - 2, replace=False)
+    return sorted({0, n - 1} | {int(i) for i in rest})
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: arrays (name -> numpy array) as <out_dir>/<name>.npy, flattened, in float64 where float32 would not hold every value (float64 data,
+    32-bit integers), float32 otherwise.  When all of them at full size exceed DUMP_BYTES, the larger ones are cut to the same number of elements each, a
+    sample of positions drawn with a seed taken from the array's name: the same positions in every run with the same arguments."""
+    os.makedirs(out_dir, exist_ok=True)
+    flat = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a).reshape(-1)
+        wide = (a.dtype.kind == "f" and a.dtype.itemsize > 4) or (a.dtype.kind in "iu" and a.dtype.itemsize > 2)
+        flat[name] = (a, np.float64 if wide else np.float32)
+
+    def total(cap):
+        return sum(min(a.size, cap) * np.dtype(t).itemsize for a, t in flat.values())
+    lo, hi = 1, max(a.size for a, _ in flat.values())
+    while lo < hi:  # the largest cap that fits
+        mid = (lo + hi + 1) // 2
+        lo, hi = (mid, hi) if total(mid) <= DUMP_BYTES else (lo, mid - 1)
+    for name, (a, t) in flat.items():
+        if a.size > lo:
+            pos = np.random.default_rng(zlib.crc32(name.encode())).choice(a.size, lo, replace=False)
+            a = a[np.sort(pos)]
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(t))
 
 
 def verify_batches(batches, distinct_n, golden_for):
@@ -461,10 +502,14 @@ def main():
                     "Otherwise which of kvazaar's all-intra searches the pass runs (the headline metric is ultrafast): "
                     "faster = CABAC coefficient cost at every QP; fast = + 32x32 CUs searched; medium-pu13 = + RDOQ (`--preset medium --pu-depth-intra 1-3`); "
                     "medium = + 8x8 CUs tried as four 4x4 PUs: BASELINE config 3's preset as it is")
+    ap.add_argument("--full", action="store_true", help="after the headline: the checks against the reference encoder's digests (verified), the auxiliary legs and the "
+                    "CPU baselines (--no-extra / --no-cpu-baseline / --no-ref-encoder leave parts out); a plain run only measures the headline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64; "
+                    "a fixed, seeded sample of the pictures and positions when the whole would exceed 64 MB)")
     ap.add_argument("--cpu-frames", type=int, default=8)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-ref-encoder", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the auxiliary legs (chain, chain_d2h, configs_extra); they only run at --gpus 1")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the auxiliary legs (chain, chain_d2h, configs_extra); they only run at --gpus 1")
     ap.add_argument("--only", default="", choices=["", "inter", "medium", "intra4k", "tiles4k", "entropy"], help="developer / profiling: run ONE auxiliary leg at a reduced size and print its "
                     "entry (tools/pmc_leg.sh collects the leg's counters this way); the headline is not measured")
     ap.add_argument("--entropy-pictures", type=int, default=384, help="developer: pictures of `--only entropy`")
@@ -477,6 +522,8 @@ def main():
     ap.add_argument("--tiles", default="", help="COLSxROWS: strong-scaling variant (BASELINE config 5): --frames pictures in total, cut into kvazaar's "
                                                 "uniform tiles, the tiles dealt to the ranks; every tile is an independent sub-picture (SURVEY.md 8e)")
     args = ap.parse_args()
+    if args.dump_outputs and args.only:
+        ap.error("--dump-outputs writes the outputs of the headline's timed steps, which --only does not run")
     args.frames_given = args.frames is not None
     if args.frames is None:
         args.frames = 1536 if not args.tiles else (384 if args.wpp else 3072)
@@ -563,7 +610,19 @@ def main():
     dt = sharding.timed_steps(step, args.steps, dist, torch.cuda.synchronize, "cuda")
     launches = state["launches"]
 
-    # ---- what was timed is checked (every rank; the verdicts are AND-ed) ----
+    if args.dump_outputs and rank == 0:  # what a caller of the pass receives (kvz_hip_batch_download / _checksums), before anything else runs on the batch
+        arrays = {}
+        for k, (b, _) in enumerate(batches):
+            pre = f"batch{k}_" if len(batches) > 1 else ""
+            arrays[pre + "checksums"] = b.checksums()
+            for i in dump_indices(b.n):
+                for name, a in b.download(i).items():
+                    arrays[f"{pre}frame{i}_{name}"] = a
+                if model.search_nxn:
+                    arrays[f"{pre}frame{i}_nxn"], arrays[f"{pre}frame{i}_mode4x4"] = b.download_partitions(i)
+        dump_outputs(args.dump_outputs, arrays)
+
+    # ---- with --full, what was timed is checked (every rank; the verdicts are AND-ed) ----
     seed0 = clip_seed(args.width, args.height)
     golden_applies = rank == 0 or bool(args.tiles)  # frame-sharded ranks > 0 hold other clips (seed + rank): consistency check only
     def golden_for(tile, picture=0):
@@ -576,17 +635,19 @@ def main():
             return per_tile[tile] if per_tile else None
         return golden_digest(args.width, args.height, seed0, args.qp, 0, None, False, bool(model.no_wpp), PRESETS[args.preset][3], picture)
 
-    verify = verify_batches(batches, len(distinct), golden_for)
-    ok_local = verify["copies_consistent"] and verify["golden_ok"] is not False
-    if dist is not None:
-        t = torch.tensor([1 if ok_local else 0, verify["golden_frames_hashed"]], dtype=torch.int64, device="cuda")
-        dist.all_reduce(t, op=dist.ReduceOp.MIN)
-        ok_all = bool(t[0].item())
-    else:
-        ok_all = ok_local
+    verify, ok_all = None, True
+    if args.full:
+        verify = verify_batches(batches, len(distinct), golden_for)
+        ok_local = verify["copies_consistent"] and verify["golden_ok"] is not False
+        if dist is not None:
+            t = torch.tensor([1 if ok_local else 0, verify["golden_frames_hashed"]], dtype=torch.int64, device="cuda")
+            dist.all_reduce(t, op=dist.ReduceOp.MIN)
+            ok_all = bool(t[0].item())
+        else:
+            ok_all = ok_local
 
     exchange = None
-    if not args.no_extra:
+    if args.full and not args.no_extra:
         try:
             exchange = exchange_leg(dist, torch, rank, world, lib)
         except Exception as e:  # auxiliary: never take the headline down
@@ -607,8 +668,6 @@ def main():
             "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "strong" if args.tiles else "weak", "vs_baseline": None,
             "dtype": "u8/i16 (f64 RD costs)", "data": "synthetic",
             "fps": value / ctus_per_frame,
-            # golden_ok None = the fixture has no encoder digest for this workload (only the copy-consistency check ran)
-            "verified": bool(ok_all and (verify["golden_ok"] is True or verify["golden_ok"] is None)), "verify": verify,
             "config": {"workload": f"{args.width}x{args.height} yuv420p 8-bit all-intra {args.preset} CTU pass (kvz_hip_intra_frames), QP {args.qp}",
                        "frames_per_gpu_per_step": None if args.tiles else args.frames, "frames_per_step": args.frames if args.tiles else args.frames * world,
                        "ctus_per_frame": ctus_per_frame, "distinct_frames": len(distinct),
@@ -624,14 +683,18 @@ def main():
                          "avg_launch_us": per_launch_s * 1e6, "algorithmic_bytes_per_launch": bytes_per_launch,
                          "note": "the CTU search is a latency x concurrency machine limited by VALU issue (limiter), not a streaming kernel (DESIGN.md 5); per-kernel HBM and MFMA fractions of the streaming primitives: bench_kernels.py"},
         }
+        if verify is not None:
+            # golden_ok None = the fixture has no encoder digest for this workload (only the copy-consistency check ran)
+            result["verified"] = bool(ok_all and (verify["golden_ok"] is True or verify["golden_ok"] is None))
+            result["verify"] = verify
         if exchange is not None:
             result["exchange"] = exchange
-        if world == 1 and not args.no_extra and args.preset == "ultrafast":  # the auxiliary legs verify against the ultrafast digests
+        if args.full and world == 1 and not args.no_extra and args.preset == "ultrafast":  # the auxiliary legs verify against the ultrafast digests
             extra_legs(args, lib, result, batches, model, model_for, HipBatch, PinnedResults)
-        elif not args.no_extra:
-            result["legs_skipped"] = ("the auxiliary legs (chain, chain_full, entropy, configs_extra) are single-GPU measurements of the ultrafast preset: run `python bench.py` "
+        elif args.full and not args.no_extra:
+            result["legs_skipped"] = ("the auxiliary legs (chain, chain_full, entropy, configs_extra) are single-GPU measurements of the ultrafast preset: run `python bench.py --full` "
                                       f"(--gpus 1) for them; this run: {world} rank(s), preset {args.preset}")
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(args, distinct, model)
             if result.get("chain_full", {}).get("value") and result["cpu_baseline"].get("value"):  # like for like: both sides search, filter and code
                 result["chain_full"]["vs_cpu_baseline"] = result["chain_full"]["value"] / result["cpu_baseline"]["value"]
@@ -675,10 +738,12 @@ def tiled_inter_bench(args, lib, dist, torch, rank, world, HipBatch, cost_model)
         rec0[ys:ys + cs].reshape(h // 2, w // 2)[y // 2:(y + th) // 2, x // 2:(x + tw) // 2] = t[tw * th:tw * th + c].reshape(th // 2, tw // 2)
         rec0[ys + cs:].reshape(h // 2, w // 2)[y // 2:(y + th) // 2, x // 2:(x + tw) // 2] = t[tw * th + c:].reshape(th // 2, tw // 2)
     cu0 = inter.intra_picture_cu_info(w, h)
-    try:
-        gold = json.load(open(os.path.join(ROOT, "tests", "golden", "inter_tiles.json"))).get(f"baseline-c4-2160p-tiles{cols}x{rows}") if args.qp == 22 else None
-    except (OSError, ValueError):
-        gold = None
+    gold = None
+    if args.full and args.qp == 22:
+        try:
+            gold = json.load(open(os.path.join(ROOT, "tests", "golden", "inter_tiles.json"))).get(f"baseline-c4-2160p-tiles{cols}x{rows}")
+        except (OSError, ValueError):
+            gold = None
     i_ok = None if gold is None else hashlib.sha256(rec0.tobytes()).hexdigest()[:24] == gold["rec"][0]
 
     def start():
@@ -688,17 +753,18 @@ def tiled_inter_bench(args, lib, dist, torch, rank, world, HipBatch, cost_model)
         seq.upload_sources(lambda i: pictures[k % len(pictures)])
         seq.run_picture(inter.veryfast_params(qps[min(k, 3)], k, mv_constraint=False))
 
-    # verification chain: B pictures 1..3 from the I picture, sequence 0 and the last one against the reference encoder / each other
-    start()
+    # verification chain (--full): B pictures 1..3 from the I picture, sequence 0 and the last one against the reference encoder / each other
     checks = []
-    for k in range(1, 4):
-        picture(k)
-        f0, c0 = seq.download_reference(0)
-        f1, c1 = seq.download_reference(n - 1)
-        ok = bool(np.array_equal(f0, f1) and np.array_equal(c0, c1))
-        if gold is not None:
-            ok = ok and hashlib.sha256(f0.tobytes()).hexdigest()[:24] == gold["rec"][k] and inter.cu_digest(c0) == gold["cu"][k]
-        checks.append(ok)
+    if args.full:
+        start()
+        for k in range(1, 4):
+            picture(k)
+            f0, c0 = seq.download_reference(0)
+            f1, c1 = seq.download_reference(n - 1)
+            ok = bool(np.array_equal(f0, f1) and np.array_equal(c0, c1))
+            if gold is not None:
+                ok = ok and hashlib.sha256(f0.tobytes()).hexdigest()[:24] == gold["rec"][k] and inter.cu_digest(c0) == gold["cu"][k]
+            checks.append(ok)
     # timing: every step is the FIRST B picture again, from the I picture's reconstruction -- the reference frames and CU records are put back from a device copy inside
     # the step (a few ms of device-to-device copies, counted), because run_picture leaves the coded picture as the reference and the same source coded against its own
     # reconstruction is a picture of skipped CUs (which the first version of this line timed for all steps but the first)
@@ -716,6 +782,14 @@ def tiled_inter_bench(args, lib, dist, torch, rank, world, HipBatch, cost_model)
         seq.run_picture(prm)
         pass_ms.append(seq.pass_ms)
     dt = sharding.timed_steps(step, args.steps, dist, torch.cuda.synchronize, "cuda")
+    if args.dump_outputs and rank == 0:  # the assembled B picture and its CU records, as every rank holds them after the step's exchange
+        arrays = {}
+        for i in dump_indices(n):
+            frame, cu = seq.download_reference(i)
+            arrays[f"seq{i}_rec"] = frame
+            for name in cu.dtype.names:
+                arrays[f"seq{i}_cu_{name}"] = cu[name]
+        dump_outputs(args.dump_outputs, arrays)
     job_ctus = n * sum(((t[2] + 63) // 64) * ((t[3] + 63) // 64) for t in tiles)
     ok_all = all(checks) and i_ok is not False
     verified = ok_all if gold is not None else None  # without the reference encoder's digests (QP != 22, file missing) the checks only say "the sequences agree": not a verdict
@@ -726,19 +800,21 @@ def tiled_inter_bench(args, lib, dist, torch, rank, world, HipBatch, cost_model)
     if rank == 0:
         value = job_ctus * args.steps / dt
         k_s = float(np.mean(pass_ms)) / 1e3
-        print(json.dumps({
+        out = {
             "metric": "CTUs/s (inter CTU pass + loop filters + reference exchange, BASELINE config 4 sharded by tile)", "value": value, "unit": "CTUs/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
             "dtype": "u8/i16 (f64 RD costs)", "data": "synthetic", "fps": value / (((w + 63) // 64) * ((h + 63) // 64)),
-            "verified": (bool(ok_all) if verified is not None else None),
-            "verify": {"i_picture_equals_reference_encoder": i_ok, "b_pictures_equal_reference_encoder_and_between_sequences": checks,
-                       "golden": "tests/golden/inter_tiles.json" if gold is not None else None,
-                       "reason": None if gold is not None else "no reference-encoder digests for this QP / tile grid: only the agreement between sequences was checked"},
             "config": {"workload": f"{w}x{h} --preset veryfast --gop lp-g4d3t1 -q {args.qp} --tiles {cols}x{rows}: one B picture (QP {qps[1]}) of {n} sequences per step", "sequences": n,
                        "tiles": len(tiles), "tiles_per_rank": seq.per_rank, "parallelism": f"--tiles {cols}x{rows} dealt to {world} GPU(s); one all-gather of pictures + one of CU records per picture"},
             "exchange": {"recv_bytes_per_rank_per_step": (world - 1) * seq.per_rank * n * (seq.slot_px + seq.slot_cu), "frame_bytes": seq.fs, "sequences": n},
             "roofline": leg_roofline("inter", "inter_ctu_ticket_kernel_fast", INTER_BYTES_PER_CTU, n * seq.ctus, k_s),
-        }))
+        }
+        if args.full:
+            out["verified"] = bool(ok_all) if verified is not None else None
+            out["verify"] = {"i_picture_equals_reference_encoder": i_ok, "b_pictures_equal_reference_encoder_and_between_sequences": checks,
+                             "golden": "tests/golden/inter_tiles.json" if gold is not None else None,
+                             "reason": None if gold is not None else "no reference-encoder digests for this QP / tile grid: only the agreement between sequences was checked"}
+        print(json.dumps(out))
     if not ok_all:
         sys.exit(1)
 

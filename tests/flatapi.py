@@ -24,6 +24,20 @@ def hip_path():
     return os.path.join(ROOT, "kvazaar_amd", "lib", "libkvz_hip.so")
 
 
+def hostsim_path():
+    """tests/hostsim/libkvz_hostsim.so, built (the recipe of tests/test_hostsim.py) when it is missing or older than its sources: the GPU tests that
+    use it may run without the CPU tests that build it.  Written under a temporary name and renamed, so that concurrent test processes never load half a file."""
+    import subprocess
+    d, csrc = os.path.join(ROOT, "tests", "hostsim"), os.path.join(ROOT, "kvazaar_amd", "csrc")
+    so = os.path.join(d, "libkvz_hostsim.so")
+    srcs = [os.path.join(d, "hostsim.cpp")] + [os.path.join(csrc, f) for f in os.listdir(csrc)]
+    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
+        tmp = os.path.join(d, f".libkvz_hostsim.{os.getpid()}.so")
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", tmp, os.path.join(d, "hostsim.cpp")])
+        os.replace(tmp, so)
+    return so
+
+
 def load_oracle():
     lib = FlatLib(oracle_path(), "kvz_oracle_")
     lib.lib.kvz_oracle_dct_matrix.restype = i16p

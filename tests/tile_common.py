@@ -2,7 +2,6 @@
 CTU pass -> loop filters -> exchange -> next picture.  The pass of a B picture's tile is pluggable (host simulation of the device sources / the device); the I picture's pass and
 the loop filters are test infrastructure (host simulation, oracle).  Shared by tests/test_dist_cpu.py (two gloo ranks) and tests/test_gpu_inter_ctu.py."""
 import ctypes as C
-import os
 
 import numpy as np
 
@@ -21,7 +20,7 @@ def tile_sub(frame, x, y, tw, th, W, H):
 
 
 def load_hostsim():
-    sim = C.CDLL(os.path.join(flatapi.ROOT, "tests", "hostsim", "libkvz_hostsim.so"))
+    sim = C.CDLL(flatapi.hostsim_path())
     ft = sim.kvz_hostsim_inter_tile
     ft.restype = None
     ft.argtypes = [C.c_int] * 4 + [C.c_uint64, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p] * 5 + [C.c_int] * 5
