@@ -100,7 +100,7 @@ template <int MAXN> __global__ void __launch_bounds__(256) dev_fme_kernel(const 
 // ---------------------------------------------------------------------------------------------------------------
 // Motion-compensated prediction of PU lists (inter.c:371-575 inter_recon_unipred / kvz_inter_recon_bipred): per PU and reference list
 // the 8-tap (luma, quarter-pel) / 4-tap (chroma, eighth-pel) separable filters of ipol-generic.c:134-211, 681-758 on the clamped
-// reference window, 14-bit intermediates; one list: clip((v + 32) >> 6), two lists: clip((v0 + v1 + 64) >> 7)
+// reference window, 14-bit intermediates; one list: clip((v + 32) >> 6) on the whole v, two lists: clip((int16(v0) + int16(v1) + 64) >> 7)
 // (picture-generic.c:553-668).  The reference branches -- integer vectors are copied (inter.c:411-428, inter_cp_with_ext_border at
 // the picture edge), fractional ones filtered, and kvz_bipred_average mixes pixel and 14-bit operands -- but a filter with the identity
 // taps {0,0,0,64,0,0,0,0} gives 64 s exactly, so every branch is the same expression and one code path serves them all
@@ -148,10 +148,10 @@ template <int MAXN> __global__ void __launch_bounds__(256) dev_inter_pred_kernel
         const int y = i / w, x = i - y * w;
         int t = 0;
         for (int k = 0; k < taps; k++) t += vf[k] * (int)s_g[(y + k) * MAXN + x];
-        const int v = (int)(i16)(t >> 6);  // the 14-bit sample (kvz_pixel_im)
+        const int v = t >> 6;  // the 14-bit sample: whole for one list (the luma (2, 2) phase reaches 33150), int16 as an operand of two (kvz_pixel_im)
         if (lists == 1) pred[poff + (long)((pu.y >> sh) + y) * fw + (pu.x >> sh) + x] = clip_pixel((v + 32) >> 6);
         else if (first) s_acc[i] = (i16)v;
-        else pred[poff + (long)((pu.y >> sh) + y) * fw + (pu.x >> sh) + x] = clip_pixel(((int)s_acc[i] + v + 64) >> 7);
+        else pred[poff + (long)((pu.y >> sh) + y) * fw + (pu.x >> sh) + x] = clip_pixel(((int)s_acc[i] + (int)(i16)v + 64) >> 7);
       }
       first = false;
     }
@@ -263,18 +263,18 @@ __global__ void __launch_bounds__(256) dev_inter_pred_wave_kernel(const u8 *ref0
               const unsigned pr = (j & 1) ? __builtin_amdgcn_alignbyte(q[base + 1 < 6 ? base + 1 : 5], q[base], 2) : q[base];
               a = dot2_i16(pr, vp[k], a);
             }
-            v[j] = (int)(i16)(a >> 6);
+            v[j] = a >> 6;  // whole for one list; int16 as an operand of two
           }
           if (lists == 1 || !first) {
             u8 o4[4];
 #pragma unroll
-            for (int j = 0; j < 4; j++) o4[j] = lists == 1 ? clip_pixel((v[j] + 32) >> 6) : clip_pixel((acc0[j] + v[j] + 64) >> 7);
+            for (int j = 0; j < 4; j++) o4[j] = lists == 1 ? clip_pixel((v[j] + 32) >> 6) : clip_pixel((acc0[j] + (int)(i16)v[j] + 64) >> 7);
             // the block leaves through LDS (the window is dead by now) so that a lane stores four bytes of a ROW
 #pragma unroll
             for (int j = 0; j < 4; j++) win[(y0 + j) * w + x] = o4[j];
           } else {
 #pragma unroll
-            for (int j = 0; j < 4; j++) acc0[j] = v[j];
+            for (int j = 0; j < 4; j++) acc0[j] = (int)(i16)v[j];
           }
         }
       }

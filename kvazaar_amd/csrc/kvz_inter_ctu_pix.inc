@@ -625,13 +625,15 @@ IC_FN void hor_pass_ref(int c, int X0, int Y0, int fi, int taps, int rows, int c
   IC_SYNC();
 }
 // One list, one plane, one tile: the tw x tw block at reference position (X0, Y0) [the integer part of the motion applied], fractional filters (hf, vf) (identity taps
-// make every branch of inter_recon_unipred the same expression, kvz_fme.hpp).  What happens to the 14-bit sample v of (y, x): mode 0 -- into L->im[0]; mode 1 -- the
-// finished sample of a prediction from one list, clip((v + 32) >> 6), into dst; mode 2 -- that of two lists, clip((L->im[0] + v + 64) >> 7) (inter.c:374-660).
+// make every branch of inter_recon_unipred the same expression, kvz_fme.hpp).  What happens to the 14-bit sample v of (y, x): mode 0 -- into L->im[0] as int16; mode 1 --
+// the finished sample of a prediction from one list, clip((v + 32) >> 6), v whole (kvz_sample_quarterpel_luma clips the int32: the luma (2, 2) phase reaches 33150);
+// mode 2 -- that of two lists, clip((L->im[0] + int16(v) + 64) >> 7) (inter.c:374-660); mode 3 -- two lists with one vector predicted as one: the operands are
+// int16(v) as in mode 2, clip((2 int16(v) + 64) >> 7) = clip((int16(v) + 32) >> 6).
 IC_FN void predict_tile(int c, int X0, int Y0, int tw, int hf, int vf, int mode, lu8 *dst, int ds)
 {
   IC_COUNT(23);
   if (hf == 0 && vf == 0) IC_COUNT(24); else if (hf == 0 || vf == 0) IC_COUNT(25);
-  if (mode != 1) IC_COUNT(26);
+  if (mode == 0 || mode == 2) IC_COUNT(26);
   const int taps = c ? 4 : 8, before = c ? 1 : 3, wr = tw + taps - 1, l2 = ilog2i(tw);
   if (hf == 0 && vf == 0) {
     // a whole-sample vector: both passes with the identity taps come to sample << 6 -- the block itself is all the window there is to read
@@ -642,7 +644,7 @@ IC_FN void predict_tile(int c, int X0, int Y0, int tw, int hf, int vf, int mode,
       for (int i = tid; i < tw * tw; i += KVZ_ICTU_THREADS) {
         const int yy = i >> l2, xx = i & (tw - 1), px = (int)L->win[yy * IC_WS + xo + xx];
         if (mode == 0) im0[i] = (i16)(px << 6);
-        else if (mode == 1) dst[yy * ds + xx] = (u8)px;
+        else if (mode != 2) dst[yy * ds + xx] = (u8)px;
         else dst[yy * ds + xx] = clip_pixel(((int)im0[i] + (px << 6) + 64) >> 7);
       }
     }
@@ -655,9 +657,10 @@ IC_FN void predict_tile(int c, int X0, int Y0, int tw, int hf, int vf, int mode,
   if (mode == 0) {
     if (c) ver_pass<4>(vf, 0, 0, tw, [=](int yy, int xx, int v) { im[(yy << l2) + xx] = (i16)v; });
     else ver_pass<8>(vf, 0, 0, tw, [=](int yy, int xx, int v) { im[(yy << l2) + xx] = (i16)v; });
-  } else if (mode == 1) {
-    if (c) ver_pass<4>(vf, 0, 0, tw, [=](int yy, int xx, int v) { dst[yy * ds + xx] = clip_pixel(((int)(i16)v + 32) >> 6); });
-    else ver_pass<8>(vf, 0, 0, tw, [=](int yy, int xx, int v) { dst[yy * ds + xx] = clip_pixel(((int)(i16)v + 32) >> 6); });
+  } else if (mode != 2) {
+    const bool wrap = mode == 3;
+    if (c) ver_pass<4>(vf, 0, 0, tw, [=](int yy, int xx, int v) { dst[yy * ds + xx] = clip_pixel(((wrap ? (int)(i16)v : v) + 32) >> 6); });
+    else ver_pass<8>(vf, 0, 0, tw, [=](int yy, int xx, int v) { dst[yy * ds + xx] = clip_pixel(((wrap ? (int)(i16)v : v) + 32) >> 6); });
   } else {
     if (c) ver_pass<4>(vf, 0, 0, tw, [=](int yy, int xx, int v) { dst[yy * ds + xx] = clip_pixel(((int)im[(yy << l2) + xx] + (int)(i16)v + 64) >> 7); });
     else ver_pass<8>(vf, 0, 0, tw, [=](int yy, int xx, int v) { dst[yy * ds + xx] = clip_pixel(((int)im[(yy << l2) + xx] + (int)(i16)v + 64) >> 7); });
@@ -671,14 +674,15 @@ IC_DEV void predict_into(int c, int x, int y, int w, const CuInfo &pu, lu8 *dst,
   for (int ty = 0; ty < nt; ty++)
     for (int tx = 0; tx < nt; tx++) {
       lu8 *d = dst + ty * tw * ds + tx * tw;
-      // (both lists hold the one reference picture: two lists with one vector average a block with itself -- (2 v + 64) >> 7 = (v + 32) >> 6, the prediction of one list)
+      // (both lists hold the one reference picture: two lists with one vector average a block with itself -- (2 v + 64) >> 7 = (v + 32) >> 6 -- predicted as one list
+      // whose 14-bit samples are still the wrapped int16 operands of two: mode 3)
       const bool twice = pu.mv_dir == 3 && pu.mv[0][0] == pu.mv[1][0] && pu.mv[0][1] == pu.mv[1][1];
       const int first = pu.mv_dir == 2 ? 1 : 0, lists = pu.mv_dir == 3 && !twice ? 2 : 1;
       if (twice) IC_COUNT(27);
       for (int k = 0; k < lists; k++) {
         const bool second = first + k != 0;
         const int mvx = second ? pu.mv[1][0] : pu.mv[0][0], mvy = second ? pu.mv[1][1] : pu.mv[0][1];
-        predict_tile(c, (x >> sh) + (mvx >> (2 + sh)) + tx * tw, (y >> sh) + (mvy >> (2 + sh)) + ty * tw, tw, c ? mvx & 7 : mvx & 3, c ? mvy & 7 : mvy & 3, lists == 1 ? 1 : (k == 0 ? 0 : 2), d, ds);
+        predict_tile(c, (x >> sh) + (mvx >> (2 + sh)) + tx * tw, (y >> sh) + (mvy >> (2 + sh)) + ty * tw, tw, c ? mvx & 7 : mvx & 3, c ? mvy & 7 : mvy & 3, twice ? 3 : (lists == 1 ? 1 : (k == 0 ? 0 : 2)), d, ds);
       }
     }
 }

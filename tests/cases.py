@@ -12,6 +12,7 @@ import ctypes as C
 
 import numpy as np
 
+import mc_reference
 import scaling_lists
 from flatapi import (A, EpolParams, IPOL_COL_LEN, IPOL_IM_PLANE, QuantParams, SaoParams, i16p, ptr, u8p)
 
@@ -436,7 +437,7 @@ def cases_ipol_sample():
     frame = A(rng.integers(0, 256, S * S, dtype=np.uint8))
     frame2 = A(np.where(rng.integers(0, 2, S * S) > 0, 255, 0).astype(np.uint8))  # worst-case ringing
     for (w, h) in [(8, 8), (16, 16), (32, 32), (64, 64), (16, 8), (8, 16), (4, 4), (24, 16), (12, 4)]:
-        for (fx, fy) in [(0, 0), (1, 0), (0, 2), (3, 3), (2, 1), (1, 3)]:
+        for (fx, fy) in [(0, 0), (1, 0), (0, 2), (3, 3), (2, 1), (1, 3), (2, 2)]:
             for fi, fr in enumerate((frame, frame2)):
                 if w > 64 or h > 64:
                     continue
@@ -462,6 +463,49 @@ def cases_ipol_sample():
                     lib.sample_octpel_chroma_hi(ptr(frame2, offset=org), S, w, h, ptr(d16), 32, 1, 1, ptr(mv))
                     return (d8.tobytes(), d16.tobytes())
                 yield (f"opel_chroma{w}x{h}-{fx}{fy}", runc)
+    # the extremes of every phase: the sign-matched 0 / 255 window that drives the phase's sample to its largest (smallest) value (tests/mc_reference.py), tiled
+    # from the block's first window.  The luma (2, 2) maximum, 33150, leaves int16: its one-list sample is 255; its two-list operand is in cases_ipol_sample_wrap
+    # (the minimising window of (2, 2) is the maximising one shifted by four rows: that plane holds maxima too)
+    for chroma, n, taps, sizes in ((False, 4, 8, [(8, 8), (16, 16), (64, 64), (32, 16), (8, 16)]), (True, 8, 4, [(4, 4), (8, 8), (32, 32), (16, 8)])):
+        for fx in range(n):
+            for fy in range(n):
+                for maximise in (True, False):
+                    fr = _extreme_plane(fx, fy, chroma, maximise, S)
+                    for (w, h) in sizes:
+                        def rune(lib, w=w, h=h, fx=fx, fy=fy, fr=fr, hi=chroma or (fx, fy) != (2, 2), chroma=chroma):
+                            mv = A(np.array([fx, fy], np.int16))
+                            d8 = A(np.zeros(64 * 64, np.uint8))
+                            d16 = A(np.zeros(64 * 64, np.int16))
+                            f8, f16 = (lib.sample_octpel_chroma, lib.sample_octpel_chroma_hi) if chroma else (lib.sample_quarterpel_luma, lib.sample_quarterpel_luma_hi)
+                            f8(ptr(fr, offset=EXT_ORG * S + EXT_ORG), S, w, h, ptr(d8), 64, 1, 1, ptr(mv))
+                            if hi:
+                                f16(ptr(fr, offset=EXT_ORG * S + EXT_ORG), S, w, h, ptr(d16), 64, 1, 1, ptr(mv))
+                            return (d8.tobytes(), d16.tobytes())
+                        yield (f"{'opel_chroma' if chroma else 'qpel_luma'}{w}x{h}-{fx}{fy}-{'max' if maximise else 'min'}", rune)
+
+
+EXT_ORG = 16  # where the blocks of the extreme-window cases start in their plane
+
+
+def _extreme_plane(fx, fy, chroma, maximise, S):
+    """an S x S plane of phase (fx, fy)'s extreme window, tiled so that the window of the sample at (EXT_ORG, EXT_ORG) is one"""
+    before = 1 if chroma else 3
+    return A(mc_reference.tiled(mc_reference.extreme_window(fx, fy, chroma, maximise), S, S, EXT_ORG - before, EXT_ORG - before).reshape(-1))
+
+
+def cases_ipol_sample_wrap():
+    """The two-list operand (kvz_sample_quarterpel_luma_hi) where the 14-bit sample leaves int16: the luma (2, 2) phase on its maximising window.  Generic
+    wraps 33150 to -32386, the reference's AVX2 strategy saturates it (tests/test_mc_reference.py): compared with the generic strategy only"""
+    S = 96
+    for maximise in (True, False):
+        fr = _extreme_plane(2, 2, False, maximise, S)
+        for (w, h) in [(8, 8), (16, 16), (32, 32), (64, 64), (16, 8), (8, 16), (64, 32)]:
+            def run(lib, w=w, h=h, fr=fr):
+                mv = A(np.array([2, 2], np.int16))
+                d16 = A(np.zeros(64 * 64, np.int16))
+                lib.sample_quarterpel_luma_hi(ptr(fr, offset=EXT_ORG * S + EXT_ORG), S, w, h, ptr(d16), 64, 1, 1, ptr(mv))
+                return (d16.tobytes(),)
+            yield (f"qpel_luma_hi{w}x{h}-22-{'max' if maximise else 'min'}", run)
 
 
 def cases_ipol_blocks():
@@ -470,8 +514,21 @@ def cases_ipol_blocks():
     rng = _rng(113)
     S = 96
     frames = A([rng.integers(0, 256, S * S, dtype=np.uint8), np.where(rng.integers(0, 2, S * S) > 0, 255, 0).astype(np.uint8)])
+    yield from _fme_sequence_cases(frames, S, 0)
+
+
+def cases_ipol_blocks_wrap():
+    """The same sequence on the luma (2, 2) extreme windows, tiled: the diagonal half-pel planes' 14-bit samples leave int16 and generic's fin() wraps them,
+    where the reference's AVX2 filters saturate -- compared with the generic strategy only"""
+    S = 96
+    frames = A([mc_reference.tiled(mc_reference.extreme_window(2, 2, False, maximise), S, S, 13 - 3 + dy, 13 - 3 + dx).reshape(-1)
+                for maximise in (True, False) for (dy, dx) in ((0, 0), (-1, 1))])
+    yield from _fme_sequence_cases(frames, S, 2)
+
+
+def _fme_sequence_cases(frames, S, first_index):
     for (w, h) in [(8, 8), (16, 16), (32, 32), (64, 64), (16, 8), (8, 16), (32, 64)]:
-        for fi, fr in enumerate(frames):
+        for fi, fr in enumerate(frames, first_index):
             for (ox, oy) in [(0, 0), (-1, 0), (1, 0), (0, -1), (0, 1), (-1, -1), (1, 1), (-1, 1), (1, -1)]:
                 org = 12 * S + 12
 
@@ -617,7 +674,11 @@ def cases_plane_checksum():
 
 ALL_GENERATORS = [cases_plane_checksum, cases_sad_satd_nxn, cases_dual, cases_reg_sad, cases_any_size, cases_ssd_versad_horsad_var,
                   cases_image_calc_sad, cases_bipred, cases_transform, cases_quant, cases_quantize_residual, cases_quant_lists, cases_quantize_residual_lists,
-                  cases_coeff_misc, cases_intra, cases_ipol_sample, cases_ipol_blocks, cases_extended_block, cases_sao]
+                  cases_coeff_misc, cases_intra, cases_ipol_sample, cases_ipol_blocks, cases_extended_block, cases_sao, cases_ipol_sample_wrap,
+                  cases_ipol_blocks_wrap]
+
+# generators on which the reference's AVX2 strategies differ from generic by design: the oracle follows generic (tests/test_oracle_vs_ref.py)
+GENERIC_ONLY = [cases_ipol_sample_wrap, cases_ipol_blocks_wrap]
 
 
 def all_cases():

@@ -271,22 +271,25 @@ def cu_digest(depth, mode):
     return hashlib.sha256(np.ascontiguousarray(depth, np.uint8).tobytes() + np.ascontiguousarray(mode, np.uint8).tobytes()).hexdigest()[:24]
 
 
-def update_inter():
+def update_inter(names=()):
     """tests/golden/inter_recon.json: the reference encoder (oracle/_ref/kvazaar_ref, --preset ... --gop lp-g4d3t1, --threads 0 so that the ref_cudump.c
     interposer sees the LCUs in order) on the clips of tests/inter_common.py CASES: digest of every picture's --debug reconstruction and of its CU decisions,
-    md5 of the bitstream"""
+    md5 of the bitstream.  With case names (--inter NAME ...): only those entries are written, the others kept"""
     import tempfile
     import inter_common as ic
-    out = {}
+    path = os.path.join(HERE, "inter_recon.json")
+    out = json.load(open(path)) if names else {}
     for case in ic.CASES:
         name, w, h, n, qp, preset, dbk, sao, owf, src = case
+        if names and name not in names:
+            continue
         frames = ic.case_frames(case)
         with tempfile.TemporaryDirectory() as d:
             rec, cu = ic.reference_encode(w, h, frames, qp, d, preset=preset, deblock=bool(dbk), sao=bool(sao), owf=owf)
             out[name] = dict(ic.digests(rec, cu), bitstream_md5=hashlib.md5(open(os.path.join(d, "out.hevc"), "rb").read()).hexdigest(),
                              clip_md5=hashlib.md5(b"".join(f.tobytes() for f in frames)).hexdigest())
         print(name, out[name]["bitstream_md5"], flush=True)
-    json.dump(out, open(os.path.join(HERE, "inter_recon.json"), "w"), indent=0, sort_keys=True)
+    json.dump(out, open(path, "w"), indent=0, sort_keys=True)
 
 
 # the tiled inter configuration (BASELINE config 4 sharded by tile, SURVEY 8e): (name, width, height, pictures, qp, tiles, clip seed, noise, pan)
@@ -378,7 +381,7 @@ def main():
     if "--inter-tiles" in sys.argv:
         return update_inter_tiles()
     if "--inter" in sys.argv:
-        return update_inter()
+        return update_inter([a for a in sys.argv[sys.argv.index("--inter") + 1:] if not a.startswith("--")])
     if "--entropy" in sys.argv:
         return update_entropy()
     ref = flatapi.load_ref(0)  # generic strategies

@@ -182,6 +182,34 @@ extern "C" void kvz_hostsim_inter_tile(int width, int height, int qp, int poc, u
     }
   free(F.ctx_out); free(slab);
 }
+// one CU's motion-compensated prediction as the inter CTU pass forms it (InterCtu::inter_predict, predict_into): the w x w CU (8, 16 or 32) at picture position
+// (x, y) under the motion of *pu (mv_dir, mv), from ref (a width x height Y|U|V frame), into out (Y w*w | U | V)
+extern "C" void kvz_hostsim_inter_predict(int width, int height, const uint8_t *ref, const kvz_hip_cu_info *pu, int x, int y, int w, uint8_t *out)
+{
+  static kvz::Tables tb;
+  kvz::build_tables(&tb);
+  static const float fbits[128] = {};
+  kvz::InterModel m;
+  kvz::inter_model_init(&m, 22, 1, 0, fbits, 0, 0, 0, 2, 3, 0, 28, width, height);
+  kvz::InterFrames F;
+  memset(&F, 0, sizeof F);
+  F.W = width; F.H = height; F.wc = (width + 63) / 64; F.hc = (height + 63) / 64; F.frame_px = (long)width * height * 3 / 2; F.cells = (long)(width / 4) * (height / 4);
+  F.src = ref; F.ref = ref;
+  kvz::InterSlab *slab = (kvz::InterSlab *)calloc(1, sizeof(kvz::InterSlab));
+  F.slabs = slab;
+  kvz::InterCtu::begin_launch(F, &m, &tb, slab);
+  kvz::InterCtu::begin_ctu(0, x & ~63, y & ~63);
+  const int lv = w == 32 ? 1 : (w == 16 ? 2 : 3);
+  kvz::InterCtu::inter_predict(lv, x, y, w, *pu, true, true);
+  for (int c = 0; c < 3; c++) {
+    const kvz::PView v = kvz::InterCtu::lvl(lv, c, x & 63, y & 63);
+    const int bw = c ? w >> 1 : w;
+    uint8_t *o = out + (c == 0 ? 0 : (c == 1 ? w * w : w * w + (w * w >> 2)));
+    for (int yy = 0; yy < bw; yy++)
+      for (int xx = 0; xx < bw; xx++) o[yy * bw + xx] = v.p[yy * v.s + xx];
+  }
+  free(slab);
+}
 #ifdef KVZ_ICTU_COUNT_PHASES
 extern "C" void kvz_hostsim_inter_phases(long *out) { for (int i = 0; i < 32; i++) { out[i] = kvz::g_ic_phases[i]; kvz::g_ic_phases[i] = 0; } }
 #endif

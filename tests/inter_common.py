@@ -166,7 +166,15 @@ CASES = [
     ("survey-416x240", 416, 240, 8, 22, "veryfast", 1, 1, 2, ("synth", 1234, "small")),    # bitstream md5 1e7a8165...
     ("survey-1080p", 1920, 1080, 4, 22, "veryfast", 1, 1, 2, ("synth", 1, "large")),
     ("baseline-c4-2160p", 3840, 2160, 4, 22, "veryfast", 1, 1, 2, ("synth", 2, "large")),    # BASELINE config 4 at its own size
+    # motion compensation at its int16 edge (mc_overflow_clip): the luma (2, 2) phase on its maximising window, where the 14-bit sample is 33150
+    ("mc-overflow", 200, 136, 3, 22, "veryfast", 1, 1, 0, ("mc-overflow", 5, 1.5, 16)),
+    ("ultrafast-mc-overflow", 200, 136, 3, 22, "ultrafast", 1, 0, 0, ("mc-overflow", 5, 1.5, 16)),  # no fractional search: whole-sample luma vectors only (asserted)
 ]
+
+# the cases whose encodes must put a one-list PU with a (2, 2) vector on a window whose 14-bit sample leaves int16 (overflowing_uni_pus)
+MC_OVERFLOW_CASES = ["mc-overflow"]
+# ... and those whose encodes use whole-sample luma vectors only (fme_level 0): the extreme content through the pass's copy path
+MC_WHOLE_SAMPLE_CASES = ["ultrafast-mc-overflow"]
 
 
 # the cases whose slice data is pinned (tests/golden/entropy_inter.json): picture QPs on both sides of fast-residual-cost 28, SAO on / off, the wavefront MV restriction, `faster`
@@ -177,10 +185,49 @@ ENTROPY_CASES = ["pan", "ultrafast", "vertical-pan-owf", "static-qp17", "two-gop
 ENTROPY_BENCH_CASES = ["baseline-c4-2160p"]
 
 
+def mc_overflow_clip(w, h, n, seed, noise, period):
+    """picture 0: a still frame of clip() with the maximising 0 / 255 window of the luma (2, 2) phase pasted every `period` samples; pictures 1..: its
+    prediction under the vector (2, 2) (tests/mc_reference.py).  The search finds (2, 2) on most blocks, and the one-list samples there are 255 where a
+    14-bit sample narrowed to int16 would give 0"""
+    import mc_reference as mc
+    f0 = clip(w, h, 1, seed, noise, (0.0, 0.0))[0].copy()
+    y = f0[:w * h].reshape(h, w)
+    win = mc.extreme_window(2, 2, False, True)
+    for yy in range(3, h - 8, period):
+        for xx in range(3, w - 8, period):
+            y[yy:yy + 8, xx:xx + 8] = win
+    f1 = np.concatenate([mc.uni(mc.filter14(p, 0, 0, p.shape[1], p.shape[0], (2, 2), i > 0)).reshape(-1) for i, (p, _) in enumerate(mc.planes_of(f0, w, h))])
+    return [f0] + [f1.copy() for _ in range(n - 1)]
+
+
+def overflowing_uni_pus(rf, cu, w, h):
+    """(one-list PUs with mv & 3 == (2, 2), those among them whose luma window reaches a 14-bit sample beyond int16 in the reference picture).  Every inter
+    CU is taken as one 2Nx2N PU, its vector and window read at the CU's origin with the CU's size: what the presets of these cases search (the inter pass
+    has no other partition); a preset with AMP / rectangular partitions would need the PU split here"""
+    import mc_reference as mc
+    n22, over = 0, 0
+    for k in range(1, len(cu)):
+        ref = rf[k - 1][:w * h].reshape(h, w)
+        for y4 in range(h // 4):
+            for x4 in range(w // 4):
+                r = cu[k][y4, x4]
+                s = 64 >> int(r["depth"])
+                if r["type"] != 2 or (4 * x4) % s or (4 * y4) % s or r["mv_dir"] not in (1, 2):
+                    continue
+                mv = tuple(int(v) for v in r["mv"][int(r["mv_dir"]) - 1])
+                if (mv[0] & 3, mv[1] & 3) != (2, 2):
+                    continue
+                n22 += 1
+                over += int(mc.filter14(ref, 4 * x4, 4 * y4, s, s, mv, False).max() > 32767)
+    return n22, over
+
+
 def case_frames(case):
     name, w, h, n, qp, preset, dbk, sao, owf, src = case
     if src[0] == "motion":
         return clip(w, h, n, src[1], src[2], src[3])
+    if src[0] == "mc-overflow":
+        return mc_overflow_clip(w, h, n, src[1], src[2], src[3])
     import kvazaar_amd.synth as synth
     return [np.concatenate([p.reshape(-1) for p in f]) for f in synth.frames(w, h, n, src[1], src[2])]
 

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import flatapi
+import mc_reference as mc
 from flatapi import A, EpolParams, IPOL_COL_LEN, IPOL_IM_PLANE, ptr, u8p
 
 
@@ -232,31 +233,9 @@ def test_oracle_inter_pred_composition_runs(oracle):
     assert np.array_equal(pred[:W * H].reshape(H, W)[0:32, 32:64] * 0 + 1, np.ones((32, 32), np.uint8))
 
 
-LF = np.array([[0, 0, 0, 64, 0, 0, 0, 0], [-1, 4, -10, 58, 17, -5, 1, 0], [-1, 4, -11, 40, 40, -11, 4, -1], [0, 1, -5, 17, 58, -10, 4, -1]])  # filter.c:66-72
-CF = np.array([[0, 64, 0, 0], [-2, 58, 10, -2], [-4, 54, 16, -2], [-6, 46, 28, -4], [-4, 36, 36, -4], [-4, 28, 46, -6], [-2, 16, 54, -4], [-2, 10, 58, -2]])  # filter.c:74-84
-
-
 def uniform_inter_pred(refs, W, H, pus):
-    """what the device kernel computes: ONE expression for every branch of the reference (identity taps for integer vectors)"""
-    pred = np.zeros(W * H * 3 // 2, np.uint8)
-    for (x, y, w, h, mv0, mv1, u0, u1) in pus:
-        for pi in range(3):
-            sh = 1 if pi else 0
-            fw, fh, off = W >> sh, H >> sh, 0 if pi == 0 else (W * H if pi == 1 else W * H * 5 // 4)
-            pw, ph, taps, before = w >> sh, h >> sh, 4 if pi else 8, 1 if pi else 3
-            vals = []
-            for use, mv, ref in ((u0, mv0, refs[0]), (u1, mv1, refs[1])):
-                if not use:
-                    continue
-                plane = ref[off:off + fw * fh].reshape(fh, fw).astype(np.int64)
-                X0, Y0 = (x >> sh) + (mv[0] >> (2 + sh)) - before, (y >> sh) + (mv[1] >> (2 + sh)) - before
-                win = plane[np.ix_(np.clip(np.arange(Y0, Y0 + ph + taps - 1), 0, fh - 1), np.clip(np.arange(X0, X0 + pw + taps - 1), 0, fw - 1))]
-                hf, vf = (CF[mv[0] & 7], CF[mv[1] & 7]) if pi else (LF[mv[0] & 3], LF[mv[1] & 3])
-                g = sum(hf[k] * win[:, k:k + pw] for k in range(taps)).astype(np.int16).astype(np.int64)
-                vals.append((sum(vf[k] * g[k:k + ph, :] for k in range(taps)) >> 6).astype(np.int16).astype(np.int64))
-            res = np.clip((vals[0] + 32) >> 6, 0, 255) if len(vals) == 1 else np.clip((vals[0] + vals[1] + 64) >> 7, 0, 255)
-            pred[off:off + fw * fh].reshape(fh, fw)[y >> sh:(y >> sh) + ph, x >> sh:(x >> sh) + pw] = res
-    return pred
+    """what the device kernel computes: ONE expression for every branch of the reference (identity taps for integer vectors) -- tests/mc_reference.py"""
+    return mc.inter_pred(refs, W, H, pus)
 
 
 def test_one_expression_covers_every_reference_branch(oracle):
@@ -267,3 +246,158 @@ def test_one_expression_covers_every_reference_branch(oracle):
     pus = [(0, 0, 64, 64, (5, -3), (0, 0), 1, 0), (64, 0, 32, 32, (8, 16), (-9, 2), 1, 1), (0, 64, 64, 32, (4, 8), (12, -4), 1, 1), (128, 64, 16, 16, (-300, 7), (2, 2), 0, 1),
            (64, 64, 8, 8, (4, 0), (0, 4), 1, 1), (96, 64, 16, 8, (-13, 70), (66, -70), 1, 1), (128, 0, 64, 64, (16, -24), (0, 0), 1, 1), (112, 64, 16, 16, (700, 700), (-3, 1), 1, 1)]
     assert np.array_equal(oracle_inter_pred(oracle, refs, W, H, pus), uniform_inter_pred(refs, W, H, pus))
+    # the luma (2, 2) phase on its maximising window, where the 14-bit sample leaves int16: one list (not narrowed), two lists (wrapped operands), the same
+    # vector in both lists, one list off the picture's corner
+    ext = A(mc.extreme_frame(W, H))
+    refs = [ext, refs[1]]
+    pus = [(0, 0, 16, 16, (2, 2), (0, 0), 1, 0), (16, 0, 32, 16, (6, -14), (0, 0), 1, 0), (64, 0, 64, 64, (-30, 10), (2, 2), 1, 1), (0, 64, 16, 16, (0, 0), (2, 2), 0, 1),
+           (128, 0, 64, 64, (2, 2), (2, 2), 1, 1), (176, 112, 16, 16, (42, 34), (0, 0), 1, 0), (0, 32, 16, 32, (-98, -94), (0, 0), 1, 0)]
+    want = oracle_inter_pred(oracle, refs, W, H, pus)
+    assert np.array_equal(want, uniform_inter_pred(refs, W, H, pus))
+    assert (want[:W * H].reshape(H, W)[3:16:8, 3:16:8] == 255).all()   # the overflowing samples of the first PU: 255, not the wrapped 0
+
+
+# ---- every branch of kvz_hip_dev_inter_pred at the edges ---------------------------------------------------------------------------------------------
+# max_pu_size 16 with width % 8 == 0: one wavefront per PU (dev_inter_pred_wave_kernel); 16 with KVZ_HIP_MC_WORKGROUP_PER_PU set: dev_inter_pred_kernel<16>;
+# 32, 64: dev_inter_pred_kernel<32>, <64> (kvz_dev.hpp kvz_hip_dev_inter_pred)
+MC_BRANCHES = {"wave16": (16, False), "workgroup16": (16, True), "workgroup32": (32, False), "workgroup64": (64, False)}
+MC_SHAPES = {16: [(16, 16), (16, 8), (8, 16), (8, 8)], 32: [(32, 32), (32, 16), (16, 32), (16, 16), (8, 8)], 64: [(64, 64), (64, 32), (32, 64), (32, 32), (16, 16), (8, 8)]}
+
+
+def tiling_pus(W, H, max_size, rng, keep=1.0):
+    """non-overlapping PUs (every prediction sample written once) of the branch's shapes covering the picture (a random `keep` share of the interior ones):
+    every luma quarter-pel and chroma eighth-pel phase, (2, 2) on half of them, vectors over every edge and far outside; one list 0, one list 1, two lists,
+    two lists with one vector"""
+    shapes = MC_SHAPES[max_size]
+    covered = np.zeros((H // 8, W // 8), bool)
+    pus, k = [], 0
+    for cy in range(H // 8):
+        for cx in range(W // 8):
+            if covered[cy, cx]:
+                continue
+            for (w, h) in shapes[k % len(shapes):] + shapes[:k % len(shapes)]:
+                if cx * 8 + w <= W and cy * 8 + h <= H and not covered[cy:cy + h // 8, cx:cx + w // 8].any():
+                    break
+            else:
+                w = h = 8
+            covered[cy:cy + h // 8, cx:cx + w // 8] = True
+            k += 1
+            x, y = cx * 8, cy * 8
+            border = x == 0 or y == 0 or x + w == W or y + h == H
+            if not border and rng.random() >= keep:
+                continue
+            mvs = []
+            for l in range(2):
+                fx, fy = (2, 2) if rng.random() < 0.5 else (int(rng.integers(0, 4)), int(rng.integers(0, 4)))
+                kind = int(rng.integers(0, 6))
+                if kind == 0:
+                    ix, iy = int(rng.integers(-W - 80, -W + 40)), int(rng.integers(-20, 20))     # far left
+                elif kind == 1:
+                    ix, iy = int(rng.integers(-20, 20)), int(rng.integers(H - 40, H + 80))       # far below
+                elif kind == 2 and border:
+                    ix, iy = (-x - w // 2 if x == 0 else (W - x - w // 2 if x + w == W else 0)), (-y - h // 2 if y == 0 else (H - y - h // 2 if y + h == H else 0))  # half over the edge
+                else:
+                    ix, iy = int(rng.integers(-24, 25)), int(rng.integers(-24, 25))
+                mvs.append((4 * ix + fx + 4 * int(rng.integers(0, 2)), 4 * iy + fy))   # an odd integer part: half a chroma sample
+            use = ((1, 0), (0, 1), (1, 1), (1, 1))[k % 4]
+            if k % 4 == 3:
+                mvs[1] = mvs[0]
+            pus.append((x, y, w, h, mvs[0], mvs[1], use[0], use[1]))
+    return pus
+
+
+def device_inter_pred(lib, dev, refs, W, H, pus, max_size):
+    lib.kvz_hip_dev_inter_pred.restype = None
+    lib.kvz_hip_dev_inter_pred.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int]
+    arr = (McPu * len(pus))()
+    for i, (x, y, w, h, mv0, mv1, u0, u1) in enumerate(pus):
+        arr[i].x, arr[i].y, arr[i].w, arr[i].h = x, y, w, h
+        arr[i].mv[0][0], arr[i].mv[0][1], arr[i].mv[1][0], arr[i].mv[1][1] = mv0[0], mv0[1], mv1[0], mv1[1]
+        arr[i].use[0], arr[i].use[1] = u0, u1
+    d0, d1 = dev.put(refs[0]), dev.put(refs[1])
+    d_pred = dev.put(np.zeros(W * H * 3 // 2, np.uint8))
+    d_pus = dev.empty(C.sizeof(arr))
+    lib.kvz_hip_dev_upload(d_pus, C.addressof(arr), C.sizeof(arr))
+    lib.kvz_hip_dev_inter_pred(d0, d1, d_pred, W, H, d_pus, len(pus), max_size)
+    got = dev.get(d_pred, (W * H * 3 // 2,), np.uint8)
+    dev.free(d0, d1, d_pred, d_pus)
+    return got
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("size", [(200, 136), (1920, 1080)], ids=["200x136", "1920x1080"])
+@pytest.mark.parametrize("branch", list(MC_BRANCHES))
+def test_dev_inter_pred_every_branch_at_the_int16_edge(oracle, monkeypatch, branch, size):
+    """each kernel of kvz_hip_dev_inter_pred against the model (tests/mc_reference.py) and, at 200x136 (chroma rows of 100: not 8-aligned), the reference's
+    branches through the oracle: one and two lists on the luma (2, 2) maximising windows (14-bit samples of 33150), every phase, vectors far outside"""
+    import kvazaar_amd
+    from kvazaar_amd.dev import Dev
+    max_size, workgroup = MC_BRANCHES[branch]
+    if workgroup:
+        monkeypatch.setenv("KVZ_HIP_MC_WORKGROUP_PER_PU", "1")   # read by every call
+    lib = kvazaar_amd.load_library()
+    dev = Dev(lib)
+    W, H = size
+    rng = np.random.default_rng(list(MC_BRANCHES).index(branch) * 7919 + W)
+    ext = A(mc.extreme_frame(W, H))
+    noise = A(rng.integers(0, 256, W * H * 3 // 2, dtype=np.uint8))
+    pus = tiling_pus(W, H, max_size, rng, keep=1.0 if W < 1000 else 0.15)
+    if len(pus) % 4 == 0:
+        pus = pus[:-1]                  # the wavefront kernel's last workgroup holds fewer than four PUs
+    assert any(p[2] < p[3] for p in pus) and any(p[2] > p[3] for p in pus)
+    for refs in ([ext, noise], [ext, ext]):
+        got = device_inter_pred(lib, dev, refs, W, H, pus, max_size)
+        want = mc.inter_pred(refs, W, H, pus)
+        bad = np.flatnonzero(got != want)
+        assert not len(bad), (len(bad), bad[:10], [p for p in pus if p[0] <= bad[0] % W < p[0] + p[2] and p[1] <= bad[0] // W < p[1] + p[3]][:1] if bad[0] < W * H else None)
+        if W < 1000:
+            assert np.array_equal(want, oracle_inter_pred(oracle, refs, W, H, pus))
+    # the content reaches the edge: one-list (2, 2) PUs whose samples are 255 where int16 would have wrapped them to 0
+    y = ext[:W * H].reshape(H, W)
+    assert sum(int((mc.filter14(y, p[0], p[1], p[2], p[3], p[4], False) > 32767).sum()) for p in pus if p[6] and not p[7] and (p[4][0] & 3, p[4][1] & 3) == (2, 2)) > 10
+
+
+@pytest.mark.gpu
+def test_dev_fme_costs_every_instantiation_quarter_pel_steps(oracle):
+    """kvz_hip_dev_fme_costs' <16>, <32> and <64> instantiations with all four steps (the `faster` search, steps = 15): all 17 costs against search_frac's
+    sequence through the oracle, on textured content and on the luma (2, 2) extreme windows (the diagonal half-pel planes' 14-bit samples wrap in fin)"""
+    import kvazaar_amd
+    from kvazaar_amd.dev import Dev
+    lib = kvazaar_amd.load_library()
+    dev = Dev(lib)
+    lib.kvz_hip_dev_fme_costs.restype = None
+    lib.kvz_hip_dev_fme_costs.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    W, H = 200, 136
+    rng = np.random.default_rng(9)
+    yy, xx = np.mgrid[0:H, 0:W]
+    smooth = np.clip(128 + 70 * np.sin(xx / 5.0) * np.cos(yy / 7.0) + rng.normal(0, 12, (H, W)), 0, 255).astype(np.uint8)
+    contents = [("textured", smooth), ("max", mc.tiled(mc.extreme_window(2, 2, False, True), H, W)), ("min", mc.tiled(mc.extreme_window(2, 2, False, False), H, W))]
+    pus = []
+    for (w, h) in [(8, 8), (16, 16), (16, 8), (8, 16), (32, 32), (32, 16), (16, 32), (64, 64), (64, 32)]:
+        for k in range(8):
+            x, y = int(rng.integers(0, (W - w) // 8 + 1)) * 8, int(rng.integers(0, (H - h) // 8 + 1)) * 8
+            mvx, mvy = int(rng.integers(-12, 13)), int(rng.integers(-12, 13))
+            if k == 0: x, y, mvx, mvy = 0, 0, -9, -7
+            if k == 1: x, y, mvx, mvy = W - w, H - h, 11, 6
+            if k == 2: mvx, mvy = -250, 3
+            if k == 3: mvx, mvy = 2, 300
+            pus.append((x, y, w, h, mvx, mvy, (k % 3) - 1, ((k // 3) % 3) - 1))
+    checked = 0
+    for label, ref_plane in contents:
+        ref = A(ref_plane.reshape(-1))
+        cur = A(np.clip(np.roll(ref_plane, (1, -2), (0, 1)).astype(np.int32) + rng.integers(-6, 7, (H, W)), 0, 255).astype(np.uint8).reshape(-1))
+        want = {p: oracle_fme(oracle, cur, ref, W, H, p) for p in pus}
+        d_cur, d_ref = dev.put(cur), dev.put(ref)
+        for max_size in (16, 32, 64):
+            sel = [p for p in pus if p[2] <= max_size and p[3] <= max_size]
+            arr = (FmePu * len(sel))(*[FmePu(*p, 0) for p in sel])
+            d_pus, d_out = dev.empty(C.sizeof(arr)), dev.empty(len(sel) * 17 * 4)
+            lib.kvz_hip_dev_upload(d_pus, C.addressof(arr), C.sizeof(arr))
+            lib.kvz_hip_dev_fme_costs(d_cur, d_ref, W, H, d_pus, len(sel), max_size, 15, d_out)
+            got = dev.get(d_out, (len(sel), 17), np.uint32)
+            bad = [(p, list(got[i]), want[p]) for i, p in enumerate(sel) if list(got[i]) != want[p]]
+            assert not bad, (label, max_size, len(bad), bad[:2])
+            checked += len(sel)
+            dev.free(d_pus, d_out)
+        dev.free(d_cur, d_ref)
+    assert checked == 3 * (4 * 8 + 7 * 8 + 9 * 8)

@@ -23,6 +23,7 @@ FAST_COST_CASES = ["pan", "ultrafast", "vertical-pan-owf", "static-qp17", "no-lo
 CABAC_COST_CASES = ["noisy-qp27", "cabac-coeff-cost-qp32", "fast-pan-owf-qp37", "ultrafast-fast-pan-owf-qp30"]     # picture QPs from 28 on: the residual coder in counting mode
 EDGE_CASES = ["ultrafast-8mod16", "superfast-8mod16-qp33"]  # 8x8 inter CUs where the picture edge forces the split below pu-depth-inter's 16x16 (search.c:702-713)
 FASTER_CASES = ["faster-pan", "faster-qp32", "faster-owf-qp27"]  # `--preset faster`: quarter-sample steps in the fractional search, CABAC coefficient cost at every QP
+MC_EDGE_CASES = ["mc-overflow", "ultrafast-mc-overflow"]  # motion compensation where the 14-bit sample leaves int16 (inter_common.mc_overflow_clip)
 
 
 @pytest.fixture(scope="module")
@@ -47,12 +48,13 @@ def hostsim_lib():
 
 
 @pytest.mark.parametrize("name", ["pan", "ultrafast", "vertical-pan-owf", "no-loop-filters", "noisy-qp27", "cabac-coeff-cost-qp32", "fast-pan-owf-qp37", "ultrafast-fast-pan-owf-qp30",
-                                  "faster-pan", "faster-qp32", "faster-owf-qp27", "ultrafast-8mod16", "superfast-8mod16-qp33"])
+                                  "faster-pan", "faster-qp32", "faster-owf-qp27", "ultrafast-8mod16", "superfast-8mod16-qp33"] + MC_EDGE_CASES)
 def test_host_simulation_of_the_device_program_equals_the_oracle(oracle, hostsim_lib, name):
     case = [c for c in ic.CASES if c[0] == name][0]
     _, w, h, n, qp, preset, dbk, sao, owf, src = case
     frames = ic.case_frames(case)
     rs, rf, cu, qps = ic.oracle_encode(oracle, w, h, frames, qp, preset=preset, deblock=bool(dbk), sao=bool(sao), mv_constraint=owf > 0)
+    assert_covers_the_overflow(name, rf, cu, w, h)
     mc = cc.model_constants()
     fb = np.array(mc["entropy_fbits"], np.float32)
     f = hostsim_lib.kvz_hostsim_inter_frame
@@ -66,6 +68,46 @@ def test_host_simulation_of_the_device_program_equals_the_oracle(oracle, hostsim
           np.ascontiguousarray(frames[k]).ctypes.data, np.ascontiguousarray(rf[k - 1]).ctypes.data, np.ascontiguousarray(cu[k - 1]).ctypes.data, rec.ctypes.data, out.ctypes.data)
         assert ic.first_difference(out[None], cu[k][None]) is None, k
         assert np.array_equal(rec, rs[k]), k
+
+
+def assert_covers_the_overflow(name, rf, cu, w, h):
+    """an MC_OVERFLOW case must keep putting one-list (2, 2) PUs on windows whose 14-bit sample leaves int16, or it no longer tests that edge; an
+    MC_WHOLE_SAMPLE case must keep to whole-sample luma vectors (and still have inter CUs)"""
+    if name in ic.MC_OVERFLOW_CASES:
+        n22, over = ic.overflowing_uni_pus(rf, cu, w, h)
+        assert over >= 8, (n22, over)
+    if name in ic.MC_WHOLE_SAMPLE_CASES:
+        b = cu[1:]
+        inter = b["type"] == 2
+        frac = [inter & ((b["mv_dir"] >> l) & 1 > 0) & ((b["mv"][..., l, :] & 3) != 0).any(axis=-1) for l in range(2)]
+        assert inter.sum() > 0 and not (frac[0] | frac[1]).any()
+
+
+def test_host_simulation_of_the_pass_prediction_at_the_int16_edge(hostsim_lib):
+    """the pass's motion-compensated prediction of a CU (InterCtu::inter_predict -> predict_into -> predict_tile) on the luma (2, 2) maximising windows,
+    against the model (tests/mc_reference.py): one list (14-bit samples of 33150 finish as 255), two lists (operands wrapped), and two lists with one vector,
+    which the pass predicts as one list -- its operands must still wrap, as the reference's bipred average of two equal int16 operands does"""
+    import mc_reference as mc
+    W, H = 128, 128
+    ext = np.ascontiguousarray(mc.extreme_frame(W, H))
+    f = hostsim_lib.kvz_hostsim_inter_predict
+    f.restype = None
+    f.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    twice_wraps = 0
+    for w in (8, 16, 32):
+        for (x, y, a, b) in [(64, 32, (14, -18), (-22, 6)), (0, 0, (-18, -26), (6, 10)), (W - w, H - w, (2, 2), (10, -6))]:
+            for (mv_dir, mv0, mv1) in [(1, a, (0, 0)), (2, (0, 0), a), (3, a, b), (3, a, a)]:
+                rec = np.zeros(1, ic.CU_DTYPE)
+                rec["type"], rec["mv_dir"], rec["mv"][0, 0], rec["mv"][0, 1] = 2, mv_dir, mv0, mv1
+                out = np.zeros(w * w * 3 // 2, np.uint8)
+                f(W, H, ext.ctypes.data, rec.ctypes.data, x, y, w, out.ctypes.data)
+                pred = mc.inter_pred([ext, ext], W, H, [(x, y, w, w, mv0, mv1, mv_dir & 1, mv_dir >> 1)])
+                want = np.concatenate([p[(y >> (c > 0)):(y + w) >> (c > 0), (x >> (c > 0)):(x + w) >> (c > 0)].reshape(-1) for c, (p, _) in enumerate(mc.planes_of(pred, W, H))])
+                assert np.array_equal(out, want), (w, x, y, mv_dir, mv0, mv1, int((out != want).sum()))
+                if mv_dir == 3 and mv0 == mv1:
+                    v = mc.filter14(ext[:W * H].reshape(H, W), x, y, w, w, mv0, False)
+                    twice_wraps += int((mc.uni(v) != mc.bi(mc.hi(v), mc.hi(v))).sum())
+    assert twice_wraps > 50   # the equal-vector PUs sit on windows where one list and two wrapped operands differ
 
 
 def test_fuzz_of_the_device_program_against_the_oracle(hostsim_lib):
@@ -93,7 +135,7 @@ def device_pass(lib, dev, w, h, srcs, refs, ref_cus, prm):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", FAST_COST_CASES + CABAC_COST_CASES + FASTER_CASES + EDGE_CASES + ["two-gops"])
+@pytest.mark.parametrize("name", FAST_COST_CASES + CABAC_COST_CASES + FASTER_CASES + EDGE_CASES + ["two-gops"] + MC_EDGE_CASES)
 def test_device_pass_equals_oracle_picture_by_picture(oracle, name):
     import kvazaar_amd
     from kvazaar_amd.dev import Dev
@@ -103,6 +145,7 @@ def test_device_pass_equals_oracle_picture_by_picture(oracle, name):
     _, w, h, n, qp, preset, dbk, sao, owf, src = case
     frames = ic.case_frames(case)
     rs, rf, cu, qps = ic.oracle_encode(oracle, w, h, frames, qp, preset=preset, deblock=bool(dbk), sao=bool(sao), mv_constraint=owf > 0)
+    assert_covers_the_overflow(name, rf, cu, w, h)
     for k in range(1, n):
         rec, got = device_pass(lib, dev, w, h, [frames[k]], [rf[k - 1]], [cu[k - 1]], params_of(case, qps[k], k))
         d = ic.first_difference(got, cu[k][None])

@@ -19,24 +19,29 @@ def oracle():
     return flatapi.load_oracle()
 
 
-def device_pu_search(lib, dev, cur, ref, w, h, pus, params):
+def device_pu_search(lib, dev, cur, ref, w, h, pus, params, max_pu_size=32):
     lib.kvz_hip_dev_pu_search.restype = C.c_int
     lib.kvz_hip_dev_pu_search.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     d_cur, d_ref, d_pus = dev.put(cur), dev.put(ref), dev.put(pus)
     d_out = dev.empty(len(pus) * ic.ME_RESULT.itemsize)
-    assert lib.kvz_hip_dev_pu_search(d_cur, d_ref, w, h, d_pus, len(pus), 32, C.addressof(params), d_out) == 0
+    assert lib.kvz_hip_dev_pu_search(d_cur, d_ref, w, h, d_pus, len(pus), max_pu_size, C.addressof(params), d_out) == 0
     got = dev.get(d_out, (len(pus),), ic.ME_RESULT)
     dev.free(d_cur, d_ref, d_pus, d_out)
     return got
 
 
-def random_pus(rng, w, h, n):
+def random_pus(rng, w, h, n, shapes=None):
+    """n PUs: squares of 8, 16 and 32 samples, or (w, h) shapes drawn from `shapes`"""
     pus = np.zeros(n, ic.ME_PU)
     for i in range(n):
-        s = int(rng.choice([8, 16, 32]))
+        if shapes is None:
+            s = int(rng.choice([8, 16, 32]))
+            pw = ph = s
+        else:
+            pw, ph = shapes[int(rng.integers(0, len(shapes)))]
         p = pus[i]
-        p["w"] = p["h"] = s
-        p["x"], p["y"] = int(rng.integers(0, (w - s) // 8 + 1)) * 8, int(rng.integers(0, (h - s) // 8 + 1)) * 8
+        p["w"], p["h"] = pw, ph
+        p["x"], p["y"] = int(rng.integers(0, (w - pw) // 8 + 1)) * 8, int(rng.integers(0, (h - ph) // 8 + 1)) * 8
         spread = int(rng.choice([2, 8, 40, 200]))
         p["mv_cand"] = rng.integers(-spread, spread + 1, (2, 2))
         if rng.random() < 0.3:
@@ -47,7 +52,7 @@ def random_pus(rng, w, h, n):
         p["merge_dir"] = rng.choice([1, 2, 3], 5)
         p["merge_mv"] = rng.integers(-spread, spread + 1, (5, 2))
         if i % 17 == 0:   # a corner PU whose candidates point far outside
-            p["x"], p["y"] = (0, 0) if i % 2 else (w - s, h - s)
+            p["x"], p["y"] = (0, 0) if i % 2 else (w - pw, h - ph)
             p["start_mv"] = (-900, -700) if i % 2 else (800, 1100)
             p["has_start"] = 1
     return pus
@@ -88,6 +93,29 @@ def test_device_search_equals_oracle_on_random_pus(oracle, fme_level, constraint
     assert len(bad) == 0, (len(bad), pus[bad[0]], want[bad[0]], got[bad[0]])
     assert (want["valid"] != 0).sum() > 1000 and (fme_level == 0 or (want["frac_valid"] != 0).sum() > 800)
     assert len({(int(a), int(b)) for a, b in want["mv"]}) > 100   # the searches really go places
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("fme_level,constraint", [(2, 0), (4, 1), (0, 0)])
+def test_device_search_of_64_sample_pus_equals_oracle(oracle, fme_level, constraint):
+    """dev_pu_search_kernel<64> (max_pu_size 64): 64x64 PUs and the smaller squares routed to the same instantiation, corners and probes far outside
+    included (the contract, include/kvz_hip_dev.h, takes square PUs only)"""
+    import kvazaar_amd
+    from kvazaar_amd.dev import Dev
+    lib = kvazaar_amd.load_library()
+    dev = Dev(lib)
+    w, h = 352, 288
+    rng = np.random.default_rng(640 + fme_level + constraint)
+    frames = ic.clip(w, h, 2, 23, 2.0, (2.75, 1.25))
+    cur, ref = frames[1][:w * h], frames[0][:w * h]
+    pus = random_pus(rng, w, h, 360, shapes=((64, 64), (64, 64), (32, 32), (16, 16), (8, 8)))
+    prm = ic.MeParams(lambda_sqrt=ic.lambda_sqrt(27), mv_constraint=constraint, sao=1, deblock=1, fme_level=fme_level)
+    want = ic.oracle_pu_search(oracle, cur, ref, w, h, pus, prm)
+    got = device_pu_search(lib, dev, cur, ref, w, h, pus, prm, max_pu_size=64)
+    bad = ic.me_results_differ(got, want, fme_level)
+    assert len(bad) == 0, (len(bad), pus[bad[0]], want[bad[0]], got[bad[0]])
+    assert (want["valid"] != 0).sum() > 250 and (fme_level == 0 or (want["frac_valid"] != 0).sum() > 200)
+    assert (pus["w"] == 64).sum() > 100 and all((pus["w"] == s).sum() > 30 for s in (8, 16, 32))
 
 
 @pytest.mark.gpu
