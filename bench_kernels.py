@@ -75,6 +75,25 @@ def main():
             report(f"{cost}_{n}x{n}", n, count, ms, 2 * n * n + 4)
         dev.free(da, db, do)
 
+    # distortion sums of whole 1080p pictures (kvz_hip_dev_picture_sse): the same two read streams as sad_NxN and no writes to speak of, so sad_64x64 of this run
+    # is its yardstick; 2 bytes per sample
+    import ctypes as C
+    w, h = 1920, 1080
+    nfr = max(8, args.batch_ctus // 340)  # 384 pictures, 1.19 GB per operand by default
+    rng = np.random.default_rng(11)
+    src = rng.integers(0, 256, w * h * 3 // 2, dtype=np.uint8)
+    rec = np.clip(src.astype(np.int16) + rng.integers(-6, 7, src.size), 0, 255).astype(np.uint8)
+    da, db, do = dev.put(np.tile(src, (nfr, 1))), dev.put(np.tile(rec, (nfr, 1))), dev.empty(24 * nfr)
+    dev.lib.kvz_hip_dev_picture_sse.restype = C.c_int
+    dev.lib.kvz_hip_dev_picture_sse.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    ms = time_call(dev, lambda: dev.lib.kvz_hip_dev_picture_sse(da, db, w, h, nfr, do), args.reps, args.warmup)
+    d = src.astype(np.int64) - rec
+    ok = bool((dev.get(do, (nfr, 3), np.uint64) == np.array([(d[:w * h] ** 2).sum(), (d[w * h:w * h * 5 // 4] ** 2).sum(), (d[w * h * 5 // 4:] ** 2).sum()], np.uint64)).all())
+    report("sse_1080p_frame", 0, nfr, ms, 2 * (w * h * 3 // 2) + 24,
+           {"path": "three v_dot4_u32_u8 per dword pair, 16-byte loads, four in flight per lane and operand; one 64-bit atomic per workgroup (the zeroing hipMemsetAsync of 24 bytes per picture is inside the timed call)",
+            "fps": round(nfr / (ms * 1e-3)), "verified": ok, "yardstick": "sad_64x64 of this run"})
+    dev.free(da, db, do)
+
     for name in ("dct4", "dct8", "dct16", "dct32", "idct4", "idct8", "idct16", "idct32"):
         kind = devapi.TRANSFORM_KINDS[name]
         n = devapi.TRANSFORM_SIZE[kind]

@@ -132,6 +132,9 @@ int kvz_hip_coeff_nxn_bins(const int16_t *coeff, int width, int type, int scan_m
 uint32_t kvz_hip_plane_checksum(const uint8_t *data, int height, int width, int stride);            /* nal-generic.c:57-82, the 32-bit sum */
 uint32_t kvz_hip_coeff_abs_sum(const int16_t *coeffs, size_t length);                        /* quant-generic.c:342-349 */
 double   kvz_hip_fast_coeff_cost(const int16_t *coeff, int32_t width, uint64_t weights);     /* :359-375 */
+/* The last step of compute_psnr (encmain.c:107-108, 138-143), on the host, no device involved: 999.99 for sse == 0, else 10.0 * log10(num_pixels * 65025.0 / sse)
+ * in double, in that order of operations.  sse: a plane's sum of squared differences (kvz_hip_batch_sse, kvz_hip_dev_picture_sse), num_pixels: the plane's samples. */
+double   kvz_hip_psnr(uint64_t sse, long num_pixels);
 
 /* ---- 2. flat: functions whose reference signature carries host structs ------------------------------------------- */
 /* All-sizes forms used by the tests (n in {4,8,16,32,64}); the typedef-exact names above forward to these. */

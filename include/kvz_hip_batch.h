@@ -133,6 +133,20 @@ int  kvz_hip_batch_checksums(kvz_hip_batch *b, uint32_t *host_out);  /* 0 / -1 l
 /* ... and the MD5 flavour of the picture hash (nal.c:88-101 kvz_image_md5, `--hash md5`): host_out[(3 f + plane) * 16 ..] = 16 digest bytes. */
 int  kvz_hip_batch_md5(kvz_hip_batch *b, uint8_t *host_out);
 
+/* Distortion of every frame: host_out[3 * f + plane] = the exact sum of squared differences between the frame's source picture and its reconstruction as the
+ * batch holds it NOW -- after kvz_hip_batch_deblock / _loop_filters if they ran: kvazaar's PSNR (encmain.c:117-145 compute_psnr, the `PSNR Y U V` of its log
+ * line, cli.c:721-753) is of the final picture.  kvz_hip_psnr (kvz_hip.h) turns a sum into that figure.  Both pictures are read where they are (3 x w h bytes
+ * per frame, kvz_hip_dev_picture_sse) and 24 bytes per frame come back: the rate of a picture is the size of its slice data (kvz_hip_batch_entropy_code), this
+ * is the other half.  Queued behind whatever the batch's stream holds and waited for; 0 / -1 like kvz_hip_batch_checksums (-1 also for a NULL argument). */
+int  kvz_hip_batch_sse(kvz_hip_batch *b, uint64_t *host_out);
+/* ... queued on the batch's stream without waiting: host_out (kvz_hip_host_alloc'ed memory, or the copy is not asynchronous) is valid after kvz_hip_batch_sync.
+ * Returns 0, or -1 for a NULL argument (nothing queued).
+ * Ordering against kvz_hip_batch_upload_all_async, which replaces the source pictures on a queue of its own: A SUM QUEUED BEFORE AN UPLOAD SEES THE OLD
+ * PICTURES, ONE QUEUED AFTER IT THE NEW ONES.  The upload starts behind the last sum queued so far (and behind the last pass, as always); a sum queued after an
+ * upload waits for it, as the next pass does.  (kvz_hip_batch_upload copies on the batch's own stream and is ordered by it.)  With no sum queued, uploads wait for
+ * exactly what they waited for before. */
+int  kvz_hip_batch_sse_async(kvz_hip_batch *b, uint64_t *host_out);
+
 /* Cost model of an I slice at `qp` (kvz_hip_intra_cost_model, adaptive contexts): HEVC context init values
  * (context.c:96-134), kvz_ctx_init (context.c:202-213), the HM entropy table (rdo.c:69-80), lambda of
  * rate_control.c:678-691.  coeff_weights = kvz_fast_coeff_get_weights(state) of the encoder (fast_coeff_cost.c:84-88). */

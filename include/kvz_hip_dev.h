@@ -253,6 +253,13 @@ void kvz_hip_dev_picture_checksums(const uint8_t *frames, int width, int height,
  * (kvz_array_md5, nal-generic.c:41-55).  One serial chain per plane, one lane each: throughput comes from the number of planes in flight. */
 void kvz_hip_dev_picture_md5(const uint8_t *frames, int width, int height, int n_frames, uint8_t *out);
 
+/* Distortion of pictures (the sums of encmain.c:117-145 compute_psnr): out[3 * f + p] = the exact sum of squared differences of plane p of frame f of `a`
+ * against the same plane of `b`, for two sets of n_frames tight planar 4:2:0 frames; kvz_hip_psnr (kvz_hip.h) turns a sum into the PSNR kvazaar prints.
+ * a, b and out are device pointers, a and b 16-byte aligned; width and height multiples of 8.  Queued on the calling thread's stream like
+ * kvz_hip_dev_picture_checksums (kvz_hip_dev_sync waits).  2 x 1.5 w h bytes read per frame, 24 written.  Returns 0, or -1 -- nothing queued -- on a bad
+ * argument (a NULL or misaligned pointer, n_frames <= 0, a width or height that is not a positive multiple of 8). */
+int kvz_hip_dev_picture_sse(const uint8_t *a, const uint8_t *b, int width, int height, int n_frames, uint64_t *out);
+
 /* Assembles a planar 4:2:0 picture from tile pictures: `tiles` (HOST memory) holds n records (x, y, w, h, slot); tile i's planar Y|U|V picture of w x h lies at
  * slots + slot * slot_bytes (device memory) and is pasted at (x, y) of the width x height frame (device memory).  One launch on `stream` (a hipStream_t; NULL = the
  * calling thread's stream of this library).  n <= 64.  Used by the reference-frame exchange of the tile-sharded inter configuration (kvazaar_amd/sharding.py). */

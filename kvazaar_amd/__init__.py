@@ -11,5 +11,13 @@ when no gfx950 device is usable.
 """
 from .build import LIB_PATH, build_library, build_tools  # noqa: F401
 from .library import load_library  # noqa: F401
+from .batch import psnr_text  # noqa: F401
+
+
+def psnr(sse, num_pixels):
+    """kvz_hip_psnr (include/kvz_hip.h): the PSNR kvazaar prints for a plane of `num_pixels` samples whose sum of squared differences is `sse`
+    (HipBatch.sse(), InterPictures.sse()); computed on the host by the library, no device involved"""
+    from . import batch
+    return batch.psnr(load_library(), sse, num_pixels)
 
 __version__ = "0.1"

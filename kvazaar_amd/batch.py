@@ -195,6 +195,28 @@ class HipBatch:
             raise BatchError("kvz_hip_batch_md5: the batch's last pass was invalid")
         return out
 
+    def sse(self):
+        """-> uint64 array [frames][3]: the exact sum of squared differences of every frame's source against its current reconstruction (after deblock /
+        loop_filters if they ran), Y, U, V (kvz_hip_batch_sse)"""
+        out = np.zeros((self.n, 3), np.uint64)
+        self.lib.kvz_hip_batch_sse.argtypes = [C.c_void_p, C.c_void_p]
+        self.lib.kvz_hip_batch_sse.restype = C.c_int
+        if self.lib.kvz_hip_batch_sse(self.handle, out.ctypes.data) != 0:
+            raise BatchError("kvz_hip_batch_sse: the batch's last pass was invalid")
+        return out
+
+    def sse_async(self, out_ptr):
+        """kvz_hip_batch_sse_async: the same queued on the batch's stream; the n x 3 uint64 at address `out_ptr` -- pinned_bytes() -- are valid after sync().  A sum queued
+        before upload_all_async sees the old pictures, one queued after it the new ones"""
+        self.lib.kvz_hip_batch_sse_async.argtypes = [C.c_void_p, C.c_void_p]
+        self.lib.kvz_hip_batch_sse_async.restype = C.c_int
+        if self.lib.kvz_hip_batch_sse_async(self.handle, out_ptr) != 0:
+            raise BatchError("kvz_hip_batch_sse_async: bad argument")
+
+    def psnr(self):
+        """-> float64 array [frames][3]: PSNR Y, U, V of every frame as kvazaar computes it (kvz_hip_psnr of sse())"""
+        return psnr_of_planes(self.lib, self.sse(), self.w, self.h)
+
     def kernel_ms(self):
         return self.lib.kvz_hip_batch_last_kernel_ms(self.handle)
 
@@ -222,6 +244,25 @@ class HipBatch:
             self.handle = None
         pinned_free(self.lib, getattr(self, "_entropy_ptr", None))
         self._entropy_ptr = self._entropy_out = None
+
+
+def psnr(lib, sse, num_pixels):
+    """kvz_hip_psnr: compute_psnr's last step (encmain.c:138-143) -- 999.99 for sse == 0, else 10 log10(num_pixels * 255^2 / sse); on the host, no device involved"""
+    lib.kvz_hip_psnr.argtypes = [C.c_uint64, C.c_long]
+    lib.kvz_hip_psnr.restype = C.c_double
+    return float(lib.kvz_hip_psnr(int(sse), int(num_pixels)))
+
+
+def psnr_of_planes(lib, sse, width, height):
+    """[..., 3] sums of squared differences of width x height 4:2:0 pictures -> float64 [..., 3] PSNR Y, U, V"""
+    sse = np.asarray(sse, np.uint64)
+    px = (width * height, width * height // 4, width * height // 4)
+    return np.array([psnr(lib, v, px[i % 3]) for i, v in enumerate(sse.reshape(-1))], np.float64).reshape(sse.shape)
+
+
+def psnr_text(psnr3):
+    """the PSNR part of kvazaar's per-picture log line (cli.c:735)"""
+    return " PSNR Y %2.4f U %2.4f V %2.4f" % tuple(float(v) for v in psnr3)
 
 
 def entropy_capacity(n, w, h):

@@ -21,6 +21,9 @@ struct kvz_hip_batch {
   hipEvent_t ev0, ev1;
   hipEvent_t ev_up = nullptr;  // kvz_hip_batch_upload_all_async: what the next pass waits for
   int up_pending = 0;
+  hipEvent_t ev_src_read = nullptr;  // behind the last reader of d_src that is not the pass (kvz_hip_batch_sse_async): what kvz_hip_batch_upload_all_async also waits for
+  int src_read_set = 0;              // ... once one has been recorded (never, unless such a reader was queued)
+  unsigned long long *d_sse = nullptr;  // kvz_hip_batch_sse: n_frames x 3 sums (allocated on first use)
   uint8_t *d_src, *d_rec, *d_depth, *d_mode;
   uint8_t *d_part, *d_mode4;  // search_nxn: NxN flag per 8x8 CU, luma mode per 4x4 unit (allocated with the first model that has it set)
   int16_t *d_coeff, *d_scratch;
@@ -66,6 +69,13 @@ inline int batch_check(kvz_hip_batch *b)
     }
   }
   return b->failed ? -1 : 0;
+}
+// a reader of the source pictures other than the pass has just been queued on the batch's stream: the next kvz_hip_batch_upload_all_async copies behind it
+inline void batch_src_read(kvz_hip_batch *b)
+{
+  if (!b->ev_src_read) KVZ_HIP_CHECK(hipEventCreateWithFlags(&b->ev_src_read, hipEventDisableTiming));
+  KVZ_HIP_CHECK(hipEventRecord(b->ev_src_read, b->stream));
+  b->src_read_set = 1;
 }
 }  // namespace kvz
 
@@ -273,6 +283,8 @@ void kvz_hip_batch_destroy(kvz_hip_batch *b)
   if (b->h_error) (void)hipHostFree(b->h_error);
   if (b->entropy_out.p) (void)hipFree(b->entropy_out.p);
   if (b->ev_up) { (void)hipEventSynchronize(b->ev_up); (void)hipEventDestroy(b->ev_up); }
+  if (b->ev_src_read) (void)hipEventDestroy(b->ev_src_read);
+  (void)hipFree(b->d_sse);
   (void)hipStreamDestroy(b->stream);
   delete b;
 }
@@ -313,6 +325,7 @@ void kvz_hip_batch_upload_all_async(kvz_hip_batch *b, const uint8_t *src)
   // the source pictures are only read by the CTU pass (and by SAO's statistics): the copy may start as soon as the batch's last pass has ended (ev1; a no-op
   // before the first pass), whatever its stream still holds behind it -- deblocking, the entropy coder, downloads
   KVZ_HIP_CHECK(hipStreamWaitEvent(up, b->ev1, 0));
+  if (b->src_read_set) KVZ_HIP_CHECK(hipStreamWaitEvent(up, b->ev_src_read, 0));  // ... and the last distortion sum queued on them (kvz_hip_batch_sse_async)
   KVZ_HIP_CHECK(hipMemcpyAsync(b->d_src, src, (size_t)b->n_frames * b->F.frame_px, hipMemcpyHostToDevice, up));
   KVZ_HIP_CHECK(hipEventRecord(b->ev_up, up));
   b->up_pending = 1;

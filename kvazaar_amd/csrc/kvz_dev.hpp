@@ -848,6 +848,62 @@ inline void launch_checksums(hipStream_t stream, const u8 *frames, int W, int H,
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// Distortion of a batch (encmain.c:117-145 compute_psnr's sums): per (picture, plane) the exact sum of squared differences of two picture sets, 64 bits each.
+// A plane is one run of bytes in both sets, a multiple of 16 long and 16-byte aligned, so this is a streaming reduction: a workgroup takes one piece of
+// `units_per_piece` 16-byte units of a luma plane (a quarter of that of a chroma plane: every workgroup of the grid has work), a lane reads one unit of both sets
+// per step, four steps' loads issued before the first use.  No byte is unpacked: sum (a - b)^2 = sum a a + sum b b - 2 sum a b, three v_dot4_u32_u8 per dword
+// pair.  Range: a lane sees at most SSE_MAX_UNITS / 256 = 16 units, 64 dot products per accumulator, 64 * 260 100 < 2^25, and the workgroup's sum of squared
+// differences is at most SSE_MAX_UNITS * 16 * 65 025 = 4 261 478 400 < 2^32 -- the wavefronts' sums are 32-bit, the workgroup's and the plane's 64-bit (a
+// 3840x2160 plane of 0 against 255 is 5.4e11).  Integer adds only: the result does not depend on the schedule.
+constexpr int SSE_MAX_UNITS = 4096;  // 64 KB of each set per workgroup
+__device__ __forceinline__ void sse_unit(const uint4 x, const uint4 y, u32 &aa, u32 &bb, u32 &ab)
+{
+  aa = __builtin_amdgcn_udot4(x.x, x.x, aa, false); bb = __builtin_amdgcn_udot4(y.x, y.x, bb, false); ab = __builtin_amdgcn_udot4(x.x, y.x, ab, false);
+  aa = __builtin_amdgcn_udot4(x.y, x.y, aa, false); bb = __builtin_amdgcn_udot4(y.y, y.y, bb, false); ab = __builtin_amdgcn_udot4(x.y, y.y, ab, false);
+  aa = __builtin_amdgcn_udot4(x.z, x.z, aa, false); bb = __builtin_amdgcn_udot4(y.z, y.z, bb, false); ab = __builtin_amdgcn_udot4(x.z, y.z, ab, false);
+  aa = __builtin_amdgcn_udot4(x.w, x.w, aa, false); bb = __builtin_amdgcn_udot4(y.w, y.w, bb, false); ab = __builtin_amdgcn_udot4(x.w, y.w, ab, false);
+}
+__global__ void __launch_bounds__(256) dev_sse_kernel(const u8 *a, const u8 *b, const int W, const int H, const long frame_bytes, const int units_per_piece, unsigned long long *out)
+{
+  __shared__ u32 s_sum[4];
+  const int fp = blockIdx.y, frame = fp / 3, plane = fp - 3 * frame;
+  const long luma = (long)W * H, offset = frame * frame_bytes + (plane == 0 ? 0 : (plane == 1 ? luma : luma * 5 / 4));
+  const int units = (int)((plane ? luma >> 2 : luma) >> 4), per = plane ? units_per_piece >> 2 : units_per_piece;  // (a 16 320 x 16 320 plane is 16.6 M units)
+  const uint4 *pa = reinterpret_cast<const uint4 *>(a + offset), *pb = reinterpret_cast<const uint4 *>(b + offset);
+  const int begin = blockIdx.x * per, end = begin + per < units ? begin + per : units;
+  u32 aa = 0, bb = 0, ab = 0;
+  int i = begin + threadIdx.x;
+  for (; i + 768 < end; i += 1024) {
+    const uint4 x0 = pa[i], x1 = pa[i + 256], x2 = pa[i + 512], x3 = pa[i + 768];
+    const uint4 y0 = pb[i], y1 = pb[i + 256], y2 = pb[i + 512], y3 = pb[i + 768];
+    sse_unit(x0, y0, aa, bb, ab); sse_unit(x1, y1, aa, bb, ab); sse_unit(x2, y2, aa, bb, ab); sse_unit(x3, y3, aa, bb, ab);
+  }
+  for (; i < end; i += 256) sse_unit(pa[i], pb[i], aa, bb, ab);
+  const u32 v = group_sum<64>(aa + bb - 2 * ab);  // exact in 32 bits: the lane's own sum of squares, see above
+  if ((threadIdx.x & 63) == 0) s_sum[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0 && begin < units) atomicAdd(&out[fp], (unsigned long long)s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3]);
+}
+__global__ void __launch_bounds__(256) dev_copy_u64_kernel(const unsigned long long *src, unsigned long long *dst, const int n)
+{
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) dst[i] = src[i];
+}
+// out [n_frames x 3] must be zero when the first launch starts (the callers queue a hipMemsetAsync in front)
+inline void launch_sse(hipStream_t stream, const u8 *a, const u8 *b, int W, int H, int n_frames, unsigned long long *out)
+{
+  const long fb = (long)W * H * 3 / 2, luma_units = (long)W * H / 16;
+  // pieces of 64 KB; of 16 KB at least (one step of four loads per lane) while the grid is smaller than a few workgroups per CU: one picture fills the device too
+  int per = SSE_MAX_UNITS;
+  while (per > 1024 && 3L * n_frames * ((luma_units + per - 1) / per) < 2048) per >>= 1;
+  const unsigned pieces = (unsigned)((luma_units + per - 1) / per);
+  for (int f0 = 0; f0 < n_frames; f0 += 16384) {  // gridDim.y <= 65535
+    const int nf = n_frames - f0 < 16384 ? n_frames - f0 : 16384;
+    hipLaunchKernelGGL(dev_sse_kernel, dim3(pieces, (unsigned)(3 * nf)), dim3(256), 0, stream, a + (long)f0 * fb, b + (long)f0 * fb, W, H, fb, per, out + 3L * f0);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // SAO parameter decision (kvz_sao.hpp): statistics + context-free candidates, one workgroup per (LCU, plane) ...
 struct SaoGeom { int W, H, wl, hl; long frame_bytes; };
 __global__ void __launch_bounds__(256) dev_sao_stats_kernel(const u8 *src, const u8 *R, const u8 *V, const u8 *D, const SaoGeom g, SaoStats *stats, SaoCand *cand)
@@ -1868,6 +1924,57 @@ int kvz_hip_batch_checksums(kvz_hip_batch *b, uint32_t *host_out)
   KVZ_HIP_CHECK(hipFreeAsync(d, b->stream));
   KVZ_HIP_CHECK(hipStreamSynchronize(b->stream));
   return kvz::batch_check(b);
+}
+
+int kvz_hip_dev_picture_sse(const uint8_t *a, const uint8_t *b, int width, int height, int n_frames, uint64_t *out)
+{
+  if (!a || !b || !out || n_frames <= 0 || width <= 0 || height <= 0 || (width & 7) || (height & 7) || (((uintptr_t)a | (uintptr_t)b) & 15) || ((uintptr_t)out & 7)) {
+    fprintf(stderr, "kvz_hip_dev_picture_sse: bad argument\n");
+    return -1;
+  }
+  static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "the kernel's 64-bit atomic add");
+  KVZ_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)n_frames * 3 * sizeof(uint64_t), be().stream));
+  kvz::launch_sse(be().stream, a, b, width, height, n_frames, (unsigned long long *)out);
+  KVZ_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+int kvz_hip_batch_sse_async(kvz_hip_batch *b, uint64_t *host_out)
+{
+  if (!b || !host_out) { fprintf(stderr, "kvz_hip_batch_sse: bad argument\n"); return -1; }
+  kvz::batch_enter(b);
+  const size_t bytes = (size_t)b->n_frames * 3 * sizeof(uint64_t);
+  if (!b->d_sse) KVZ_HIP_CHECK(hipMalloc((void **)&b->d_sse, bytes));
+  if (b->up_pending) { KVZ_HIP_CHECK(hipStreamWaitEvent(b->stream, b->ev_up, 0)); b->up_pending = 0; }  // pictures on their way: this call comes after that upload, it sees them
+  KVZ_HIP_CHECK(hipMemsetAsync(b->d_sse, 0, bytes, b->stream));
+  kvz::launch_sse(b->stream, b->d_src, b->d_rec, b->F.W, b->F.H, b->n_frames, b->d_sse);
+  KVZ_HIP_CHECK(hipGetLastError());
+  kvz::batch_src_read(b);  // a later kvz_hip_batch_upload_all_async overwrites the source pictures behind this point
+  // Pinned memory is written by a kernel, not by the copy engine: in a chain of two batches this point comes right behind the OTHER batch's coder, whose slice data
+  // (13 ms per 1 536 1080p pictures) is on its way down then -- a device-to-host copy of these few KB would queue behind it, and this batch's coder behind the copy
+  hipPointerAttribute_t attr;
+  if (hipPointerGetAttributes(&attr, host_out) == hipSuccess && attr.type == hipMemoryTypeHost && attr.devicePointer) {
+    const int n = b->n_frames * 3;
+    hipLaunchKernelGGL(kvz::dev_copy_u64_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, b->stream, b->d_sse, (unsigned long long *)attr.devicePointer, n);
+    KVZ_HIP_CHECK(hipGetLastError());
+  } else {
+    (void)hipGetLastError();  // (an address the runtime does not know: plain host memory)
+    KVZ_HIP_CHECK(hipMemcpyAsync(host_out, b->d_sse, bytes, hipMemcpyDeviceToHost, b->stream));
+  }
+  return 0;
+}
+
+int kvz_hip_batch_sse(kvz_hip_batch *b, uint64_t *host_out)
+{
+  if (kvz_hip_batch_sse_async(b, host_out) != 0) return -1;
+  KVZ_HIP_CHECK(hipStreamSynchronize(b->stream));
+  return kvz::batch_check(b);
+}
+
+double kvz_hip_psnr(uint64_t sse, long num_pixels)
+{
+  if (sse == 0) return 999.99;  // encmain.c:107 MAX_PSNR
+  return 10.0 * log10(num_pixels * 65025.0 / sse);  // encmain.c:108, 142
 }
 
 }  // extern "C"

@@ -163,6 +163,25 @@ class InterPictures:
             raise RuntimeError("kvz_hip_dev_entropy_code_inter failed")
         return self._entropy_out[:total], sizes
 
+    def sse(self):
+        """-> uint64 array [n][3]: the exact sum of squared differences of the current source set against d_rec as it stands, Y, U, V (kvz_hip_dev_picture_sse).
+        After loop_filters() it is the distortion of the final picture, the one kvazaar's PSNR is of; call it before advance(), which swaps d_rec away"""
+        f = self.lib.kvz_hip_dev_picture_sse
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        d_out = self.dev.empty(self.n * 24)
+        try:
+            if f(self.d_src, self.d_rec, self.w, self.h, self.n, d_out) != 0:
+                raise RuntimeError("kvz_hip_dev_picture_sse: bad argument")
+            return self.dev.get(d_out, (self.n, 3), np.uint64)
+        finally:
+            self.dev.free(d_out)
+
+    def psnr(self):
+        """-> float64 array [n][3]: PSNR Y, U, V of the pictures just encoded as kvazaar computes it"""
+        from .batch import psnr_of_planes
+        return psnr_of_planes(self.lib, self.sse(), self.w, self.h)
+
     def advance(self):
         """the pictures just encoded (after their loop filters) and their CU records become the references of the next picture"""
         self.d_ref, self.d_rec = self.d_rec, self.d_ref
