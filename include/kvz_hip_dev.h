@@ -159,7 +159,9 @@ typedef struct kvz_hip_inter_params {
    * records): motion vectors may leave the tile (search_inter.c:94-187: mv-constraint none), reference samples are read at tile offset + position and replicated at the
    * FRAME's edges (inter.c:80-81, search_inter.c:217-218), the co-located record of the search's starting point likewise (search_inter.c:1286-1287).  The temporal merge /
    * AMVP candidates are read at the TILE-LOCAL position of the frame's array and checked against the frame's size, as the reference does (inter.c:836-905 takes x, y of
-   * the tile and encoder_control->in.width).  All zero: the picture is the frame. */
+   * the tile and encoder_control->in.width).  All zero: the picture is the frame.
+   * Sizes (-1 otherwise, before anything is launched): width, height, ref_width, ref_height multiples of 8 up to 16320 (255 CTUs), and fewer than 2^23 4x4 units in the
+   * picture and in the reference frame (16320x8192 is covered, 16320x8256 is not): the pass addresses CU records with 24-bit multiplies. */
   int32_t ref_width, ref_height, tile_x, tile_y;
   int32_t no_tmvp;             /* !cfg.tmvp_enable: no temporal merge / AMVP candidates (inter.c:1295-1302, 1471-1476) -- kvazaar switches TMVP off whenever tiles are used (cfg.c:920-975) */
 } kvz_hip_inter_params;

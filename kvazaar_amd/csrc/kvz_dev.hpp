@@ -1379,14 +1379,13 @@ int kvz_hip_dev_inter_ctu_pass_tiles(const uint8_t *src, const uint8_t *ref, con
     fprintf(stderr, "kvz_hip_dev_inter_ctu_pass: kvz_hip_inter_params.struct_size %u is not this library's %zu (zero the struct, set struct_size = sizeof, build against the library's headers)\n", p ? p->struct_size : 0u, sizeof(kvz_hip_inter_params));
     return -1;
   }
-  if (!p || width <= 0 || height <= 0 || (width & 7) || (height & 7) || width > 64 * 255 || height > 64 * 255 || n_pictures > 65535) { fprintf(stderr, "kvz_hip_dev_inter_ctu_pass: bad geometry\n"); return -1; }
+  const int refused = kvz::inter_pass_geometry_refused(width, height, n_pictures, p->ref_width, p->ref_height, p->tile_x, p->tile_y);
+  if (refused == 1) { fprintf(stderr, "kvz_hip_dev_inter_ctu_pass: bad geometry\n"); return -1; }
   if (p->qp < 0 || p->qp > 51) { fprintf(stderr, "kvz_hip_dev_inter_ctu_pass: picture QP %d outside 0..51\n", p->qp); return -1; }
   if (p->fme_level < 0 || p->fme_level > 4 || p->pu_depth_inter_max < 1 || p->pu_depth_inter_max > 3 || p->poc < 1 || p->fast_residual_cost < 0 || p->fast_residual_cost > 51) { fprintf(stderr, "kvz_hip_dev_inter_ctu_pass: unsupported parameters\n"); return -1; }
-  if (p->ref_width || p->ref_height) {  // the pictures are tiles of a ref_width x ref_height frame
-    if ((p->ref_width & 7) || (p->ref_height & 7) || p->tile_x < 0 || p->tile_y < 0 || (p->tile_x & 7) || (p->tile_y & 7) || p->tile_x + width > p->ref_width || p->tile_y + height > p->ref_height) {
-      fprintf(stderr, "kvz_hip_dev_inter_ctu_pass: the %dx%d tile at (%d, %d) does not lie in the %dx%d reference frame\n", width, height, p->tile_x, p->tile_y, p->ref_width, p->ref_height);
-      return -1;
-    }
+  if (refused) {  // the pictures are tiles of a ref_width x ref_height frame
+    fprintf(stderr, "kvz_hip_dev_inter_ctu_pass: the %dx%d tile at (%d, %d) does not lie in the %dx%d reference frame, or that frame is beyond what the pass addresses\n", width, height, p->tile_x, p->tile_y, p->ref_width, p->ref_height);
+    return -1;
   }
   hipStream_t st = be().stream;
   const int wc = (width + 63) / 64, hc = (height + 63) / 64, ctus = wc * hc;

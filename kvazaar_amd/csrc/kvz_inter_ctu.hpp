@@ -56,9 +56,23 @@ static long g_ic_phases[32]; static int g_ic_cat = 31;
 #define KVZ_LDS
 #define KVZ_GLB
 #define IC_WGVAR static
-static inline int mul24(int a, int b) { return a * b; }
-static inline unsigned umul24(unsigned a, unsigned b) { return a * b; }
-static inline int mul24v(int a, int b) { return a * b; }
+// the 24-bit multiplies as the device executes them (v_mul_i32_i24 / v_mul_u32_u24): both operands cut to their low 24 bits (sign-extended / masked), the low 32 bits
+// of the product.  An operand that does not fit is counted: a call site whose "fits in 24 bits" comment is wrong shows here, not only on the device
+static unsigned long long g_mul24_violations;
+static inline int sext24(int a) { return (int)(((unsigned)a & 0xffffffu) ^ 0x800000u) - 0x800000; }
+static inline int mul24(int a, int b)
+{
+  const int a24 = sext24(a), b24 = sext24(b);
+  g_mul24_violations += (a24 != a) + (b24 != b);
+  return (int)(unsigned)((long long)a24 * b24);
+}
+static inline unsigned umul24(unsigned a, unsigned b)
+{
+  const unsigned a24 = a & 0xffffffu, b24 = b & 0xffffffu;
+  g_mul24_violations += (a24 != a) + (b24 != b);
+  return (unsigned)((unsigned long long)a24 * b24);
+}
+static inline int mul24v(int a, int b) { return mul24(a, b); }
 #else
 // a 32-bit multiply is a quarter-rate instruction, the 24-bit one a full-rate one: rows, strides, cell indices and the div_by products all fit
 __device__ __forceinline__ int mul24(int a, int b) { return __mul24(a, b); }
@@ -451,6 +465,8 @@ struct InterCtu {
   }
   // the CU info of luma position (fx, fy), which lies outside the CU under evaluation (a neighbour: every caller asks for one): inside this CTU the decided picture's
   // record -- a finished CU looks the same from every level --, else the frame's (finished CTUs)
+  // LIMIT: the cell index is a signed 24-bit operand of the second multiply, so a picture (and, in cand_fetch, a reference frame) has fewer than 2^23 4x4 cells --
+  // inter_pass_geometry_refused (kvz_inter_host.hpp) refuses larger ones before anything is launched
   IC_DEV CuInfo cell_at(int fx, int fy)
   {
     IC_COUNT(17);

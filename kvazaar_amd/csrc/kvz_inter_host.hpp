@@ -41,6 +41,24 @@ inline void b_slice_residual_init_values(uint8_t v[KVZ_HIP_CX_ABS_CHROMA + 2 - K
   for (int i = 0; i < 2; i++) v[KVZ_HIP_CX_ABS_CHROMA - b + i] = absf[4 + i];
 }
 
+// The geometry kvz_hip_dev_inter_ctu_pass[_tiles] covers: pictures of whole 8x8 blocks up to 255 CTUs a side (the ticket packs the CTU column and row into a byte each),
+// and -- ref_w / ref_h non-zero: the pictures are tiles of that frame -- a tile that lies in its reference frame on the 8-sample grid.  The kernel addresses CU
+// records with 24-bit multiplies, (cell index) * sizeof(CuInfo) in InterCtu::cell_at and cand_fetch: the signed 24-bit operand holds a cell index below 2^23, so a
+// picture or a reference frame of 2^23 or more 4x4 cells is refused, as is a reference frame beyond the 64 * 255 samples a picture may have.  0 = covered
+inline int inter_pass_geometry_refused(int width, int height, int n_pictures, int ref_w, int ref_h, int tile_x, int tile_y)
+{
+  const int max_side = 64 * 255;
+  const long max_cells = 1l << 23;
+  if (width <= 0 || height <= 0 || (width & 7) || (height & 7) || width > max_side || height > max_side || n_pictures > 65535) return 1;
+  if ((long)(width / 4) * (height / 4) >= max_cells) return 1;
+  if (ref_w || ref_h) {
+    if (ref_w <= 0 || ref_h <= 0 || (ref_w & 7) || (ref_h & 7) || ref_w > max_side || ref_h > max_side) return 2;
+    if (tile_x < 0 || tile_y < 0 || (tile_x & 7) || (tile_y & 7) || tile_x + width > ref_w || tile_y + height > ref_h) return 2;
+    if ((long)(ref_w / 4) * (ref_h / 4) >= max_cells) return 2;
+  }
+  return 0;
+}
+
 inline void inter_model_init(InterModel *m, int qp, int poc, uint64_t coeff_weights, const float fbits[128], int mv_constraint, int sao, int deblock, int fme_level,
                              int pu_depth_inter_max, int no_wpp, int fast_residual_cost, int pic_w = 0, int pic_h = 0, int ref_w = 0, int ref_h = 0, int tile_x = 0, int tile_y = 0, int no_tmvp = 0)
 {

@@ -210,6 +210,17 @@ extern "C" void kvz_hostsim_inter_predict(int width, int height, const uint8_t *
   }
   free(slab);
 }
+// the 24-bit multiplies of the inter pass (kvz_inter_ctu.hpp mul24 / umul24 / mul24v, modelled as the device executes them): operands that did not fit in 24 bits
+// since the last reset, the stand-ins themselves for their unit test, and the geometry check of kvz_hip_dev_inter_ctu_pass[_tiles] (0 = accepted)
+extern "C" unsigned long long kvz_hostsim_mul24_violations(void) { return kvz::g_mul24_violations; }
+extern "C" void kvz_hostsim_mul24_reset(void) { kvz::g_mul24_violations = 0; }
+extern "C" int kvz_hostsim_mul24(int a, int b) { return kvz::mul24(a, b); }
+extern "C" int kvz_hostsim_mul24v(int a, int b) { return kvz::mul24v(a, b); }
+extern "C" unsigned kvz_hostsim_umul24(unsigned a, unsigned b) { return kvz::umul24(a, b); }
+extern "C" int kvz_hostsim_inter_geometry_refused(int width, int height, int n_pictures, int ref_w, int ref_h, int tile_x, int tile_y)
+{
+  return kvz::inter_pass_geometry_refused(width, height, n_pictures, ref_w, ref_h, tile_x, tile_y);
+}
 #ifdef KVZ_ICTU_COUNT_PHASES
 extern "C" void kvz_hostsim_inter_phases(long *out) { for (int i = 0; i < 32; i++) { out[i] = kvz::g_ic_phases[i]; kvz::g_ic_phases[i] = 0; } }
 #endif

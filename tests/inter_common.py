@@ -144,7 +144,8 @@ def first_difference(a, b, fields=("type", "depth", "skipped", "merged", "merge_
     return None
 
 
-# (name, width, height, frames, qp, preset, deblock, sao, owf, clip) -- clip = ("motion", seed, noise, pan) of clip() above or ("synth", seed, kind) of kvazaar_amd/synth.py.
+# (name, width, height, frames, qp, preset, deblock, sao, owf, clip) -- clip = ("motion", seed, noise, pan) of clip() above, ("hard", seed, kind, pan) of hard_clip() below
+# or ("synth", seed, kind) of kvazaar_amd/synth.py.
 # tests/golden/inter_recon.json holds, per case, the REFERENCE encoder's digests (reconstruction per picture, CU decisions per picture, its bitstream's md5)
 CASES = [
     ("pan", 200, 136, 4, 22, "veryfast", 1, 1, 0, ("motion", 5, 1.5, (1.25, -0.5))),
@@ -169,7 +170,17 @@ CASES = [
     # motion compensation at its int16 edge (mc_overflow_clip): the luma (2, 2) phase on its maximising window, where the 14-bit sample is 33150
     ("mc-overflow", 200, 136, 3, 22, "veryfast", 1, 1, 0, ("mc-overflow", 5, 1.5, 16)),
     ("ultrafast-mc-overflow", 200, 136, 3, 22, "ultrafast", 1, 0, 0, ("mc-overflow", 5, 1.5, 16)),  # no fractional search: whole-sample luma vectors only (asserted)
+    # the ends of what the API accepts, pinned with the reference encoder's digests: --qp 0 (I picture at QP 0, B pictures from 2 on) and --qp 51 (every picture at 51),
+    # `faster` with its B pictures at 51, a picture smaller than one CTU, and per-sample 0 / 255 content under a whole-sample pan
+    ("qp0", 200, 136, 3, 0, "veryfast", 1, 1, 0, ("motion", 41, 1.5, (1.25, -0.5))),
+    ("qp51", 200, 136, 3, 51, "veryfast", 1, 1, 0, ("motion", 42, 2.0, (-2.0, 1.0))),
+    ("faster-owf-qp49", 200, 136, 3, 49, "faster", 1, 1, 2, ("motion", 43, 1.5, (0.75, 1.5))),
+    ("smooth-40x24", 40, 24, 4, 27, "veryfast", 1, 1, 0, ("hard", 44, "smooth", (1.5, -0.75))),
+    ("binary-pan-qp12", 136, 72, 3, 12, "veryfast", 1, 1, 0, ("hard", 45, "binary", (3.0, -2.0))),
 ]
+
+QP_END_CASES = ["qp0", "qp51", "faster-owf-qp49"]
+SMALL_AND_HARD_CASES = ["smooth-40x24", "binary-pan-qp12"]
 
 # the cases whose encodes must put a one-list PU with a (2, 2) vector on a window whose 14-bit sample leaves int16 (overflowing_uni_pus)
 MC_OVERFLOW_CASES = ["mc-overflow"]
@@ -179,7 +190,7 @@ MC_WHOLE_SAMPLE_CASES = ["ultrafast-mc-overflow"]
 
 # the cases whose slice data is pinned (tests/golden/entropy_inter.json): picture QPs on both sides of fast-residual-cost 28, SAO on / off, the wavefront MV restriction, `faster`
 ENTROPY_CASES = ["pan", "ultrafast", "vertical-pan-owf", "static-qp17", "two-gops", "no-loop-filters", "deblock-only", "survey-416x240", "noisy-qp27", "cabac-coeff-cost-qp32",
-                 "faster-pan", "faster-qp32", "ultrafast-8mod16"]
+                 "faster-pan", "faster-qp32", "ultrafast-8mod16"] + QP_END_CASES + SMALL_AND_HARD_CASES
 
 # ... and BASELINE config 4 at its own size: fixture entry only (bench.py's leg and the GPU test check the device against it)
 ENTROPY_BENCH_CASES = ["baseline-c4-2160p"]
@@ -228,6 +239,8 @@ def case_frames(case):
         return clip(w, h, n, src[1], src[2], src[3])
     if src[0] == "mc-overflow":
         return mc_overflow_clip(w, h, n, src[1], src[2], src[3])
+    if src[0] == "hard":
+        return hard_clip(src[2], w, h, n, src[1], src[3])
     import kvazaar_amd.synth as synth
     return [np.concatenate([p.reshape(-1) for p in f]) for f in synth.frames(w, h, n, src[1], src[2])]
 
@@ -361,13 +374,20 @@ def oracle_sequence_for_entropy(oracle, case):
     """everything the device's B-picture coder needs of a sequence, from the oracle: per picture the final CU records, the levels of every CTU, the SAO decisions
     (kvz_hip_sao_params arrays + merge) and the picture QPs"""
     name, w, h, n, qp, preset, dbk, sao, owf, src = case
+    return oracle_encode_parts(oracle, w, h, case_frames(case), qp, preset=preset, deblock=bool(dbk), sao=bool(sao), mv_constraint=owf > 0)
+
+
+def oracle_encode_parts(oracle, w, h, frames, qp, preset="veryfast", deblock=True, sao=None, mv_constraint=False, gop=(4, 3), no_wpp=False, overrides=None):
+    """kvz_oracle_lowdelay_encode_parts with the arguments of oracle_encode"""
+    n = len(frames)
     p = dict(PRESETS[preset])
-    p["sao"] = int(sao)
-    cfg = LowdelayCfg(qp=qp, gop_len=4, gop_depth=3, intra_period=64, deblock=int(dbk), mv_constraint=int(owf > 0), no_wpp=0, ra8_qp_model=1, **p)
+    p.update(overrides or {})
+    if sao is not None:
+        p["sao"] = int(sao)
+    cfg = LowdelayCfg(qp=qp, gop_len=gop[0], gop_depth=gop[1], intra_period=64, deblock=int(deblock), mv_constraint=int(mv_constraint), no_wpp=int(no_wpp), ra8_qp_model=1, **p)
     mc = cc.model_constants()
     fb = (C.c_float * 128)(*mc["entropy_fbits"])
     wts = (C.c_uint64 * 52)(*[int(mc["coeff_weights"][str(q)]) for q in range(52)])
-    frames = case_frames(case)
     fs, cells, ctus = w * h * 3 // 2, (w // 4) * (h // 4), ((w + 63) // 64) * ((h + 63) // 64)
     src_all = np.ascontiguousarray(np.concatenate(frames))
     cu = np.zeros(n * cells, CU_DTYPE)
@@ -381,3 +401,114 @@ def oracle_sequence_for_entropy(oracle, case):
       merge.ctypes.data, qps.ctypes.data)
     return dict(cu=cu.reshape(n, cells), coeff=coeff.reshape(n, ctus * 6144), sao_luma=sao_l.reshape(n, ctus, 15), sao_chroma=sao_c.reshape(n, ctus, 15),
                 merge=merge.reshape(n, ctus), qps=qps, ctus=ctus)
+
+
+# ---- the fuzz of the inter path: one drawing function for the CPU tools (tools/fuzz_inter_oracle.py against the reference encoder, tools/fuzz_inter.py: host simulation
+# against the oracle) and the device (tests/test_gpu_inter_fuzz.py), so that all three meet the same distribution ----
+FUZZ_CONTENT = ("motion", "binary", "blocks", "noise", "flat", "smooth")
+FUZZ_GOPS = ((4, 3), (8, 4), (2, 2), (3, 2))
+
+
+def hard_clip(kind, w, h, n, seed, pan):
+    """n frames (Y|U|V bytes each) of content where SAD / SATD / SSD sums, levels and escape codes are largest, under a global pan (whole- or sub-sample, bilinear;
+    the padded planes wrap around) so that motion search has something to find.  kind: "binary" every sample 0 or 255, "blocks" 0 / 255 in 4x4 blocks, "noise"
+    uniform 0..255, "flat" every sample 0, 128 or 255 (by seed), "smooth" a sine texture over the whole 0..255 range"""
+    rng = np.random.default_rng(seed)
+    planes = []
+    for c in range(3):
+        H2, W2 = (h + 64) >> (c > 0), (w + 64) >> (c > 0)
+        if kind == "binary":
+            p = 255.0 * rng.integers(0, 2, (H2, W2))
+        elif kind == "blocks":
+            p = 255.0 * np.kron(rng.integers(0, 2, ((H2 + 3) // 4, (W2 + 3) // 4)), np.ones((4, 4)))[:H2, :W2]
+        elif kind == "noise":
+            p = rng.integers(0, 256, (H2, W2)).astype(np.float64)
+        elif kind == "flat":
+            p = np.full((H2, W2), float((0, 128, 255)[seed % 3]))
+        elif kind == "smooth":
+            yy, xx = np.mgrid[0:H2, 0:W2].astype(np.float64) * (2 if c else 1)
+            ph = rng.uniform(0, 6.28, 3)
+            p = 127.5 + 100 * np.sin(xx / 7.0 + ph[0]) * np.cos(yy / 11.0 + ph[1]) + 60 * np.sin((xx - 3 * yy) / 23.0 + ph[2])
+        else:
+            raise ValueError(kind)
+        planes.append(p)
+
+    def shift(p, dx, dy):
+        ix, iy = int(np.floor(dx)), int(np.floor(dy))
+        fx, fy = dx - ix, dy - iy
+        q = np.roll(p, (-iy, -ix), (0, 1))
+        q = (1 - fx) * q + fx * np.roll(q, -1, 1)
+        return (1 - fy) * q + fy * np.roll(q, -1, 0)
+
+    out = []
+    for i in range(n):
+        fr = []
+        for c, p in enumerate(planes):
+            s, o = (2.0, 16) if c else (1.0, 32)
+            q = shift(p, pan[0] * i / s, pan[1] * i / s)[o:o + (h >> (c > 0)), o:o + (w >> (c > 0))]
+            fr.append(np.clip(np.rint(q), 0, 255).astype(np.uint8).reshape(-1))
+        out.append(np.concatenate(fr))
+    return out
+
+
+def draw_fuzz_case(rng, max_frames=3):
+    """one round of the inter fuzz: picture size (any multiple of 8 from 8 to 264, a good third of the draws below 64 in one or both dimensions, some 8 wide or high),
+    content, --qp 0..51, preset, GOP, switches and the options that differ from the preset's.  Only what the passes cover is drawn: nothing is filtered afterwards"""
+    regime = int(rng.integers(0, 5))
+    w, h = int(rng.integers(1, 34)) * 8, int(rng.integers(1, 34)) * 8
+    if regime == 0:
+        w, h = int(rng.integers(1, 8)) * 8, int(rng.integers(1, 8)) * 8
+    elif regime == 1:
+        if rng.integers(0, 2):
+            w = int(rng.integers(1, 8)) * 8
+        else:
+            h = int(rng.integers(1, 8)) * 8
+    if rng.integers(0, 12) == 0:
+        if rng.integers(0, 2):
+            w = 8
+        else:
+            h = 8
+    kinds = [k for k in FUZZ_CONTENT if k != "motion" or (w > 40 and h > 40)]  # clip()'s rectangles draw from w - 40, h - 40
+    kind = kinds[int(rng.integers(0, len(kinds)))]
+    n = int(rng.integers(2, max_frames + 1))
+    qp = int(rng.integers(0, 52))
+    preset = ("ultrafast", "superfast", "veryfast", "faster")[int(rng.integers(0, 4))]
+    dbk, sao, no_wpp = int(rng.integers(0, 2)), int(rng.integers(0, 2)), int(rng.integers(0, 4) == 0)
+    ref_owf = 2 * int(rng.integers(0, 2))               # the reference encoder's --owf
+    owf = int(ref_owf > 0 and not no_wpp)               # the motion restriction is cfg.owf && cfg.wpp
+    gop = FUZZ_GOPS[int(rng.integers(0, len(FUZZ_GOPS)))] if rng.integers(0, 5) else (4, 3)
+    seed = int(rng.integers(1, 1 << 30))
+    speed = float(rng.choice([3, 9, 9]))
+    pan = (float(rng.uniform(-speed, speed)), float(rng.uniform(-speed, speed)))
+    if rng.integers(0, 2):
+        pan = (float(round(pan[0])), float(round(pan[1])))  # whole-sample pan: binary content stays binary
+    noise = float(rng.uniform(0, 3))
+    ov = {}  # options that differ from the preset's: --subme 0..4, --fast-residual-cost
+    if rng.integers(0, 3) == 0:
+        ov["fme_level"] = int(rng.integers(0, 5))
+    if rng.integers(0, 3) == 0:
+        ov["fast_residual_cost"] = int(rng.choice([0, 20, 28, 35, 51]))
+    return dict(w=w, h=h, n=n, qp=qp, preset=preset, deblock=dbk, sao=sao, no_wpp=no_wpp, owf=owf, ref_owf=ref_owf, gop=gop, kind=kind, seed=seed, pan=pan, noise=noise, overrides=ov)
+
+
+def fuzz_frames(c, seed=None):
+    seed = c["seed"] if seed is None else seed
+    if c["kind"] == "motion":
+        return clip(c["w"], c["h"], c["n"], seed, c["noise"], c["pan"])
+    return hard_clip(c["kind"], c["w"], c["h"], c["n"], seed, c["pan"])
+
+
+def fuzz_options(c):
+    """the search options of a drawn case: the preset's with the overrides"""
+    p = dict(PRESETS[c["preset"]])
+    p.update(c["overrides"])
+    return p
+
+
+def fuzz_oracle_kwargs(c):
+    return dict(preset=c["preset"], deblock=bool(c["deblock"]), sao=bool(c["sao"]), mv_constraint=bool(c["owf"]), gop=c["gop"], no_wpp=bool(c["no_wpp"]), overrides=c["overrides"])
+
+
+def describe_fuzz_case(c):
+    return "%dx%d x %d %s %s lp-g%dd%d qp %d dbk %d sao %d owf %d no_wpp %d %s pan (%.2f, %.2f)" % (
+        c["w"], c["h"], c["n"], c["kind"], c["preset"], c["gop"][0], c["gop"][1], c["qp"], c["deblock"], c["sao"], c["owf"], c["no_wpp"], c["overrides"], c["pan"][0], c["pan"][1])

@@ -2,6 +2,7 @@
 torch.distributed.run, exercised with the oracle as the per-rank worker.  Property: the CTU pass over a clip is the
 same whether one process does all frames or two ranks do half each (frames are independent), checked through a
 checksum of per-frame checksums gathered across ranks."""
+import ctypes
 import hashlib
 import os
 import socket
@@ -216,9 +217,13 @@ def _tiled_inter_worker(rank, world, port, clip, out):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)
     sim = tc.load_hostsim()
+    sim.kvz_hostsim_mul24_violations.restype = ctypes.c_ulonglong
+    sim.kvz_hostsim_mul24_reset()
     pictures, records = tc.tiled_inter_chain(clip, rank, world, dist, tc.hostsim_tile_pass(sim), sim)
+    violations = torch.tensor([int(sim.kvz_hostsim_mul24_violations())], dtype=torch.int64)  # operands of the pass's 24-bit multiplies that did not fit, of all ranks
+    dist.all_reduce(violations)
     if rank == 0:
-        out.put(ic.digests(pictures, records))
+        out.put(dict(ic.digests(pictures, records), violations=int(violations[0])))
     dist.destroy_process_group()
 
 
@@ -254,6 +259,7 @@ def test_two_rank_tiled_inter_chain_equals_reference_encoder(clip):
     assert got is not None, "a rank failed"
     assert got["rec"] == want["rec"], "final pictures differ from the reference encoder's"
     assert got["cu"] == want["cu"], "CU decisions differ from the reference encoder's"
+    assert got["violations"] == 0, "a 24-bit multiply of the pass met an operand that does not fit"
 
 
 def test_bench_gpus_2_self_launch_starts_two_ranks():

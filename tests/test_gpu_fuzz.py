@@ -55,7 +55,7 @@ def test_hip_medium_ctu_pass_fuzz_equals_oracle(oracle):
     bad = []
     for i in range(24):
         w, h = int(rng.integers(1, 18)) * 8, int(rng.integers(1, 14)) * 8
-        qp = int(rng.choice([7, 12, 17, 22, 27, 32, 37, 42]))
+        qp = int(rng.choice([0, 7, 12, 17, 22, 27, 32, 37, 42, 47, 51]))
         rdoq, s32, nxn = int(rng.integers(0, 4) > 0), int(rng.integers(0, 4) > 0), int(rng.integers(0, 4) > 0)
         if not (rdoq or nxn):
             rdoq = 1  # at least one of the switches that select this kernel

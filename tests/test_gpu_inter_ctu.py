@@ -23,6 +23,7 @@ FAST_COST_CASES = ["pan", "ultrafast", "vertical-pan-owf", "static-qp17", "no-lo
 CABAC_COST_CASES = ["noisy-qp27", "cabac-coeff-cost-qp32", "fast-pan-owf-qp37", "ultrafast-fast-pan-owf-qp30"]     # picture QPs from 28 on: the residual coder in counting mode
 EDGE_CASES = ["ultrafast-8mod16", "superfast-8mod16-qp33"]  # 8x8 inter CUs where the picture edge forces the split below pu-depth-inter's 16x16 (search.c:702-713)
 FASTER_CASES = ["faster-pan", "faster-qp32", "faster-owf-qp27"]  # `--preset faster`: quarter-sample steps in the fractional search, CABAC coefficient cost at every QP
+END_CASES = ic.QP_END_CASES + ic.SMALL_AND_HARD_CASES  # --qp 0 / 51 / `faster` at 49, a 40x24 picture, per-sample 0 / 255 content
 MC_EDGE_CASES = ["mc-overflow", "ultrafast-mc-overflow"]  # motion compensation where the 14-bit sample leaves int16 (inter_common.mc_overflow_clip)
 
 
@@ -48,7 +49,7 @@ def hostsim_lib():
 
 
 @pytest.mark.parametrize("name", ["pan", "ultrafast", "vertical-pan-owf", "no-loop-filters", "noisy-qp27", "cabac-coeff-cost-qp32", "fast-pan-owf-qp37", "ultrafast-fast-pan-owf-qp30",
-                                  "faster-pan", "faster-qp32", "faster-owf-qp27", "ultrafast-8mod16", "superfast-8mod16-qp33"] + MC_EDGE_CASES)
+                                  "faster-pan", "faster-qp32", "faster-owf-qp27", "ultrafast-8mod16", "superfast-8mod16-qp33"] + MC_EDGE_CASES + END_CASES)
 def test_host_simulation_of_the_device_program_equals_the_oracle(oracle, hostsim_lib, name):
     case = [c for c in ic.CASES if c[0] == name][0]
     _, w, h, n, qp, preset, dbk, sao, owf, src = case
@@ -61,6 +62,7 @@ def test_host_simulation_of_the_device_program_equals_the_oracle(oracle, hostsim
     f.restype = None
     f.argtypes = [C.c_int] * 4 + [C.c_uint64, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p] * 5
     p = ic.PRESETS[preset]
+    hostsim_lib.kvz_hostsim_mul24_reset()
     for k in range(1, n):
         rec = np.zeros(w * h * 3 // 2, np.uint8)
         out = np.zeros((h // 4, w // 4), ic.CU_DTYPE)
@@ -68,6 +70,88 @@ def test_host_simulation_of_the_device_program_equals_the_oracle(oracle, hostsim
           np.ascontiguousarray(frames[k]).ctypes.data, np.ascontiguousarray(rf[k - 1]).ctypes.data, np.ascontiguousarray(cu[k - 1]).ctypes.data, rec.ctypes.data, out.ctypes.data)
         assert ic.first_difference(out[None], cu[k][None]) is None, k
         assert np.array_equal(rec, rs[k]), k
+    assert mul24_violations(hostsim_lib) == 0  # every operand of the pass's 24-bit multiplies fitted: the device's v_mul_i32_i24 / v_mul_u32_u24 compute the same
+
+
+def mul24_violations(sim):
+    sim.kvz_hostsim_mul24_violations.restype = C.c_ulonglong
+    return int(sim.kvz_hostsim_mul24_violations())
+
+
+@pytest.mark.parametrize("name", ["survey-1080p", "baseline-c4-2160p"])
+def test_host_simulation_at_the_benchmarked_sizes_keeps_the_24_bit_multiplies_in_range(oracle, hostsim_lib, name):
+    """the first B picture of the two large sequences through the simulated device program: the operands that grow with the picture (rows x stride, cell index x record
+    size, the div_by products) at the sizes the project benchmarks -- equal to the oracle, and no operand beyond 24 bits"""
+    case = [c for c in ic.CASES if c[0] == name][0]
+    _, w, h, n, qp, preset, dbk, sao, owf, src = case
+    frames = ic.case_frames(case)[:2]
+    rs, rf, cu, qps = ic.oracle_encode(oracle, w, h, frames, qp, preset=preset, deblock=bool(dbk), sao=bool(sao), mv_constraint=owf > 0)
+    mc = cc.model_constants()
+    fb = np.array(mc["entropy_fbits"], np.float32)
+    f = hostsim_lib.kvz_hostsim_inter_frame
+    f.restype = None
+    f.argtypes = [C.c_int] * 4 + [C.c_uint64, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p] * 5
+    p = ic.PRESETS[preset]
+    hostsim_lib.kvz_hostsim_mul24_reset()
+    rec = np.zeros(w * h * 3 // 2, np.uint8)
+    out = np.zeros((h // 4, w // 4), ic.CU_DTYPE)
+    f(w, h, int(qps[1]), 1, int(mc["coeff_weights"][str(int(qps[1]))]), fb.ctypes.data, int(owf > 0), int(sao), int(dbk), p["fme_level"], p["pu_depth_inter_max"], 0, p["fast_residual_cost"],
+      np.ascontiguousarray(frames[1]).ctypes.data, np.ascontiguousarray(rf[0]).ctypes.data, np.ascontiguousarray(cu[0]).ctypes.data, rec.ctypes.data, out.ctypes.data)
+    assert ic.first_difference(out[None], cu[1][None]) is None
+    assert np.array_equal(rec, rs[1])
+    assert mul24_violations(hostsim_lib) == 0
+
+
+def test_host_simulation_models_the_24_bit_multiplies(hostsim_lib):
+    """mul24 / mul24v / umul24 of the host simulation against Python integers: operands cut to 24 bits (sign-extended / masked), the low 32 bits of the product --
+    what v_mul_i32_i24 / v_mul_u32_u24 compute -- and every operand that did not fit counted"""
+    sim = hostsim_lib
+    for g in (sim.kvz_hostsim_mul24, sim.kvz_hostsim_mul24v):
+        g.restype, g.argtypes = C.c_int32, [C.c_int32, C.c_int32]
+    sim.kvz_hostsim_umul24.restype, sim.kvz_hostsim_umul24.argtypes = C.c_uint32, [C.c_uint32, C.c_uint32]
+
+    def sext(v, bits):
+        v &= (1 << bits) - 1
+        return v - (1 << bits) if v >> (bits - 1) else v
+    edges = [0, 1, -1, 22, 4080, 16320, 65535, -(1 << 23), (1 << 23) - 1, 1 << 23, (1 << 24) - 1, 1 << 24, (1 << 24) + 5, -(1 << 23) - 1, -(1 << 24), (1 << 31) - 1, -(1 << 31)]
+    beyond_32_bits = 0
+    for a in edges:
+        for b in edges:
+            sim.kvz_hostsim_mul24_reset()
+            exact = sext(a, 24) * sext(b, 24)
+            beyond_32_bits += int(not -(1 << 31) <= exact < (1 << 31))
+            assert sim.kvz_hostsim_mul24(a, b) == sext(exact, 32), (a, b)
+            assert sim.kvz_hostsim_mul24v(a, b) == sext(exact, 32), (a, b)
+            assert mul24_violations(sim) == 2 * (int(sext(a, 24) != a) + int(sext(b, 24) != b)), (a, b)
+            if a >= 0 and b >= 0:
+                sim.kvz_hostsim_mul24_reset()
+                assert sim.kvz_hostsim_umul24(a, b) == ((a & 0xffffff) * (b & 0xffffff)) & 0xffffffff, (a, b)
+                assert mul24_violations(sim) == int(a >> 24 != 0) + int(b >> 24 != 0), (a, b)
+    assert beyond_32_bits > 10
+    # where the operands fit and the product does, the model is the plain multiply
+    sim.kvz_hostsim_mul24_reset()
+    assert sim.kvz_hostsim_mul24(2159, 3840) == 2159 * 3840 and sim.kvz_hostsim_mul24(-3, 16320) == -3 * 16320 and sim.kvz_hostsim_umul24(1000, (1 << 20) // 3 + 1) == 1000 * ((1 << 20) // 3 + 1)
+    assert sim.kvz_hostsim_umul24((1 << 24) - 1, (1 << 20) + 1) == (((1 << 24) - 1) * ((1 << 20) + 1)) & 0xffffffff  # a product beyond 2^32: its low half
+    assert mul24_violations(sim) == 0
+
+
+def test_inter_pass_geometry_check_at_its_borders(hostsim_lib):
+    """inter_pass_geometry_refused (kvz_inter_host.hpp), the check kvz_hip_dev_inter_ctu_pass[_tiles] makes before it launches anything: InterCtu::cell_at and cand_fetch
+    multiply a cell index by the record size with the signed 24-bit multiply, so a picture or a reference frame of 2^23 or more 4x4 cells is refused, and a reference frame
+    may be no larger than a picture may be (255 CTUs a side)"""
+    g = hostsim_lib.kvz_hostsim_inter_geometry_refused
+    g.restype, g.argtypes = C.c_int, [C.c_int] * 7
+    assert (16320 // 4) * (8256 // 4) >= 1 << 23 > (16320 // 4) * (8192 // 4)
+    for (w, h) in ((16320, 8192), (8192, 16320), (8192, 4320), (3840, 2160), (8, 8), (11584, 11576)):
+        assert g(w, h, 1, 0, 0, 0, 0) == 0, (w, h)
+        assert g(8, 8, 1, w, h, w - 8, h - 8) == 0, (w, h)  # ... and as the reference frame of a tile in its far corner
+    for (w, h) in ((16320, 8256), (8256, 16320), (16320, 16320), (11592, 11592), (16328, 64), (64, 16328), (0, 64), (64, -8), (68, 64), (64, 60)):
+        assert g(w, h, 1, 0, 0, 0, 0) != 0, (w, h)
+    for (rw, rh) in ((16320, 8256), (16328, 64), (16384, 4096), (64, 16328), (100, 64), (1 << 30, 64), (-64, 64), (128, 0)):
+        assert g(64, 64, 1, rw, rh, 0, 0) != 0, (rw, rh)
+    for (tx, ty) in ((128, 0), (4, 0), (0, 8), (-8, 0)):  # a tile that leaves its 128x64 frame, or off the 8-sample grid
+        assert g(64, 64, 1, 128, 64, tx, ty) != 0, (tx, ty)
+    assert g(64, 64, 65535, 0, 0, 0, 0) == 0 and g(64, 64, 65536, 0, 0, 0, 0) != 0
 
 
 def assert_covers_the_overflow(name, rf, cu, w, h):
@@ -111,12 +195,15 @@ def test_host_simulation_of_the_pass_prediction_at_the_int16_edge(hostsim_lib):
 
 
 def test_fuzz_of_the_device_program_against_the_oracle(hostsim_lib):
-    """tools/fuzz_inter.py: random clips, sizes that cut CTUs (incl. 8 mod 16), --qp 10..44, ultrafast / superfast / veryfast / faster, GOPs of 2 / 3 / 4 / 8, fast pans,
-    loop filters / motion restriction / WPP on and off -- the simulated device program must equal the oracle on every B picture"""
+    """tools/fuzz_inter.py on the rounds of inter_common.draw_fuzz_case: pictures from 8x8 to 264x264 in steps of 8, --qp 0..51, ultrafast / superfast / veryfast / faster,
+    GOPs of 2 / 3 / 4 / 8, loop filters / motion restriction / WPP on and off, the textured clip and binary / block / noise / flat / full-range content -- the simulated
+    device program must equal the oracle on every B picture, its coder must write the oracle's slice data, and no 24-bit multiply may meet an operand that does not fit
+    (the tool exits non-zero on that count)"""
     import sys
-    r = subprocess.run([sys.executable, os.path.join(flatapi.ROOT, "tools", "fuzz_inter.py"), "60", "9"], capture_output=True, text=True, timeout=900)
+    r = subprocess.run([sys.executable, os.path.join(flatapi.ROOT, "tools", "fuzz_inter.py"), "200", "9"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
-    assert "0 of 60 rounds differ" in r.stdout
+    assert "0 of 200 rounds differ" in r.stdout
+    assert "\n0 operands of 24-bit multiplies did not fit\n" in r.stdout
 
 
 def device_pass(lib, dev, w, h, srcs, refs, ref_cus, prm):
@@ -135,7 +222,7 @@ def device_pass(lib, dev, w, h, srcs, refs, ref_cus, prm):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", FAST_COST_CASES + CABAC_COST_CASES + FASTER_CASES + EDGE_CASES + ["two-gops"] + MC_EDGE_CASES)
+@pytest.mark.parametrize("name", FAST_COST_CASES + CABAC_COST_CASES + FASTER_CASES + EDGE_CASES + ["two-gops"] + MC_EDGE_CASES + END_CASES)
 def test_device_pass_equals_oracle_picture_by_picture(oracle, name):
     import kvazaar_amd
     from kvazaar_amd.dev import Dev
@@ -172,7 +259,7 @@ def test_device_pass_on_baseline_config_4(oracle):
 
 
 CHAIN_CASES = ["deblock-only", "ultrafast", "pan", "vertical-pan-owf", "static-qp17", "no-loop-filters", "survey-416x240", "survey-1080p", "baseline-c4-2160p",
-               "noisy-qp27", "cabac-coeff-cost-qp32", "ultrafast-fast-pan-owf-qp30", "faster-pan", "faster-qp32"]
+               "noisy-qp27", "cabac-coeff-cost-qp32", "ultrafast-fast-pan-owf-qp30", "faster-pan", "faster-qp32"] + END_CASES
 
 
 @pytest.mark.gpu
@@ -253,6 +340,12 @@ def test_device_pass_rejects_what_it_does_not_cover():
     for bad in (dict(qp=52), dict(qp=-1), dict(fme_level=5), dict(fast_residual_cost=52), dict(poc=0), dict(pu_depth_inter_max=4)):
         p = InterParams(**{**{n: getattr(ok, n) for n, _ in InterParams._fields_}, **bad})
         assert lib.kvz_hip_dev_inter_ctu_pass(None, None, None, None, None, None, 64, 64, 1, C.addressof(p)) == -1
+    # 2^23 or more 4x4 cells in the picture or in the reference frame, a reference frame beyond 255 CTUs a side: refused before anything is launched
+    # (inter_pass_geometry_refused; test_inter_pass_geometry_check_at_its_borders walks the borders on the CPU)
+    assert lib.kvz_hip_dev_inter_ctu_pass(None, None, None, None, None, None, 16320, 8256, 1, C.addressof(ok)) == -1
+    for bad in (dict(ref_width=16320, ref_height=8256), dict(ref_width=16384, ref_height=64)):
+        p = InterParams(**{**{n: getattr(ok, n) for n, _ in InterParams._fields_}, **bad})
+        assert lib.kvz_hip_dev_inter_ctu_pass(None, None, None, None, None, None, 64, 64, 1, C.addressof(p)) == -1
 
 
 @pytest.mark.gpu
@@ -283,7 +376,9 @@ def test_device_tile_pass_in_the_tiled_chain(clip):
         return rec[0], cu[0]
 
     spec = [c for c in mg.INTER_TILE_CLIPS if c[0] == clip][0]
+    sim.kvz_hostsim_mul24_reset()
     pictures, records = tc.tiled_inter_chain(spec, 0, 1, None, device_tile_pass, sim)
+    assert mul24_violations(sim) == 0
     want = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "inter_tiles.json")))[clip]
     got = ic.digests(pictures, records)
     assert got["rec"] == want["rec"] and got["cu"] == want["cu"]

@@ -91,13 +91,14 @@ def test_oracle_vs_compiled_reference_cu_by_cu(oracle, name):
 
 def test_fuzz_of_the_oracle_against_the_reference_encoder():
     """tools/fuzz_inter_oracle.py: random clips and switch settings through the oracle and through the compiled reference encoder (how the forced-split rule of
-    search.c:702-713 was found: 8x8 inter CUs at the edge of pictures whose size is 8 mod 16 under `ultrafast` / `superfast`)"""
+    search.c:702-713 was found: 8x8 inter CUs at the edge of pictures whose size is 8 mod 16 under `ultrafast` / `superfast`).  The rounds are those of
+    inter_common.draw_fuzz_case: --qp 0..51, pictures from 8x8 to 264x264, binary / block / noise / flat / full-range content next to the textured clip"""
     if not os.path.exists(os.path.join(flatapi.ROOT, "oracle", "_ref", "kvazaar_ref")):
         pytest.skip("oracle/_ref not built (the GPU box): the committed digests are the check there")
     import subprocess, sys
-    r = subprocess.run([sys.executable, os.path.join(flatapi.ROOT, "tools", "fuzz_inter_oracle.py"), "40", "5"], capture_output=True, text=True, timeout=900)
+    r = subprocess.run([sys.executable, os.path.join(flatapi.ROOT, "tools", "fuzz_inter_oracle.py"), "120", "5"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
-    assert "0 of 40 rounds differ" in r.stdout
+    assert "0 of 120 rounds differ" in r.stdout
 
 
 def test_default_threading_gives_the_constrained_result():
