@@ -163,6 +163,52 @@ KVZ_DEV u8 load_shared_byte(const u8 *p)
   return (u8)(w >> (8 * (a & 3)));
 #endif
 }
+// ... and four of them: the dword at p (4-aligned), as the bytes lie in memory
+KVZ_DEV u32 load_shared_dword(const u8 *p)
+{
+#ifdef KVZ_HOSTSIM
+  u32 w;
+  __builtin_memcpy(&w, p, 4);
+  return w;
+#else
+  return __hip_atomic_load((const unsigned *)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#endif
+}
+
+// ---- wide movers: the code that only moves data does it N = 4, 8 or 16 bytes per lane and instruction (LDS b32 / b64 / b128, memory dword / x2 / x4).  Both ends
+// of a move are N-aligned; why is said where the move is made.  The host build copies the same bytes and promises its compiler nothing about alignment.  The loops
+// around them stay rolled: unrolled, their address registers pushed the CTU kernel over its 128 registers into more scratch memory.
+#ifdef KVZ_HOSTSIM
+#define KVZ_ALIGNED(p, n) (p)
+#define KVZ_ROLLED
+#else
+#define KVZ_ALIGNED(p, n) __builtin_assume_aligned((p), (n))
+#define KVZ_ROLLED _Pragma("nounroll")
+#endif
+// The lane's index as a mover sees it, opaque to the compiler: the row, column and addresses a mover derives from it are then computed where they are used.  Left
+// transparent, they are the same in every call, get hoisted out of the loops around the calls and stay in registers across the search phases.
+KVZ_DEV int mover_lane(int tid)
+{
+#ifndef KVZ_HOSTSIM
+  asm volatile("" : "+v"(tid));
+#endif
+  return tid;
+}
+template <int N> struct alignas(N) WideBytes { u32 w[N / 4]; };
+template <int N> KVZ_DEV WideBytes<N> wide_load(const void *src)
+{
+  WideBytes<N> v;
+  __builtin_memcpy(&v, KVZ_ALIGNED(src, N), N);
+  return v;
+}
+template <int N> KVZ_DEV void wide_store(void *dst, const WideBytes<N> &v) { __builtin_memcpy(KVZ_ALIGNED(dst, N), &v, N); }
+template <int N> KVZ_DEV void wide_move(void *dst, const void *src) { wide_store<N>(dst, wide_load<N>(src)); }
+template <int N> KVZ_DEV WideBytes<N> wide_zero()
+{
+  WideBytes<N> v;
+  for (int i = 0; i < N / 4; i++) v.w[i] = 0;
+  return v;
+}
 
 // One per 8x8 (min CU), 4 bytes: 4 levels x 64 of them live in LDS.  tr_depth 4 marks an NxN CU (four 4x4 PUs, search.c:691): `mode` is then its first PU's,
 // all four are in NxnLds::mode4, and `cbf` holds bits of its own: bit j (0..3) = PU j has luma levels, bits 5 / 10 = the 4x4 U / V block has (see nxn_attempt()).
@@ -221,11 +267,11 @@ struct CtuFrames {
 #define KVZ_BORDER_BYTES 512
 
 template <bool CABAC> struct CtuSharedT {
-  alignas(8) u8 org[1536];   // source pixels of the 32x32 quadrant being searched: Y 32x32 | U 16x16 | V 16x16 (load_org())
+  alignas(16) u8 org[1536];  // source pixels of the 32x32 quadrant being searched: Y 32x32 | U 16x16 | V 16x16 (load_org())
   // Reconstruction.  kvazaar keeps one full lcu_t per depth (search.c:103-122); what those copies hold at any time is
   // (a) the pixels already decided, identical in every level that can see them, plus (b) one candidate per depth for the
   // CU being tried.  So: one decided picture + one candidate buffer per depth, sized to that depth's CU.
-  u8 dec[6144];              // decided pixels, Y 64x64 | U 32x32 | V 32x32.  The depth-0 candidate (64x64 merge) reuses it:
+  alignas(16) u8 dec[6144];  // decided pixels, Y 64x64 | U 32x32 | V 32x32.  The depth-0 candidate (64x64 merge) reuses it:
                              // by then the split result has been written to the frame (run()).
 #if defined(KVZ_CTU_PROFILE) && !defined(KVZ_HOSTSIM)
   unsigned long long prof_rq[16];   // rdoq_block_wave's sections and sizes (luma blocks, so one wavefront adds), flushed with prof_acc
@@ -243,18 +289,18 @@ template <bool CABAC> struct CtuSharedT {
   union {
     struct {
       alignas(16) i16 tb_big[1536];
-      u8 c1[1536];             // depth-1 candidate (32x32 merge): Y 1024 | U 256 | V 256
+      alignas(16) u8 c1[1536]; // depth-1 candidate (32x32 merge): Y 1024 | U 256 | V 256
     };
     struct {
       alignas(16) i16 tb_small[2 * 384];
       alignas(8) u8 org_t[256];  // the CU's source block transposed (horizontal modes are predicted and scored transposed)
-      u8 c2[384];              // depth-2 candidate (16x16 CU):     Y 256 | U 64 | V 64
+      alignas(16) u8 c2[384];  // depth-2 candidate (16x16 CU):     Y 256 | U 64 | V 64
       // (the depth-3 candidates -- the four 8x8 CUs of the current 16x16 -- are written straight into `dec`: nothing reads that region of the decided picture
       // before the 16x16 decision, which either keeps them or overwrites them with c2)
       // quantised levels of the four 8x8 CUs of the current 16x16, laid out like lv2_coeff (Y 4 x 64 | U 4 x 16 | V 4 x 16, children in z-order): like the larger
       // challengers' they only go to HBM if the split wins (commit()) -- every evaluated 8x8 CU storing its levels was three quarters of the pass's write traffic.
       // Also what the CABAC coefficient cost of an 8x8 CU reads (levels_lds()).
-      alignas(8) i16 lv3_coeff[384];
+      alignas(16) i16 lv3_coeff[384];
       // Rough search, the 15 angular modes with a negative displacement (11..25): the main reference with its projected
       // extension (intra-generic.c:97-123), already picked from the filtered / unfiltered, top / left arrays.  Entry
       // [mode - 11][KVZ_MREF_ORG + q] is ref_main[q], q in [-w, w + 1] -- all such a mode can touch.  The other modes read
@@ -263,8 +309,14 @@ template <bool CABAC> struct CtuSharedT {
       u32 satd_raw[35][4];     // sum |Hadamard| per (mode, 8x8 block) before the per-block rounding
     };
   };
-  alignas(8) i16 lv2_coeff[384];        // quantised levels of the 16x16 CU being tried (Y 256 | U 64 | V 64): they only go to HBM if it wins
-  alignas(8) i16 lv1_coeff[1536];       // ... and of the 32x32 merge being tried (Y 1024 | U 256 | V 256)
+  alignas(16) i16 lv2_coeff[384];       // quantised levels of the 16x16 CU being tried (Y 256 | U 64 | V 64): they only go to HBM if it wins
+  alignas(16) i16 lv1_coeff[1536];      // ... and of the 32x32 merge being tried (Y 1024 | U 256 | V 256)
+  // (here, behind lv1_coeff, the matrices start on a 16-byte boundary with no padding: a lane's row of the 8-point matrix is one ds_read_b128)
+#ifdef KVZ_HOSTSIM
+  alignas(16) i16 dct32[32 * 32];      // HEVC core transform matrix; the 16/8/4-point matrices are its rows 2k/4k/8k (dct-generic.c:46-120)
+#else
+  alignas(16) i16 dct_small[64 + 16];  // the 8- and 4-point matrices: larger transforms run on the matrix cores from Tables::dct_i8
+#endif
   u32 acc[16];               // [0..2] ssd per plane, [3..5] coeff weight sums, [6..8] non-zero counts
   int8_t preds[3];
   int best_mode;
@@ -278,11 +330,6 @@ template <bool CABAC> struct CtuSharedT {
   u8 bpx_left[3][66];        // x = ox-1, y = oy-1 .. oy+63   (index 0 = corner)
   u8 bpx_top[3][98];         // y = oy-1, x = ox-1 .. ox+95   (index 0 = corner)
   u8 nb_depth[2][8], nb_mode[2][8];  // [0 left / 1 top][8x8 index]
-#ifdef KVZ_HOSTSIM
-  i16 dct32[32 * 32];        // HEVC core transform matrix; the 16/8/4-point matrices are its rows 2k/4k/8k (dct-generic.c:46-120)
-#else
-  i16 dct_small[64 + 16];    // the 8- and 4-point matrices: larger transforms run on the matrix cores from Tables::dct_i8
-#endif
   u8 dcval[3];               // DC value of the current references per plane
   int8_t mode_disp[35];      // angular parameters per mode (intra-generic.c:59-60, 70-76): signed sample displacement,
   int16_t mode_inv[35];      //   inverse angle, and whether the mode projects on the top reference
@@ -2335,6 +2382,31 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
     KVZ_SYNC();
   }
 
+  // ---------------------------------------------------------------- wide movers (see wide_move)
+  // `bytes` (a multiple of 16) at 16-aligned addresses: zeroed / copied, 16 bytes per lane and trip
+  KVZ_DEV static void zero_run(void *dst, int bytes, int tid)
+  {
+    KVZ_ROLLED for (int o = mover_lane(tid) * 16; o < bytes; o += KVZ_CTU_THREADS * 16) wide_store<16>(static_cast<u8 *>(dst) + o, wide_zero<16>());
+  }
+  KVZ_DEV static void copy_run(void *dst, const void *src, int bytes, int tid)
+  {
+    KVZ_ROLLED for (int o = mover_lane(tid) * 16; o < bytes; o += KVZ_CTU_THREADS * 16) wide_move<16>(static_cast<u8 *>(dst) + o, static_cast<const u8 *>(src) + o);
+  }
+  // A CU's quantised levels between a challenger block `flat` (Y n | U n/4 | V n/4) and their place in a CTU's block (Y 4096 | U 1024 | V 1024, each in z-order: the
+  // CU's levels are the runs [zy, zy + n) and [zc, zc + n/4) of the planes), eight levels per lane and trip; skip(e): leave out the eight from flat[e] on.
+  // n >= 256: runs and blocks start on multiples of 16 bytes (blocks are 12 288 bytes apart in their arrays, lv*_coeff are aligned in LDS).
+  template <bool TO_BLOCK, class Skip>
+  KVZ_DEV static void move_levels(i16 *block, i16 *flat, int n, unsigned zy, unsigned zc, int tid, Skip skip)
+  {
+    const int nc = n >> 2;
+    KVZ_ROLLED for (int e = mover_lane(tid) * 8; e < n + 2 * nc; e += KVZ_CTU_THREADS * 8) {
+      if (skip(e)) continue;
+      const int k = e - n;
+      i16 *at = block + (k < 0 ? zy + e : plane_off(1 + (k >= nc)) + zc + (k & (nc - 1)));
+      if (TO_BLOCK) wide_move<16>(at, flat + e); else wide_move<16>(flat + e, at);
+    }
+  }
+
   // The work-tree copies of search.c:55-122 for the region (xl, yl, w), in one phase:
   //   CU info      level cu_from -> levels cu_to_lo..cu_to_hi (copy_cu_info),
   //   pixels       candidate of depth pix_lv -> decided picture (copy_cu_pixels; -1: the decided picture already holds them),
@@ -2362,35 +2434,30 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
         }
       }
       if (pix_lv >= 0) {
-        for (int e = tid; e < w * w; e += KVZ_CTU_THREADS) {
-          const int px = xl + (e & (w - 1)), py = yl + (e >> lw);
-          s->dec[py * 64 + px] = cv.at(0, px, py);
-        }
-        for (int e = tid; e < 2 * cw * cw; e += KVZ_CTU_THREADS) {
-          const int c = 1 + (e >= cw * cw), k = e & (cw * cw - 1), px = (xl >> 1) + (k & (cw - 1)), py = (yl >> 1) + (k >> (lw - 1));
-          s->dec[plane_off(c) + py * 32 + px] = cv.at(c, px, py);
+        // a 16x16 or 32x32 candidate (c2 / c1): 16 luma samples or 8 chroma samples per lane.  Rows of the candidate and of the decided picture start at
+        // multiples of the CU's width (of half of it for chroma) in 16-aligned buffers.
+        const int nl = (w * w) >> 4, nc = (cw * cw) >> 3;
+        KVZ_ROLLED for (int u = mover_lane(tid); u < nl + 2 * nc; u += KVZ_CTU_THREADS) {
+          if (u < nl) {
+            const int px = xl + ((u << 4) & (w - 1)), py = yl + ((u << 4) >> lw);
+            wide_move<16>(&s->dec[py * 64 + px], &cv.at(0, px, py));
+          } else {
+            const int c = 1 + (u - nl >= nc), k = ((u - nl) & (nc - 1)) << 3, px = (xl >> 1) + (k & (cw - 1)), py = (yl >> 1) + (k >> (lw - 1));
+            wide_move<8>(&s->dec[plane_off(c) + py * 32 + px], &cv.at(c, px, py));
+          }
         }
       }
       if (coeffs || (split_won && res_depth == 2)) {
         i16 *dst = coeff_level(3);
         const unsigned zy = zorder(xl, yl), zc = zorder(xl >> 1, yl >> 1);
         if (w == 16) {  // the challengers' levels never left LDS: the 16x16 CU's, or -- the split wins -- those of the 8x8 CUs that lie inside the picture
-          const i16 *src = split_won ? s->lv3_coeff : s->lv2_coeff;
-          for (int e = tid; e < 384; e += KVZ_CTU_THREADS) {
-            const int q = e < 256 ? e >> 6 : ((e - 256) >> 4) & 3;
-            if (split_won && (cx + xl + 8 * (q & 1) >= F.W || cy + yl + 8 * (q >> 1) >= F.H)) continue;  // never evaluated (search_d2): the output block keeps its zeros
-            dst[e < 256 ? zy + e : plane_off(1 + ((e - 256) >> 6)) + zc + ((e - 256) & 63)] = src[e];
-          }
-        } else if (w == 32) {
-          for (int e = tid; e < 1536; e += KVZ_CTU_THREADS) dst[e < 1024 ? zy + e : plane_off(1 + ((e - 1024) >> 8)) + zc + ((e - 1024) & 255)] = s->lv1_coeff[e];
-        } else {
-          const i16 *src = coeff_level(0);
-          for (int e = tid; e < w * w; e += KVZ_CTU_THREADS) dst[zy + e] = src[zy + e];
-          for (int e = tid; e < 2 * cw * cw; e += KVZ_CTU_THREADS) {
-            const int c = e >= cw * cw, k = c ? e - cw * cw : e;
-            dst[plane_off(1 + c) + zc + k] = src[plane_off(1 + c) + zc + k];
-          }
-        }
+          const int fx = cx + xl, fy = cy + yl;
+          move_levels<true>(dst, split_won ? s->lv3_coeff : s->lv2_coeff, 256, zy, zc, tid, [&](int e) {
+            const int q = e < 256 ? e >> 6 : ((e - 256) >> 4) & 3;  // which 8x8 CU the eight levels belong to
+            return split_won && (fx + 8 * (q & 1) >= F.W || fy + 8 * (q >> 1) >= F.H);  // never evaluated (search_d2): the output block keeps its zeros
+          });
+        } else if (w == 32) move_levels<true>(dst, s->lv1_coeff, 1024, zy, zc, tid, [](int) { return false; });
+        else copy_run(dst, coeff_level(0), 6144 * 2, tid);  // the whole CTU: both blocks are laid out alike
       }
     }
     KVZ_SYNC();
@@ -2781,37 +2848,57 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
   // ---------------------------------------------------------------- CTU driver
   // Stages the source pixels of the 32x32 quadrant at (a1x, a1y), zero outside the picture (search.c:1084 FILL + :1151-1171).
   // One thread also runs `first` (bookkeeping of the caller that nobody reads before the barrier).
-  template <class First = NoHook>
-  KVZ_DEV void load_org(First first = First())
+  // Pictures are multiples of 8 wide and high (kvz_hip_batch_create), so in a frame of [Y | U | V] every luma row starts on a multiple of 8 bytes and every chroma
+  // row and plane on a multiple of 4 -- of 16 and 8 when the width is a multiple of 16 -- and a group of that many samples that starts on such a multiple lies
+  // inside the picture or outside it as a whole.  The movers between a frame and LDS take U = 16 or 8: luma moves in units of U bytes, chroma in units of U / 2,
+  // which makes the number of units per row the same in every plane.  Plane origins are computed once per call; behind them offsets are 32 bits.
+  KVZ_DEV bool wide16() const { return (F.W & 15) == 0; }  // uniform
+  template <int U, class First>
+  KVZ_DEV void load_org_units(First first)
   {
+    constexpr int L2 = U == 16 ? 1 : 2, UC = U / 2;  // log2 of the units per row: 32 luma / 16 chroma samples
+    const u8 *src = F.src + (long)frame * F.frame_px;
+    const unsigned off_u = (unsigned)F.W * (unsigned)F.H, off_v = off_u + (off_u >> 2);
+    const int fwc = F.W >> 1, fhc = F.H >> 1, ox = cx + a1x, oy = cy + a1y;
     KVZ_FOR_THREADS(tid) {
       first(tid);
-      for (int c = 0; c < 3; c++) {
-        const int sh = c ? 1 : 0, l2 = 5 - sh, qw = 1 << l2, fw = F.W >> sh, fh = F.H >> sh, ox = (cx + a1x) >> sh, oy = (cy + a1y) >> sh;
-        const u8 *src = frame_src(c);
-        u8 *dst = s->org + (c == 0 ? 0 : (c == 1 ? 1024 : 1280));
-        for (int e = tid; e < qw * qw; e += KVZ_CTU_THREADS) {
-          const int px = ox + (e & (qw - 1)), py = oy + (e >> l2);
-          dst[e] = (px < fw && py < fh) ? src[(long)py * fw + px] : 0;
+      KVZ_ROLLED for (int u = mover_lane(tid); u < (64 << L2); u += KVZ_CTU_THREADS) {  // rows 0..31 Y, 32..47 U, 48..63 V: wavefronts never straddle luma and chroma
+        const int row = u >> L2, k = u & ((1 << L2) - 1);
+        if (row < 32) {
+          const int px = ox + k * U, py = oy + row;
+          WideBytes<U> v = wide_zero<U>();
+          if (px < F.W && py < F.H) v = wide_load<U>(src + (unsigned)(py * F.W + px));
+          wide_store<U>(s->org + row * 32 + k * U, v);
+        } else {
+          const int r = row - 32, px = (ox >> 1) + k * UC, py = (oy >> 1) + (r & 15);
+          WideBytes<UC> v = wide_zero<UC>();
+          if (px < fwc && py < fhc) v = wide_load<UC>(src + (r < 16 ? off_u : off_v) + (unsigned)(py * fwc + px));
+          wide_store<UC>(s->org + 1024 + r * 16 + k * UC, v);
         }
       }
     }
     KVZ_SYNC();
   }
+  template <class First = NoHook>
+  KVZ_DEV void load_org(First first = First())
+  {
+    if (wide16()) load_org_units<16>(first); else load_org_units<8>(first);
+  }
   KVZ_DEV void init()
   {
-    KVZ_FOR_THREADS(tid) {
-      for (int e = tid; e < 6144; e += KVZ_CTU_THREADS) s->dec[e] = 0;
+    KVZ_FOR_THREADS(lane) {
+      const int tid = mover_lane(lane);  // nothing of this phase is worth a register beyond it
+      zero_run(s->dec, 6144, tid);
       for (int lv = 0; lv < 4; lv++)
         if (tid < 64) { CtuCu z = { 0, 0, 0, 0, 0 }; s->cu[lv][tid] = z; }
       // Coefficient buffers start zeroed like the lcu_t copies (search.c:1084).  Only observable for CTUs that stick out
       // of the picture: inside the picture every coefficient that reaches level 0 was written by a transform unit first.
       if (cx + 64 > F.W || cy + 64 > F.H)
-        for (int lv = 0; lv < 4; lv += 3) { i16 *cf = coeff_level(lv); for (int e = tid; e < 6144; e += KVZ_CTU_THREADS) cf[e] = 0; }
+        for (int lv = 0; lv < 4; lv += 3) zero_run(coeff_level(lv), 6144 * 2, tid);
 #ifdef KVZ_HOSTSIM
       for (int e = tid; e < 1024; e += KVZ_CTU_THREADS) s->dct32[e] = tb->dct[3][e];
 #else
-      for (int e = tid; e < 80; e += KVZ_CTU_THREADS) s->dct_small[e] = e < 64 ? tb->dct[1][e] : tb->dct[0][e - 64];
+      if (tid < 10) wide_move<16>(s->dct_small + 8 * tid, tid < 8 ? tb->dct[1] + 8 * tid : tb->dct[0] + 8 * (tid - 8));  // eight entries per lane: Tables is 16-aligned, its matrices 2 KB apart
 #endif
       // neighbour CTUs (complete: they come earlier in the dependency order): border pixels and CU info from their records
       {
@@ -2821,31 +2908,35 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
         const u8 *r_top = cty > 0 ? base + (long)((cty - 1) * F.wc + ctx) * KVZ_BORDER_BYTES : nullptr;
         const u8 *r_tl = (ctx > 0 && cty > 0) ? base + (long)((cty - 1) * F.wc + ctx - 1) * KVZ_BORDER_BYTES : nullptr;
         const u8 *r_tr = (cty > 0 && ctx + 1 < F.wc) ? base + (long)((cty - 1) * F.wc + ctx + 1) * KVZ_BORDER_BYTES : nullptr;
-        for (int c = 0; c < 3; c++) {
-          const int lw = c ? 32 : 64, po = c == 0 ? 0 : (c == 1 ? 64 : 96);  // plane offset inside a 128-byte row / column record
-          for (int i = tid; i < lw + 2; i += KVZ_CTU_THREADS) {  // left column incl. corner: index i <-> y = oy - 1 + i
-            u8 v = 0;
-            if (i == 0) { if (r_tl) v = load_shared_byte(r_tl + po + lw - 1); }
-            else if (i <= lw) { if (r_left) v = load_shared_byte(r_left + 128 + po + i - 1); }
-            s->bpx_left[c][i] = v;
-          }
-          for (int i = tid; i < lw + (lw >> 1) + 2; i += KVZ_CTU_THREADS) {  // top row incl. corner: index i <-> x = ox - 1 + i
-            u8 v = 0;
-            if (i == 0) { if (r_tl) v = load_shared_byte(r_tl + po + lw - 1); }
-            else if (i <= lw) { if (r_top) v = load_shared_byte(r_top + po + i - 1); }
-            else if (r_tr) v = load_shared_byte(r_tr + po + i - 1 - lw);
-            s->bpx_top[c][i] = v;
-          }
-        }
-        if (tid < 16) {
-          const int side = tid >> 3, i = tid & 7;
+        // One lane per dword of a record, 95 lanes at once.  Lanes 0..79, border pixels -- per plane (Y 40 | U 20 | V 20 lanes), w4 = a quarter of the CTU's width in
+        // it: w4 dwords of the left CTU's right column -> bpx_left[c][1..], w4 of the upper CTU's bottom row and w4 / 2 of the upper-right CTU's -> bpx_top[c][1..]
+        // (index i <-> y = oy - 1 + i / x = ox - 1 + i: the corner in front puts these four bytes on an odd address).  Lanes 80..82: the corner of a plane, the last
+        // sample of the upper-left CTU's bottom row.  Lanes 83..90: the eight dwords of nb_depth | nb_mode.
+        if (tid < 80) {
+          const int c = tid < 40 ? 0 : (tid < 60 ? 1 : 2), t = tid - (c == 0 ? 0 : (c == 1 ? 40 : 60)), w4 = c ? 8 : 16, po = c == 0 ? 0 : (c == 1 ? 64 : 96);  // po: the plane inside a 128-byte row / column record
+          const int part = t < w4 ? 0 : (t < 2 * w4 ? 1 : 2), j = 4 * (t - part * w4);
+          const u8 *r = part == 0 ? r_left : (part == 1 ? r_top : r_tr);
+          const u32 v = r ? load_shared_dword(r + (part == 0 ? 128 : 0) + po + j) : 0;
+          __builtin_memcpy(part == 0 ? &s->bpx_left[c][1 + j] : &s->bpx_top[c][1 + (part == 1 ? 0 : 4 * w4) + j], &v, 4);
+        } else if (tid < 83) {
+          const int c = tid - 80, po = c == 0 ? 0 : (c == 1 ? 64 : 96), lw = c ? 32 : 64;
+          const u8 v = r_tl ? (u8)(load_shared_dword(r_tl + po + lw - 4) >> 24) : 0;
+          s->bpx_left[c][0] = v; s->bpx_top[c][0] = v;
+        } else if (tid < 91) {
+          // record [256..287]: depth, mode of the bottom 8x8 row, depth, mode of the right 8x8 column, 8 bytes each
+          const int k = tid - 83, side = (k >> 1) & 1, what = k >> 2;  // what: 0 depth, 1 mode; side: 0 left, 1 top
           const u8 *r = side == 0 ? r_left : r_top;
-          s->nb_depth[side][i] = r ? load_shared_byte(r + 256 + (side == 0 ? 16 : 0) + i) : 0;
-          s->nb_mode[side][i] = r ? load_shared_byte(r + 256 + (side == 0 ? 24 : 8) + i) : 0;
+          const u32 v = r ? load_shared_dword(r + 256 + (side == 0 ? 16 : 0) + what * 8 + (k & 1) * 4) : 0;
+          static_assert(__builtin_offsetof(CtuSharedT<CABAC>, nb_mode) == __builtin_offsetof(CtuSharedT<CABAC>, nb_depth) + 16 && __builtin_offsetof(CtuSharedT<CABAC>, nb_depth) % 4 == 0, "nb_depth | nb_mode as eight dwords");
+          wide_store<4>(&s->nb_depth[0][0] + 4 * k, WideBytes<4>{ { v } });
+        } else if (tid < 94) {  // one entry behind each: nothing behind the left column, the next sample of the upper-right CTU's row
+          const int c = tid - 91, po = c == 0 ? 0 : (c == 1 ? 64 : 96), lw = c ? 32 : 64;
+          s->bpx_left[c][lw + 1] = 0;
+          s->bpx_top[c][lw + (lw >> 1) + 1] = r_tr ? (u8)load_shared_dword(r_tr + po + (lw >> 1)) : 0;
         }
         if constexpr (NXN) {
           if (m->search_nxn) {
-            if (tid < 16) rl->nb_mode4_left[tid] = r_left ? load_shared_byte(r_left + 448 + tid) : 0;
+            if (tid >= 96 && tid < 100) wide_store<4>(rl->nb_mode4_left + 4 * (tid - 96), WideBytes<4>{ { r_left ? load_shared_dword(r_left + 448 + 4 * (tid - 96)) : 0 } });
             for (int e = tid; e < 4 * 64; e += KVZ_CTU_THREADS) reinterpret_cast<u32 *>(rl->mode4)[e] = 0;
             if (tid == 0) rl->n_pu = -1;
           }
@@ -2861,17 +2952,23 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
       if (v >= 128 && v < 136) s->qs[(v - 128) >> 1][v & 1] = quant_scalars_dev(2 + ((v - 128) >> 1), (v & 1) ? 2 : 0);
       if (v < 128) s->entropy_fbits[v] = m->entropy_fbits[v];
       if (v < 64) s->ctx_lps[v] = tb->ctx_next[1][2 * v];
-      if (v < (cabac_on() ? KVZ_CX_COUNT : KVZ_CX_SYNTAX_COUNT)) {  // the residual contexts are only looked at with the CABAC coefficient cost
+      }
+      {
         // the row's contexts: from the CTU to the left; a row's first CTU from the second CTU of the row above (WPP; rows of a
         // one-CTU-wide picture and the first row start from the slice-start state, encoderstate.c:1218) -- or, without WPP, from
-        // the last CTU of the row above (one coder runs through the picture in raster order)
-        const int ctx = cx >> 6, cty = cy >> 6;
-        const u8 *base = F.border + (long)frame * F.wc * F.hc * KVZ_BORDER_BYTES;
-        const int seed = m->no_wpp ? F.wc - 1 : (F.wc > 1 ? 1 : -1);
-        const u8 *r = ctx > 0 ? base + (long)(cty * F.wc + ctx - 1) * KVZ_BORDER_BYTES : ((cty > 0 && seed >= 0) ? base + (long)((cty - 1) * F.wc + seed) * KVZ_BORDER_BYTES : nullptr);
-        const u8 st = (r && m->adaptive) ? load_shared_byte(r + 288 + v) : m->ctx_init[v];
-        s->pre[0].s[v] = st; s->cab.s[v] = st;
-      }
+        // the last CTU of the row above (one coder runs through the picture in raster order).  Four per lane (the record's and the model's are 4-aligned);
+        // the residual contexts are only looked at with the CABAC coefficient cost, and without it the ten syntax contexts come as two dwords and a half one.
+        const int n = cabac_on() ? KVZ_CX_COUNT : KVZ_CX_SYNTAX_COUNT, v = 4 * tid;
+        if (v < n) {
+          const int ctx = cx >> 6, cty = cy >> 6;
+          const u8 *base = F.border + (long)frame * F.wc * F.hc * KVZ_BORDER_BYTES;
+          const int seed = m->no_wpp ? F.wc - 1 : (F.wc > 1 ? 1 : -1);
+          const u8 *r = ctx > 0 ? base + (long)(cty * F.wc + ctx - 1) * KVZ_BORDER_BYTES : ((cty > 0 && seed >= 0) ? base + (long)((cty - 1) * F.wc + seed) * KVZ_BORDER_BYTES : nullptr);
+          u32 st = (r && m->adaptive) ? load_shared_dword(r + 288 + v) : wide_load<4>(m->ctx_init + v).w[0];
+          if (n - v < 4) st &= 0xffffu;  // bytes 10, 11 of the syntax-only set are nobody's
+          wide_store<4>(s->pre[0].s + v, WideBytes<4>{ { st } });
+          wide_store<4>(s->cab.s + v, WideBytes<4>{ { st } });
+        }
       }
 
     }
@@ -2881,26 +2978,44 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
   // copy_lcu_to_cu_data (search.c:1180-1207), pixel half: CtuShared::dec -> frame reconstruction and the pixel part of the
   // border record the right / lower neighbours read.  May run twice for a CTU (see run()): every lane rewrites the
   // addresses it wrote the first time, so the later values win.
-  KVZ_DEV void write_rec()
+  template <int U>
+  KVZ_DEV void write_rec_units()
   {
+    constexpr int L2 = U == 16 ? 2 : 3, UC = U / 2;  // log2 of the units per row (64 luma / 32 chroma samples), see load_org_units()
     const u8 *fin = s->dec;
+    u8 *dst = F.rec + (long)frame * F.frame_px;
+    const unsigned off_u = (unsigned)F.W * (unsigned)F.H, off_v = off_u + (off_u >> 2);
+    const int fwc = F.W >> 1, fhc = F.H >> 1;
+    u8 *rec = F.border + ((long)frame * F.wc * F.hc + ctu_index()) * KVZ_BORDER_BYTES;
     KVZ_FOR_THREADS(tid) {
-      for (int c = 0; c < 3; c++) {
-        const int sh = c ? 1 : 0, lw = 64 >> sh, fw = F.W >> sh, fh = F.H >> sh, ox = cx >> sh, oy = cy >> sh;
-        u8 *dst = const_cast<u8 *>(frame_rec(c));
-        for (int e = tid; e < lw * lw; e += KVZ_CTU_THREADS) {
-          const int px = ox + e % lw, py = oy + e / lw;
-          if (px < fw && py < fh) dst[(long)py * fw + px] = fin[plane_off(c) + e];
+      KVZ_ROLLED for (int u = mover_lane(tid); u < (128 << L2); u += KVZ_CTU_THREADS) {  // rows 0..63 Y, 64..95 U, 96..127 V: a trip is all luma or all chroma
+        const int row = u >> L2, k = u & ((1 << L2) - 1);
+        if (row < 64) {
+          const int px = cx + k * U, py = cy + row;
+          if (px < F.W && py < F.H) wide_move<U>(dst + (unsigned)(py * F.W + px), fin + row * 64 + k * U);
+        } else {
+          const int r = row - 64, px = (cx >> 1) + k * UC, py = (cy >> 1) + (r & 31);
+          if (px < fwc && py < fhc) wide_move<UC>(dst + (r < 32 ? off_u : off_v) + (unsigned)(py * fwc + px), fin + 4096 + r * 32 + k * UC);
         }
       }
-      u8 *r = F.border + ((long)frame * F.wc * F.hc + ctu_index()) * KVZ_BORDER_BYTES;
-      for (int v = tid; v < 128; v += KVZ_CTU_THREADS) {
-        const int c = v < 64 ? 0 : (v < 96 ? 1 : 2), i = v < 64 ? v : (v - 64) & 31, lw = c ? 32 : 64;
-        r[v] = fin[plane_off(c) + (lw - 1) * lw + i];        // bottom row
-        r[128 + v] = fin[plane_off(c) + i * lw + lw - 1];    // right column
+      // the pixel lines of the border record (Y 64 | U 32 | V 32 each), a dword per lane: the bottom row on one wavefront, the right column -- four samples
+      // gathered -- on the other
+      const int bl = mover_lane(tid), t = bl & 63;
+      if (t < 32 && bl < 128) {
+        const int c = t < 16 ? 0 : (t < 24 ? 1 : 2), i = 4 * (c == 0 ? t : (t - 16) & 7), lw = c ? 32 : 64;
+        if (bl < 64) wide_move<4>(rec + 4 * t, fin + plane_off(c) + (lw - 1) * lw + i);
+        else {
+          const u8 *col = fin + plane_off(c) + i * lw + lw - 1;
+          const u32 v = (u32)col[0] | ((u32)col[lw] << 8) | ((u32)col[2 * lw] << 16) | ((u32)col[3 * lw] << 24);
+          wide_store<4>(rec + 128 + 4 * t, WideBytes<4>{ { v } });
+        }
       }
     }
     KVZ_SYNC();
+  }
+  KVZ_DEV void write_rec()
+  {
+    if (wide16()) write_rec_units<16>(); else write_rec_units<8>();
   }
   // The syntax kvazaar writes for the finished CTU (kvz_encode_coding_tree, encode_coding_tree.c:745-940, with
   // encode_intra_coding_unit :467-652 and encode_transform_coeff :193-309), reduced to the bins that touch the ten contexts:
@@ -2987,13 +3102,12 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
   // levels come back from the CTU's output block one 32x32 quadrant at a time, staged in lv1_coeff by all lanes.
   KVZ_DEV void code_ctu_residual()
   {
-    const i16 *fin = coeff_level(3);
+    i16 *fin = coeff_level(3);
     for (int q = 0; q < 4; q++) {
       const int qxl = (q & 1) * 32, qyl = (q >> 1) * 32;
       if (cx + qxl >= F.W || cy + qyl >= F.H) continue;
       KVZ_FOR_THREADS(tid) {
-        for (int e = tid; e < 1536; e += KVZ_CTU_THREADS)
-          s->lv1_coeff[e] = fin[e < 1024 ? q * 1024 + e : plane_off(1 + ((e - 1024) >> 8)) + q * 256 + ((e - 1024) & 255)];
+        move_levels<false>(fin, s->lv1_coeff, 1024, q * 1024, q * 256, tid, [](int) { return false; });
       }
       KVZ_SYNC();
       KVZ_FOR_THREADS(tid) {
@@ -3053,26 +3167,51 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
   KVZ_DEV void finish_info()
   {
     KVZ_FOR_THREADS(tid) {
-      if (tid < 64) {
-        const int fx = cx + (tid & 7) * 8, fy = cy + (tid >> 3) * 8;
-        if (fx < F.W && fy < F.H) {
-          const long i = (long)frame * (F.H >> 3) * (F.W >> 3) + (long)(fy >> 3) * (F.W >> 3) + (fx >> 3);
-          F.cu_depth[i] = s->cu[0][tid].depth;
-          F.cu_mode[i] = s->cu[0][tid].mode;
+      // The CU maps, one entry per 8x8 cell.  A picture whose width is a multiple of 32 has map rows (and maps) that are multiples of 4 entries, and a group of four
+      // cells is inside it or outside as a whole: a lane then packs four cells and stores a dword per map.  Otherwise an entry per lane.
+      const int mw = F.W >> 3;
+      const unsigned map_at = (unsigned)(cy >> 3) * (unsigned)mw + (unsigned)(cx >> 3);
+      u8 *depth_map = F.cu_depth + (long)frame * (F.H >> 3) * mw, *mode_map = F.cu_mode + (long)frame * (F.H >> 3) * mw;
+      const int ml = mover_lane(tid);
+      if ((F.W & 31) == 0) {
+        if (ml < 16) {
+          const int cell = (ml >> 1) * 8 + (ml & 1) * 4;
+          if (cx + (ml & 1) * 32 < F.W && cy + (ml >> 1) * 8 < F.H) {
+            u32 d = 0, md = 0;
+            for (int j = 0; j < 4; j++) { const CtuCu cu = s->cu[0][cell + j]; d |= (u32)cu.depth << (8 * j); md |= (u32)cu.mode << (8 * j); }
+            const unsigned i = map_at + (unsigned)(ml >> 1) * (unsigned)mw + (ml & 1) * 4;
+            wide_store<4>(depth_map + i, WideBytes<4>{ { d } });
+            wide_store<4>(mode_map + i, WideBytes<4>{ { md } });
+          }
+        }
+      } else if (ml < 64) {
+        if (cx + (ml & 7) * 8 < F.W && cy + (ml >> 3) * 8 < F.H) {
+          const unsigned i = map_at + (unsigned)(ml >> 3) * (unsigned)mw + (ml & 7);
+          depth_map[i] = s->cu[0][ml].depth;
+          mode_map[i] = s->cu[0][ml].mode;
         }
       }
       u8 *r = F.border + ((long)frame * F.wc * F.hc + ctu_index()) * KVZ_BORDER_BYTES;
       if (tid == 0) {
         F.ctu_cost[(long)frame * F.wc * F.hc + ctu_index()] = s->res[0];
         if (m->adaptive) code_ctu_syntax(&s->pre[0]);  // moves the syntax contexts only
-        for (int i = 0; i < KVZ_CX_SYNTAX_COUNT; i++) r[288 + i] = s->pre[0].s[i];
+        // the ten syntax contexts leave as 8 + 4 bytes: the two behind them are residual contexts (final since code_ctu_residual()) or, without the CABAC
+        // coefficient cost, nobody's and zero
+        static_assert(KVZ_CX_SYNTAX_COUNT == 10, "8 + 2 of 4");
+        wide_move<8>(r + 288, s->pre[0].s);
+        WideBytes<4> t = wide_load<4>(s->pre[0].s + 8);
+        if (!cabac_on()) t.w[0] &= 0xffffu;
+        wide_store<4>(r + 296, t);
       }
-      if (cabac_on())
-        for (int v = KVZ_CX_SYNTAX_COUNT + tid; v < KVZ_CX_COUNT; v += KVZ_CTU_THREADS) r[288 + v] = s->pre[0].s[v];  // residual contexts: final since code_ctu_residual()
-      for (int v = tid; v < 32; v += KVZ_CTU_THREADS) {
-        const int i = v & 7;
-        const CtuCu *cu = &s->cu[0][v < 16 ? 56 + i : i * 8 + 7];
-        r[256 + v] = ((v >> 3) & 1) ? cu->mode : cu->depth;
+      if (cabac_on() && ml >= 3 && ml < KVZ_CX_COUNT / 4) wide_move<4>(r + 288 + 4 * ml, s->pre[0].s + 4 * ml);  // the other residual contexts, a dword per lane
+      if (ml >= 64 && ml < 72) {  // record [256..287], a dword per lane: depth, mode of the bottom 8x8 row, then of the right 8x8 column (read back by init())
+        const int k = ml - 64, i0 = (k & 1) * 4;
+        u32 v = 0;
+        for (int j = 0; j < 4; j++) {
+          const CtuCu cu = s->cu[0][k < 4 ? 56 + i0 + j : (i0 + j) * 8 + 7];
+          v |= (u32)((k >> 1) & 1 ? cu.mode : cu.depth) << (8 * j);
+        }
+        wide_store<4>(r + 256 + 4 * k, WideBytes<4>{ { v } });
       }
       if constexpr (NXN) {
         if (m->search_nxn) {
@@ -3285,7 +3424,7 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
     if (!descend) return;
     u8 *stash = reinterpret_cast<u8 *>(coeff_level(0));
     if (inside) {
-      KVZ_FOR_THREADS(tid) { for (int e = tid; e < 1536 / 4; e += KVZ_CTU_THREADS) reinterpret_cast<u32 *>(stash)[e] = reinterpret_cast<const u32 *>(s->c1)[e]; }
+      KVZ_FOR_THREADS(tid) { copy_run(stash, s->c1, 1536, tid); }
       KVZ_SYNC();
     }
     for (int q2 = 0; q2 < 4; q2++) {
@@ -3294,7 +3433,7 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
     }
     if (inside && !(s->split_cost[1] < s->cost[1])) {  // the 32x32 CU wins: its pixels back into the candidate buffer for commit()
       KVZ_SYNC();
-      KVZ_FOR_THREADS(tid) { for (int e = tid; e < 1536 / 4; e += KVZ_CTU_THREADS) reinterpret_cast<u32 *>(s->c1)[e] = reinterpret_cast<const u32 *>(stash)[e]; }
+      KVZ_FOR_THREADS(tid) { copy_run(s->c1, stash, 1536, tid); }
       KVZ_SYNC();
     }
   }
