@@ -35,6 +35,7 @@
 #include "../../include/kvz_hip_types.h"
 #include "kvz_ops.hpp"
 #include "kvz_rdoq.hpp"
+#include "kvz_residual.hpp"
 
 namespace kvz {
 
@@ -77,13 +78,7 @@ KVZ_DEV void block_add(u32 *dst, u32 v)
 #ifdef KVZ_HOSTSIM
   *dst += v;
 #else
-  // row_shr 8 / 4 / 2 / 1 within each row of 16 lanes (lanes shifted in from outside the row read 0): lane 15 of a row ends
-  // up with the row's sum; the four row sums are then picked out by lane index.  No LDS traffic, no dependent shuffles.
-  int x = (int)v;
-  x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xF, 0xF, true);
-  x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xF, 0xF, true);
-  x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xF, 0xF, true);
-  x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xF, 0xF, true);
+  const int x = row16_sum((int)v);  // the four row sums are then picked out by lane index
   const u32 total = (u32)(__builtin_amdgcn_readlane(x, 15) + __builtin_amdgcn_readlane(x, 31) + __builtin_amdgcn_readlane(x, 47) + __builtin_amdgcn_readlane(x, 63));
   if ((threadIdx.x & 63) == 0 && total) atomicAdd(dst, total);
 #endif
@@ -462,12 +457,6 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
     const int sh = c ? 1 : 0;
     return s->org + (c == 0 ? 0 : (c == 1 ? 1024 : 1280)) + (pyl - (a1y >> sh)) * (32 >> sh) + pxl - (a1x >> sh);
   }
-  KVZ_DEV static unsigned zorder(int x, int y)  // cu.h:385-421
-  {
-    unsigned r = 0;
-    for (int b = 0; b < 4; b++) r |= (((x >> (2 + b)) & 1) << (2 * b)) | (((y >> (2 + b)) & 1) << (2 * b + 1));
-    return r * 16;
-  }
   KVZ_DEV static int cbf_is_set(uint16_t cbf, int depth, int plane) { return (cbf & ((0x1f >> depth) << (5 * plane))) != 0; }
   KVZ_DEV static void cbf_set(uint16_t *cbf, int depth, int plane) { *cbf |= (0x10 >> depth) << (5 * plane); }
   KVZ_DEV static void cbf_clear(uint16_t *cbf, int depth, int plane) { *cbf &= ~((0x1f >> depth) << (5 * plane)); }
@@ -540,13 +529,7 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
     int l = 1, a = 1;
     if (left >= 0 && KVZ_NB_TYPE(left) == 1) l = KVZ_NB_MODE(left);
     if (above >= 0 && KVZ_NB_TYPE(above) == 1 && (y & 63) != 0) a = KVZ_NB_MODE(above);
-    if (l == a) {
-      if (l > 1) { preds[0] = (int8_t)l; preds[1] = (int8_t)(((l + 29) % 32) + 2); preds[2] = (int8_t)(((l - 1) % 32) + 2); }
-      else { preds[0] = 0; preds[1] = 1; preds[2] = 26; }
-    } else {
-      preds[0] = (int8_t)l; preds[1] = (int8_t)a;
-      if (l && a) preds[2] = 0; else preds[2] = (l + a) < 2 ? 26 : 1;
-    }
+    intra_mpm(l, a, preds);
   }
   // CABAC_FBITS_UPDATE (cabac.h:133-139) on context idx of `c`: the price of `bin` (CTX_ENTROPY_FBITS, cabac.h:131), then -- if
   // `update`, and unless the model freezes the contexts at their slice-start state -- the transition kvz_cabac_encode_bin
@@ -649,21 +632,16 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
   // the bits of one transform block's residual syntax priced on context set *c, whose states move only with `update` (the coder works
   // on a copy of the search contexts, `update` flag included).  Sign data hiding, transform skip and encryption are off in this
   // configuration.  coeff: log2w x log2w levels, row-major, in LDS; type 0 luma / 2 chroma; scan 0 diagonal, 1 horizontal, 2 vertical.
-  // One lane.  HEVC scans are hierarchical -- 4x4 groups in group order, the same 16-position pattern inside each group -- so both
-  // orders come from three packed constants instead of the 1024-entry tables.
-  KVZ_DEV static int scan_in_group(int scan, int k)  // raster index inside the 4x4 group of the k-th position (tables.c kvz_g_sig_last_scan, 4x4 entries)
+  // The scans, context increments and the last position's layout are kvz_syntax.hpp's.
+  // Tables::diag8 for scan_group(): RDOQ instantiations have it staged per CTU in LDS (run()) -- a load from global memory in front of every group of a 32x32 block otherwise
+  KVZ_DEV const u8 *diag8() const
   {
-    const unsigned long long pat = scan == 0 ? 0xfbe7ad369c258140ull : (scan == 1 ? 0xfedcba9876543210ull : 0xfb73ea62d951c840ull);
-    return (int)((pat >> (4 * k)) & 15);
+    if constexpr (RDOQ) return rl->diag8;
+    else return tb->diag8;
   }
-  KVZ_DEV int group_of(int log2w, int scan, int i) const  // raster index of the i-th group in group order (tables.h:45-89 g_sig_last_scan_cg)
-  {
-    if (log2w == 2) return 0;
-    if (log2w == 3) return scan == 1 ? i : ((0x3120 >> (4 * i)) & 3);
-    if (log2w == 4) return scan_in_group(0, i);
-    if constexpr (RDOQ) return rl->diag8[i];  // staged per CTU (run()): a load from global memory in front of every group of a 32x32 block otherwise
-    else return tb->diag8[i];
-  }
+#ifdef KVZ_HOSTSIM
+  // The host simulation's stand-in for coeff_cabac_bits_wave below, one lane: the shared walk of the block's syntax (kvz_residual.hpp) with a sink that prices
+  // its bins.  The whole block at its first share (part 0 or 1), nothing at part 2.  (The device's forms are compared with the same oracle by the GPU tests.)
   KVZ_DEV double coeff_bin(CtxSet *c, bool update, int idx, int bin) const
   {
     const int st = c->s[idx];
@@ -671,15 +649,23 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
     if (update) c->s[idx] = (u8)ctx_next(st, bin);
     return bits;
   }
-  KVZ_DEV static int coeff_remain_bits(int symbol, int r_param)  // cabac.c:275-301 kvz_cabac_write_coeff_remain: number of bypass bins
+  struct CoeffPriceSink {
+    const CtuProgramT *p; CtxSet *c; bool update; double bits;
+    void ctx(int idx, int bin) { bits += p->coeff_bin(c, update, idx, bin); }
+    void ep(u32, int n) { bits += n; }
+  };
+  KVZ_DEV double coeff_cabac_bits_wave(CtxSet *c, bool update, const i16 *coeff, int log2w, int type, int scan, int part = 0) const
   {
-    if (symbol < (3 << r_param)) return (symbol >> r_param) + 1 + r_param;
-    int length = r_param, code = symbol - (3 << r_param);
-    while (code >= (1 << length)) { code -= 1 << length; length++; }
-    return 3 + length + 1 - r_param + length;
+    if (part == 2) return 0;
+    bool any = false;
+    for (int i = 0; i < (1 << (2 * log2w)); i++) any |= coeff[i] != 0;
+    if (!any) return 0;  // get_coeff_cabac_cost: no coefficient, no bits
+    CoeffPriceSink sink{ this, c, update && m->adaptive, 0.0 };
+    entropy_coeff_nxn(sink, tb, coeff, log2w, type, scan);
+    return sink.bits;
   }
-#ifndef KVZ_HOSTSIM
-  // The same count without the loop: the escape length L satisfies 2^L <= symbol - 2 * 2^r < 2^(L + 1)
+#else
+  // cabac.c:275-301 kvz_cabac_write_coeff_remain, the number of bypass bins, without its loop: the escape length L satisfies 2^L <= symbol - 2 * 2^r < 2^(L + 1)
   KVZ_DEV static int coeff_remain_bits_flat(int symbol, int r_param)
   {
     const int length = 31 - __builtin_clz((unsigned)imax(symbol - (2 << r_param), 1));
@@ -703,106 +689,7 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
     }
     return esc ? (unsigned)coeff_remain_bits_flat(absval - base_level, rice) : 0u;
   }
-#endif
-  KVZ_DEV static int sig_ctx_inc(int pattern, int scan, int px, int py, int log2w, int type)  // context.c:366-399 kvz_context_get_sig_ctx_inc
-  {
-    if (px + py == 0) return 0;
-    if (log2w == 2) return (int)((0x8877886654325410ull >> (4 * (4 * py + px))) & 15);  // ctx_ind_map
-    const int offset = log2w == 3 ? (scan == 0 ? 9 : 15) : (type == 0 ? 21 : 12), xs = px & 3, ys = py & 3;
-    int cnt;
-    if (pattern == 0) cnt = xs + ys <= 2 ? (xs + ys == 0 ? 2 : 1) : 0;
-    else if (pattern == 1) cnt = ys <= 1 ? (ys == 0 ? 2 : 1) : 0;
-    else if (pattern == 2) cnt = xs <= 1 ? (xs == 0 ? 2 : 1) : 0;
-    else cnt = 2;
-    return ((type == 0 && ((px >> 2) + (py >> 2)) > 0) ? 3 : 0) + offset + cnt;
-  }
-  KVZ_DEV double coeff_cabac_bits(CtxSet *c, bool update, const i16 *coeff, int log2w, int type, int scan) const
-  {
-    update = update && m->adaptive;
-    const int w = 1 << log2w, side = w >> 2, ngroups = side * side;
-    // which groups hold a level: four levels per 8-byte LDS read
-    unsigned long long sig = 0;
-    for (int g = 0; g < ngroups; g++) {
-      const int gy = g >> (log2w - 2), gx = g & (side - 1);
-      unsigned long long any = 0;
-      for (int r = 0; r < 4; r++) { unsigned long long four; __builtin_memcpy(&four, coeff + ((gy * 4 + r) << log2w) + gx * 4, 8); any |= four; }
-      if (any) sig |= 1ull << g;
-    }
-    if (!sig) return 0;  // get_coeff_cabac_cost: no coefficient, no bits
-    int last_group = ngroups - 1;
-    while (!((sig >> group_of(log2w, scan, last_group)) & 1)) last_group--;
-    double bits = 0;
-    int c1 = 1;
-    bool first = true;
-    for (int i = last_group; i >= 0; i--) {
-      const int g = group_of(log2w, scan, i), gy = g >> (log2w - 2), gx = g & (side - 1);
-      const i16 *base = coeff + ((gy * 4) << log2w) + gx * 4;
-      int abs_coeff[16], num = 0, k = 15;
-      if (first) {
-        // the last significant position and its coding (encode_coding_tree.c:63-115 kvz_encode_last_significant_xy)
-        while (!base[((scan_in_group(scan, k) >> 2) << log2w) + (scan_in_group(scan, k) & 3)]) k--;
-        const int r = scan_in_group(scan, k);
-        int lx = gx * 4 + (r & 3), ly = gy * 4 + (r >> 2);
-        abs_coeff[num++] = iabs(base[((r >> 2) << log2w) + (r & 3)]);
-        k--;
-        if (scan == 2) { const int tmp = lx; lx = ly; ly = tmp; }
-        const int index = log2w - 2, ctx_offset = type ? 0 : (index * 3 + (index + 1) / 4), shift = type ? index : (index + 3) / 4;
-        const int bx = (type ? KVZ_HIP_CX_LAST_X_CHROMA : KVZ_HIP_CX_LAST_X_LUMA) + ctx_offset, by = (type ? KVZ_HIP_CX_LAST_Y_CHROMA : KVZ_HIP_CX_LAST_Y_LUMA) + ctx_offset;
-        const unsigned long long gidx_lo = 0x7777666655443210ull;  // g_group_idx[0..15] (encoderstate.h:397); [16..23] = 8, [24..31] = 9
-        const int gxi = lx < 16 ? (int)((gidx_lo >> (4 * lx)) & 15) : (lx < 24 ? 8 : 9), gyi = ly < 16 ? (int)((gidx_lo >> (4 * ly)) & 15) : (ly < 24 ? 8 : 9);
-        const int gmax = w - 1 < 16 ? (int)((gidx_lo >> (4 * (w - 1))) & 15) : 9;
-        for (int q = 0; q < gxi; q++) bits += coeff_bin(c, update, bx + (q >> shift), 1);
-        if (gxi < gmax) bits += coeff_bin(c, update, bx + (gxi >> shift), 0);
-        for (int q = 0; q < gyi; q++) bits += coeff_bin(c, update, by + (q >> shift), 1);
-        if (gyi < gmax) bits += coeff_bin(c, update, by + (gyi >> shift), 0);
-        if (gxi > 3) bits += (gxi - 2) / 2;  // suffixes: bypass bins
-        if (gyi > 3) bits += (gyi - 2) / 2;
-      }
-      const bool right = gx < side - 1 && ((sig >> (g + 1)) & 1), lower = gy < side - 1 && ((sig >> (g + side)) & 1);
-      bool coded = (sig >> g) & 1;
-      if (i == last_group || i == 0) coded = true;  // inferred; the DC group is then scanned like a significant one
-      else bits += coeff_bin(c, update, KVZ_HIP_CX_SIG_CG + type + (right || lower), coded);  // context.c:315-327
-      if (coded) {
-        const int pattern = log2w == 2 ? -1 : (int)right + ((int)lower << 1);  // context.c:339-351
-        for (; k >= 0; k--) {
-          const int r = scan_in_group(scan, k), px = gx * 4 + (r & 3), py = gy * 4 + (r >> 2);
-          const int level = base[((r >> 2) << log2w) + (r & 3)];
-          if (k > 0 || i == 0 || num) bits += coeff_bin(c, update, (type == 0 ? KVZ_HIP_CX_SIG_LUMA : KVZ_HIP_CX_SIG_CHROMA) + sig_ctx_inc(pattern, scan, px, py, log2w, type), level != 0);
-          if (level) abs_coeff[num++] = iabs(level);
-        }
-      }
-      first = false;
-      if (num > 0) {
-        int ctx_set = (i > 0 && type == 0) ? 2 : 0;
-        if (c1 == 0) ctx_set++;
-        c1 = 1;
-        const int base_one = (type == 0 ? KVZ_HIP_CX_ONE_LUMA : KVZ_HIP_CX_ONE_CHROMA) + 4 * ctx_set, num_c1 = num < 8 ? num : 8;
-        int first_c2 = -1;
-        for (int q = 0; q < num_c1; q++) {
-          const int symbol = abs_coeff[q] > 1;
-          bits += coeff_bin(c, update, base_one + c1, symbol);
-          if (symbol) { c1 = 0; if (first_c2 == -1) first_c2 = q; }
-          else if (c1 < 3 && c1 > 0) c1++;
-        }
-        if (c1 == 0 && first_c2 != -1) bits += coeff_bin(c, update, (type == 0 ? KVZ_HIP_CX_ABS_LUMA : KVZ_HIP_CX_ABS_CHROMA) + ctx_set, abs_coeff[first_c2] > 2);
-        bits += num;  // signs
-        if (c1 == 0 || num > 8) {
-          int first_coeff2 = 1, go_rice = 0;
-          for (int q = 0; q < num; q++) {
-            const int base_level = q < 8 ? 2 + first_coeff2 : 1;
-            if (abs_coeff[q] >= base_level) {
-              bits += coeff_remain_bits(abs_coeff[q] - base_level, go_rice);
-              if (abs_coeff[q] > 3 * (1 << go_rice)) go_rice = go_rice + 1 < 4 ? go_rice + 1 : 4;
-            }
-            if (abs_coeff[q] >= 2) first_coeff2 = 0;
-          }
-        }
-      }
-    }
-    return bits;
-  }
-#ifndef KVZ_HOSTSIM
-  // The same count by a whole wavefront (all 64 lanes call it, converged; every argument wavefront-uniform).  What is parallel:
+  // The count by a whole wavefront (all 64 lanes call it, converged; every argument wavefront-uniform).  What is parallel:
   // the group masks (one lane per 4x4 group, one ballot), and inside a coded group the sixteen scan positions -- level, context
   // increment of its significance flag -- on sixteen lanes.  What stays serial is only what the standard makes serial: with
   // `update` the chain of state changes (one table lookup per bin, operands fetched from the lanes with v_readlane); without it
@@ -869,7 +756,7 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
     }
     const unsigned long long sig = __ballot(any);
     if (!sig) return 0;
-    const unsigned long long ord = __ballot(lane < ngroups && ((sig >> group_of(log2w, scan, lane < ngroups ? lane : 0)) & 1));
+    const unsigned long long ord = __ballot(lane < ngroups && ((sig >> scan_group(log2w, scan, lane < ngroups ? lane : 0, diag8())) & 1));
     const int last_group = 63 - __builtin_clzll(ord);
     auto price = [&](int ctx, int bin) -> unsigned { return (unsigned)(s->entropy_fbits[c->s[ctx] ^ bin] * 32768.0f); };
     unsigned acc = 0, byp = 0;        // per lane: Q15 price sum, bypass bins
@@ -877,7 +764,7 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
     int prev_c1_zero = 0;
     const int k = lane & 15;
     for (int i = last_group; i >= 0; i--) {
-      const int g = uni(group_of(log2w, scan, i)), gy = g >> (log2w - 2), gx = g & (side - 1);
+      const int g = uni(scan_group(log2w, scan, i, diag8())), gy = g >> (log2w - 2), gx = g & (side - 1);
       const i16 *base = coeff + ((gy * 4) << log2w) + gx * 4;
       const bool right = gx < side - 1 && ((sig >> (g + 1)) & 1), lower = gy < side - 1 && ((sig >> (g + side)) & 1);
       bool coded = (sig >> g) & 1;
@@ -893,11 +780,8 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
         const int k_last = 31 - __builtin_clz(nzmask), rl = scan_in_group(scan, k_last);
         int lx = gx * 4 + (rl & 3), ly = gy * 4 + (rl >> 2);
         if (scan == 2) { const int tmp = lx; lx = ly; ly = tmp; }
-        const int index = log2w - 2, ctx_offset = type ? 0 : (index * 3 + (index + 1) / 4), shift = type ? index : (index + 3) / 4;
-        const int bx = (type ? KVZ_HIP_CX_LAST_X_CHROMA : KVZ_HIP_CX_LAST_X_LUMA) + ctx_offset, by = (type ? KVZ_HIP_CX_LAST_Y_CHROMA : KVZ_HIP_CX_LAST_Y_LUMA) + ctx_offset;
-        const unsigned long long gidx_lo = 0x7777666655443210ull;
-        const int gxi = lx < 16 ? (int)((gidx_lo >> (4 * lx)) & 15) : (lx < 24 ? 8 : 9), gyi = ly < 16 ? (int)((gidx_lo >> (4 * ly)) & 15) : (ly < 24 ? 8 : 9);
-        const int gmax = w - 1 < 16 ? (int)((gidx_lo >> (4 * (w - 1))) & 15) : 9;
+        const LastPosCtx lp = last_pos_ctx(log2w, type);
+        const int shift = lp.shift, bx = lp.base_x, by = lp.base_y, gmax = group_idx(w - 1), gxi = group_idx(lx), gyi = group_idx(ly);
         if (lane < gxi || (lane == gxi && gxi < gmax)) acc += price(bx + (lane >> shift), lane < gxi);
         { const int l2 = lane - 16; if (l2 >= 0 && (l2 < gyi || (l2 == gyi && gyi < gmax))) acc += price(by + (l2 >> shift), l2 < gyi); }
         if (gxi > 3) bypass += (unsigned long long)((gxi - 2) / 2);
@@ -930,20 +814,11 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
       }
     }
     // rows of 16 lanes first (each row's sum fits 32 bits), then the four row totals
-    unsigned x = acc;
-    x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xF, 0xF, true);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xF, 0xF, true);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xF, 0xF, true);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xF, 0xF, true);
-    unsigned y = byp;
-    y += __builtin_amdgcn_update_dpp(0, y, 0x118, 0xF, 0xF, true);
-    y += __builtin_amdgcn_update_dpp(0, y, 0x114, 0xF, 0xF, true);
-    y += __builtin_amdgcn_update_dpp(0, y, 0x112, 0xF, 0xF, true);
-    y += __builtin_amdgcn_update_dpp(0, y, 0x111, 0xF, 0xF, true);
+    const int x = row16_sum((int)acc), y = row16_sum((int)byp);
     unsigned long long q15 = 0;
     for (int row = 0; row < 4; row++) {
-      q15 += (unsigned)__builtin_amdgcn_readlane((int)x, 16 * row + 15);
-      bypass += (unsigned)__builtin_amdgcn_readlane((int)y, 16 * row + 15);
+      q15 += (unsigned)__builtin_amdgcn_readlane(x, 16 * row + 15);
+      bypass += (unsigned)__builtin_amdgcn_readlane(y, 16 * row + 15);
     }
     q15 += bypass << 15;
     return (double)q15 / 32768.0;
@@ -967,7 +842,7 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
     const unsigned long long sig = __ballot(any);  // bit g: group g (raster) holds a level
     if (!sig) return 0;
     WaveCtx wc = wave_ctx_load(c, lane, type);
-    const unsigned long long ord = __ballot(lane < ngroups && ((sig >> group_of(log2w, scan, lane < ngroups ? lane : 0)) & 1));  // the same in group order
+    const unsigned long long ord = __ballot(lane < ngroups && ((sig >> scan_group(log2w, scan, lane < ngroups ? lane : 0, diag8())) & 1));  // the same in group order
     const int last_group = 63 - __builtin_clzll(ord);
     unsigned long long q15 = 0;
     unsigned acc_par = 0;  // per lane: Q15 prices of the bins counted one context per lane
@@ -980,7 +855,7 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
     };
     bool prev_gt1 = false;  // the previous group with levels held one above 1 (c1 == 0 at its end)
     for (int i = last_group; i >= 0; i--) {
-      const int g = uni(group_of(log2w, scan, i)), gy = g >> (log2w - 2), gx = g & (side - 1);
+      const int g = uni(scan_group(log2w, scan, i, diag8())), gy = g >> (log2w - 2), gx = g & (side - 1);
       const i16 *base = coeff + ((gy * 4) << log2w) + gx * 4;
       const bool right = gx < side - 1 && ((sig >> (g + 1)) & 1), lower = gy < side - 1 && ((sig >> (g + side)) & 1);
       bool coded = (sig >> g) & 1;
@@ -998,11 +873,8 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
         const int k_last = 31 - __builtin_clz(nzmask), rl = scan_in_group(scan, k_last);
         int lx = gx * 4 + (rl & 3), ly = gy * 4 + (rl >> 2);
         if (scan == 2) { const int tmp = lx; lx = ly; ly = tmp; }
-        const int index = log2w - 2, ctx_offset = type ? 0 : (index * 3 + (index + 1) / 4), shift = type ? index : (index + 3) / 4;
-        const int bx = (type ? KVZ_HIP_CX_LAST_X_CHROMA : KVZ_HIP_CX_LAST_X_LUMA) + ctx_offset, by = (type ? KVZ_HIP_CX_LAST_Y_CHROMA : KVZ_HIP_CX_LAST_Y_LUMA) + ctx_offset;
-        const unsigned long long gidx_lo = 0x7777666655443210ull;
-        const int gxi = lx < 16 ? (int)((gidx_lo >> (4 * lx)) & 15) : (lx < 24 ? 8 : 9), gyi = ly < 16 ? (int)((gidx_lo >> (4 * ly)) & 15) : (ly < 24 ? 8 : 9);
-        const int gmax = w - 1 < 16 ? (int)((gidx_lo >> (4 * (w - 1))) & 15) : 9;
+        const LastPosCtx lp = last_pos_ctx(log2w, type);
+        const int shift = lp.shift, bx = lp.base_x, by = lp.base_y, gmax = group_idx(w - 1), gxi = group_idx(lx), gyi = group_idx(ly);
         const int jx = lane - wlane_last(bx), jy = lane - wlane_last(by);
         int ones = 0;
         bool zero = false;
@@ -1073,32 +945,15 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
       }
     }
     {  // rows of 16 lanes first (each row's sum fits 32 bits), then the four row totals
-      unsigned x = acc_par;
-      x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xF, 0xF, true);
-      x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xF, 0xF, true);
-      x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xF, 0xF, true);
-      x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xF, 0xF, true);
-      for (int row = 0; row < 4; row++) q15 += (unsigned)__builtin_amdgcn_readlane((int)x, 16 * row + 15);
-      unsigned y = byp_par;  // lanes 0..15 only
-      y += __builtin_amdgcn_update_dpp(0, y, 0x118, 0xF, 0xF, true);
-      y += __builtin_amdgcn_update_dpp(0, y, 0x114, 0xF, 0xF, true);
-      y += __builtin_amdgcn_update_dpp(0, y, 0x112, 0xF, 0xF, true);
-      y += __builtin_amdgcn_update_dpp(0, y, 0x111, 0xF, 0xF, true);
-      q15 += (unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)y, 15) << 15;
+      const int x = row16_sum((int)acc_par);
+      for (int row = 0; row < 4; row++) q15 += (unsigned)__builtin_amdgcn_readlane(x, 16 * row + 15);
+      const int y = row16_sum((int)byp_par);  // lanes 0..15 only
+      q15 += (unsigned long long)(unsigned)__builtin_amdgcn_readlane(y, 15) << 15;
     }
     wave_ctx_store(c, wc, lane, type, part);
     return (double)q15 / 32768.0;
   }
 #endif
-  // encoderstate.c:1761-1775 kvz_get_scan_order for an intra CU (the chroma mode is the luma mode here)
-  KVZ_DEV static int scan_order(int mode, int depth)
-  {
-    if (depth >= 3) {
-      if (mode >= 6 && mode <= 14) return 2;
-      if (mode >= 22 && mode <= 30) return 1;
-    }
-    return 0;
-  }
   // Levels of the unit being evaluated / priced, in LDS: 8x8 CUs (the child a3q of the current 16x16), 16x16 CUs and 32x32 merges keep theirs there anyway
   // (lv3_coeff / lv2_coeff / lv1_coeff); with the CABAC model the 32x32 units of the 64x64 attempt stage a copy in lv1_coeff (recon_tus stage 4)
   KVZ_DEV i16 *levels_lds(int lv, int c) const
@@ -1873,11 +1728,7 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
 #ifdef KVZ_HOSTSIM
     if (tid < 96) acc3[tid < 64 ? 0 : (tid < 80 ? 1 : 2)] += v;
 #else
-    int x = (int)v;
-    x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xF, 0xF, true);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xF, 0xF, true);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xF, 0xF, true);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xF, 0xF, true);
+    const int x = row16_sum((int)v);
     const u32 r0 = (u32)__builtin_amdgcn_readlane(x, 15), r1 = (u32)__builtin_amdgcn_readlane(x, 31), r2 = (u32)__builtin_amdgcn_readlane(x, 47), r3 = (u32)__builtin_amdgcn_readlane(x, 63);
     if ((tid & 63) == 0) {  // one writer per slot and stage: the slots were zeroed in stage 1
       if (tid < 64) acc3[0] += r0 + r1 + r2 + r3;
@@ -2028,7 +1879,7 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
     const int sh = c ? 1 : 0;
     if ((NXN && lv == 4) || lv == 3) return levels_lds(lv, c);
     return lv == 2 ? s->lv2_coeff + (c == 0 ? 0 : (c == 1 ? 256 : 320))
-         : lv == 1 ? s->lv1_coeff + (c == 0 ? 0 : (c == 1 ? 1024 : 1280)) : coeff_level(lv) + plane_off(c) + zorder(xl >> sh, yl >> sh);
+         : lv == 1 ? s->lv1_coeff + (c == 0 ? 0 : (c == 1 ? 1024 : 1280)) : coeff_level(lv) + plane_off(c) + ctu_zorder(xl >> sh, yl >> sh);
   }
   // Entry (k, i) of the transform of a 2^l2 block of plane c: the DCT, except 4x4 intra luma (strategies-dct.c:82-86, 111-115: the DST), which only the PUs of
   // an NxN CU have
@@ -2106,7 +1957,7 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
           RdoqWaveArgs ra;
           ra.ptab = (KVZ_LDS_PTR(const i32))rl->ptab; ra.coef = (KVZ_LDS_PTR(const i16))tbuf(t, 0, c); ra.dest = (KVZ_LDS_PTR(i16))cout;
           ra.diag8 = (KVZ_LDS_PTR(const u8))rl->diag8; ra.lambda = m->lambda; ra.qp = m->qp; ra.log2w = l2; ra.type = c ? 2 : 0;
-          ra.scan_mode = scan_order(mode, depth);
+          ra.scan_mode = intra_scan_order(mode, depth);
           // tr_depth = cu->tr_depth - cu->depth: 1 for the 32x32 units of the 64x64 attempt (level 0), 0 otherwise -- plus one for an NxN CU
           // (quant-generic.c:237-238): 2 for the blocks of its PUs (level 4)
           ra.tr_depth = lv == 4 ? 2 : (lv == 0 ? 1 : 0);
@@ -2219,37 +2070,35 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
   KVZ_DEV QuantScalars quant_scalars_dev(int log2w, int type) const
   {
     // quant-generic.c:57-66, 303-339 with flat scaling lists, 8 bit, I slice (kvz_tables.hpp quant_scalars)
-    const int quant_scales[6] = { 26214, 23302, 20560, 18396, 16384, 14564 }, inv_scales[6] = { 40, 45, 51, 57, 64, 72 };
-    const u8 chroma_scale[58] = { 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 29, 30, 31, 32,
-                                  33, 33, 34, 34, 35, 35, 36, 36, 37, 37, 38, 39, 40, 41, 42, 43, 44, 45, 46, 47, 48, 49, 50, 51 };
-    int qps = m->qp;
-    if (type != 0) { int q = iclip(0, 57, m->qp); qps = chroma_scale[q]; }
+    const int qps = type == 0 ? m->qp : chroma_qp(m->qp);
     QuantScalars q;
     const int transform_shift = 15 - 8 - log2w;
     q.q_bits = 14 + qps / 6 + transform_shift;
     q.add = 171 << (q.q_bits - 9);
-    q.flat_q = quant_scales[qps % 6];
+    q.flat_q = quant_scale(qps % 6);
     q.dq_shift = 20 - 14 - transform_shift;
-    q.dq_scale = inv_scales[qps % 6] << (qps / 6);
+    q.dq_scale = inv_quant_scale(qps % 6) << (qps / 6);
     q.dq_list = 0; q.dq_qp_per = qps / 6;
     return q;
   }
 
-  // get_coeff_cabac_cost (rdo.c:220-263) of the planes of one transform unit that have levels, luma first (search.c:518-547).
-  // On the device the callers bring the whole wavefront that plays threads 0..63 (KVZ_UNIT_COEFF_BITS), in the host simulation thread 0.
+  // Who prices coefficients with the CABAC model -- THE place where the device and the host simulation part.  Device: every lane of both wavefronts (the wavefront
+  // forms are cooperative).  Host simulation: one thread stands for each wavefront, 0 and 64, and its coeff_cabac_bits_wave is the one-lane coder -- threads run one
+  // after the other there, so all of thread 0's blocks come before thread 64's; the two roles' contexts are disjoint, which is what lets the device run them side by side.
+#ifdef KVZ_HOSTSIM
+  KVZ_DEV static bool prices_coeffs(int tid) { return tid == 0 || tid == 64; }
+#else
+  KVZ_DEV static bool prices_coeffs(int) { return true; }
+#endif
+  // get_coeff_cabac_cost (rdo.c:220-263) of the planes of one transform unit that have levels, luma first (search.c:518-547): the calling thread's share of the bits.
+  // The wavefront playing threads 0..63 takes the luma block's coded-group and significance flags (coeff_cabac_bits_wave's part 1, the longest chains), the other
+  // one the two chroma blocks and then the luma block's other classes (part 2) -- luma and chroma contexts are disjoint and so are the two classes of luma
+  // contexts, so the chains are independent even with updates on.
   KVZ_DEV double unit_coeff_bits(CtxSet *c, bool update, int lv, int depth, int mode, int cb_y, int cb_u, int cb_v, int tid) const
   {
-    const int lw = 6 - depth, lc = depth >= 3 ? 2 : lw - 1, scan = scan_order(mode, depth);
+    const int lw = 6 - depth, lc = depth >= 3 ? 2 : lw - 1, scan = intra_scan_order(mode, depth);
     double bits = 0;
-#ifdef KVZ_HOSTSIM
-    (void)tid;
-    if (cb_y) bits += coeff_cabac_bits(c, update, levels_lds(lv, 0), lw, 0, scan);
-    if (cb_u) bits += coeff_cabac_bits(c, update, levels_lds(lv, 1), lc, 2, scan);
-    if (cb_v) bits += coeff_cabac_bits(c, update, levels_lds(lv, 2), lc, 2, scan);
-#else  // both wavefronts are here: the one playing threads 0..63 takes the luma block, the other one the two chroma blocks -- luma and
-       // chroma contexts are disjoint, so the two chains (Y | U -> V) are independent even with updates on
-    // ... and the luma block's own bins split again: its significance flags (the longest chains) stay on the first wavefront, the second one
-    // takes the luma block's other classes after the chroma blocks
+    if (!prices_coeffs(tid)) return bits;
     if (tid < 64) {
       if (cb_y) bits += coeff_cabac_bits_wave(c, update, levels_lds(lv, 0), lw, 0, scan, 1);
     } else {
@@ -2257,23 +2106,12 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
       if (cb_v) bits += coeff_cabac_bits_wave(c, update, levels_lds(lv, 2), lc, 2, scan);
       if (cb_y) bits += coeff_cabac_bits_wave(c, update, levels_lds(lv, 0), lw, 0, scan, 2);
     }
-#endif
     return bits;
   }
   // ... of the unit just reconstructed (levels in levels_lds(lv), non-zero counts in acc[6..8]) into *out, for thread 0 to pick up
   // in a later phase (same wavefront: no barrier needed in between)
-#ifdef KVZ_HOSTSIM
-#define KVZ_UNIT_COEFF_BITS(tid) ((tid) == 0)
-#else
-#define KVZ_UNIT_COEFF_BITS(tid) ((tid) < 64)
-#endif
   KVZ_DEV void price_unit_coeffs(CtxSet *c, bool update, int lv, int depth, int mode, double *out) const
   {
-#ifdef KVZ_HOSTSIM
-    KVZ_FOR_THREADS(tid) {
-      if (tid == 0) *out = unit_coeff_bits(c, update, lv, depth, mode, s->acc[6] != 0, s->acc[7] != 0, s->acc[8] != 0, tid);
-    }
-#else
     // the two wavefronts' shares meet in two doubles that alias child_acc[3][1..4]: dead here -- it is only written after the fourth
     // unit of the 64x64 attempt has been priced, and read right after that loop (try_merge)
     double *part = reinterpret_cast<double *>(&s->child_acc[3][1]);
@@ -2285,7 +2123,6 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
     KVZ_FOR_THREADS(tid) {
       if (tid == 0) *out = part[0] + part[1];  // multiples of 2^-15 far below 2^38: the sum is exact in any order
     }
-#endif
   }
   // search.c:425-541 cu_rd_cost_tr_split_accurate for one leaf TU group whose sums sit in s->acc (lane 0 only)
   // `known_coeff_bits`: the units of the 64x64 attempt had their coefficients priced when their levels were staged (try_merge)
@@ -2449,7 +2286,7 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
       }
       if (coeffs || (split_won && res_depth == 2)) {
         i16 *dst = coeff_level(3);
-        const unsigned zy = zorder(xl, yl), zc = zorder(xl >> 1, yl >> 1);
+        const unsigned zy = ctu_zorder(xl, yl), zc = ctu_zorder(xl >> 1, yl >> 1);
         if (w == 16) {  // the challengers' levels never left LDS: the 16x16 CU's, or -- the split wins -- those of the 8x8 CUs that lie inside the picture
           const int fx = cx + xl, fy = cy + yl;
           move_levels<true>(dst, split_won ? s->lv3_coeff : s->lv2_coeff, 256, zy, zc, tid, [&](int e) {
@@ -2708,7 +2545,7 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
         RdoqWaveArgs ra;
         ra.ptab = (KVZ_LDS_PTR(const i32))rl->ptab; ra.coef = (KVZ_LDS_PTR(const i16))tbuf(t, 0, c); ra.dest = (KVZ_LDS_PTR(i16))levels_lds(4, c);
         ra.diag8 = (KVZ_LDS_PTR(const u8))rl->diag8; ra.lambda = m->lambda; ra.qp = m->qp; ra.log2w = 2; ra.type = c ? 2 : 0;
-        ra.scan_mode = scan_order(mode, 4);
+        ra.scan_mode = intra_scan_order(mode, 4);
         ra.tr_depth = 2;  // cu->tr_depth - cu->depth + 1 for an NxN CU (quant-generic.c:237-238)
 #if defined(KVZ_CTU_PROFILE) && !defined(KVZ_HOSTSIM)
         ra.prof = s->prof_rq;
@@ -3111,14 +2948,9 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
       }
       KVZ_SYNC();
       KVZ_FOR_THREADS(tid) {
-#ifdef KVZ_HOSTSIM
-        if (tid == 0) {
-#else
-        // independent chains on the two wavefronts: the significance flags of the luma blocks on one, the chroma blocks and the luma blocks' other
-        // classes on the other (coeff_cabac_bits_wave's `part`)
-        const bool luma_role = tid < 64, chroma_role = !luma_role;
-        {  // both wavefronts walk the quadrant's units (everything they branch on is wavefront-uniform)
-#endif
+        if (prices_coeffs(tid)) {
+          // independent chains on the two wavefronts, split as in unit_coeff_bits(); both walk the quadrant's units (everything they branch on is wavefront-uniform)
+          const bool luma_role = tid < 64, chroma_role = !luma_role;
           CtxSet *c = &s->pre[0];
           int i = 16 * q;
           while (i < 16 * q + 16) {
@@ -3128,34 +2960,23 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
             if (NXN && cu->tr_depth == 4) {
               // four 4x4 luma blocks, each scanned by its own PU's mode, then the 4x4 chroma blocks under the first PU's (encode_coding_tree.c:148-163)
               const u8 *pm = rl->mode4[0][(yl >> 3) * 8 + (xl >> 3)];
-              const i16 *y4 = s->lv1_coeff + (zorder(xl, yl) - q * 1024), *u4 = s->lv1_coeff + 1024 + (zorder(xl >> 1, yl >> 1) - q * 256);
-              const int cscan = scan_order(pm[0], 4);
-#ifdef KVZ_HOSTSIM
-              for (int j = 0; j < 4; j++) if ((cu->cbf >> j) & 1) coeff_cabac_bits(c, true, y4 + 16 * j, 2, 0, scan_order(pm[j], 4));
-              if ((cu->cbf >> 5) & 1) coeff_cabac_bits(c, true, u4, 2, 2, cscan);
-              if ((cu->cbf >> 10) & 1) coeff_cabac_bits(c, true, u4 + 256, 2, 2, cscan);
-#else
-              for (int j = 0; j < 4; j++) if (luma_role && ((cu->cbf >> j) & 1)) coeff_cabac_bits_wave(c, true, y4 + 16 * j, 2, 0, scan_order(pm[j], 4), 1);
+              const i16 *y4 = s->lv1_coeff + (ctu_zorder(xl, yl) - q * 1024), *u4 = s->lv1_coeff + 1024 + (ctu_zorder(xl >> 1, yl >> 1) - q * 256);
+              const int cscan = intra_scan_order(pm[0], 4);
+              for (int j = 0; j < 4; j++) if (luma_role && ((cu->cbf >> j) & 1)) coeff_cabac_bits_wave(c, true, y4 + 16 * j, 2, 0, intra_scan_order(pm[j], 4), 1);
               if (chroma_role && ((cu->cbf >> 5) & 1)) coeff_cabac_bits_wave(c, true, u4, 2, 2, cscan);
               if (chroma_role && ((cu->cbf >> 10) & 1)) coeff_cabac_bits_wave(c, true, u4 + 256, 2, 2, cscan);
-              for (int j = 0; j < 4; j++) if (chroma_role && ((cu->cbf >> j) & 1)) coeff_cabac_bits_wave(c, true, y4 + 16 * j, 2, 0, scan_order(pm[j], 4), 2);
-#endif
+              for (int j = 0; j < 4; j++) if (chroma_role && ((cu->cbf >> j) & 1)) coeff_cabac_bits_wave(c, true, y4 + 16 * j, 2, 0, intra_scan_order(pm[j], 4), 2);
               i += 1;
               continue;
             }
             const int td = cu->depth < 1 ? 1 : cu->depth;  // a 64x64 CU codes four 32x32 units, each read at its own origin
-            const int lw = 6 - td, lc = td == 3 ? 2 : lw - 1, scan = scan_order(cu->mode, td);
-            const i16 *y = s->lv1_coeff + (zorder(xl, yl) - q * 1024), *u = s->lv1_coeff + 1024 + (zorder(xl >> 1, yl >> 1) - q * 256);
-#ifdef KVZ_HOSTSIM
-            if (cbf_is_set(cu->cbf, td, 0)) coeff_cabac_bits(c, true, y, lw, 0, scan);
-            if (cbf_is_set(cu->cbf, td, 1)) coeff_cabac_bits(c, true, u, lc, 2, scan);
-            if (cbf_is_set(cu->cbf, td, 2)) coeff_cabac_bits(c, true, u + 256, lc, 2, scan);
-#else
+            const int lw = 6 - td, lc = td == 3 ? 2 : lw - 1, scan = intra_scan_order(cu->mode, td);
+            const i16 *y = s->lv1_coeff + (ctu_zorder(xl, yl) - q * 1024), *u = s->lv1_coeff + 1024 + (ctu_zorder(xl >> 1, yl >> 1) - q * 256);
+            // (spelled out: with unit_coeff_bits() called here the CABAC kernels' register allocation moves -- SGPR spills 188 -> 184 in the headline one)
             if (luma_role && cbf_is_set(cu->cbf, td, 0)) coeff_cabac_bits_wave(c, true, y, lw, 0, scan, 1);
             if (chroma_role && cbf_is_set(cu->cbf, td, 1)) coeff_cabac_bits_wave(c, true, u, lc, 2, scan);
             if (chroma_role && cbf_is_set(cu->cbf, td, 2)) coeff_cabac_bits_wave(c, true, u + 256, lc, 2, scan);
             if (chroma_role && cbf_is_set(cu->cbf, td, 0)) coeff_cabac_bits_wave(c, true, y, lw, 0, scan, 2);
-#endif
             i += 1 << (2 * (3 - td));
           }
         }

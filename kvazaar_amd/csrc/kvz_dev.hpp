@@ -785,7 +785,7 @@ inline void deblock_frames_on(hipStream_t stream, u8 *frames, int width, int hei
   g.tc1 = deblock_tc(iclip(0, 53, qp + 2 * tc_off));  // filter.c:496-497 with strength 1
   g.beta = deblock_beta(iclip(0, 51, qp + 2 * beta_off));
   g.tc = deblock_tc(iclip(0, 53, qp + 2 + 2 * tc_off));                  // filter.c:496-497 with strength 2
-  g.tc_c = deblock_tc(iclip(0, 53, chroma_qp_of(qp) + 2 + 2 * tc_off));  // filter.c:592-595
+  g.tc_c = deblock_tc(iclip(0, 53, chroma_qp(qp) + 2 + 2 * tc_off));  // filter.c:592-595
   const int cw = width >> 1, ch = height >> 1;
   auto grid = [](long n) { return dim3((unsigned)((n + 255) / 256)); };
   const long lv = (long)n_frames * (width >> 3) * (height >> 2), lh = (long)n_frames * (width >> 2) * (height >> 3);

@@ -114,26 +114,12 @@ struct DeferSink {
   }
 };
 
-KVZ_DEV unsigned entropy_zorder(int x, int y)  // cu.h:385-421 with width 64: Morton index of the 4x4 block times 16
-{
-  unsigned r = 0;
-  for (int b = 0; b < 4; b++) r |= (((unsigned)(x >> (2 + b)) & 1u) << (2 * b)) | (((unsigned)(y >> (2 + b)) & 1u) << (2 * b + 1));
-  return r * 16;
-}
 KVZ_DEV bool entropy_any(const i16 *c, int n)
 {
   // levels are stored as 16-bit values, blocks are 8-byte aligned (16 levels at least)
   const unsigned long long *q = (const unsigned long long *)c;
   for (int i = 0; i < n / 4; i++) if (q[i]) return true;
   return false;
-}
-KVZ_DEV int entropy_scan_order(int mode, int depth)  // encoderstate.c:1761-1775 kvz_get_scan_order, intra
-{
-  if (depth >= 3) {
-    if (mode >= 6 && mode <= 14) return 2;
-    if (mode >= 22 && mode <= 30) return 1;
-  }
-  return 0;
 }
 
 // Per-call form (strategies-encode.h:49-65 kvz_encode_coeff_nxn): the bins of ONE transform block.  out[0] = number of records, out[1..] the records (as many as fit
@@ -165,18 +151,18 @@ struct EntropyCtu {  // one CTU of one picture
   {
     const int w = 64 >> depth;
     const int cw = depth >= 3 ? 4 : w / 2;
-    if (c == 0) return entropy_any(ctu + entropy_zorder(xl, yl), w * w);
-    return entropy_any(ctu + (c == 1 ? 4096 : 5120) + entropy_zorder((xl & ~7) / 2, (yl & ~7) / 2), cw * cw);
+    if (c == 0) return entropy_any(ctu + ctu_zorder(xl, yl), w * w);
+    return entropy_any(ctu + (c == 1 ? 4096 : 5120) + ctu_zorder((xl & ~7) / 2, (yl & ~7) / 2), cw * cw);
   }
   // encode_transform_unit (encode_coding_tree.c:117-190) of the block at (x, y), tree depth `depth`
   template <class S> KVZ_DEV void transform_unit(S &s, int x, int y, int depth, bool cb_y, bool cu_u, bool cu_v) const
   {
     const int xl = x & 63, yl = y & 63, log2w = 6 - depth, log2c = depth == 4 ? 2 : log2w - 1;
-    if (cb_y) s.tu(tb, ctu, (int)entropy_zorder(xl, yl), log2w, 0, entropy_scan_order(mode_at(x, y), depth));
+    if (cb_y) s.tu(tb, ctu, (int)ctu_zorder(xl, yl), log2w, 0, intra_scan_order(mode_at(x, y), depth));
     if (depth == 4 && (x % 8 == 0 || y % 8 == 0)) return;  // the 4x4 chroma blocks follow the last luma block, under the first PU's mode
-    const int cscan = entropy_scan_order(mode_at(x & ~7, y & ~7), depth), cxl = (xl & ~7) / 2, cyl = (yl & ~7) / 2;
-    if (cu_u) s.tu(tb, ctu, 4096 + (int)entropy_zorder(cxl, cyl), log2c, 2, cscan);
-    if (cu_v) s.tu(tb, ctu, 5120 + (int)entropy_zorder(cxl, cyl), log2c, 2, cscan);
+    const int cscan = intra_scan_order(mode_at(x & ~7, y & ~7), depth), cxl = (xl & ~7) / 2, cyl = (yl & ~7) / 2;
+    if (cu_u) s.tu(tb, ctu, 4096 + (int)ctu_zorder(cxl, cyl), log2c, 2, cscan);
+    if (cu_v) s.tu(tb, ctu, 5120 + (int)ctu_zorder(cxl, cyl), log2c, 2, cscan);
   }
   // encode_transform_coeff (encode_coding_tree.c:193-310) of an intra CU: one level of implicit split at most (64x64 CUs, NxN CUs), no split_transform_flag is ever coded
   template <class S> KVZ_DEV void transform_tree(S &s, int x, int y, int depth, bool nxn) const
@@ -206,17 +192,6 @@ struct EntropyCtu {  // one CTU of one picture
       if (cb_y | cb_u | cb_v) transform_unit(s, qx, qy, d, cb_y, cb_u, cb_v);
     }
   }
-  // intra.c:84-126 kvz_intra_get_dir_luma_predictor
-  KVZ_DEV static void mpm_candidates(int l, int a, int preds[3])
-  {
-    if (l == a) {
-      if (l > 1) { preds[0] = l; preds[1] = ((l + 29) % 32) + 2; preds[2] = ((l - 1) % 32) + 2; }
-      else { preds[0] = 0; preds[1] = 1; preds[2] = 26; }
-    } else {
-      preds[0] = l; preds[1] = a;
-      if (l && a) preds[2] = 0; else preds[2] = (l + a) < 2 ? 26 : 1;
-    }
-  }
   // the leaf of kvz_encode_coding_tree: part_mode, encode_intra_coding_unit (encode_coding_tree.c:467-652), the transform tree
   template <class S> KVZ_DEV void coding_unit(S &s, int x, int y, int depth) const
   {
@@ -228,7 +203,7 @@ struct EntropyCtu {  // one CTU of one picture
       const int px = x + 4 * (j & 1), py = y + 4 * (j >> 1);
       modes[j] = mode_at(px, py);
       const int l = px > 0 ? mode_at(px - 1, py) : 1, a = (py % 64 > 0 && py > 0) ? mode_at(px, py - 1) : 1;
-      mpm_candidates(l, a, preds[j]);
+      intra_mpm(l, a, preds[j]);
       mpm[j] = -1;
       for (int i = 2; i >= 0; i--) if (preds[j][i] == modes[j]) mpm[j] = i;
     }
@@ -465,7 +440,7 @@ struct EntropyCtuB {
       if (x > 0 && at(x - 1, y).type == 1) l = at(x - 1, y).mode;
       if (y % 64 > 0 && y > 0 && at(x, y - 1).type == 1) a = at(x, y - 1).mode;
       int preds[3], mpm = -1;
-      EntropyCtu::mpm_candidates(l, a, preds);
+      intra_mpm(l, a, preds);
       for (int i = 2; i >= 0; i--) if (preds[i] == cur.mode) mpm = i;
       s.ctx(KVZ_HIP_CX_INTRA, mpm != -1);
       if (mpm != -1) { s.ep(mpm == 0 ? 0 : 1, 1); if (mpm != 0) s.ep(mpm == 1 ? 0 : 1, 1); }
@@ -482,11 +457,11 @@ struct EntropyCtuB {
       s.ctx(KVZ_HIP_CX_CBF_CHROMA, cb_u);
       s.ctx(KVZ_HIP_CX_CBF_CHROMA, cb_v);
       s.ctx(KVZ_HIP_CX_CBF_LUMA + 1, cb_y);
-      scan = entropy_scan_order(cur.mode, depth);
+      scan = intra_scan_order(cur.mode, depth);
     }
-    if (cb_y) s.tu(tb, ctu, (int)entropy_zorder(xl, yl), log2w, 0, scan);
-    if (cb_u) s.tu(tb, ctu, 4096 + (int)entropy_zorder(xl / 2, yl / 2), log2c, 2, scan);
-    if (cb_v) s.tu(tb, ctu, 5120 + (int)entropy_zorder(xl / 2, yl / 2), log2c, 2, scan);
+    if (cb_y) s.tu(tb, ctu, (int)ctu_zorder(xl, yl), log2w, 0, scan);
+    if (cb_u) s.tu(tb, ctu, 4096 + (int)ctu_zorder(xl / 2, yl / 2), log2c, 2, scan);
+    if (cb_v) s.tu(tb, ctu, 5120 + (int)ctu_zorder(xl / 2, yl / 2), log2c, 2, scan);
   }
   template <class S> KVZ_DEV void coding_tree(S &s) const
   {

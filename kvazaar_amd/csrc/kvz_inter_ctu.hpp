@@ -356,12 +356,6 @@ struct InterCtu {
     const int sh = c ? 1 : 0;
     return PView{ (lu8 *)L->orgq + (c == 0 ? 0 : (c == 1 ? 1024 : 1280)) + ((yl & 31) >> sh) * (32 >> sh) + ((xl & 31) >> sh), 32 >> sh };
   }
-  IC_DEV unsigned zorder(int x, int y)
-  {
-    unsigned r = 0;
-    for (int b = 0; b < 4; b++) r |= (((unsigned)(x >> (2 + b)) & 1u) << (2 * b)) | (((unsigned)(y >> (2 + b)) & 1u) << (2 * b + 1));
-    return r * 16;
-  }
   // the quantised levels of the depth-lv CU at (xl, yl): candidates of depth 1 and 2 in the workgroup's scratch, a depth-3 CU's straight in the output block
   IC_DEV gi16 *out_coef() { return (gi16 *)g_ic.coef_out; }
   IC_DEV gi16 *coef(int lv, int c, int xl, int yl)
@@ -369,7 +363,7 @@ struct InterCtu {
     const int sh = c ? 1 : 0;
     if (lv == 1) return (gi16 *)S->cand1 + (c == 0 ? 0 : (c == 1 ? 1024 : 1280));
     if (lv == 2) return (gi16 *)S->cand2 + (c == 0 ? 0 : (c == 1 ? 256 : 320));
-    return out_coef() + (c == 0 ? 0 : (c == 1 ? 4096 : 5120)) + zorder(xl >> sh, yl >> sh);
+    return out_coef() + (c == 0 ? 0 : (c == 1 ? 4096 : 5120)) + ctu_zorder(xl >> sh, yl >> sh);
   }
   IC_DEV int plane_off(int c) { const int n = F.W * F.H; return c == 0 ? 0 : (c == 1 ? n : n + (n >> 2)); }  // (W, H even: n * 5 / 4 exactly)
   // plane c of the picture's reference FRAME (K->ref_w x K->ref_h; the picture lies at (K->tile_x, K->tile_y) in it)
@@ -399,11 +393,7 @@ struct InterCtu {
 #ifdef KVZ_HOSTSIM
     return part;
 #else
-    int x = (int)part;  // wave64: row_shr 8 / 4 / 2 / 1 inside rows of 16 lanes, then the four row totals
-    x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xF, 0xF, true);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xF, 0xF, true);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xF, 0xF, true);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xF, 0xF, true);
+    const int x = row16_sum((int)part);  // wave64: the four row totals
     return (u32)(__builtin_amdgcn_readlane(x, 15) + __builtin_amdgcn_readlane(x, 31) + __builtin_amdgcn_readlane(x, 47) + __builtin_amdgcn_readlane(x, 63));
 #endif
   }

@@ -301,13 +301,7 @@ IC_DEV void mpm_candidates(int y, bool has_left, const CuInfo &left, bool has_ab
   int l = 1, a = 1;
   if (has_left && left.type == 1) l = left.mode;
   if (has_above && above.type == 1 && y % 64 != 0) a = above.mode;
-  if (l == a) {
-    if (l > 1) { preds[0] = (int8_t)l; preds[1] = (int8_t)(((l + 29) % 32) + 2); preds[2] = (int8_t)(((l - 1) % 32) + 2); }
-    else { preds[0] = 0; preds[1] = 1; preds[2] = 26; }
-  } else {
-    preds[0] = (int8_t)l; preds[1] = (int8_t)a;
-    if (l && a) preds[2] = 0; else preds[2] = (int8_t)((l + a) < 2 ? 26 : 1);
-  }
+  intra_mpm(l, a, preds);
 }
 IC_DEV double luma_mode_bits(int mode, const int8_t preds[3], bool update)
 {
@@ -344,14 +338,6 @@ IC_FN double mock_encode_b(int x, int y, int depth, const CuInfo cu, bool update
   return bits;
 }
 
-IC_DEV int scan_order(int intra_mode, int depth)
-{
-  if (depth >= 3) {
-    if (intra_mode >= 6 && intra_mode <= 14) return 2;
-    if (intra_mode >= 22 && intra_mode <= 30) return 1;
-  }
-  return 0;
-}
 // cu_rd_cost_tr_split_accurate (search.c:425-550) of a CU whose transform tree is one unit (depth >= 1); coefficients priced as kvz_get_coeff_cost does (rdo.c:311-340):
 // the fast estimate the quantisation left in ccost, or -- picture QP >= 28 -- the residual coder in counting mode on the search contexts, luma then Cb then Cr, after
 // the tree's own flags as the reference orders them
@@ -372,7 +358,7 @@ IC_FN double rd_cost_b(int lv, int xl, int yl, int depth, const CuInfo pred, boo
   const u32 luma_ssd = L->ssd[0], chroma_ssd = L->ssd[1];
   if (!skip_residual) {
     if (M->coeff_cabac) {
-      const int scan = pred.type == 1 ? scan_order(pred.mode, depth) : 0;
+      const int scan = pred.type == 1 ? intra_scan_order(pred.mode, depth) : 0;
       if (cb_y) coeff_bits += coeff_bits_cabac(coef(lv, 0, xl, yl), ilog2i(width), 0, scan, update);
       if (cb_u) coeff_bits += coeff_bits_cabac(coef(lv, 1, xl, yl), ilog2i(cw), 2, scan, update);
       if (cb_v) coeff_bits += coeff_bits_cabac(coef(lv, 2, xl, yl), ilog2i(cw), 2, scan, update);
@@ -628,7 +614,7 @@ template <int DEPTH> IC_FN_CALL void code_coding_tree_b(int x, int y)
     price(IX_CBF_CHROMA, cb_u, true);
     price(IX_CBF_CHROMA, cb_v, true);
     price(IX_CBF_LUMA + 1, cb_y, true);
-    if (M->coeff_cabac) code_residual(x - cx, y - cy, depth, scan_order(cur.mode, depth), cb_y, cb_u, cb_v);
+    if (M->coeff_cabac) code_residual(x - cx, y - cy, depth, intra_scan_order(cur.mode, depth), cb_y, cb_u, cb_v);
   }
 }
 

@@ -133,11 +133,7 @@ template <int MAXN> __global__ void __launch_bounds__(256) dev_pu_search_kernel(
           const u8 *row = ref + (long)iclip(0, H - 1, Y + ryy) * W;
           for (int j = 0; j < per; j++) { const int c = s_cur[run + j], r = row[iclip(0, W - 1, X + rxx + j)]; part += (u32)(c > r ? c - r : r - c); }
         }
-        int x = (int)part;  // wave64 sum: row_shr 8 / 4 / 2 / 1 inside rows of 16 lanes, then the four row totals
-        x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xF, 0xF, true);
-        x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xF, 0xF, true);
-        x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xF, 0xF, true);
-        x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xF, 0xF, true);
+        const int x = row16_sum((int)part);  // wave64 sum: the four row totals
         const u32 total = (u32)(__builtin_amdgcn_readlane(x, 15) + __builtin_amdgcn_readlane(x, 31) + __builtin_amdgcn_readlane(x, 47) + __builtin_amdgcn_readlane(x, 63));
         if (lane == 0) s_sad[buf][k] = total;
       }

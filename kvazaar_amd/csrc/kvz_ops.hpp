@@ -41,6 +41,19 @@ KVZ_HD int iclip(int lo, int hi, int v) { return v < lo ? lo : (v > hi ? hi : v)
 KVZ_HD int imin(int a, int b) { return a < b ? a : b; }
 KVZ_HD int imax(int a, int b) { return a > b ? a : b; }
 KVZ_DEV u8 clip_pixel(int v) { return (u8)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
+#ifndef KVZ_HOSTSIM
+// Sums along the rows of 16 lanes of a wavefront: DPP row_shr 8 / 4 / 2 / 1 (lanes shifted in from outside the row read 0), so lane k of a row ends up with the sum of
+// the row's lanes 0..k and lane 15 with the row's total -- read the four totals with v_readlane 15 / 31 / 47 / 63.  No LDS traffic, no dependent shuffles.
+// Every lane of the wavefront must be here.
+KVZ_DEV int row16_sum(int v)
+{
+  v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, true);
+  v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xF, 0xF, true);
+  v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xF, 0xF, true);
+  v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, true);
+  return v;
+}
+#endif
 
 // ------------------------------------------------------------------------------------------------
 // Constant tables, uploaded once (kvz_tables.hpp builds them on the host).

@@ -10,74 +10,20 @@
 // kvz_hip_rdoq_blocks, kvz_hip_quantize_residual_rdoq) run it one wavefront per block (RdoqOp).  Rounds 2-3 also carried a one-lane transcription of rdo.c:661-1000 for the
 // per-call path; it is gone.
 #pragma once
-#include "kvz_ops.hpp"
+#include "kvz_syntax.hpp"
 
 namespace kvz {
 
-// The coefficient scans by arithmetic (HEVC scans are hierarchical: 4x4 groups in group order, sixteen positions inside a group): no table in memory on the
-// chain from one coefficient to the next.  diag8: the up-right diagonal order of an 8x8 grid (Tables::diag8), the group order of a 32x32 block.
+// Where a scan position lies in the block, by arithmetic (kvz_syntax.hpp: group order, then the position inside the group).  diag8: Tables::diag8, wherever the caller keeps it.
 template <class PtrU8> struct RdoqScanT {
   int log2w, mode;
   PtrU8 diag8;
-  KVZ_DEV static u32 in_group(int scan, int k)  // raster index inside the 4x4 group of its k-th position (tables.c kvz_g_sig_last_scan, 4x4 entries)
-  {
-    const unsigned long long pat = scan == 0 ? 0xfbe7ad369c258140ull : (scan == 1 ? 0xfedcba9876543210ull : 0xfb73ea62d951c840ull);
-    return (u32)((pat >> (4 * k)) & 15);
-  }
-  KVZ_DEV u32 cg(int i) const  // raster index of the i-th group in group order (tables.h:45-89 g_sig_last_scan_cg)
-  {
-    if (log2w == 2) return 0;
-    if (log2w == 3) return mode == 1 ? (u32)i : (u32)((0x3120 >> (4 * i)) & 3);
-    if (log2w == 4) return in_group(0, i);
-    return diag8[i];
-  }
   KVZ_DEV u32 pos(int scanpos) const  // raster index of a scan position in the block
   {
-    const u32 g = cg(scanpos >> 4), r = in_group(mode, scanpos & 15), side = 1u << (log2w - 2);
+    const u32 g = (u32)scan_group(log2w, mode, scanpos >> 4, diag8), r = (u32)scan_in_group(mode, scanpos & 15), side = 1u << (log2w - 2);
     return ((((g >> (log2w - 2)) << 2) + (r >> 2)) << log2w) + ((g & (side - 1)) << 2) + (r & 3);
   }
 };
-using RdoqScan = RdoqScanT<const u8 *>;
-
-KVZ_DEV int rdoq_group_idx(int pos)  // g_group_idx (rdo.c:60): index of the last-position prefix group
-{
-  return pos < 4 ? pos : (pos < 6 ? 4 : (pos < 8 ? 5 : (pos < 12 ? 6 : (pos < 16 ? 7 : (pos < 24 ? 8 : 9)))));
-}
-
-// quant tables of the flat lists: kvz_g_quant_scales (scalinglist.c:78)
-KVZ_DEV int rdoq_quant_scale(int qp_rem)
-{
-  return qp_rem == 0 ? 26214 : (qp_rem == 1 ? 23302 : (qp_rem == 2 ? 20560 : (qp_rem == 3 ? 18396 : (qp_rem == 4 ? 16384 : 14564))));
-}
-
-// chroma QP of a luma QP (kvz_get_scaled_qp, transform.c:141-155 with kvz_g_chroma_scale :56-62: H.265 table 8-10), 8 bit
-KVZ_DEV int rdoq_scaled_qp(int type, int qp)
-{
-  if (type == 0) return qp;
-  const int q = iclip(0, 57, qp);
-  if (q < 30) return q;
-  if (q >= 43) return q - 6;
-  const int tab[13] = { 29, 30, 31, 32, 33, 33, 34, 34, 35, 35, 36, 36, 37 };  // kvz_g_chroma_scale[30..42]
-  return tab[q - 30];
-}
-
-// context.c:366-399 kvz_context_get_sig_ctx_inc
-KVZ_DEV int rdoq_sig_ctx_inc(int pattern, int scan_idx, int pos_x, int pos_y, int log2w, int type)
-{
-  if (pos_x + pos_y == 0) return 0;
-  if (log2w == 2) {
-    const unsigned long long map = 0x8877886654325410ull;  // ctx_ind_map[16], one nibble each, entry 0 lowest
-    return (int)((map >> (4 * (4 * pos_y + pos_x))) & 15);
-  }
-  const int offset = log2w == 3 ? (scan_idx == 0 ? 9 : 15) : (type == 0 ? 21 : 12);
-  const int xs = pos_x & 3, ys = pos_y & 3;
-  int cnt;
-  if (pattern == 0) cnt = (xs + ys <= 2) ? ((xs + ys == 0) ? 2 : 1) : 0;
-  else if (pattern == 1) cnt = (ys <= 1) ? ((ys == 0) ? 2 : 1) : 0;
-  else if (pattern == 2) cnt = (xs <= 1) ? ((xs == 0) ? 2 : 1) : 0;
-  else cnt = 2;
-  return ((type == 0 && ((pos_x >> 2) + (pos_y >> 2)) > 0) ? 3 : 0) + offset + cnt;
-}
 
 // ---------------------------------------------------------------------------------------------------------------------------------------------------
 // The block by a whole WAVEFRONT (the CTU pass, kvz_ctu.hpp recon_tus; RdoqOp at the end of this file), one 4x4 coefficient group at a time.
@@ -299,15 +245,15 @@ KVZ_RDOQ_WAVE_FN void rdoq_block_wave(const RdoqWaveArgs c, int lane)
   (void)lane;
   const int width = 1 << log2w, n = width * width;
   const int transform_shift = 15 - 8 - log2w;
-  const int qp_scaled = rdoq_scaled_qp(type, qp);
+  const int qp_scaled = type == 0 ? qp : chroma_qp(qp);  // kvz_get_scaled_qp (transform.c:141-155), 8 bit
   const i32 q_bits = 14 + qp_scaled / 6 + transform_shift;
-  const i32 q = rdoq_quant_scale(qp_scaled % 6);
+  const i32 q = quant_scale(qp_scaled % 6);
   // scalinglist.c:349-367: err_scale = 2^15 * 2^(-2 transform_shift) / q / q -- two IEEE divisions of a power of two, and a power of two goes through a rounding
   // unchanged: the result is ((1 / q) / q) * 2^(15 - 2 transform_shift) exactly, the first factor one of six constants (folded at compile time, IEEE double), the product
   // exact.  (Two double-precision divisions per block were some eighty instructions in front of everything else.)
+  auto inv_qq_of = [](int r) { return (1.0 / (double)quant_scale(r)) / (double)quant_scale(r); };
   const int qr = qp_scaled % 6;
-  const double inv_qq = qr == 0 ? (1.0 / 26214.0) / 26214.0 : (qr == 1 ? (1.0 / 23302.0) / 23302.0 : (qr == 2 ? (1.0 / 20560.0) / 20560.0
-                      : (qr == 3 ? (1.0 / 18396.0) / 18396.0 : (qr == 4 ? (1.0 / 16384.0) / 16384.0 : (1.0 / 14564.0) / 14564.0))));
+  const double inv_qq = qr == 0 ? inv_qq_of(0) : (qr == 1 ? inv_qq_of(1) : (qr == 2 ? inv_qq_of(2) : (qr == 3 ? inv_qq_of(3) : (qr == 4 ? inv_qq_of(4) : inv_qq_of(5)))));
   const double temp = inv_qq * (double)(1 << (15 - 2 * transform_shift));  // 15 - 2 transform_shift = 5 .. 11
   const int num_blk_side = width >> 2;
   const RdoqScanT<KVZ_LDS_PTR(const u8)> sc{ log2w, scan_mode, c.diag8 };
@@ -342,10 +288,8 @@ KVZ_RDOQ_WAVE_FN void rdoq_block_wave(const RdoqWaveArgs c, int lane)
   // rdo.c:480-509 calc_last_bits: entry k of the x / y table on lane k (k <= 9): the prices of the prefix's 1-bins before k, and of the 0-bin that ends it
   WaveArr<i32> lx_bits, ly_bits;
   {
-    const int cb = log2w - 2;
-    const int off = type ? 0 : (cb * 3 + ((cb + 1) >> 2)), shift = type ? cb : ((cb + 3) >> 2);
-    const int bx = (type ? KVZ_HIP_CX_LAST_X_CHROMA : KVZ_HIP_CX_LAST_X_LUMA) + off, by = (type ? KVZ_HIP_CX_LAST_Y_CHROMA : KVZ_HIP_CX_LAST_Y_LUMA) + off;
-    const int kmax = rdoq_group_idx(width - 1);
+    const LastPosCtx lp = last_pos_ctx(log2w, type);
+    const int shift = lp.shift, bx = lp.base_x, by = lp.base_y, kmax = group_idx(width - 1);
 #ifdef KVZ_HOSTSIM
     KVZ_WAVE_LANES(l, 64) {
       i32 bits_x = 0, bits_y = 0;
@@ -355,15 +299,11 @@ KVZ_RDOQ_WAVE_FN void rdoq_block_wave(const RdoqWaveArgs c, int lane)
       KVZ_WA_SET(lx_bits, l, bits_x); KVZ_WA_SET(ly_bits, l, bits_y);
     }
 #else
-    // every lane its own entry's two bins (four independent reads), the sums before it by a prefix scan along the row (DPP row_shr, zeros shifted in)
+    // every lane its own entry's two bins (four independent reads), the sums before it by a prefix scan along the row (row16_sum)
     const bool in = lane < kmax;
     const int cxk = (lane & 15) >> shift;
     const i32 x1 = in ? c.price(bx + cxk, 1) : 0, x0 = in ? c.price(bx + cxk, 0) : 0, y1 = in ? c.price(by + cxk, 1) : 0, y0 = in ? c.price(by + cxk, 0) : 0;
-    i32 sx = x1, sy = y1;
-    sx += __builtin_amdgcn_update_dpp(0, sx, 0x111, 0xF, 0xF, true); sy += __builtin_amdgcn_update_dpp(0, sy, 0x111, 0xF, 0xF, true);
-    sx += __builtin_amdgcn_update_dpp(0, sx, 0x112, 0xF, 0xF, true); sy += __builtin_amdgcn_update_dpp(0, sy, 0x112, 0xF, 0xF, true);
-    sx += __builtin_amdgcn_update_dpp(0, sx, 0x114, 0xF, 0xF, true); sy += __builtin_amdgcn_update_dpp(0, sy, 0x114, 0xF, 0xF, true);
-    sx += __builtin_amdgcn_update_dpp(0, sx, 0x118, 0xF, 0xF, true); sy += __builtin_amdgcn_update_dpp(0, sy, 0x118, 0xF, 0xF, true);
+    const i32 sx = row16_sum(x1), sy = row16_sum(y1);
     lx_bits.v = sx - x1 + x0; ly_bits.v = sy - y1 + y0;  // lanes up to kmax (<= 9, the first row) are read
 #endif
   }
@@ -399,7 +339,7 @@ KVZ_RDOQ_WAVE_FN void rdoq_block_wave(const RdoqWaveArgs c, int lane)
     p.c0 = in_chain ? err * err * temp : 0.0;
     p.dhi = e_hi * e_hi * temp; p.dlo = e_lo * e_lo * temp;
     const u32 pos_y = blkpos >> log2w, pos_x = blkpos - (pos_y << log2w);
-    const int ctx_sig = p.last ? 0 : rdoq_sig_ctx_inc(pattern_sig_ctx, scan_mode, (int)pos_x, (int)pos_y, log2w, type);
+    const int ctx_sig = p.last ? 0 : sig_ctx_inc(pattern_sig_ctx, scan_mode, (int)pos_x, (int)pos_y, log2w, type);
     p.s0 = in_chain ? c.lambda * c.price(sig_base + ctx_sig, 0) : 0.0;
     p.s1 = c.lambda * c.price(sig_base + ctx_sig, 1);
     return p;
@@ -413,7 +353,7 @@ KVZ_RDOQ_WAVE_FN void rdoq_block_wave(const RdoqWaveArgs c, int lane)
   };
   KVZ_RQ_PROF(0);
   for (int cgs = cg_last_scanpos; cgs >= 0; cgs--) {
-    const u32 cg_blkpos = sc.cg(cgs), cg_pos_y = cg_blkpos / num_blk_side, cg_pos_x = cg_blkpos - cg_pos_y * num_blk_side;
+    const u32 cg_blkpos = (u32)scan_group(log2w, scan_mode, cgs, c.diag8), cg_pos_y = cg_blkpos / num_blk_side, cg_pos_x = cg_blkpos - cg_pos_y * num_blk_side;
     u32 right = 0, lower = 0;  // context.c:339-351 / 315-327
     if ((int)cg_pos_x < num_blk_side - 1) right = (u32)(sig_groups >> (cg_pos_y * num_blk_side + cg_pos_x + 1)) & 1;
     if ((int)cg_pos_y < num_blk_side - 1) lower = (u32)(sig_groups >> ((cg_pos_y + 1) * num_blk_side + cg_pos_x)) & 1;
@@ -608,7 +548,7 @@ KVZ_RDOQ_WAVE_FN void rdoq_block_wave(const RdoqWaveArgs c, int lane)
   int found_last = 0;
   for (int cgs = cg_last_scanpos; cgs >= 0 && !found_last; cgs--) {
     walk.add(-KVZ_WA_GET(cg_cost_of, cgs));
-    if (!((sig_groups >> sc.cg(cgs)) & 1)) continue;
+    if (!((sig_groups >> (u32)scan_group(log2w, scan_mode, cgs, c.diag8)) & 1)) continue;
     // the group's positions again: levels and costs from the classes the first pass decided them in, and lambda times the rate of ending the block at a level
     // (rdo.c:465-478 get_rate_last)
     const int pat2 = (int)(((cgs < 32 ? pat_lo >> (2 * cgs) : pat_hi >> (2 * (cgs - 32)))) & 3);
@@ -620,7 +560,7 @@ KVZ_RDOQ_WAVE_FN void rdoq_block_wave(const RdoqWaveArgs c, int lane)
       const Pos p = position(cgs, l, width == 4 ? -1 : pat2);
       const u32 pos_y = (u32)p.blkpos >> log2w, pos_x = (u32)p.blkpos - (pos_y << log2w);
       const u32 px = scan_mode == 2 ? pos_y : pos_x, py = scan_mode == 2 ? pos_x : pos_y;  // SCAN_VER swaps (rdo.c:934)
-      const int gx = rdoq_group_idx((int)px), gy = rdoq_group_idx((int)py);
+      const int gx = group_idx((int)px), gy = group_idx((int)py);
       const i32 lxb = KVZ_WA_AT(lx_bits, l, gx), lyb = KVZ_WA_AT(ly_bits, l, gy);  // every lane takes part in the exchange (converged here)
       i32 level = p.ma < 0 ? -1 : 0;
       double cc = p.c0 + p.s0, cs = p.s0, lc = 0;

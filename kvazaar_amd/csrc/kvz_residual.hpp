@@ -1,32 +1,14 @@
 // kvz_residual.hpp -- the residual syntax of one transform block, kvz_encode_coeff_nxn (strategies/generic/encode_coding_tree-generic.c:40-283 with
 // kvz_encode_last_significant_xy encode_coding_tree.c:63-115, kvz_context_get_sig_ctx_inc context.c:366-399, kvz_cabac_write_coeff_remain cabac.c:275-301), written
 // against a SINK of bins: `s.ctx(context, value)` for a context-coded bin (contexts in the KVZ_HIP_CX_* numbering of include/kvz_hip_types.h), `s.ep(value, bits)`
-// for a run of bypass bins.  Two sinks exist: the entropy coder's record list (kvz_entropy.hpp BinSink: the real mode) and the inter CTU pass's price counter
-// (kvz_inter_ctu.hpp PriceSink: the counting mode of get_coeff_cabac_cost, rdo.c:220-263) -- which bins a block has does not depend on what is done with them.
+// for a run of bypass bins.  Three sinks exist: the entropy coder's record list (kvz_entropy.hpp BinSink: the real mode) and the price counters of the two CTU passes
+// (kvz_inter_ctu.hpp PriceSink and kvz_ctu.hpp CoeffPriceSink: the counting mode of get_coeff_cabac_cost, rdo.c:220-263; the intra pass's only in host simulation, its
+// device forms are wavefront-wide) -- which bins a block has does not depend on what is done with them.
 #pragma once
-#include "kvz_ops.hpp"
+#include "kvz_syntax.hpp"
 #include "kvz_tables.hpp"
-#include "../../include/kvz_hip_types.h"
 
 namespace kvz {
-
-KVZ_DEV int entropy_sig_ctx_inc(int pattern_sig_ctx, int scan_idx, int pos_x, int pos_y, int log2_size, int type)  // context.c:366-399
-{
-  if (pos_x + pos_y == 0) return 0;
-  if (log2_size == 2) { const unsigned long long map = 0x8877886654325410ull; return (int)((map >> (4 * (4 * pos_y + pos_x))) & 15); }  // ctx_ind_map
-  const int offset = log2_size == 3 ? (scan_idx == 0 ? 9 : 15) : (type == 0 ? 21 : 12);
-  const int xs = pos_x & 3, ys = pos_y & 3;
-  int cnt;
-  if (pattern_sig_ctx == 0) cnt = xs + ys <= 2 ? (xs + ys == 0 ? 2 : 1) : 0;
-  else if (pattern_sig_ctx == 1) cnt = ys <= 1 ? (ys == 0 ? 2 : 1) : 0;
-  else if (pattern_sig_ctx == 2) cnt = xs <= 1 ? (xs == 0 ? 2 : 1) : 0;
-  else cnt = 2;
-  return ((type == 0 && ((pos_x >> 2) + (pos_y >> 2)) > 0) ? 3 : 0) + offset + cnt;
-}
-KVZ_DEV int entropy_group_idx(int v)  // encoderstate.h:397 g_group_idx
-{
-  return v < 4 ? v : (v < 6 ? 4 : (v < 8 ? 5 : (v < 12 ? 6 : (v < 16 ? 7 : (v < 24 ? 8 : 9)))));
-}
 
 // kvz_encode_coeff_nxn_generic: the residual syntax of one transform block (sign hiding, transform skip, encryption off), cut at the coefficient group so that a caller can
 // run it a group at a time (the entropy coder's bin stage keeps the lanes of a wavefront in the same piece of code that way): entropy_tu_begin -- which groups are
@@ -41,10 +23,9 @@ KVZ_DEV int entropy_cg_of(const u32 *scan, int i, int log2_size)  // g_sig_last_
   const int width = 1 << log2_size, p = (int)scan[i << 4];
   return (((p >> log2_size) >> 2) << (log2_size - 2)) + ((p & (width - 1)) >> 2);
 }
-// The scan of a block is group-major with the 4x4 pattern of its type inside every group (kvz_tables.hpp: scan[n] = group origin + pattern[n & 15]): position y * 4 + x of
-// scan index i inside a group is nibble i of these constants -- diagonal, horizontal, vertical.  A group's sixteen levels are four 8-byte rows: loaded once, looked up in
-// registers (a lane's loads are what the bin stage is bound by: one lane per CTU, 64 cache lines per load instruction).
-KVZ_DEV unsigned long long entropy_scan_pattern(int scan_mode) { return scan_mode == 0 ? 0xfbe7ad369c258140ull : (scan_mode == 1 ? 0xfedcba9876543210ull : 0xfb73ea62d951c840ull); }
+// The scan of a block is group-major with the 4x4 pattern of its type inside every group (kvz_tables.hpp: scan[n] = group origin + pattern[n & 15], kvz_syntax.hpp
+// scan_pattern16).  A group's sixteen levels are four 8-byte rows: loaded once, looked up in registers (a lane's loads are what the bin stage is bound by: one lane per
+// CTU, 64 cache lines per load instruction).
 struct CgRows {
   unsigned long long r0, r1, r2, r3;
   KVZ_DEV void load(const i16 *coeff, int width, int cg_x, int cg_y)
@@ -75,7 +56,7 @@ template <class Sink> KVZ_DEV void entropy_tu_begin(Sink &s, const Tables *tb, T
   int scan_cg_last = nbs * nbs - 1;
   while (!((sig_cg >> entropy_cg_of(scan, scan_cg_last, log2_size)) & 1)) scan_cg_last--;
   int scan_pos_last = scan_cg_last * 16 + 15;
-  const unsigned long long pat = entropy_scan_pattern(scan_mode);
+  const unsigned long long pat = scan_pattern16(scan_mode);
   const int last_cg = entropy_cg_of(scan, scan_cg_last, log2_size), last_cg_y = last_cg >> (log2_size - 2), last_cg_x = last_cg & (nbs - 1);  // (nbs = 2^(log2_size - 2): a division by it is ~25 instructions where the compiler cannot see that)
   CgRows rows;
   rows.load(coeff, width, last_cg_x, last_cg_y);
@@ -84,15 +65,13 @@ template <class Sink> KVZ_DEV void entropy_tu_begin(Sink &s, const Tables *tb, T
   const int pos_last = (last_cg_y * 4 + (p_last >> 2)) * width + last_cg_x * 4 + (p_last & 3);
   {  // kvz_encode_last_significant_xy (encode_coding_tree.c:63-115)
     int lx = pos_last & (width - 1), ly = pos_last >> log2_size;
-    const int index = log2_size - 2;
-    const int ctx_offset = type ? 0 : (index * 3 + (index + 1) / 4), shift = type ? index : (index + 3) / 4;
-    const int base_x = type ? KVZ_HIP_CX_LAST_X_CHROMA : KVZ_HIP_CX_LAST_X_LUMA, base_y = type ? KVZ_HIP_CX_LAST_Y_CHROMA : KVZ_HIP_CX_LAST_Y_LUMA;
+    const LastPosCtx lp = last_pos_ctx(log2_size, type);
     if (scan_mode == 2) { const int tmp = lx; lx = ly; ly = tmp; }
-    const int gx = entropy_group_idx(lx), gy = entropy_group_idx(ly), gmax = entropy_group_idx(width - 1);
-    for (int i = 0; i < gx; i++) s.ctx(base_x + ctx_offset + (i >> shift), 1);
-    if (gx < gmax) s.ctx(base_x + ctx_offset + (gx >> shift), 0);
-    for (int i = 0; i < gy; i++) s.ctx(base_y + ctx_offset + (i >> shift), 1);
-    if (gy < gmax) s.ctx(base_y + ctx_offset + (gy >> shift), 0);
+    const int gx = group_idx(lx), gy = group_idx(ly), gmax = group_idx(width - 1);
+    for (int i = 0; i < gx; i++) s.ctx(lp.base_x + (i >> lp.shift), 1);
+    if (gx < gmax) s.ctx(lp.base_x + (gx >> lp.shift), 0);
+    for (int i = 0; i < gy; i++) s.ctx(lp.base_y + (i >> lp.shift), 1);
+    if (gy < gmax) s.ctx(lp.base_y + (gy >> lp.shift), 0);
     const int min_in_group[10] = { 0, 1, 2, 3, 4, 6, 8, 12, 16, 24 };
     if (gx > 3) s.ep((u32)(lx - min_in_group[gx]), (gx - 2) / 2);
     if (gy > 3) s.ep((u32)(ly - min_in_group[gy]), (gy - 2) / 2);
@@ -113,7 +92,7 @@ template <class Sink> KVZ_DEV void entropy_tu_cg(Sink &s, const Tables *tb, TuWa
     const int sub_pos = i << 4, cg_blk_pos = entropy_cg_of(scan, i, log2_size), cg_pos_y = cg_blk_pos >> (log2_size - 2), cg_pos_x = cg_blk_pos & (nbs - 1);
     int abs_coeff[16], num_non_zero = 0;
     u32 coeff_signs = 0, go_rice = 0;
-    const unsigned long long pat = entropy_scan_pattern(scan_mode);
+    const unsigned long long pat = scan_pattern16(scan_mode);
     CgRows rows{ 0, 0, 0, 0 };  // (an insignificant group is all zero: the first group's flag is inferred, its levels are still walked)
     if ((sig_cg >> cg_blk_pos) & 1) rows.load(coeff, width, cg_pos_x, cg_pos_y);
     if (scan_pos_sig == scan_pos_last) { const int v = rows.at((int)((pat >> (4 * (scan_pos_last & 15))) & 15)); abs_coeff[0] = iabs(v); coeff_signs = v < 0; num_non_zero = 1; scan_pos_sig--; }
@@ -125,7 +104,7 @@ template <class Sink> KVZ_DEV void entropy_tu_cg(Sink &s, const Tables *tb, TuWa
       const int pattern = width == 4 ? -1 : right + (lower << 1);  // context.c:339-351
       for (; scan_pos_sig >= sub_pos; scan_pos_sig--) {
         const int p = (int)((pat >> (4 * (scan_pos_sig & 15))) & 15), pos_y = cg_pos_y * 4 + (p >> 2), pos_x = cg_pos_x * 4 + (p & 3), v = rows.at(p);
-        if (scan_pos_sig > sub_pos || i == 0 || num_non_zero) s.ctx(base_sig + entropy_sig_ctx_inc(pattern, scan_mode, pos_x, pos_y, log2_size, type), v != 0);
+        if (scan_pos_sig > sub_pos || i == 0 || num_non_zero) s.ctx(base_sig + sig_ctx_inc(pattern, scan_mode, pos_x, pos_y, log2_size, type), v != 0);
         if (v) { abs_coeff[num_non_zero++] = iabs(v); coeff_signs = 2 * coeff_signs + (v < 0); }
       }
     } else scan_pos_sig = sub_pos - 1;

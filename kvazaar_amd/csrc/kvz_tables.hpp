@@ -8,7 +8,7 @@
 #pragma once
 #include <string.h>
 
-#include "kvz_ops.hpp"
+#include "kvz_syntax.hpp"
 
 namespace kvz {
 
@@ -48,8 +48,7 @@ inline u16 half_bits_of_int(int v)
   return (u16)(sign | ((e + 15) << 10) | ((a << (10 - e)) & 0x3ff));
 }
 
-// Deblocking thresholds, H.265 Table 8-12 (filter.c:46-65 kvz_g_tc_table_8x8 / kvz_g_beta_table_8x8) and the chroma QP
-// mapping of Table 8-10 (transform.c:56-62 kvz_g_chroma_scale)
+// Deblocking thresholds, H.265 Table 8-12 (filter.c:46-65 kvz_g_tc_table_8x8 / kvz_g_beta_table_8x8)
 inline int deblock_tc(int q)  // q in [0, 53]
 {
   static const unsigned char first_q_of_next[] = { 18, 27, 31, 35, 38, 40, 42, 43, 44, 45, 46 };  // tc' steps 0 -> 1 -> ... -> 10 -> 11
@@ -60,12 +59,6 @@ inline int deblock_tc(int q)  // q in [0, 53]
   return v;
 }
 inline int deblock_beta(int q) { return q < 16 ? 0 : (q <= 28 ? q - 10 : 2 * q - 38); }  // q in [0, 51]
-inline int chroma_qp_of(int qp)
-{
-  static const unsigned char t[58] = { 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 29, 30, 31, 32,
-                                       33, 33, 34, 34, 35, 35, 36, 36, 37, 37, 38, 39, 40, 41, 42, 43, 44, 45, 46, 47, 48, 49, 50, 51 };
-  return t[qp < 0 ? 0 : (qp > 57 ? 57 : qp)];
-}
 
 // Entropy bits of the HEVC CABAC state machine, fixed point 1<<15 (HM 12.0 sm_entropyBits, as tabulated in
 // rdo.c:69-80 kvz_entropy_bits); CTX_ENTROPY_FBITS = value / 32768 (rdo.c:83, cabac.h:131).  Standard constant data.
@@ -102,7 +95,7 @@ inline void build_tables(Tables *t)
       }
   }
   {  // a unit to the above-right / below-left is usable iff it comes earlier in z-order (cu.h:385-421) than the unit itself
-    auto z = [](int x4, int y4) { unsigned r = 0; for (int b = 0; b < 4; b++) r |= (((x4 >> b) & 1u) << (2 * b)) | (((y4 >> b) & 1u) << (2 * b + 1)); return r; };
+    auto z = [](int x4, int y4) { return ctu_zorder(4 * x4, 4 * y4); };
     for (int r = 0; r < 16; r++)
       for (int c = 0; c < 16; c++) {
         int n = 0;
@@ -190,28 +183,24 @@ inline int ilog2(int w) { int l = 0; while ((1 << l) < w) l++; return l; }
 // transform.c:141-155 kvz_get_scaled_qp
 inline int scaled_qp(int type, int qp, int qp_offset)
 {
-  static const uint8_t chroma_scale[58] = { 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 29, 30, 31, 32,
-                                            33, 33, 34, 34, 35, 35, 36, 36, 37, 37, 38, 39, 40, 41, 42, 43, 44, 45, 46, 47, 48, 49, 50, 51 };
   if (type == 0) return qp + qp_offset;
   int q = qp < -qp_offset ? -qp_offset : (qp > 57 ? 57 : qp);
-  return q < 0 ? q + qp_offset : chroma_scale[q] + qp_offset;
+  return q < 0 ? q + qp_offset : chroma_qp(q) + qp_offset;
 }
 
 // quant-generic.c:57-66 (forward) and :303-339 (inverse) scalars for a width x width block of plane type
 // (`type` as the reference passes it: 0 luma, 2/3 chroma).
 inline QuantScalars quant_scalars(int qp, int bitdepth, int slice_is_intra, int scaling_list, int width, int type)
 {
-  static const int quant_scales[6] = { 26214, 23302, 20560, 18396, 16384, 14564 };  // scalinglist.c:78
-  static const int inv_quant_scales[6] = { 40, 45, 51, 57, 64, 72 };                // scalinglist.c:79
   QuantScalars q;
   const int log2_tr = ilog2(width);
   const int qps = scaled_qp(type, qp, (bitdepth - 8) * 6);
   const int transform_shift = 15 - bitdepth - log2_tr;
   q.q_bits = 14 + qps / 6 + transform_shift;
   q.add = (slice_is_intra ? 171 : 85) << (q.q_bits - 9);
-  q.flat_q = quant_scales[qps % 6];
+  q.flat_q = quant_scale(qps % 6);
   q.dq_shift = 20 - 14 - transform_shift + (scaling_list ? 4 : 0);
-  q.dq_scale = inv_quant_scales[qps % 6] << (qps / 6);
+  q.dq_scale = inv_quant_scale(qps % 6) << (qps / 6);
   q.dq_list = scaling_list;
   q.dq_qp_per = qps / 6;
   return q;
