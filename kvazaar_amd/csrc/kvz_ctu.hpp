@@ -1889,13 +1889,144 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
     return dct_at(l2, k, i);
   }
 
+  // ---- the arithmetic stages of recon_tus() for units of 16 and 32 samples: a lane task is a row segment of EIGHT samples of one plane (the 8x8 CU has
+  // recon_cu8; one sample per lane and trip was three trips on two wavefronts for a 16x16 CU and twelve for a 32x32 unit).  Where the tasks sit:
+  //   16x16 CU    32 luma + 8 U + 8 V tasks, ONE trip on the wavefront playing threads 0..63: DPP rows 0-1 luma, the first half of row 2 U, of row 3 V
+  //   32x32 unit  trip 0: 128 luma tasks on both wavefronts; trip 1: 32 U (rows 0-1) + 32 V (rows 2-3) on the first
+  // so a DPP row of sixteen lanes never mixes planes and ONE row reduction per trip serves all three planes of a stage (wide_add), as plane_add does for the 8x8 CU.
+  // Returns the plane of thread tid's task in `trip` (-1: none) and which eight samples of the plane: elements 8 seg .. 8 seg + 7, row-major.
+  KVZ_DEV static int wide_trips(int lw) { return lw == 4 ? 1 : 2; }
+  // a wavefront-uniform value as a scalar (the host runs one thread at a time)
+  KVZ_DEV static int wide_uni(int v)
+  {
+#ifdef KVZ_HOSTSIM
+    return v;
+#else
+    return __builtin_amdgcn_readfirstlane(v);
+#endif
+  }
+  KVZ_DEV static int wide_task(int lw, int trip, int tid, int *seg)
+  {
+    *seg = 0;
+    if (lw == 4) {
+      if (tid < 32) { *seg = tid; return 0; }
+      if (tid >= 64 || (tid & 15) >= 8) return -1;
+      *seg = tid & 7;
+      return tid < 48 ? 1 : 2;
+    }
+    if (trip == 0) { *seg = tid; return 0; }
+    if (tid >= 64) return -1;
+    *seg = tid & 31;
+    return 1 + (tid >> 5);
+  }
+  // Sum of a trip's lane values per plane, added to s->acc[base + plane]; every lane of a wavefront that has tasks in the trip comes here (lanes without a task
+  // with 0).  `packed`: the value is count << 24 | weight sum (eight coefficients a lane: a row of sixteen lanes stays below 2^23 and 128, so the packed word
+  // survives the row reduction and is taken apart before rows are added up) and goes to acc[3 + plane] / acc[6 + plane].
+  KVZ_DEV void wide_add(int lw, int trip, int tid, int c, u32 v, bool packed, int base) const
+  {
+#ifdef KVZ_HOSTSIM
+    (void)lw; (void)trip; (void)tid;
+    if (c < 0) return;
+    if (packed) { s->acc[3 + c] += v & 0xffffffu; s->acc[6 + c] += v >> 24; }
+    else s->acc[base + c] += v;
+#else
+    (void)c;
+    if ((lw == 4 || trip == 1) && tid >= 64) return;  // wavefront-uniform: the other wavefront has no tasks in this trip
+    const int x = row16_sum((int)v);
+    const u32 r0 = (u32)__builtin_amdgcn_readlane(x, 15), r1 = (u32)__builtin_amdgcn_readlane(x, 31), r2 = (u32)__builtin_amdgcn_readlane(x, 47), r3 = (u32)__builtin_amdgcn_readlane(x, 63);
+    if ((tid & 63) == 0) {
+      auto put = [&](int plane, u32 a, u32 b) {
+        if (packed) {
+          const u32 ws = (a & 0xffffffu) + (b & 0xffffffu), n = (a >> 24) + (b >> 24);
+          if (n) { atomicAdd(&s->acc[3 + plane], ws); atomicAdd(&s->acc[6 + plane], n); }  // no levels, no weights: coeff_weights' entry 0 is that of a zero level
+          else if (ws) atomicAdd(&s->acc[3 + plane], ws);
+        } else if (a + b) atomicAdd(&s->acc[base + plane], a + b);
+      };
+      if (lw == 4) { put(0, r0, r1); put(1, r2, 0); put(2, r3, 0); }
+      else if (trip == 0) { put(0, r0, r1); put(0, r2, r3); }
+      else { put(1, r0, r1); put(2, r2, r3); }
+    }
+#endif
+  }
+  // kvz_intra_predict (intra.c:252-301) for the eight samples (px0 .. px0 + 7, py) of plane c of a 2^l2 unit, l2 >= 3: predict_pixel() sample for sample, with
+  // what only depends on the mode and the row worked out once.  `mode` is uniform, so every branch on it is one for the wavefront.  Chroma: unfiltered
+  // references, no edge filters; 32-wide luma: no edge filters.
+  KVZ_DEV void predict_row8(int l2, int mode, int c, int px0, int py, u8 out[8]) const
+  {
+    const int w = 1 << l2;
+    const bool edges = c == 0 && w < 32;  // intra.c:207-219 intra_post_process_angular, intra-generic.c:210-241
+    const u8 *top = s->ref[c][0], *left = s->ref[c][1];
+    if (c == 0 && mode != 1 && (mode == 0 || imin(iabs(mode - 26), iabs(mode - 10)) > (l2 == 3 ? 7 : (l2 == 4 ? 1 : 0)))) { top = s->fref[0]; left = s->fref[1]; }
+    if (mode == 0) {  // intra-generic.c:165-201: (w-1-x) L + (x+1) TR + (w-1-y) T[x] + (y+1) BL + w, the terms without x first
+      const int l = left[py + 1], tr = top[w + 1], bl = left[w + 1];
+      const int hb = (w - 1) * l + tr + (py + 1) * bl + w, dl = tr - l, wy = w - 1 - py;
+      for (int k = 0; k < 8; k++) out[k] = (u8)(((px0 + k) * dl + top[px0 + k + 1] * wy + hb) >> (l2 + 1));
+    } else if (mode == 1) {
+      const int dc = s->dcval[c];
+      for (int k = 0; k < 8; k++) out[k] = (u8)dc;
+      if (edges) {
+        if (py == 0) for (int k = 0; k < 8; k++) out[k] = (u8)((top[px0 + k + 1] + 3 * dc + 2) >> 2);
+        if (px0 == 0) out[0] = (u8)(py == 0 ? (left[1] + 2 * dc + top[1] + 2) >> 2 : (left[py + 1] + 3 * dc + 2) >> 2);
+      }
+    } else {  // intra-generic.c:49-155
+      const int disp = s->mode_disp[mode], inv = s->mode_inv[mode];
+      const bool vertical = mode >= 18;
+      const u8 *main_ref = vertical ? top : left, *side_ref = vertical ? left : top;
+      if (vertical) {  // one displacement for the row: nine samples of the (extended) main reference
+        const int delta = (py + 1) * disp, di = delta >> 5, df = delta & 31;
+        int r[9];
+        if (disp >= 0) for (int j = 0; j < 9; j++) r[j] = main_ref[px0 + di + j + 1];
+        else for (int j = 0; j < 9; j++) r[j] = angular_ref(main_ref, side_ref, px0 + di + j, inv);
+        for (int k = 0; k < 8; k++) out[k] = (u8)(((32 - df) * r[k] + df * r[k + 1] + 16) >> 5);  // df == 0 (mode 26 among them) leaves r[k]
+        if (edges && mode == 26 && px0 == 0) out[0] = (u8)iclip(0, 255, (int)out[0] + ((left[py + 1] - left[0]) >> 1));
+      } else {         // the displacement runs along the row
+        for (int k = 0; k < 8; k++) {
+          const int delta = (px0 + k + 1) * disp, di = delta >> 5, df = delta & 31;
+          const int r1 = disp >= 0 ? (int)main_ref[py + di + 1] : angular_ref(main_ref, side_ref, py + di, inv);
+          const int r2 = disp >= 0 ? (int)main_ref[py + di + 2] : angular_ref(main_ref, side_ref, py + di + 1, inv);
+          int v = ((32 - df) * r1 + df * r2 + 16) >> 5;
+          if (edges && mode == 10 && py == 0) v = iclip(0, 255, v + ((top[px0 + k + 1] - top[0]) >> 1));
+          out[k] = (u8)v;
+        }
+      }
+    }
+  }
+
   KVZ_DEV void recon_tus(int lv, const TuSet &t, int depth, int mode, bool refs_ready = false)
   {
     const int xl = t.x - cx, yl = t.y - cy;
     const CandView cv = cand_view(lv);
+    // units of 16 and 32 samples run stages 1, 4 and 7 eight samples a lane (wide_task); the quantiser of the RDOQ instantiation stays as it is: its levels come
+    // from rdoq_block_wave and its register budget is at the limit
+    const bool wide = KVZ_CTU_THREADS == 128 && t.lw >= 4 && t.lc == t.lw - 1;
     if (!refs_ready) build_refs(lv, t.x, t.y, t.lw, t.lc, t.lw != 0, t.lc != 0);
     if (!RDOQ && KVZ_CTU_THREADS == 128 && t.lw == 3 && t.lc == 2) { recon_cu8(lv, t, depth, mode); return; }
+#if defined(KVZ_CTU_PROFILE) && !defined(KVZ_HOSTSIM)
+    // the stage clock of the units larger than 8x8 goes to the PU half of prof_acc, idle where no NxN partition is tried: tools/ctu_profile.py prints both paths side by side
+    struct InLarge { CtuSharedT<CABAC> *s; bool on; __device__ InLarge(CtuSharedT<CABAC> *s_, bool on_) : s(s_), on(on_) { if (on && threadIdx.x == 0) s->prof_pu = 1; } __device__ ~InLarge() { if (on && threadIdx.x == 0) s->prof_pu = 0; } } in_large(s, !NXN && t.lw >= 4);
+#endif
     // stage 1: prediction -> rec (as kvazaar blits it before quantising) and residual
+    if (wide) {
+      const int umode = wide_uni(mode);
+      KVZ_FOR_THREADS(tid) {
+        if (tid < 16) s->acc[tid] = 0;
+        for (int trip = 0; trip < wide_trips(t.lw); trip++) {
+          int seg;
+          const int c = wide_task(t.lw, trip, mover_lane(tid), &seg);
+          if (c < 0) continue;
+          // one b64 write of the row to the candidate, one b128 write of the residual (every buffer starts 16-aligned and a segment is 8 samples of a row whose
+          // origin is a multiple of 8 in its plane)
+          const int l2 = tu_log2(t, c), sh = c ? 1 : 0, py = seg >> (l2 - 3), px0 = (seg << 3) & ((1 << l2) - 1);
+          u8 p[8], o[8];
+          i16 res[8];
+          predict_row8(l2, umode, c, px0, py, p);
+          __builtin_memcpy(o, KVZ_ALIGNED(org_at(c, (xl >> sh) + px0, (yl >> sh) + py), 8), 8);
+          for (int k = 0; k < 8; k++) res[k] = (i16)((int)o[k] - (int)p[k]);
+          __builtin_memcpy(KVZ_ALIGNED(&cv.at(c, (xl >> sh) + px0, (yl >> sh) + py), 8), p, 8);
+          __builtin_memcpy(KVZ_ALIGNED(tbuf(t, 0, c) + (seg << 3), 16), res, 16);
+        }
+      }
+    } else
     KVZ_FOR_THREADS(tid) {
       if (tid < 16) s->acc[tid] = 0;
       for (int c = 0; c < 3; c++) {
@@ -1976,6 +2107,40 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
       KVZ_SYNC();
       KVZ_PROF(KVZ_P_RDOQ);
     }
+    if (!RDOQ && wide) {
+      const bool to_stage = cabac_on() && lv == 0;  // see levels_lds()
+      KVZ_FOR_THREADS(tid) {
+        const u32 cw_lo = (u32)wide_uni((int)(u32)m->coeff_weights), cw_hi = (u32)wide_uni((int)(u32)(m->coeff_weights >> 32));  // scalars for the call
+        for (int trip = 0; trip < wide_trips(t.lw); trip++) {
+          int seg;
+          const int c = wide_task(t.lw, trip, mover_lane(tid), &seg);
+          u32 packed = 0;
+          if (c >= 0) {
+            const int l2 = tu_log2(t, c);
+            const QuantScalars q = s->qs[l2 - 2][c ? 1 : 0];
+            i16 cf[8], lvl[8], dq[8];
+            __builtin_memcpy(cf, KVZ_ALIGNED(tbuf(t, 0, c) + (seg << 3), 16), 16);
+            u32 wsum = 0, nz = 0;
+            for (int k = 0; k < 8; k++) {  // the arithmetic of the narrow loop below, element for element
+              int level = (int)(((u32)iabs(cf[k]) * (u32)q.flat_q + (u32)q.add) >> q.q_bits);
+              if (cf[k] < 0) level = -level;
+              level = iclip(-32768, 32767, level);
+              lvl[k] = (i16)level;
+              int a = iabs(level);
+              nz += a != 0;
+              if (a > 3) a = 3;
+              wsum += ((a & 2) ? cw_hi : cw_lo) >> (16 * (a & 1)) & 0xffff;
+              dq[k] = (i16)iclip(-32768, 32767, (level * q.dq_scale + (1 << (q.dq_shift - 1))) >> q.dq_shift);
+            }
+            __builtin_memcpy(KVZ_ALIGNED(coeff_dst(lv, c, xl, yl) + (seg << 3), 16), lvl, 16);
+            if (to_stage) __builtin_memcpy(KVZ_ALIGNED(levels_lds(lv, c) + (seg << 3), 16), lvl, 16);
+            __builtin_memcpy(KVZ_ALIGNED(tbuf(t, 1, c) + (seg << 3), 16), dq, 16);
+            packed = wsum | (nz << 24);
+          }
+          wide_add(t.lw, trip, tid, c, packed, true, 0);
+        }
+      }
+    } else
     KVZ_FOR_THREADS(tid) {
       for (int c = 0; c < 3; c++) {
         const int l2 = tu_log2(t, c);
@@ -2038,6 +2203,28 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
     KVZ_PROF(KVZ_P_IDCT);
     // stage 7: reconstruction (quant-generic.c:266-277) + SSD against the source (search.c:500-505, 512-523)
     KVZ_FOR_THREADS(tid) {
+      if (wide) {
+        for (int trip = 0; trip < wide_trips(t.lw); trip++) {
+          int seg;
+          const int c = wide_task(t.lw, trip, mover_lane(tid), &seg);
+          u32 ssd = 0;
+          if (c >= 0) {
+            const int l2 = tu_log2(t, c), sh = c ? 1 : 0, py = seg >> (l2 - 3), px0 = (seg << 3) & ((1 << l2) - 1);
+            u8 *rp = &cv.at(c, (xl >> sh) + px0, (yl >> sh) + py);
+            u8 v[8], o[8];
+            __builtin_memcpy(v, KVZ_ALIGNED(rp, 8), 8);
+            __builtin_memcpy(o, KVZ_ALIGNED(org_at(c, (xl >> sh) + px0, (yl >> sh) + py), 8), 8);
+            if (s->acc[6 + c] != 0) {
+              i16 res[8];
+              __builtin_memcpy(res, KVZ_ALIGNED(tbuf(t, 1, c) + (seg << 3), 16), 16);
+              for (int k = 0; k < 8; k++) v[k] = (u8)iclip(0, 255, (int)(i16)(res[k] + v[k]));
+              __builtin_memcpy(KVZ_ALIGNED(rp, 8), v, 8);
+            }
+            for (int k = 0; k < 8; k++) { const int d = (int)o[k] - (int)v[k]; ssd += (u32)(d * d); }
+          }
+          wide_add(t.lw, trip, tid, c, ssd, false, 0);
+        }
+      } else
       for (int c = 0; c < 3; c++) {
         const int l2 = tu_log2(t, c);
         if (!l2) continue;

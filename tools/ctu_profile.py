@@ -15,7 +15,7 @@ RDOQ_SECTIONS = ["setup / last position / final", "group: positions", "group: de
 
 
 def main():
-    out = os.path.join(ROOT, "kvazaar_amd", "lib", "variants", "libkvz_hip_prof.so")  # built ahead (cross-compiles without a GPU): python tools/ctu_profile.py --build
+    out = os.environ.get("KVZ_PROFILE_LIB") or os.path.join(ROOT, "kvazaar_amd", "lib", "variants", "libkvz_hip_prof.so")  # built ahead (cross-compiles without a GPU): python tools/ctu_profile.py --build
     if "--build" in sys.argv or not os.path.exists(out):
         from kvazaar_amd import build
         build.build_variant("prof", ["-DKVZ_CTU_PROFILE", "-DKVZ_RDOQ_WAVES_PER_EU=3"] + os.environ.get("KVZ_PROFILE_FLAGS", "").split())  # the timers cost registers: 3 wavefronts per SIMD there
@@ -51,6 +51,17 @@ def main():
     tot = sum(buf[:len(NAMES)])
     tot_all = tot + sum(buf[2 * len(NAMES) + 16:3 * len(NAMES) + 16])
     nctu = n * 510
+    pu = 2 * len(NAMES) + 16
+    # the instantiations without NxN book the reconstructions of units larger than 8x8 in the PU half (recon_tus): the table shows both paths side by side
+    split = not (os.environ.get("KVZ_PROFILE_RDOQ") or os.environ.get("KVZ_PROFILE_NXN")) and sum(buf[pu:pu + len(NAMES)]) > 0
+    if split:
+        print(f"kernel_ms {b.kernel_ms():.2f}  cycles/CTU {tot_all / nctu:.0f}")
+        print(f"{'':11s} {'all':>10s}                 | {'8x8 path + the rest':>28s} | {'larger units (recon_tus, 16x16 / 32x32)':>40s}")
+        for i, nm in enumerate(NAMES):
+            a, l = buf[i], buf[pu + i]
+            print(f"{nm:11s} {(a + l) / nctu:10.0f} cyc/CTU  {100.0 * (a + l) / tot_all:5.1f}% | {a / nctu:8.0f} {100.0 * a / tot_all:5.1f}% {buf[len(NAMES) + i] / nctu:7.1f} marks/CTU | "
+                  f"{l / nctu:8.0f} {100.0 * l / tot_all:5.1f}% {buf[pu + len(NAMES) + i] / nctu:7.1f} marks/CTU")
+        return
     print(f"kernel_ms {b.kernel_ms():.2f}  cycles/CTU {tot_all / nctu:.0f} (outside the 4x4 PUs {tot / nctu:.0f})")
     for i, nm in enumerate(NAMES):
         print(f"{nm:11s} {buf[i] / nctu:10.0f} cyc/CTU  {100.0 * buf[i] / tot_all:5.1f}%  {buf[len(NAMES) + i] / nctu:7.1f} marks/CTU")
@@ -64,7 +75,6 @@ def main():
             calls = buf[base + 4 + k]
             if calls:
                 print(f"  luma {4 << k:2d}x{4 << k:<2d} blocks: {calls / nctu:7.1f} per CTU, {buf[base + k] / calls:9.0f} cycles each, {buf[base + k] / nctu:10.0f} per CTU")
-    pu = 2 * len(NAMES) + 16
     if sum(buf[pu:pu + len(NAMES)]):
         print("inside the 4x4 PUs of the NxN attempt (eval_pu; included in the table above? no: listed separately, the table above is the rest):")
         for i, nm in enumerate(NAMES):

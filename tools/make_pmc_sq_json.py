@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """profiles/<tag>_pmc_sq.json from the committed measurements of a round: SQ counters of the bench workload (tools/pmc_sq.sh log), the
 measured SIMD time per wave64 VALU instruction (tools/valu_issue_bench.hip output) and the static opcode mix of the CTU kernel
-(tools/valu_mix.py).  usage: tools/make_pmc_sq_json.py <tag> <kernel_ms>   (files profiles/<tag>_{pmc_sq.log,valu_issue.jsonl,valu_mix.json})"""
+(tools/valu_mix.py).  usage: tools/make_pmc_sq_json.py <tag> <kernel_ms> [issue_tag]   (files profiles/<tag>_{pmc_sq.log,valu_mix.json} and
+profiles/<issue_tag>_valu_issue.jsonl; issue_tag defaults to tag: the instruction costs are the hardware's, an earlier round's measurement of them holds for a later kernel)"""
 import json
 import os
 import re
@@ -9,6 +10,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tag, kernel_ms = sys.argv[1], float(sys.argv[2])
+issue_tag = sys.argv[3] if len(sys.argv) > 3 else tag
 P = lambda name: os.path.join(ROOT, "profiles", f"{tag}_{name}")
 c = {}
 for line in open(P("pmc_sq.log")):
@@ -16,7 +18,7 @@ for line in open(P("pmc_sq.log")):
     if m:
         c[m.group(1)] = float(m.group(2))
 ns = {}
-for line in open(P("valu_issue.jsonl")):
+for line in open(os.path.join(ROOT, "profiles", f"{issue_tag}_valu_issue.jsonl")):
     d = json.loads(line)
     if "instruction" in d:
         ns[d["instruction"]] = d["k8"]["simd_ns_per_wave_inst"]
@@ -33,7 +35,7 @@ out = {
     "insts_valu": c["SQ_INSTS_VALU"], "insts_salu": c["SQ_INSTS_SALU"], "insts_lds": c["SQ_INSTS_LDS"], "insts_mfma": c.get("SQ_INSTS_MFMA"),
     "cycles_per_valu_inst": None,
     "simd_ns_per_valu_inst": {"fast_class": fast_ns, "slow_class": slow_ns, "static_fast_share": share,
-                              "source": f"profiles/{tag}_valu_issue.jsonl (k8 = saturated SIMDs, wall clock), profiles/{tag}_valu_mix.json"},
+                              "source": f"profiles/{issue_tag}_valu_issue.jsonl (k8 = saturated SIMDs, wall clock), profiles/{tag}_valu_mix.json"},
     "valu_issue_frac": frac(share * fast_ns + (1 - share) * slow_ns),
     "valu_issue_frac_range": [frac(fast_ns), frac(slow_ns)],
     "lane_utilisation": c["SQ_THREAD_CYCLES_VALU"] / (c["SQ_ACTIVE_INST_VALU"] * 64),
