@@ -35,16 +35,16 @@
 #include "../../include/kvz_hip_types.h"
 #include "kvz_ops.hpp"
 #include "kvz_rdoq.hpp"
+#include "kvz_recon.hpp"
 #include "kvz_residual.hpp"
 
 namespace kvz {
 
 // Lanes per CTU.  Measured on MI355X (profiles/experiments, 1080p): two wavefronts per CTU beat four (twice the
 // wavefronts that only skip through the lane-starved stages, half the registers each); with the LDS footprint just
-// under 20 KB eight such workgroups fit a CU = four wavefronts per SIMD at 128 VGPRs.  Any multiple of 64 works.
-#ifndef KVZ_CTU_THREADS
+// under 20 KB eight such workgroups fit a CU = four wavefronts per SIMD at 128 VGPRs.  Decided, not a knob: the program is written for
+// exactly two wavefronts (static_assert below).
 #define KVZ_CTU_THREADS 128
-#endif
 #ifdef KVZ_HOSTSIM
 #define KVZ_FOR_THREADS(tid) for (int tid = 0; tid < KVZ_CTU_THREADS; ++tid)
 #ifdef KVZ_HOSTSIM_COUNT_SYNCS
@@ -343,7 +343,8 @@ static_assert(__builtin_offsetof(CtuSharedT<true>, fref) == __builtin_offsetof(C
               "Tables::mref_tab addresses the filtered references 408 bytes behind the unfiltered ones");
 static_assert(KVZ_MREF_STRIDE == kMrefStride && KVZ_MREF_ORG == kMrefOrg && sizeof(((CtuSharedT<true> *)0)->ref[0][0]) == kMrefRefRow && kMrefFiltered == 408,
               "Tables::mref_tab (kvz_tables.hpp) is built for this layout of the reference arrays");
-static_assert(KVZ_CTU_THREADS >= 128, "rough_search requests four table entries per lane ahead of build_mref (mref_pre[4]): 510 entries need at least 128 lanes");
+static_assert(KVZ_CTU_THREADS == 128, "two wavefronts per CTU: thread 64 is 'the other wavefront' (recon_cu8, eval_pu, wide_task, rdoq_unit, prices_coeffs, kHookThread), a 16x16 CU's "
+                                      "128 (mode, block) pairs are one round of rough_search, plane_sums routes DPP rows per wavefront, and mref_pre[4] covers Tables::mref_tab's 510 entries");
 
 // Offset of plane c (0 Y, 1 U, 2 V) in a CTU's 6144-entry block: 0, 4096, 5120.  Arithmetic, not a table: indexed by a per-lane plane a constant array is a
 // load from global memory on the critical path of the phase.
@@ -385,7 +386,7 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
   int a1x, a1y, a2x, a2y;  // CTU-local luma origin of the depth-1 / depth-2 CU whose candidates are live (uniform)
   // The thread that runs a CU's scalar bookkeeping inside the first phase of its reference build (cu_header, price_modes: a serial chain of LDS lookups and
   // double-precision products): one of the OTHER wavefront than the one whose lanes fetch the reference samples of an 8x8 CU, so the two run side by side
-  static constexpr int kHookThread = KVZ_CTU_THREADS > 64 ? 64 : 0;
+  static constexpr int kHookThread = 64;
   int a3q = 0;             // which 8x8 child of the depth-2 CU is being evaluated (z-order; uniform): its slot in CtuShared::lv3_coeff
   int lane_rot = 0;        // see KVZ_FOR_THREADS
 #if defined(KVZ_CTU_PROFILE) && !defined(KVZ_HOSTSIM)
@@ -403,6 +404,15 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
 #endif
 
   // ---------------------------------------------------------------- small uniform helpers
+  // a wavefront-uniform value as a scalar (the host runs one thread at a time)
+  KVZ_DEV static int uni(int v)
+  {
+#ifdef KVZ_HOSTSIM
+    return v;
+#else
+    return __builtin_amdgcn_readfirstlane(v);
+#endif
+  }
   KVZ_DEV const u8 *frame_rec(int c) const { return F.rec + (long)frame * F.frame_px + (c == 0 ? 0 : c == 1 ? (long)F.W * F.H : (long)F.W * F.H * 5 / 4); }
   KVZ_DEV const u8 *frame_src(int c) const { return F.src + (long)frame * F.frame_px + (c == 0 ? 0 : c == 1 ? (long)F.W * F.H : (long)F.W * F.H * 5 / 4); }
   KVZ_DEV int ctu_index() const { return (cy >> 6) * F.wc + (cx >> 6); }
@@ -695,7 +705,6 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
   // `update` the chain of state changes (one table lookup per bin, operands fetched from the lanes with v_readlane); without it
   // even the significance flags are priced by their lanes and summed with DPP.  Prices are accumulated in Q15 integers -- every
   // table entry is a multiple of 2^-15 -- so the sum is exact and order-free, and equals the double sum of the one-lane version.
-  KVZ_DEV static int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
   // The state machine of the residual contexts in REGISTERS for the duration of one block, one context per lane and register so that a bin is
   // v_readlane / v_writelane with a scalar lane number and a handful of scalar operations -- no LDS round trip, no byte insertion on the chain
   // from one bin's state to the next.  Three registers, every class of contexts inside one of them (r = index - KVZ_HIP_CX_SIG_CG):
@@ -1059,15 +1068,7 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
   {
     const int w = 1 << log2w;
     const u8 *top = s->ref[c][0], *left = s->ref[c][1];
-    if (c == 0 && mode != 1 && w != 4) {
-      bool filt;
-      if (mode == 0) filt = true;
-      else {
-        const int thres = log2w == 3 ? 7 : (log2w == 4 ? 1 : 0);
-        filt = imin(iabs(mode - 26), iabs(mode - 10)) > thres;
-      }
-      if (filt) { top = s->fref[0]; left = s->fref[1]; }
-    }
+    if (c == 0 && luma_reads_filtered(log2w, mode)) { top = s->fref[0]; left = s->fref[1]; }
     if (mode == 0) return planar_pixel(log2w, x, y, top, left);
     if (mode == 1) {
       const int dc = s->dcval[c];
@@ -1390,7 +1391,7 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
   template <int L2>
   KVZ_DEV void build_mref(int tid, const u32 *pre = nullptr)
   {
-    constexpr int W = 1 << L2, NQ = 2 * W + 2, THRES = L2 == 3 ? 7 : (L2 == 4 ? 1 : 0), N = (15 * NQ + KVZ_CTU_THREADS - 1) / KVZ_CTU_THREADS;
+    constexpr int W = 1 << L2, NQ = 2 * W + 2, N = (15 * NQ + KVZ_CTU_THREADS - 1) / KVZ_CTU_THREADS;
     u8 vals[N];
     if constexpr (L2 != 5) {
       static_assert(N * KVZ_CTU_THREADS <= 512, "Tables::mref_tab rows");
@@ -1404,7 +1405,7 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
     }
     for (int k = 0; k < N; k++) {
       const int i = imin(tid + k * KVZ_CTU_THREADS, 15 * NQ - 1), mode = 11 + i / NQ, q = i % NQ - W;
-      const bool vertical = mode >= 18, filt = imin(iabs(mode - 26), iabs(mode - 10)) > THRES;
+      const bool vertical = mode >= 18, filt = luma_reads_filtered(L2, mode);
       const u8 *top = filt ? s->fref[0] : s->ref[0][0], *left = filt ? s->fref[1] : s->ref[0][1];
       const u8 *main_ref = vertical ? top : left, *side_ref = vertical ? left : top;
       const int idx = q >= 0 ? q : (128 + (-q) * (int)s->mode_inv[mode]) >> 8;
@@ -1628,14 +1629,12 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
         s->satd_raw[mode][b] = angular_block_satd<false>(log2w, mode, bx, by, xl, yl, 0);
       }
 #else
-      // modes 2..33: TWO lanes per (mode, block), rows 0..3 and 4..7 of the block (angular_block_satd<true>): 64 lane tasks for an 8x8 CU -- one wavefront --,
-      // 256 for a 16x16 one
-      if (log2w == 4 && KVZ_CTU_THREADS == 128) {
-        // a 16x16 CU has 128 (mode, block) pairs: ONE lane each, all eight rows in the lane (angular_block_satd<false>) -- one round of the two wavefronts where the
-        // paired form needs two, and no exchange stage
+      // modes 2..33
+      if (log2w == 4) {
+        // a 16x16 CU has 128 (mode, block) pairs: ONE lane each, all eight rows in the lane (angular_block_satd<false>) -- one round of the two wavefronts, no exchange stage
         const int mode = 2 + (tid >> 2), b = tid & 3;
         s->satd_raw[mode][b] = angular_block_satd<false>(4, mode, (b & 1) * 8, (b >> 1) * 8, xl, yl, 0);
-      } else
+      } else  // an 8x8 CU (nblk 1): TWO lanes per mode, rows 0..3 and 4..7 of the block (angular_block_satd<true>) -- 64 lane tasks, one wavefront
       for (int t = tid; t < 64 * nblk; t += KVZ_CTU_THREADS) {
         const int p = t >> 1, mode = 2 + (p >> lb), b = p & (nblk - 1), bx = (b & ((w >> 3) - 1)) * 8, by = (b >> (log2w - 3)) * 8;
         const u32 v = angular_block_satd<true>(log2w, mode, bx, by, xl, yl, t & 1);
@@ -1692,13 +1691,13 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
 #endif
   }
 
-  // Both passes of a 16- or 32-point transform of plane c, in place on x.  Device: wavefront c (mod the wavefronts of the
-  // workgroup) runs them chained through MFMA registers (kvz_mfma.hpp).  Host: one thread, scalar loops through a temporary --
-  // the same integers (dct-generic.c:559-579: the forward intermediate wraps to int16, both inverse stages clip).
+  // Both passes of a 16- or 32-point transform of plane c, in place on x.  Device: luma on the wavefront playing threads 0..63, V too,
+  // U on the other one, chained through MFMA registers (kvz_mfma.hpp).  Host: one thread, scalar loops through a temporary --
+  // the same integers (fwd_point / inv_point).
   KVZ_DEV void transform_big(int l2, i16 *x, bool inverse, int tid, int c) const
   {
 #ifndef KVZ_HOSTSIM
-    if ((tid >> 6) != c % (KVZ_CTU_THREADS / 64)) return;
+    if ((tid >> 6) != (c & 1)) return;
     if (l2 == 5) mfma_transform_block<32>(x, x, inverse, tb, tid & 63);
     else mfma_transform_block<16>(x, x, inverse, tb, tid & 63);
 #else
@@ -1708,33 +1707,72 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
     for (int pass = 0; pass < 2; pass++) {
       const i16 *src = pass == 0 ? x : tmp;
       i16 *dst = pass == 0 ? tmp : x;
-      const int shift = inverse ? (pass == 0 ? 7 : 12) : (pass == 0 ? l2 - 1 : l2 + 6), add = 1 << (shift - 1);
+      const int shift = inverse ? (pass == 0 ? 7 : 12) : (pass == 0 ? l2 - 1 : l2 + 6);
       for (int e = 0; e < n * n; e++) {
-        int a = 0;
-        if (!inverse) { const int k = e >> l2, j = e & (n - 1); for (int i = 0; i < n; i++) a += dct_at(l2, k, i) * (int)src[(j << l2) + i]; }
-        else { const int j = e >> l2, i = e & (n - 1); for (int k = 0; k < n; k++) a += dct_at(l2, k, i) * (int)src[(k << l2) + j]; }
-        dst[e] = inverse ? (i16)iclip(-32768, 32767, (a + add) >> shift) : (i16)((a + add) >> shift);
+        const int hi = e >> l2, lo = e & (n - 1);  // forward: output (k = hi, row j = lo); inverse: output (row j = hi, i = lo)
+        dst[e] = inverse ? inv_point(n, [&](int k) { return dct_at(l2, k, lo); }, src, hi, n, shift) : fwd_point(n, [&](int i) { return dct_at(l2, hi, i); }, src, lo << l2, shift);
       }
     }
 #endif
   }
 
-  // intra_recon_tb_leaf (intra.c:561-608) + kvz_quantize_residual (quant-generic.c:198-292) for the planes of `t`,
-  // written into work-tree level lv.  Sets the cbf bits of the CU's info entry.  One barrier per stage.
-  // Per-plane sums of the fused 8x8-CU stages: lanes 0..63 carry luma, 64..79 U, 80..95 V (the rest contribute 0).  Device: DPP
-  // row reduction, then the luma wavefront adds its four row sums to acc3[0], the other one rows 0 / 1 to acc3[1] / acc3[2].
-  KVZ_DEV void plane_add(u32 *acc3, u32 v, int tid) const
+  // ---- the per-plane sums of a reconstruction stage (s->acc: [0..2] SSD, [3..5] weight sums, [6..8] counts of levels).  Every lane decomposition below places its
+  // lanes so that a DPP row of sixteen lanes never mixes planes: ONE row reduction (row16_sum + four v_readlane) serves all three planes of a stage, and the
+  // decompositions differ only in which plane a row belongs to:
+  //   ROWS_CU8    recon_cu8, eval_pu: the wavefront playing threads 0..63 is all luma; on the other one row 0 is U and row 1 V
+  //   ROWS_W16    a 16x16 CU, one trip on the first wavefront: rows 0-1 luma, row 2 U, row 3 V
+  //   ROWS_W32_Y  a 32x32 unit, trip 0: both wavefronts all luma
+  //   ROWS_W32_C  ... trip 1: the first wavefront, rows 0-1 U, rows 2-3 V
+  // `packed`: v is a sum of LevelCost words.  ROWS_CU8 has one writer per slot and stage -- each wavefront owns its planes' slots -- and at most 64 words per
+  // plane, so it adds the word as it is to acc[3 + plane] and finish_planes() takes it apart when the unit is done.  The wide layouts (eight words a lane, a
+  // row stays below 128 levels and 2^23) add from both wavefronts and take the word apart here, before rows are added up.
+  // Every lane of a wavefront that has tasks in the trip comes here, lanes without a task with c = -1 and v = 0.
+  enum RowPlan { ROWS_CU8, ROWS_W16, ROWS_W32_Y, ROWS_W32_C };
+  KVZ_DEV void plane_sums(RowPlan plan, int tid, int c, u32 v, bool packed, int base) const
   {
 #ifdef KVZ_HOSTSIM
-    if (tid < 96) acc3[tid < 64 ? 0 : (tid < 80 ? 1 : 2)] += v;
+    (void)tid;
+    if (c < 0) return;
+    if (packed && plan != ROWS_CU8) { s->acc[3 + c] += v & 0xffffffu; s->acc[6 + c] += v >> 24; }
+    else s->acc[base + c] += v;
 #else
+    (void)c;
+    if ((plan == ROWS_W16 || plan == ROWS_W32_C) && tid >= 64) return;  // wavefront-uniform: the other wavefront has no tasks in this trip
     const int x = row16_sum((int)v);
     const u32 r0 = (u32)__builtin_amdgcn_readlane(x, 15), r1 = (u32)__builtin_amdgcn_readlane(x, 31), r2 = (u32)__builtin_amdgcn_readlane(x, 47), r3 = (u32)__builtin_amdgcn_readlane(x, 63);
-    if ((tid & 63) == 0) {  // one writer per slot and stage: the slots were zeroed in stage 1
-      if (tid < 64) acc3[0] += r0 + r1 + r2 + r3;
-      else { acc3[1] += r0; acc3[2] += r1; }
+    if ((tid & 63) != 0) return;
+    if (plan == ROWS_CU8) {
+      if (tid < 64) s->acc[base] += r0 + r1 + r2 + r3;
+      else { s->acc[base + 1] += r0; s->acc[base + 2] += r1; }
+      return;
     }
+    auto put = [&](int plane, u32 a, u32 b) {
+      if (packed) {
+        const u32 ws = (a & 0xffffffu) + (b & 0xffffffu), n = (a >> 24) + (b >> 24);
+        if (n) { atomicAdd(&s->acc[3 + plane], ws); atomicAdd(&s->acc[6 + plane], n); }  // no levels, no weights: coeff_weights' entry 0 is that of a zero level
+        else if (ws) atomicAdd(&s->acc[3 + plane], ws);
+      } else if (a + b) atomicAdd(&s->acc[base + plane], a + b);
+    };
+    if (plan == ROWS_W16) { put(0, r0, r1); put(1, r2, 0); put(2, r3, 0); }
+    else if (plan == ROWS_W32_Y) { put(0, r0, r1); put(0, r2, r3); }
+    else { put(1, r0, r1); put(2, r2, r3); }
 #endif
+  }
+  // The end of a unit, for planes c0 .. c1 - 1, by the one thread that owns them: a packed sum of LevelCost words is taken apart (weight sum, count: what the
+  // cost reads), and "the plane has levels" becomes the cbf bit of the TU's top-left CU entry (transform.c:314, 409-411) -- or, for a PU of the NxN attempt
+  // (level 4), waits in RdoqLds until the partition wins (nxn_attempt).
+  KVZ_DEV void finish_planes(int lv, int xl, int yl, int depth, int c0, int c1, bool packed) const
+  {
+    for (int c = c0; c < c1; c++) {
+      u32 n = s->acc[6 + c];
+      if (packed) { const u32 pk = s->acc[3 + c]; n = pk >> 24; s->acc[3 + c] = pk & 0xffffffu; s->acc[6 + c] = n; }
+      if (NXN && lv == 4) { if (c == 0) rl->pu_cbf[rl->n_pu] = n != 0; else rl->pu_cbf_c[c - 1] = n != 0; }
+      else {
+        CtuCu *cu = &s->cu[lv][(yl >> 3) * 8 + (xl >> 3)];
+        cbf_clear(&cu->cbf, depth, c);
+        if (n) cbf_set(&cu->cbf, depth, c);
+      }
+    }
   }
   // The 8x8 CU -- an 8x8 luma and two 4x4 chroma units, 96 samples -- with every stage of recon_tus() in ONE pass, one lane per
   // sample of any plane: three quarters of the CUs the search evaluates are these, and a loop per plane runs each stage's code
@@ -1769,10 +1807,12 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
     KVZ_CU8_STAGE(stage1)
     KVZ_WAVE_SYNC();
     KVZ_PROF(KVZ_P_RPRED);
+    // The four transform passes below are fwd_point / inv_point (kvz_recon.hpp) spelled out: called through the helpers the same values come out, but the
+    // 32x32-search kernel then spills five more VGPRs (scratch 48 -> 68 B per lane).  Everything else of a sample's arithmetic is the shared text.
     auto stage2 = [&](auto luma, int tid) {  // forward transform (dct-generic.c:559-568), first pass
       KVZ_CU8_ROLE(tid);
-      constexpr int shift = l2 - 1, add = 1 << (shift - 1);
       const int k = e >> l2, j = e & (n - 1);
+      constexpr int shift = l2 - 1, add = 1 << (shift - 1);
       const i16 *src = tbuf(t, 0, c);
       int a = 0;
 #pragma unroll
@@ -1788,37 +1828,31 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
       u32 packed = 0;
       auto stage3 = [&](auto luma, int tid_) {
         KVZ_CU8_ROLE(tid_);
-        constexpr int shift = l2 + 6, add = 1 << (shift - 1);
         const int k = e >> l2, j = e & (n - 1);
+        constexpr int shift = l2 + 6, add = 1 << (shift - 1);
         const i16 *src = tbuf(t, 1, c);
         int a = 0;
 #pragma unroll
         for (int i = 0; i < n; i++) a += dct_at(l2, k, i) * (int)src[(j << l2) + i];
         const int cf = (i16)((a + add) >> shift);
         const QuantScalars q = s->qs[l2 - 2][LUMA ? 0 : 1];
-        int level = (int)(((u32)iabs(cf) * (u32)q.flat_q + (u32)q.add) >> q.q_bits);
-        if (cf < 0) level = -level;
-        level = iclip(-32768, 32767, level);
+        const int level = quant_level(cf, q);
         levels_lds(lv, c)[e] = (i16)level;  // lv == 3 here
-        int al = iabs(level);
-        const u32 nz = al != 0;
-        if (al > 3) al = 3;
-        const u32 wsum = (u32)((m->coeff_weights >> (16 * al)) & 0xffff);
-        tbuf(t, 0, c)[e] = (i16)iclip(-32768, 32767, (level * q.dq_scale + (1 << (q.dq_shift - 1))) >> q.dq_shift);
-        packed = wsum | (nz << 24);
+        tbuf(t, 0, c)[e] = dequant_level(level, q);
+        packed = level_cost(level, m->coeff_weights).word();
       };
       if (tid < 64) stage3(std::true_type(), tid); else if (tid < 96) stage3(std::false_type(), tid);
       // the plane's weight sum (< 2^22) and its count of levels travel in ONE word: one reduction instead of two.  (Per-lane LDS atomics instead of the DPP
       // reduction -- profiles/experiments, r05_g -- take 7 k instructions per CTU off the vector pipe and cost 6 % throughput: 64 lanes on one address.)
-      plane_add(&s->acc[3], packed, tid);
+      plane_sums(ROWS_CU8, tid, tid < 64 ? 0 : (tid < 80 ? 1 : (tid < 96 ? 2 : -1)), packed, true, 3);
     }
     KVZ_WAVE_SYNC();
     KVZ_PROF(KVZ_P_QUANT);
     auto stage4 = [&](auto luma, int tid) {  // inverse transform (dct-generic.c:570-579), first pass; only observable when the plane has coefficients
       KVZ_CU8_ROLE(tid);
       if (s->acc[3 + c] >> 24) {
-        constexpr int shift = 7, add = 1 << (shift - 1);
         const int j = e >> l2, i = e & (n - 1);
+        constexpr int shift = 7, add = 1 << (shift - 1);
         const i16 *src = tbuf(t, 0, c);
         int a = 0;
 #pragma unroll
@@ -1838,34 +1872,25 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
         u8 *rp = &cv.at(c, (xl >> sh) + (e & (n - 1)), (yl >> sh) + (e >> l2));
         int v = *rp;
         if (s->acc[3 + c] >> 24) {
-          constexpr int shift = 12, add = 1 << (shift - 1);
           const int j = e >> l2, i = e & (n - 1);
+          constexpr int shift = 12, add = 1 << (shift - 1);
           const i16 *src = tbuf(t, 1, c);
           int a = 0;
 #pragma unroll
           for (int k = 0; k < n; k++) a += dct_at(l2, k, i) * (int)src[(k << l2) + j];
           const i16 res = (i16)iclip(-32768, 32767, (a + add) >> shift);
-          v = iclip(0, 255, (int)(i16)(res + v));
+          v = recon_sample(v, res);
           *rp = (u8)v;
         }
-        const int d = (int)*org_at(c, (xl >> sh) + (e & (n - 1)), (yl >> sh) + (e >> l2)) - v;
-        ssd = (u32)(d * d);
+        ssd = sq_err(*org_at(c, (xl >> sh) + (e & (n - 1)), (yl >> sh) + (e >> l2)), v);
       };
       if (tid < 64) stage5(std::true_type(), tid); else if (tid < 96) stage5(std::false_type(), tid);
-      plane_add(&s->acc[0], ssd, tid);
+      plane_sums(ROWS_CU8, tid, tid < 64 ? 0 : (tid < 80 ? 1 : (tid < 96 ? 2 : -1)), ssd, false, 0);
     }
     KVZ_SYNC();
     KVZ_FOR_THREADS(tid) {
-      if (tid == 0) {  // cbf bits of the TU's top-left CU entry (transform.c:314, 409-411): all three planes' counts, so behind the barrier; only thread 0 reads them
-                       // next (eval_cu's cost phase, same thread: no barrier in between)
-        CtuCu *cu = &s->cu[lv][(yl >> 3) * 8 + (xl >> 3)];
-        for (int cc = 0; cc < 3; cc++) {
-          const u32 packed = s->acc[3 + cc];  // unpacked for the cost: weight sum, count
-          s->acc[3 + cc] = packed & 0xffffffu; s->acc[6 + cc] = packed >> 24;
-          cbf_clear(&cu->cbf, depth, cc);
-          if (packed >> 24) cbf_set(&cu->cbf, depth, cc);
-        }
-      }
+      // all three planes' counts, so behind the barrier; only thread 0 reads the results next (eval_cu's cost phase, same thread: no barrier in between)
+      if (tid == 0) finish_planes(lv, xl, yl, depth, 0, 3, true);
     }
     if (cabac_on()) KVZ_SYNC();  // the counting-mode coder runs on every lane and asks acc[6..8] which planes have levels (price_unit_coeffs)
     KVZ_PROF(KVZ_P_RECON);
@@ -1873,38 +1898,53 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
 #undef KVZ_CU8_STAGE
   }
 
-  // Where the quantised levels of plane c of a transform unit at (xl, yl) go when work-tree level lv evaluates it (see coeff_level())
+  // The levels of a unit's blocks from kvz_rdoq (quant-generic.c:234-244), a block per wavefront (rdoq_block_wave): the one playing threads 0..63 takes the luma
+  // block, the other one U then V (`chroma`: the unit has them).  The host simulation's threads 0 and 64 stand for the wavefronts and run the one-lane form.  On
+  // the contexts of the row's coder as they stood when this CTU began (RdoqLds::ptab from pre[0] = state->cabac, rdo.c:665).  From tbuf(t, 0, c) to levels_lds(lv, c),
+  // whatever the work-tree level: CUs whose levels live in HBM (the units of the 64x64 attempt) have a staging copy there for the coefficient cost anyway.
+  KVZ_DEV void rdoq_unit(int tid, int lv, const TuSet &t, bool chroma, int depth, int mode) const
+  {
+#ifdef KVZ_HOSTSIM
+    const int wv = tid == 0 ? 0 : (tid == 64 ? 1 : -1), lane = 0;
+#else
+    const int wv = tid >> 6, lane = tid & 63;
+#endif
+    for (int c = 0; c < (chroma ? 3 : 1); c++) {
+      if (wv != (c ? 1 : 0)) continue;
+      RdoqWaveArgs ra;
+      ra.ptab = (KVZ_LDS_PTR(const i32))rl->ptab; ra.coef = (KVZ_LDS_PTR(const i16))tbuf(t, 0, c); ra.dest = (KVZ_LDS_PTR(i16))levels_lds(lv, c);
+      ra.diag8 = (KVZ_LDS_PTR(const u8))rl->diag8; ra.lambda = m->lambda; ra.qp = m->qp; ra.log2w = tu_log2(t, c); ra.type = c ? 2 : 0;
+      ra.scan_mode = intra_scan_order(mode, depth);
+      // tr_depth = cu->tr_depth - cu->depth: 1 for the 32x32 units of the 64x64 attempt (level 0), 0 otherwise -- plus one for an NxN CU
+      // (quant-generic.c:237-238): 2 for the blocks of its PUs (level 4)
+      ra.tr_depth = lv == 4 ? 2 : (lv == 0 ? 1 : 0);
+#if defined(KVZ_CTU_PROFILE) && !defined(KVZ_HOSTSIM)
+      ra.prof = s->prof_rq;  // LDS: one global atomic per call and section would be the hottest cache line of the device
+      const unsigned long long tc0 = __builtin_amdgcn_s_memtime();
+#endif
+      rdoq_block_wave(ra, lane);
+#if defined(KVZ_CTU_PROFILE) && !defined(KVZ_HOSTSIM)
+      if (c == 0 && lane == 0) ra.prof[7] += __builtin_amdgcn_s_memtime() - tc0;  // the call as the caller sees it: minus the routine's own clock = what calling it costs
+#endif
+    }
+  }
+  // Where the quantised levels of plane c of a transform unit at (xl, yl) go when work-tree level lv (0..3) evaluates it (see coeff_level())
   KVZ_DEV i16 *coeff_dst(int lv, int c, int xl, int yl) const
   {
     const int sh = c ? 1 : 0;
-    if ((NXN && lv == 4) || lv == 3) return levels_lds(lv, c);
+    if (lv == 3) return levels_lds(lv, c);
     return lv == 2 ? s->lv2_coeff + (c == 0 ? 0 : (c == 1 ? 256 : 320))
          : lv == 1 ? s->lv1_coeff + (c == 0 ? 0 : (c == 1 ? 1024 : 1280)) : coeff_level(lv) + plane_off(c) + ctu_zorder(xl >> sh, yl >> sh);
-  }
-  // Entry (k, i) of the transform of a 2^l2 block of plane c: the DCT, except 4x4 intra luma (strategies-dct.c:82-86, 111-115: the DST), which only the PUs of
-  // an NxN CU have
-  KVZ_DEV int tmat(int l2, int c, int k, int i) const
-  {
-    if (NXN && l2 == 2 && c == 0) return tb->dst4[4 * k + i];
-    return dct_at(l2, k, i);
   }
 
   // ---- the arithmetic stages of recon_tus() for units of 16 and 32 samples: a lane task is a row segment of EIGHT samples of one plane (the 8x8 CU has
   // recon_cu8; one sample per lane and trip was three trips on two wavefronts for a 16x16 CU and twelve for a 32x32 unit).  Where the tasks sit:
   //   16x16 CU    32 luma + 8 U + 8 V tasks, ONE trip on the wavefront playing threads 0..63: DPP rows 0-1 luma, the first half of row 2 U, of row 3 V
   //   32x32 unit  trip 0: 128 luma tasks on both wavefronts; trip 1: 32 U (rows 0-1) + 32 V (rows 2-3) on the first
-  // so a DPP row of sixteen lanes never mixes planes and ONE row reduction per trip serves all three planes of a stage (wide_add), as plane_add does for the 8x8 CU.
+  // (plane_sums: ROWS_W16, ROWS_W32_Y, ROWS_W32_C).
   // Returns the plane of thread tid's task in `trip` (-1: none) and which eight samples of the plane: elements 8 seg .. 8 seg + 7, row-major.
   KVZ_DEV static int wide_trips(int lw) { return lw == 4 ? 1 : 2; }
-  // a wavefront-uniform value as a scalar (the host runs one thread at a time)
-  KVZ_DEV static int wide_uni(int v)
-  {
-#ifdef KVZ_HOSTSIM
-    return v;
-#else
-    return __builtin_amdgcn_readfirstlane(v);
-#endif
-  }
+  KVZ_DEV static RowPlan wide_rows(int lw, int trip) { return lw == 4 ? ROWS_W16 : (trip == 0 ? ROWS_W32_Y : ROWS_W32_C); }
   KVZ_DEV static int wide_task(int lw, int trip, int tid, int *seg)
   {
     *seg = 0;
@@ -1919,35 +1959,6 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
     *seg = tid & 31;
     return 1 + (tid >> 5);
   }
-  // Sum of a trip's lane values per plane, added to s->acc[base + plane]; every lane of a wavefront that has tasks in the trip comes here (lanes without a task
-  // with 0).  `packed`: the value is count << 24 | weight sum (eight coefficients a lane: a row of sixteen lanes stays below 2^23 and 128, so the packed word
-  // survives the row reduction and is taken apart before rows are added up) and goes to acc[3 + plane] / acc[6 + plane].
-  KVZ_DEV void wide_add(int lw, int trip, int tid, int c, u32 v, bool packed, int base) const
-  {
-#ifdef KVZ_HOSTSIM
-    (void)lw; (void)trip; (void)tid;
-    if (c < 0) return;
-    if (packed) { s->acc[3 + c] += v & 0xffffffu; s->acc[6 + c] += v >> 24; }
-    else s->acc[base + c] += v;
-#else
-    (void)c;
-    if ((lw == 4 || trip == 1) && tid >= 64) return;  // wavefront-uniform: the other wavefront has no tasks in this trip
-    const int x = row16_sum((int)v);
-    const u32 r0 = (u32)__builtin_amdgcn_readlane(x, 15), r1 = (u32)__builtin_amdgcn_readlane(x, 31), r2 = (u32)__builtin_amdgcn_readlane(x, 47), r3 = (u32)__builtin_amdgcn_readlane(x, 63);
-    if ((tid & 63) == 0) {
-      auto put = [&](int plane, u32 a, u32 b) {
-        if (packed) {
-          const u32 ws = (a & 0xffffffu) + (b & 0xffffffu), n = (a >> 24) + (b >> 24);
-          if (n) { atomicAdd(&s->acc[3 + plane], ws); atomicAdd(&s->acc[6 + plane], n); }  // no levels, no weights: coeff_weights' entry 0 is that of a zero level
-          else if (ws) atomicAdd(&s->acc[3 + plane], ws);
-        } else if (a + b) atomicAdd(&s->acc[base + plane], a + b);
-      };
-      if (lw == 4) { put(0, r0, r1); put(1, r2, 0); put(2, r3, 0); }
-      else if (trip == 0) { put(0, r0, r1); put(0, r2, r3); }
-      else { put(1, r0, r1); put(2, r2, r3); }
-    }
-#endif
-  }
   // kvz_intra_predict (intra.c:252-301) for the eight samples (px0 .. px0 + 7, py) of plane c of a 2^l2 unit, l2 >= 3: predict_pixel() sample for sample, with
   // what only depends on the mode and the row worked out once.  `mode` is uniform, so every branch on it is one for the wavefront.  Chroma: unfiltered
   // references, no edge filters; 32-wide luma: no edge filters.
@@ -1956,7 +1967,7 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
     const int w = 1 << l2;
     const bool edges = c == 0 && w < 32;  // intra.c:207-219 intra_post_process_angular, intra-generic.c:210-241
     const u8 *top = s->ref[c][0], *left = s->ref[c][1];
-    if (c == 0 && mode != 1 && (mode == 0 || imin(iabs(mode - 26), iabs(mode - 10)) > (l2 == 3 ? 7 : (l2 == 4 ? 1 : 0)))) { top = s->fref[0]; left = s->fref[1]; }
+    if (c == 0 && luma_reads_filtered(l2, mode)) { top = s->fref[0]; left = s->fref[1]; }
     if (mode == 0) {  // intra-generic.c:165-201: (w-1-x) L + (x+1) TR + (w-1-y) T[x] + (y+1) BL + w, the terms without x first
       const int l = left[py + 1], tr = top[w + 1], bl = left[w + 1];
       const int hb = (w - 1) * l + tr + (py + 1) * bl + w, dl = tr - l, wy = w - 1 - py;
@@ -1992,22 +2003,27 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
     }
   }
 
+  // intra_recon_tb_leaf (intra.c:561-608) + kvz_quantize_residual (quant-generic.c:198-292) for the three planes of `t` -- a CU of 8, 16 or 32 luma samples with
+  // its chroma blocks (4x4 for the 8x8 CU), or a 32x32 unit of a 64x64 CU -- written into work-tree level lv (0..3; the PUs of level 4 have eval_pu).  Sets the cbf
+  // bits of the CU's info entry.  One barrier per stage.
   KVZ_DEV void recon_tus(int lv, const TuSet &t, int depth, int mode, bool refs_ready = false)
   {
     const int xl = t.x - cx, yl = t.y - cy;
     const CandView cv = cand_view(lv);
     // units of 16 and 32 samples run stages 1, 4 and 7 eight samples a lane (wide_task); the quantiser of the RDOQ instantiation stays as it is: its levels come
     // from rdoq_block_wave and its register budget is at the limit
-    const bool wide = KVZ_CTU_THREADS == 128 && t.lw >= 4 && t.lc == t.lw - 1;
-    if (!refs_ready) build_refs(lv, t.x, t.y, t.lw, t.lc, t.lw != 0, t.lc != 0);
-    if (!RDOQ && KVZ_CTU_THREADS == 128 && t.lw == 3 && t.lc == 2) { recon_cu8(lv, t, depth, mode); return; }
+    const bool wide = t.lw >= 4;
+    if (!refs_ready) build_refs(lv, t.x, t.y, t.lw, t.lc, true, true);
+    if (!RDOQ && t.lw == 3) { recon_cu8(lv, t, depth, mode); return; }
+    // From here on the stages written one sample per lane and trip (stages 1 and 7 where !wide, stage 4 whenever the levels come from kvz_rdoq) serve the RDOQ
+    // instantiation alone, and of these stages 1 and 7 exactly one case: its 8x8 CU.
 #if defined(KVZ_CTU_PROFILE) && !defined(KVZ_HOSTSIM)
     // the stage clock of the units larger than 8x8 goes to the PU half of prof_acc, idle where no NxN partition is tried: tools/ctu_profile.py prints both paths side by side
     struct InLarge { CtuSharedT<CABAC> *s; bool on; __device__ InLarge(CtuSharedT<CABAC> *s_, bool on_) : s(s_), on(on_) { if (on && threadIdx.x == 0) s->prof_pu = 1; } __device__ ~InLarge() { if (on && threadIdx.x == 0) s->prof_pu = 0; } } in_large(s, !NXN && t.lw >= 4);
 #endif
     // stage 1: prediction -> rec (as kvazaar blits it before quantising) and residual
     if (wide) {
-      const int umode = wide_uni(mode);
+      const int umode = uni(mode);
       KVZ_FOR_THREADS(tid) {
         if (tid < 16) s->acc[tid] = 0;
         for (int trip = 0; trip < wide_trips(t.lw); trip++) {
@@ -2030,9 +2046,7 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
     KVZ_FOR_THREADS(tid) {
       if (tid < 16) s->acc[tid] = 0;
       for (int c = 0; c < 3; c++) {
-        const int l2 = tu_log2(t, c);
-        if (!l2) continue;
-        const int w = 1 << l2, sh = c ? 1 : 0;
+        const int l2 = tu_log2(t, c), w = 1 << l2, sh = c ? 1 : 0;
         for (int e = tid; e < w * w; e += KVZ_CTU_THREADS) {
           const int px = e & (w - 1), py = e >> l2;
           const u8 p = predict_pixel(l2, mode, c, px, py);
@@ -2047,9 +2061,7 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
     for (int pass = 0; pass < 2; pass++) {
       KVZ_FOR_THREADS(tid) {
         for (int c = 0; c < 3; c++) {
-          const int l2 = tu_log2(t, c);
-          if (!l2) continue;
-          const int n = 1 << l2, shift = pass == 0 ? l2 - 1 : l2 + 6, add = 1 << (shift - 1);
+          const int l2 = tu_log2(t, c), n = 1 << l2;
           const i16 *src = tbuf(t, pass, c);
           i16 *dst = tbuf(t, pass ^ 1, c);
           if (l2 >= 4) {  // 16 / 32 points: both passes at once (pass 0 only), in place on buffer 0, by one wavefront per plane
@@ -2058,9 +2070,7 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
           }
           for (int e = tid; e < n * n; e += KVZ_CTU_THREADS) {
             const int k = e >> l2, j = e & (n - 1);
-            int a = 0;
-            for (int i = 0; i < n; i++) a += tmat(l2, c, k, i) * (int)src[(j << l2) + i];
-            dst[e] = (i16)((a + add) >> shift);
+            dst[e] = fwd_point(n, [&](int i) { return dct_at(l2, k, i); }, src, j << l2, pass == 0 ? l2 - 1 : l2 + 6);
           }
         }
       }
@@ -2068,49 +2078,16 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
     }
     KVZ_PROF(KVZ_P_FDCT);
     // stage 4: quantise (quant-generic.c:57-81) -> coefficient store + cost sums; dequantise (:335-339) -> tb[1]
-    // With RDOQ (quant-generic.c:234-244) the levels come from kvz_rdoq instead: serial per block, so one lane per plane runs it -- luma on the
-    // first wavefront, U and V on two lanes of the other -- on the contexts of the row's coder as they stood when this CTU began (pre[0] =
-    // state->cabac, rdo.c:665), and the loop below takes the levels from where it left them.
+    // With RDOQ (quant-generic.c:234-244) the levels come from kvz_rdoq instead (rdoq_unit), and the loop below takes them from levels_lds() and moves them on.
     if (RDOQ && m->rdoq) {
-      KVZ_FOR_THREADS(tid) {
-        // one wavefront per block (rdoq_block_wave): the one playing threads 0..63 takes the luma block, the next one U then V
-#ifdef KVZ_HOSTSIM
-        const int wv = tid == 0 ? 0 : (tid == 64 ? 1 : -1), lane = 0;
-#else
-        const int wv = tid >> 6, lane = tid & 63;
-#endif
-        for (int c = 0; c < 3; c++) {
-          const int l2 = tu_log2(t, c);
-          if (!l2 || wv != (c ? 1 : 0)) continue;
-          // the levels go to LDS whatever the work-tree level: CUs whose levels live in HBM (8x8 CUs, the units of the 64x64 attempt) have a staging copy
-          // for the coefficient cost anyway (levels_lds); the loop below moves them on
-          i16 *cout = (lv == 3 || lv == 0) ? levels_lds(lv, c) : coeff_dst(lv, c, xl, yl);
-          RdoqWaveArgs ra;
-          ra.ptab = (KVZ_LDS_PTR(const i32))rl->ptab; ra.coef = (KVZ_LDS_PTR(const i16))tbuf(t, 0, c); ra.dest = (KVZ_LDS_PTR(i16))cout;
-          ra.diag8 = (KVZ_LDS_PTR(const u8))rl->diag8; ra.lambda = m->lambda; ra.qp = m->qp; ra.log2w = l2; ra.type = c ? 2 : 0;
-          ra.scan_mode = intra_scan_order(mode, depth);
-          // tr_depth = cu->tr_depth - cu->depth: 1 for the 32x32 units of the 64x64 attempt (level 0), 0 otherwise -- plus one for an NxN CU
-          // (quant-generic.c:237-238): 2 for the blocks of its PUs (level 4)
-          ra.tr_depth = lv == 4 ? 2 : (lv == 0 ? 1 : 0);
-#if defined(KVZ_CTU_PROFILE) && !defined(KVZ_HOSTSIM)
-          ra.prof = s->prof_rq;  // LDS: one global atomic per call and section would be the hottest cache line of the device
-#endif
-#if defined(KVZ_CTU_PROFILE) && !defined(KVZ_HOSTSIM)
-          const unsigned long long tc0 = __builtin_amdgcn_s_memtime();
-          rdoq_block_wave(ra, lane);
-          if (c == 0 && lane == 0) ra.prof[7] += __builtin_amdgcn_s_memtime() - tc0;  // the call as the caller sees it: minus the routine's own clock = what calling it costs
-#else
-          rdoq_block_wave(ra, lane);
-#endif
-        }
-      }
+      KVZ_FOR_THREADS(tid) { rdoq_unit(tid, lv, t, true, depth, mode); }
       KVZ_SYNC();
       KVZ_PROF(KVZ_P_RDOQ);
     }
     if (!RDOQ && wide) {
       const bool to_stage = cabac_on() && lv == 0;  // see levels_lds()
       KVZ_FOR_THREADS(tid) {
-        const u32 cw_lo = (u32)wide_uni((int)(u32)m->coeff_weights), cw_hi = (u32)wide_uni((int)(u32)(m->coeff_weights >> 32));  // scalars for the call
+        const u32 cw_lo = (u32)uni((int)(u32)m->coeff_weights), cw_hi = (u32)uni((int)(u32)(m->coeff_weights >> 32));  // scalars for the call
         for (int trip = 0; trip < wide_trips(t.lw); trip++) {
           int seg;
           const int c = wide_task(t.lw, trip, mover_lane(tid), &seg);
@@ -2121,55 +2098,41 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
             i16 cf[8], lvl[8], dq[8];
             __builtin_memcpy(cf, KVZ_ALIGNED(tbuf(t, 0, c) + (seg << 3), 16), 16);
             u32 wsum = 0, nz = 0;
-            for (int k = 0; k < 8; k++) {  // the arithmetic of the narrow loop below, element for element
-              int level = (int)(((u32)iabs(cf[k]) * (u32)q.flat_q + (u32)q.add) >> q.q_bits);
-              if (cf[k] < 0) level = -level;
-              level = iclip(-32768, 32767, level);
+            for (int k = 0; k < 8; k++) {
+              const int level = quant_level(cf[k], q);
               lvl[k] = (i16)level;
-              int a = iabs(level);
-              nz += a != 0;
-              if (a > 3) a = 3;
-              wsum += ((a & 2) ? cw_hi : cw_lo) >> (16 * (a & 1)) & 0xffff;
-              dq[k] = (i16)iclip(-32768, 32767, (level * q.dq_scale + (1 << (q.dq_shift - 1))) >> q.dq_shift);
+              const LevelCost lc = level_cost(level, cw_lo, cw_hi);
+              wsum += lc.weight;
+              nz += lc.nonzero;
+              dq[k] = dequant_level(level, q);
             }
+            packed = wsum | (nz << 24);
             __builtin_memcpy(KVZ_ALIGNED(coeff_dst(lv, c, xl, yl) + (seg << 3), 16), lvl, 16);
             if (to_stage) __builtin_memcpy(KVZ_ALIGNED(levels_lds(lv, c) + (seg << 3), 16), lvl, 16);
             __builtin_memcpy(KVZ_ALIGNED(tbuf(t, 1, c) + (seg << 3), 16), dq, 16);
-            packed = wsum | (nz << 24);
           }
-          wide_add(t.lw, trip, tid, c, packed, true, 0);
+          plane_sums(wide_rows(t.lw, trip), tid, c, packed, true, 3);
         }
       }
     } else
     KVZ_FOR_THREADS(tid) {
       for (int c = 0; c < 3; c++) {
-        const int l2 = tu_log2(t, c);
-        if (!l2) continue;
-        const int n2 = 1 << (2 * l2);
-        const QuantScalars qf = s->qs[l2 - 2][c ? 1 : 0];  // forward and inverse share the plane's scaled QP (U and V alike)
-        const QuantScalars qi = qf;
+        const int l2 = tu_log2(t, c), n2 = 1 << (2 * l2);
+        const QuantScalars q = s->qs[l2 - 2][c ? 1 : 0];  // forward and inverse share the plane's scaled QP (U and V alike)
         i16 *cout = coeff_dst(lv, c, xl, yl);
         i16 *stage = (cabac_on() && lv == 0) ? levels_lds(lv, c) : nullptr;  // see levels_lds(); an 8x8 CU's destination IS its LDS slot
         const i16 *src = tbuf(t, 0, c);
         i16 *dq = tbuf(t, 1, c);
-        u32 wsum = 0, nz = 0;
+        u32 wsum = 0, nz = 0;  // apart: block_add sums up to 1024 levels a plane, more than the count of a packed word holds
         for (int e = tid; e < n2; e += KVZ_CTU_THREADS) {
-          const int cf = src[e];
-          // |cf| * q + add < 2^31 for 8-bit flat lists (32767 * 26214 + (171 << 18)), so 32-bit arithmetic is exact
           int level;
           if (RDOQ && m->rdoq) { level = (stage ? stage : cout)[e]; if (stage) cout[e] = (i16)level; }  // kvz_rdoq left them in LDS (above)
-          else {
-            level = (int)(((u32)iabs(cf) * (u32)qf.flat_q + (u32)qf.add) >> qf.q_bits);
-            if (cf < 0) level = -level;
-            level = iclip(-32768, 32767, level);
-            cout[e] = (i16)level;
-          }
+          else { level = quant_level(src[e], q); cout[e] = (i16)level; }
           if (stage && !(RDOQ && m->rdoq)) stage[e] = (i16)level;
-          int a = iabs(level);
-          nz += a != 0;
-          if (a > 3) a = 3;
-          wsum += (u32)((m->coeff_weights >> (16 * a)) & 0xffff);
-          dq[e] = (i16)iclip(-32768, 32767, (level * qi.dq_scale + (1 << (qi.dq_shift - 1))) >> qi.dq_shift);
+          const LevelCost lc = level_cost(level, m->coeff_weights);
+          wsum += lc.weight;
+          nz += lc.nonzero;
+          dq[e] = dequant_level(level, q);
         }
         block_add(&s->acc[3 + c], wsum);
         block_add(&s->acc[6 + c], nz);
@@ -2181,9 +2144,8 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
     for (int pass = 0; pass < 2; pass++) {
       KVZ_FOR_THREADS(tid) {
         for (int c = 0; c < 3; c++) {
-          const int l2 = tu_log2(t, c);
-          if (!l2 || !s->acc[6 + c]) continue;
-          const int n = 1 << l2, shift = pass == 0 ? 7 : 12, add = 1 << (shift - 1);
+          const int l2 = tu_log2(t, c), n = 1 << l2;
+          if (!s->acc[6 + c]) continue;
           const i16 *src = tbuf(t, pass ^ 1, c);
           i16 *dst = tbuf(t, pass, c);
           if (l2 >= 4) {  // both passes at once, in place on buffer 1 (where the dequantised coefficients are)
@@ -2192,9 +2154,7 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
           }
           for (int e = tid; e < n * n; e += KVZ_CTU_THREADS) {
             const int j = e >> l2, i = e & (n - 1);
-            int a = 0;
-            for (int k = 0; k < n; k++) a += tmat(l2, c, k, i) * (int)src[(k << l2) + j];
-            dst[e] = (i16)iclip(-32768, 32767, (a + add) >> shift);
+            dst[e] = inv_point(n, [&](int k) { return dct_at(l2, k, i); }, src, j, n, pass == 0 ? 7 : 12);
           }
         }
       }
@@ -2217,56 +2177,30 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
             if (s->acc[6 + c] != 0) {
               i16 res[8];
               __builtin_memcpy(res, KVZ_ALIGNED(tbuf(t, 1, c) + (seg << 3), 16), 16);
-              for (int k = 0; k < 8; k++) v[k] = (u8)iclip(0, 255, (int)(i16)(res[k] + v[k]));
+              for (int k = 0; k < 8; k++) v[k] = (u8)recon_sample(v[k], res[k]);
               __builtin_memcpy(KVZ_ALIGNED(rp, 8), v, 8);
             }
-            for (int k = 0; k < 8; k++) { const int d = (int)o[k] - (int)v[k]; ssd += (u32)(d * d); }
+            for (int k = 0; k < 8; k++) ssd += sq_err(o[k], v[k]);
           }
-          wide_add(t.lw, trip, tid, c, ssd, false, 0);
+          plane_sums(wide_rows(t.lw, trip), tid, c, ssd, false, 0);
         }
       } else
       for (int c = 0; c < 3; c++) {
-        const int l2 = tu_log2(t, c);
-        if (!l2) continue;
-        const int w = 1 << l2, sh = c ? 1 : 0;
+        const int l2 = tu_log2(t, c), w = 1 << l2, sh = c ? 1 : 0;
         const bool has = s->acc[6 + c] != 0;
         u32 ssd = 0;
         for (int e = tid; e < w * w; e += KVZ_CTU_THREADS) {
           u8 *rp = &cv.at(c, (xl >> sh) + (e & (w - 1)), (yl >> sh) + (e >> l2));
           int v = *rp;
-          if (has) { v = iclip(0, 255, (int)(i16)(tbuf(t, 1, c)[e] + v)); *rp = (u8)v; }
-          const int d = (int)*org_at(c, (xl >> sh) + (e & (w - 1)), (yl >> sh) + (e >> l2)) - v;
-          ssd += (u32)(d * d);
+          if (has) { v = recon_sample(v, tbuf(t, 1, c)[e]); *rp = (u8)v; }
+          ssd += sq_err(*org_at(c, (xl >> sh) + (e & (w - 1)), (yl >> sh) + (e >> l2)), v);
         }
         block_add(&s->acc[c], ssd);
       }
-      if (tid == 0) {  // cbf bits of the TU's top-left CU entry (transform.c:314, 409-411)
-        if (NXN && lv == 4) {  // a PU of the NxN attempt: its flags wait in RdoqLds until the partition wins (nxn_attempt)
-          rl->pu_cbf[rl->n_pu] = s->acc[6] != 0;
-          if (t.lc) { rl->pu_cbf_c[0] = s->acc[7] != 0; rl->pu_cbf_c[1] = s->acc[8] != 0; }
-        } else {
-          CtuCu *cu = &s->cu[lv][(yl >> 3) * 8 + (xl >> 3)];
-          for (int c = 0; c < 3; c++) if (tu_log2(t, c)) { cbf_clear(&cu->cbf, depth, c); if (s->acc[6 + c]) cbf_set(&cu->cbf, depth, c); }
-        }
-      }
+      if (tid == 0) finish_planes(lv, xl, yl, depth, 0, 3, false);
     }
     KVZ_SYNC();
     KVZ_PROF(KVZ_P_RECON);
-  }
-
-  KVZ_DEV QuantScalars quant_scalars_dev(int log2w, int type) const
-  {
-    // quant-generic.c:57-66, 303-339 with flat scaling lists, 8 bit, I slice (kvz_tables.hpp quant_scalars)
-    const int qps = type == 0 ? m->qp : chroma_qp(m->qp);
-    QuantScalars q;
-    const int transform_shift = 15 - 8 - log2w;
-    q.q_bits = 14 + qps / 6 + transform_shift;
-    q.add = 171 << (q.q_bits - 9);
-    q.flat_q = quant_scale(qps % 6);
-    q.dq_shift = 20 - 14 - transform_shift;
-    q.dq_scale = inv_quant_scale(qps % 6) << (qps / 6);
-    q.dq_list = 0; q.dq_qp_per = qps / 6;
-    return q;
   }
 
   // Who prices coefficients with the CABAC model -- THE place where the device and the host simulation part.  Device: every lane of both wavefronts (the wavefront
@@ -2627,6 +2561,8 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
     const int idx = 4 * k + i;
     return (int)(int8_t)(u8)((idx < 8 ? lo : hi) >> (8 * (idx & 7)));
   }
+  // Entry (k, i) of the transform of a PU's 4x4 block of plane c: the DST for intra luma (strategies-dct.c:82-86, 111-115), the DCT for chroma
+  KVZ_DEV int pu_tmat(int c, int k, int i) const { return c == 0 ? dst4_at(k, i) : dct_at(2, k, i); }
   // search_cu at depth 4 (search.c:646-1063 with depth > MAX_DEPTH: cu depth stays 3, search.c:691): PU j of the 8x8 CU at (rl->a3x, rl->a3y).
   // ONE pass per wavefront instead of the general stages of build_refs / recon_tus with a workgroup barrier each (a 4x4 block occupies sixteen lanes): the wavefront
   // playing threads 0..63 takes the luma block from its references to its reconstruction, the other one -- with the first PU -- the CU's 4x4 U and V blocks
@@ -2707,13 +2643,8 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
       KVZ_FOR_THREADS(tid) {
         KVZ_PU_ROLE(tid);
         if (c >= 0) {
-          const int shift = pass == 0 ? 1 : 8, add = 1 << (shift - 1);
-          const i16 *src = tbuf(t, pass, c);
           const int k = e >> 2, jj = e & 3;
-          int a = 0;
-#pragma unroll
-          for (int i = 0; i < 4; i++) a += (c == 0 ? dst4_at(k, i) : dct_at(2, k, i)) * (int)src[(jj << 2) + i];
-          tbuf(t, pass ^ 1, c)[e] = (i16)((a + add) >> shift);
+          tbuf(t, pass ^ 1, c)[e] = fwd_point(4, [&](int i) { return pu_tmat(c, k, i); }, tbuf(t, pass, c), jj << 2, pass == 0 ? 1 : 8);
         }
       }
       KVZ_WAVE_SYNC();
@@ -2721,29 +2652,7 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
     KVZ_PROF(KVZ_P_FDCT);
     // ---- kvz_rdoq (quant-generic.c:234-244), a block per wavefront: luma | U then V
     const bool rdoq = m->rdoq != 0;
-    KVZ_FOR_THREADS(tid) {
-#ifdef KVZ_HOSTSIM
-      const int wv = tid == 0 ? 0 : (tid == 64 ? 1 : -1), lane = 0;
-#else
-      const int wv = tid >> 6, lane = tid & 63;
-#endif
-      for (int c = 0; c < 3; c++) {
-        if (!rdoq || wv != (c ? 1 : 0) || (c && !chroma)) continue;
-        RdoqWaveArgs ra;
-        ra.ptab = (KVZ_LDS_PTR(const i32))rl->ptab; ra.coef = (KVZ_LDS_PTR(const i16))tbuf(t, 0, c); ra.dest = (KVZ_LDS_PTR(i16))levels_lds(4, c);
-        ra.diag8 = (KVZ_LDS_PTR(const u8))rl->diag8; ra.lambda = m->lambda; ra.qp = m->qp; ra.log2w = 2; ra.type = c ? 2 : 0;
-        ra.scan_mode = intra_scan_order(mode, 4);
-        ra.tr_depth = 2;  // cu->tr_depth - cu->depth + 1 for an NxN CU (quant-generic.c:237-238)
-#if defined(KVZ_CTU_PROFILE) && !defined(KVZ_HOSTSIM)
-        ra.prof = s->prof_rq;
-        const unsigned long long tc0 = __builtin_amdgcn_s_memtime();
-        rdoq_block_wave(ra, lane);
-        if (c == 0 && lane == 0) ra.prof[7] += __builtin_amdgcn_s_memtime() - tc0;
-#else
-        rdoq_block_wave(ra, lane);
-#endif
-      }
-    }
+    KVZ_FOR_THREADS(tid) { if (rdoq) rdoq_unit(tid, 4, t, chroma, 4, mode); }
     KVZ_WAVE_SYNC();
     KVZ_PROF(KVZ_P_RDOQ);
     // ---- (without RDOQ: quantise;) cost sums of the levels; dequantise (quant-generic.c:335-339)
@@ -2754,21 +2663,11 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
         const QuantScalars q = s->qs[0][c ? 1 : 0];
         int level;
         if (rdoq) level = levels_lds(4, c)[e];
-        else {  // quant-generic.c:57-81
-          const int cf = tbuf(t, 0, c)[e];
-          level = (int)(((u32)iabs(cf) * (u32)q.flat_q + (u32)q.add) >> q.q_bits);
-          if (cf < 0) level = -level;
-          level = iclip(-32768, 32767, level);
-          levels_lds(4, c)[e] = (i16)level;
-        }
-        int al = iabs(level);
-        const u32 nz = al != 0;
-        if (al > 3) al = 3;
-        const u32 wsum = (u32)((m->coeff_weights >> (16 * al)) & 0xffff);
-        tbuf(t, 1, c)[e] = (i16)iclip(-32768, 32767, (level * q.dq_scale + (1 << (q.dq_shift - 1))) >> q.dq_shift);
-        packed = wsum | (nz << 24);
+        else { level = quant_level(tbuf(t, 0, c)[e], q); levels_lds(4, c)[e] = (i16)level; }
+        tbuf(t, 1, c)[e] = dequant_level(level, q);
+        packed = level_cost(level, m->coeff_weights).word();
       }
-      plane_add(&s->acc[3], packed, tid);  // weight sum (< 2^22) and count of levels in one word
+      plane_sums(ROWS_CU8, tid, c, packed, true, 3);
     }
     KVZ_WAVE_SYNC();
     KVZ_PROF(KVZ_P_QUANT);
@@ -2776,12 +2675,8 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
     KVZ_FOR_THREADS(tid) {
       KVZ_PU_ROLE(tid);
       if (c >= 0 && (s->acc[3 + c] >> 24)) {
-        const i16 *src = tbuf(t, 1, c);
         const int jj = e >> 2, i = e & 3;
-        int a = 0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) a += (c == 0 ? dst4_at(k, i) : dct_at(2, k, i)) * (int)src[(k << 2) + jj];
-        tbuf(t, 0, c)[e] = (i16)iclip(-32768, 32767, (a + 64) >> 7);
+        tbuf(t, 0, c)[e] = inv_point(4, [&](int k) { return pu_tmat(c, k, i); }, tbuf(t, 1, c), jj, 4, 7);
       }
     }
     KVZ_WAVE_SYNC();
@@ -2793,32 +2688,18 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
         u8 *rp = &cv.at(c, (xl >> sh) + (e & 3), (yl >> sh) + (e >> 2));
         int v = *rp;
         if (s->acc[3 + c] >> 24) {
-          const i16 *src = tbuf(t, 0, c);
           const int jj = e >> 2, i = e & 3;
-          int a = 0;
-#pragma unroll
-          for (int k = 0; k < 4; k++) a += (c == 0 ? dst4_at(k, i) : dct_at(2, k, i)) * (int)src[(k << 2) + jj];
-          const i16 res = (i16)iclip(-32768, 32767, (a + 2048) >> 12);
-          v = iclip(0, 255, (int)(i16)(res + v));
+          v = recon_sample(v, inv_point(4, [&](int k) { return pu_tmat(c, k, i); }, tbuf(t, 0, c), jj, 4, 12));
           *rp = (u8)v;
         }
-        const int d = (int)*org_at(c, (xl >> sh) + (e & 3), (yl >> sh) + (e >> 2)) - v;
-        ssd = (u32)(d * d);
+        ssd = sq_err(*org_at(c, (xl >> sh) + (e & 3), (yl >> sh) + (e >> 2)), v);
       }
-      plane_add(&s->acc[0], ssd, tid);
+      plane_sums(ROWS_CU8, tid, c, ssd, false, 0);
     }
     KVZ_WAVE_SYNC();
-    KVZ_FOR_THREADS(tid) {  // each wavefront unpacks its planes' sums; the coded-block flags wait in RdoqLds until the partition wins (nxn_attempt)
-      if (tid == 0) {
-        const u32 pk = s->acc[3];
-        s->acc[3] = pk & 0xffffffu; s->acc[6] = pk >> 24;
-        rl->pu_cbf[rl->n_pu] = (pk >> 24) != 0;
-      }
-      if (tid == 64 && chroma) {
-        const u32 pu = s->acc[4], pv = s->acc[5];
-        s->acc[4] = pu & 0xffffffu; s->acc[7] = pu >> 24; s->acc[5] = pv & 0xffffffu; s->acc[8] = pv >> 24;
-        rl->pu_cbf_c[0] = (pu >> 24) != 0; rl->pu_cbf_c[1] = (pv >> 24) != 0;
-      }
+    KVZ_FOR_THREADS(tid) {  // each wavefront finishes its own planes
+      if (tid == 0) finish_planes(4, xl, yl, 3, 0, 1, true);
+      if (tid == 64 && chroma) finish_planes(4, xl, yl, 3, 1, 3, true);
     }
     KVZ_SYNC();
     KVZ_PROF(KVZ_P_RECON);
@@ -2973,7 +2854,7 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
         s->mode_disp[mode] = (int8_t)(mode < 2 ? 0 : (md < 0 ? -disp_tab[ad] : disp_tab[ad]));
         s->mode_inv[mode] = (int16_t)(mode < 2 ? 0 : inv_tab[ad]);
       }
-      if (v >= 128 && v < 136) s->qs[(v - 128) >> 1][v & 1] = quant_scalars_dev(2 + ((v - 128) >> 1), (v & 1) ? 2 : 0);
+      if (v >= 128 && v < 136) s->qs[(v - 128) >> 1][v & 1] = quant_scalars(m->qp, 8, 1, 0, 4 << ((v - 128) >> 1), (v & 1) ? 2 : 0);  // 8 bit, I slice, flat lists
       if (v < 128) s->entropy_fbits[v] = m->entropy_fbits[v];
       if (v < 64) s->ctx_lps[v] = tb->ctx_next[1][2 * v];
       }

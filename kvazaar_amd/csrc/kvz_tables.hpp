@@ -8,6 +8,7 @@
 #pragma once
 #include <string.h>
 
+#include "kvz_recon.hpp"
 #include "kvz_syntax.hpp"
 
 namespace kvz {
@@ -121,10 +122,10 @@ inline void build_tables(Tables *t)
   }
   for (int l2 = 3; l2 <= 4; l2++) {  // Tables::mref_tab (kvz_ctu.hpp build_mref; the layout constants kMref* below are asserted against the kernel's there)
     static const int inv_tab[9] = { 0, 4096, 1638, 910, 630, 482, 390, 315, 256 };
-    const int w = 1 << l2, nq = 2 * w + 2, thres = l2 == 3 ? 7 : 1;
+    const int w = 1 << l2, nq = 2 * w + 2;
     for (int i = 0; i < 15 * nq; i++) {
       const int mode = 11 + i / nq, q = i % nq - w, vertical = mode >= 18, md = vertical ? mode - 26 : 10 - mode, ad = md < 0 ? -md : md;
-      const int d26 = mode > 26 ? mode - 26 : 26 - mode, d10 = mode > 10 ? mode - 10 : 10 - mode, filt = (d26 < d10 ? d26 : d10) > thres;
+      const bool filt = luma_reads_filtered(l2, mode);
       int idx = q >= 0 ? q : (128 + (-q) * inv_tab[ad]) >> 8;
       if (idx > 2 * w) idx = 2 * w;
       const int main_side = vertical ? 0 : 1, side = q >= 0 ? main_side : 1 - main_side;  // 0 top, 1 left
@@ -178,10 +179,10 @@ inline void build_tables(Tables *t)
   memcpy(t->chroma_filter, cf, sizeof cf);
 }
 
-inline int ilog2(int w) { int l = 0; while ((1 << l) < w) l++; return l; }
+KVZ_HD int ilog2(int w) { int l = 0; while ((1 << l) < w) l++; return l; }
 
 // transform.c:141-155 kvz_get_scaled_qp
-inline int scaled_qp(int type, int qp, int qp_offset)
+KVZ_HD int scaled_qp(int type, int qp, int qp_offset)
 {
   if (type == 0) return qp + qp_offset;
   int q = qp < -qp_offset ? -qp_offset : (qp > 57 ? 57 : qp);
@@ -189,8 +190,8 @@ inline int scaled_qp(int type, int qp, int qp_offset)
 }
 
 // quant-generic.c:57-66 (forward) and :303-339 (inverse) scalars for a width x width block of plane type
-// (`type` as the reference passes it: 0 luma, 2/3 chroma).
-inline QuantScalars quant_scalars(int qp, int bitdepth, int slice_is_intra, int scaling_list, int width, int type)
+// (`type` as the reference passes it: 0 luma, 2/3 chroma).  Host and device: the intra CTU pass derives its eight sets per CTU (kvz_ctu.hpp init()).
+KVZ_HD QuantScalars quant_scalars(int qp, int bitdepth, int slice_is_intra, int scaling_list, int width, int type)
 {
   QuantScalars q;
   const int log2_tr = ilog2(width);

@@ -1,6 +1,6 @@
 """Units of 16 and 32 samples run the arithmetic stages of their reconstruction (kvz_ctu.hpp recon_tus: prediction, quantise / dequantise, reconstruct + SSD)
 eight samples per lane: a 16x16 CU as 48 lane tasks in one trip of one wavefront, a 32x32 unit as 192 in two.  Every output equals the oracle's -- host
-simulation here (it runs the same decomposition: wide_task / predict_row8 / wide_add), the device under -m gpu -- and a test of the pictures themselves fails when
+simulation here (it runs the same decomposition: wide_task / predict_row8 / plane_sums, the per-sample arithmetic of kvz_recon.hpp), the device under -m gpu -- and a test of the pictures themselves fails when
 they stop exercising that code: every class of intra mode decided at depths 0, 1 and 2, every pattern of planes with levels among the decided 32x32 regions.
 Pictures whose CTUs are cut by the border (the list of tests/test_ctu_movers.py) put such units next to the picture's edge."""
 import ctypes as C
