@@ -185,6 +185,30 @@ long kvz_hip_batch_entropy_code_then(kvz_hip_batch *b, const kvz_hip_intra_cost_
 void kvz_hip_batch_entropy_defer_download(kvz_hip_batch *b, int on);
 uint64_t kvz_hip_default_coeff_weights(int qp);
 
+/* ---- Pictures under different cost models in one launch (kvz_hip_picture_models, kvz_hip_types.h) ----
+ * The entry points above take ONE model -- one QP, one lambda, one set of initial context states -- for the whole batch; pictures of streams at different QPs would have
+ * to go in one small launch per QP, the latency-bound regime the batch exists to avoid.  These mirror them one for one with a model per picture.  Each picture's
+ * outputs are those of the single-model call on a batch of that picture's QP; a table of one model is the single-model call.  Every one of them returns -1 (the loop
+ * filters: mark the batch failed, kvz_hip_batch_sync -> -1) with a message on stderr and NOTHING queued for: a struct_size this library does not know, of the table or
+ * of any model; n_models < 1; a model index out of range; models that disagree in adaptive / no_wpp / search_32x32 / rdoq / search_nxn / entropy_fbits; rdoq with
+ * a model without coeff_cabac; the KVZ_HIP_SCHED=wave schedule.  The table is kept in a device buffer of the batch and copied only when it differs from the last
+ * call's: a steady chain of calls with one table pays one copy.
+ * The pass runs the instantiation with the CABAC coefficient model when ANY model has coeff_cabac; pictures whose model has not are priced by the fast estimate
+ * through that instantiation's run-time switch. */
+int  kvz_hip_intra_frames_models(kvz_hip_batch *b, const kvz_hip_picture_models *models);
+/* kvz_hip_batch_loop_filters (with sao == 0: kvz_hip_batch_deblock) with every picture's own QP in the deblocking thresholds and its own lambda and SAO contexts in the
+ * SAO decision. */
+int  kvz_hip_batch_loop_filters_models(kvz_hip_batch *b, const kvz_hip_picture_models *models, int deblock, int beta_offset_div2, int tc_offset_div2, int sao);
+/* kvz_hip_batch_entropy_code_tiles (not_last == NULL: kvz_hip_batch_entropy_code): every substream starts from its picture's own initial context states.  Nothing else in
+ * the slice data depends on the QP; parameter sets and slice headers (slice_qp_delta) stay with the host. */
+long kvz_hip_batch_entropy_code_models(kvz_hip_batch *b, const kvz_hip_picture_models *models, int sao, const uint8_t *not_last, uint8_t *out, size_t capacity,
+                                       uint32_t *substream_bytes);
+/* kvz_hip_batch_entropy_code_then with tables: `next`'s pass is kvz_hip_intra_frames_models(next, next_models).  Same contract: -3 (nothing queued on either batch) when
+ * next != NULL and next_models is not a table `next` can run; in every other case, -1 and -2 included, `next`'s pass has been queued exactly once when the call
+ * returns -- also when `models` is a table `b` cannot run (-1, nothing queued on `b`). */
+long kvz_hip_batch_entropy_code_then_models(kvz_hip_batch *b, const kvz_hip_picture_models *models, int sao, const uint8_t *not_last, uint8_t *out, size_t capacity,
+                                            uint32_t *substream_bytes, kvz_hip_batch *next, const kvz_hip_picture_models *next_models);
+
 #ifdef __cplusplus
 }
 #endif

@@ -140,6 +140,18 @@ typedef struct kvz_hip_intra_cost_model {
   float    entropy_fbits[128];/* kvz_f_entropy_bits (rdo.c:69-83) */
 } kvz_hip_intra_cost_model;
 
+/* The cost models of ONE batched launch whose pictures do not share a model (kvz_hip_batch.h, the kvz_hip_*_models entry points): pictures of streams that run at
+ * different QPs in one batch.  Every picture stays an ordinary constant-QP picture under the model model_of_picture names -- what the single-model entry point
+ * makes of it in a batch of its own, byte for byte.  The models of one table may differ in qp, lambda, lambda_sqrt, coeff_weights, ctx_init and (without rdoq)
+ * coeff_cabac; they must agree in adaptive, no_wpp, search_32x32, rdoq, search_nxn and entropy_fbits, which select the kernel, the order of the CTUs and the one
+ * price table of the launch.  struct_size as in kvz_hip_intra_cost_model: sizeof of the caller's headers. */
+typedef struct kvz_hip_picture_models {
+  uint32_t struct_size;
+  int32_t  n_models;                        /* >= 1 */
+  const kvz_hip_intra_cost_model *models;   /* [n_models] */
+  const uint16_t *model_of_picture;         /* [n_frames of the batch]: each < n_models */
+} kvz_hip_picture_models;
+
 /* Per-CTU result record of the batched pass: what kvazaar keeps in cu_array / lcu_t for the CTU. */
 #define KVZ_HIP_CTU_COEFFS 6144 /* 64*64 Y + 32*32 U + 32*32 V coefficients, each plane in lcu_t z-order (cu.h:385-421) */
 

@@ -36,6 +36,54 @@ def cost_model(lib, qp, weights=None):
     return m
 
 
+class PictureModelsStruct(C.Structure):
+    """kvz_hip_picture_models (include/kvz_hip_types.h)"""
+    _fields_ = [("struct_size", C.c_uint32), ("n_models", C.c_int32), ("models", C.POINTER(CostModel)), ("model_of_picture", C.POINTER(C.c_uint16))]
+
+
+class PictureModels:
+    """A cost model per picture of a batch (kvz_hip_picture_models): pictures of streams at different QPs in one launch.  qps: the QP of every picture of the batch, in
+    order; the table holds one model per distinct QP.  weights: fast-coefficient-cost weights for every QP (an int), per QP (a dict or a callable), or None for kvazaar's
+    built-in table.  switches: CostModel fields set on every model (adaptive, no_wpp, search_32x32, rdoq, search_nxn, coeff_cabac) -- the first five must be the same for
+    all models of a table, which this guarantees.  HipBatch.launch / run / loop_filters / entropy_code take it wherever they take a CostModel.  The object owns the ctypes
+    arrays the struct points into: keep it alive while a call uses it."""
+
+    def __init__(self, lib, qps, weights=None, **switches):
+        qps = [int(q) for q in qps]
+        if not qps:
+            raise ValueError("PictureModels: no pictures")
+        self.qps = qps
+        distinct = sorted(set(qps))
+        row = {q: i for i, q in enumerate(distinct)}
+        self.models = (CostModel * len(distinct))()
+        for i, q in enumerate(distinct):
+            w = weights(q) if callable(weights) else (weights[q] if isinstance(weights, dict) else weights)
+            m = cost_model(lib, q, w)
+            for k, v in switches.items():
+                if k not in ("adaptive", "no_wpp", "search_32x32", "rdoq", "search_nxn", "coeff_cabac"):
+                    raise TypeError(f"PictureModels: {k} is not a switch of the cost model")
+                setattr(m, k, int(v))
+            self.models[i] = m
+        self.index = (C.c_uint16 * len(qps))(*[row[q] for q in qps])
+        self.struct = PictureModelsStruct(C.sizeof(PictureModelsStruct), len(distinct), self.models, self.index)
+
+    def model_of(self, picture):
+        """the CostModel picture `picture` runs under"""
+        return self.models[self.index[picture]]
+
+    # what HipBatch reads of a model, table or not
+    @property
+    def no_wpp(self):
+        return self.models[0].no_wpp
+
+    def __len__(self):
+        return len(self.qps)
+
+
+def _is_table(model):
+    return isinstance(model, PictureModels)
+
+
 def outputs(width, height):
     """host arrays of one picture's results: reconstruction Y|U|V, coefficients, CU depth / intra mode per 8x8, CTU costs"""
     nctu = ((width + 63) // 64) * ((height + 63) // 64)
@@ -95,8 +143,19 @@ class HipBatch:
         self.lib.kvz_hip_batch_upload_all_async.restype = None
         self.lib.kvz_hip_batch_upload_all_async(self.handle, src_ptr)
 
+    def _check_table(self, models):
+        if len(models) != self.n:
+            raise ValueError(f"PictureModels of {len(models)} pictures for a batch of {self.n}")
+
     def launch(self, model):
-        """asynchronous on the batch's stream; returns the number of kernel launches"""
+        """asynchronous on the batch's stream; returns the number of kernel launches.  model: a CostModel for every picture, or a PictureModels table
+        (kvz_hip_intra_frames_models)"""
+        if _is_table(model):
+            self._check_table(model)
+            f = self.lib.kvz_hip_intra_frames_models
+            f.argtypes = [C.c_void_p, C.POINTER(PictureModelsStruct)]
+            f.restype = C.c_int
+            return f(self.handle, C.byref(model.struct))
         return self.lib.kvz_hip_intra_frames(self.handle, C.byref(model))
 
     def order_after(self, other):
@@ -132,7 +191,18 @@ class HipBatch:
             self.sync()
 
     def loop_filters(self, model, deblock=True, sao=True, beta_offset_div2=0, tc_offset_div2=0, wait=True):
-        """kvz_hip_batch_loop_filters: deblocking + SAO decision + SAO reconstruction on the batch's stream"""
+        """kvz_hip_batch_loop_filters: deblocking + SAO decision + SAO reconstruction on the batch's stream (a PictureModels table: kvz_hip_batch_loop_filters_models,
+        every picture with its own QP, lambda and SAO contexts; with sao=False that is the deblocking of a mixed batch)"""
+        if _is_table(model):
+            self._check_table(model)
+            f = self.lib.kvz_hip_batch_loop_filters_models
+            f.argtypes = [C.c_void_p, C.POINTER(PictureModelsStruct), C.c_int, C.c_int, C.c_int, C.c_int]
+            f.restype = C.c_int
+            if f(self.handle, C.byref(model.struct), int(deblock), beta_offset_div2, tc_offset_div2, int(sao)) != 0:
+                raise BatchError("kvz_hip_batch_loop_filters_models: the batch cannot run this table (see stderr)")
+            if wait:
+                self.sync()
+            return
         f = self.lib.kvz_hip_batch_loop_filters
         f.argtypes = [C.c_void_p, C.POINTER(CostModel), C.c_int, C.c_int, C.c_int, C.c_int]
         f.restype = None
@@ -143,9 +213,18 @@ class HipBatch:
     def entropy_code(self, model, sao=False, capacity=None, not_last=None, then=None):
         """kvz_hip_batch_entropy_code: the slice data of every picture of the batch, coded on the device from the results of the last launch (and, with sao, of the
         last loop_filters(sao=True)).  -> (bytes of all substreams back to back, sizes as an array [frame][substream]).  then = (batch, model): that batch's pass is
-        started once this coder's first stage is through (kvz_hip_batch_entropy_code_then)"""
-        f = self.lib.kvz_hip_batch_entropy_code_then
-        f.argtypes = [C.c_void_p, C.POINTER(CostModel), C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+        started once this coder's first stage is through (kvz_hip_batch_entropy_code_then).  With a PictureModels table as `model` every picture's substreams start
+        from its own initial contexts (kvz_hip_batch_entropy_code_then_models); `then` then names a batch with a table of its own"""
+        table = _is_table(model)
+        if table:
+            self._check_table(model)
+            if then and not _is_table(then[1]):
+                raise TypeError("entropy_code with a PictureModels table: then = (batch, PictureModels)")
+            then = (then[0], then[1].struct) if then else None
+        elif then and _is_table(then[1]):
+            raise TypeError("entropy_code with a CostModel: then = (batch, CostModel)")
+        f = self.lib.kvz_hip_batch_entropy_code_then_models if table else self.lib.kvz_hip_batch_entropy_code_then
+        f.argtypes = [C.c_void_p, C.POINTER(PictureModelsStruct if table else CostModel), C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
         f.restype = C.c_long
         flags = None if not_last is None else np.ascontiguousarray(not_last, np.uint8)  # tiles: 1 = other tiles of the slice follow
         assert flags is None or flags.size == self.n
@@ -155,7 +234,7 @@ class HipBatch:
             pinned_free(self.lib, getattr(self, "_entropy_ptr", None))
             self._entropy_ptr, self._entropy_out = pinned_bytes(self.lib, capacity)  # the slice data is downloaded by the call: a pinned destination, no staging copy
         sizes = np.zeros((self.n, rows), np.uint32)
-        total = f(self.handle, C.byref(model), int(sao), flags.ctypes.data if flags is not None else None, self._entropy_out.ctypes.data, capacity, sizes.ctypes.data,
+        total = f(self.handle, C.byref(model.struct if table else model), int(sao), flags.ctypes.data if flags is not None else None, self._entropy_out.ctypes.data, capacity, sizes.ctypes.data,
                   then[0].handle if then else None, C.addressof(then[1]) if then else None)
         if total < 0:
             # -1 the coder, -2 the next batch's launch (in both cases that pass is queued and wants a sync), -3 bad next model (nothing queued)

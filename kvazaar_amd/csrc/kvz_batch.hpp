@@ -8,6 +8,8 @@
 
 #include "../../include/kvz_hip_batch.h"
 #include "kvz_ctu.hpp"
+#include "kvz_entropy.hpp"  // KVZ_ENTROPY_CTX_ROW: the rows of a model table
+#include "kvz_picture_models.hpp"
 #include "kvz_runtime.hpp"
 
 #include "kvz_ctu_kernels.hpp"
@@ -47,6 +49,10 @@ struct kvz_hip_batch {
   void *d_sao_stats, *d_sao_cand;
   unsigned long long *d_sao_recs;
   float *d_sao_fbits;
+  // the model table of the kvz_hip_*_models entry points on the device -- the two pointers of a CtuModelTable (also behind the ticket words, for the pass) | CtuModel rows | their ctx_init rows | qp_of_picture | model_of_picture (kvz::ModelTableView) --
+  // and the host image it was copied from: a call with the same table skips the copy, like last_entropy
+  kvz::DevBuf d_models;
+  std::vector<uint8_t> h_models;
   int device;   // the batch's buffers and stream live here; every entry point binds the calling thread to it
   int failed;   // sticky: a CTU hand-off wait of some run timed out, the results of that run are invalid
   unsigned long long wait_ticks;
@@ -108,15 +114,6 @@ inline int ctx_state(int qp, int init_value)
   return st >= 64 ? ((st - 64) << 1) + 1 : (63 - st) << 1;
 }
 
-// the struct versions this library knows (include/kvz_hip_types.h struct_size): the current one
-inline bool cost_model_known(const kvz_hip_intra_cost_model *m, const char *who)
-{
-  if (m && m->struct_size == sizeof(kvz_hip_intra_cost_model)) return true;
-  fprintf(stderr, "%s: kvz_hip_intra_cost_model.struct_size %u is not this library's %zu (caller built against other headers, or the struct was not set up by kvz_hip_intra_cost_model_init)\n",
-          who, m ? m->struct_size : 0u, sizeof(kvz_hip_intra_cost_model));
-  return false;
-}
-
 inline void cost_model_init(int qp, uint64_t coeff_weights, kvz_hip_intra_cost_model *m)
 {
   // I-slice rows of context.c:96-193 (HEVC spec tables 9-5 ff.); 154 = CNU, never coded
@@ -168,6 +165,61 @@ inline void cost_model_init(int qp, uint64_t coeff_weights, kvz_hip_intra_cost_m
   m->ctx_init[KVZ_HIP_CX_SAO_TYPE] = (uint8_t)ctx_state(qp, 200);
   m->adaptive = 1;
   m->coeff_cabac = qp >= 28;  // `ultrafast`: fast-residual-cost 28 (cfg.c:485-512), rdo.c:311-340
+}
+
+
+// ---- per-picture models (kvz_hip_picture_models) ----
+// Where the parts of kvz_hip_batch::d_models are: what the kernels of a mixed launch are handed
+struct ModelTableView {
+  CtuModelTable ctu;             // the SAO decision: compact rows + the row of every picture
+                                 // (the CTU pass reads the same two pointers behind the batch's ticket words: kvz_ctu_kernels.hpp KVZ_SCHED_TABLE_AT)
+  const uint8_t *ctx_rows;       // the entropy coder: [n_models][KVZ_ENTROPY_CTX_ROW]
+  const int32_t *qp_of_picture;  // deblocking: [n_frames]
+};
+// The table (checked by picture_models_known) on the device: copied when it differs from what the batch holds (the sources are the caller's: staged before this returns)
+inline ModelTableView picture_models_stage(kvz_hip_batch *b, const kvz_hip_picture_models *pm)
+{
+  const size_t n = (size_t)pm->n_models, nf = (size_t)b->n_frames, ctx_bytes = KVZ_ENTROPY_CTX_ROW;  // a model's ctx_init and zeros up to what the entropy coder reads of a row
+  static_assert(sizeof(((kvz_hip_intra_cost_model *)0)->ctx_init) <= KVZ_ENTROPY_CTX_ROW && KVZ_ENTROPY_CTXS <= KVZ_ENTROPY_CTX_ROW, "a row of initial states");
+  const size_t at_rows = 16, at_ctx = (at_rows + n * sizeof(CtuModel) + 15) & ~(size_t)15, at_qp = at_ctx + n * ctx_bytes, at_index = at_qp + nf * sizeof(int32_t), bytes = at_index + nf * sizeof(uint16_t);
+  bool fresh = false;
+  if (bytes > b->d_models.bytes) {
+    KVZ_HIP_CHECK(hipStreamSynchronize(b->stream));  // a launch in flight may still read the old one
+    if (b->d_models.p) KVZ_HIP_CHECK(hipFree(b->d_models.p));
+    b->d_models.bytes = bytes + bytes / 8;
+    KVZ_HIP_CHECK(hipMalloc(&b->d_models.p, b->d_models.bytes));
+    fresh = true;
+  }
+  uint8_t *d = (uint8_t *)b->d_models.p;
+  std::vector<uint8_t> image(bytes, 0);
+  for (size_t i = 0; i < n; i++) {
+    CtuModel cm;
+    memset(&cm, 0, sizeof cm);  // (padding bytes take part in the comparison below)
+    ctu_model_from(&pm->models[i], &cm);
+    cm.entropy_fbits = b->d_entropy;
+    cm.ctx_init = d + at_ctx + i * ctx_bytes;
+    memcpy(image.data() + at_rows + i * sizeof(CtuModel), &cm, sizeof cm);
+    memcpy(image.data() + at_ctx + i * ctx_bytes, pm->models[i].ctx_init, sizeof pm->models[i].ctx_init);
+  }
+  for (size_t f = 0; f < nf; f++) {
+    const int32_t qp = pm->models[pm->model_of_picture[f]].qp;
+    memcpy(image.data() + at_qp + f * sizeof(int32_t), &qp, sizeof qp);
+  }
+  memcpy(image.data() + at_index, pm->model_of_picture, nf * sizeof(uint16_t));
+  ModelTableView v;
+  v.ctu.models = (const CtuModel *)(d + at_rows);
+  v.ctu.model_of_picture = (const uint16_t *)(d + at_index);
+  static_assert(sizeof(CtuModelTable) <= 16 && sizeof(CtuModelTable) <= (KVZ_SCHED_TICKET_WORDS - KVZ_SCHED_TABLE_AT) * sizeof(unsigned), "at_rows, d_ticket");
+  memcpy(image.data(), &v.ctu, sizeof v.ctu);
+  if (fresh || image != b->h_models) {
+    KVZ_HIP_CHECK(hipMemcpyAsync(d, image.data(), bytes, hipMemcpyHostToDevice, b->stream));
+    KVZ_HIP_CHECK(hipMemcpyAsync(b->d_ticket + KVZ_SCHED_TABLE_AT, image.data(), sizeof(CtuModelTable), hipMemcpyHostToDevice, b->stream));
+    KVZ_HIP_CHECK(hipStreamSynchronize(b->stream));
+    b->h_models.swap(image);
+  }
+  v.ctx_rows = d + at_ctx;
+  v.qp_of_picture = (const int32_t *)(d + at_qp);
+  return v;
 }
 
 }  // namespace kvz
@@ -248,8 +300,8 @@ kvz_hip_batch *kvz_hip_batch_create_on(int device, int width, int height, int n_
     KVZ_HIP_CHECK(hipMemcpy(b->d_items_raster, items.data(), items.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     KVZ_HIP_CHECK(hipMalloc((void **)&b->d_done, nctu * sizeof(unsigned)));
     KVZ_HIP_CHECK(hipMemsetAsync(b->d_done, 0, nctu * sizeof(unsigned), b->stream));
-    KVZ_HIP_CHECK(hipMalloc((void **)&b->d_ticket, 4 * sizeof(unsigned)));  // the ticket, the error word, two words of what the first CTU to give up saw
-    KVZ_HIP_CHECK(hipMemsetAsync(b->d_ticket, 0, 4 * sizeof(unsigned), b->stream));
+    KVZ_HIP_CHECK(hipMalloc((void **)&b->d_ticket, kvz::KVZ_SCHED_TICKET_WORDS * sizeof(unsigned)));  // the ticket, the error word, two words of what the first CTU to give up saw; the model table's pointers
+    KVZ_HIP_CHECK(hipMemsetAsync(b->d_ticket, 0, kvz::KVZ_SCHED_TICKET_WORDS * sizeof(unsigned), b->stream));
     b->d_error = b->d_ticket + 1;
     KVZ_HIP_CHECK(hipHostMalloc((void **)&b->h_error, 64, hipHostMallocDefault));
     *b->h_error = 0;
@@ -284,7 +336,7 @@ void kvz_hip_batch_destroy(kvz_hip_batch *b)
   if (b->entropy_out.p) (void)hipFree(b->entropy_out.p);
   if (b->ev_up) { (void)hipEventSynchronize(b->ev_up); (void)hipEventDestroy(b->ev_up); }
   if (b->ev_src_read) (void)hipEventDestroy(b->ev_src_read);
-  (void)hipFree(b->d_sse);
+  (void)hipFree(b->d_sse); (void)hipFree(b->d_models.p);
   (void)hipStreamDestroy(b->stream);
   delete b;
 }
@@ -400,14 +452,16 @@ void kvz_hip_batch_order_after(kvz_hip_batch *b, kvz_hip_batch *other)
   KVZ_HIP_CHECK(hipEventDestroy(ev));  // released once the wait has been satisfied
 }
 
-int kvz_hip_intra_frames(kvz_hip_batch *b, const kvz_hip_intra_cost_model *model)
+// The pass of kvz_hip_intra_frames (!table: `model` for every picture) and of kvz_hip_intra_frames_models (table: picture_models_stage has put it on the device; `model` = its first: the switches and
+// the price table every model shares; any_cabac: some model prices coefficients with the CABAC model -- that instantiation then prices the others' through its run-time switch)
+static int kvz_intra_frames_queue(kvz_hip_batch *b, const kvz_hip_intra_cost_model *model, bool table, bool any_cabac)
 {
-  if (!b || !kvz::cost_model_known(model, "kvz_hip_intra_frames")) return -1;
   kvz::batch_enter(b);
   const kvz::CtuFrames &F = b->F;
   int launches = 0;
   kvz::CtuModel cm;
   kvz::ctu_model_from(model, &cm);
+  cm.coeff_cabac = any_cabac;
   cm.entropy_fbits = b->d_entropy;
   cm.ctx_init = (const uint8_t *)(b->d_entropy + 128);
   if (b->up_pending) { KVZ_HIP_CHECK(hipStreamWaitEvent(b->stream, b->ev_up, 0)); b->up_pending = 0; }  // pictures on their way (kvz_hip_batch_upload_all_async)
@@ -432,7 +486,7 @@ int kvz_hip_intra_frames(kvz_hip_batch *b, const kvz_hip_intra_cost_model *model
     b->epoch++;
     KVZ_HIP_CHECK(hipMemsetAsync(b->d_ticket, 0, sizeof(unsigned), b->stream));  // the error word behind it stays: sticky across runs
     KVZ_HIP_CHECK(hipEventRecord(b->ev0, b->stream));
-    kvz::CtuSched sc{ cm.no_wpp ? b->d_items_raster : b->d_items, b->d_ticket, b->d_done, b->d_error, b->total_items, b->epoch, cm.no_wpp, b->wait_ticks };
+    kvz::CtuSched sc{ cm.no_wpp ? b->d_items_raster : b->d_items, b->d_ticket, b->d_done, b->d_error, b->total_items, b->epoch, cm.no_wpp | (table ? kvz::KVZ_SCHED_MODEL_TABLE : 0), b->wait_ticks };
     // two instantiations: the one without the CABAC coefficient model carries none of its code, registers or context storage
     // (the instantiations that search 32x32 CUs, --pu-depth-intra 1-3, are separate ones too: the others stay as they were)
     if (cm.rdoq || cm.search_nxn) {  // --rdoq and / or NxN partitions (preset `medium`): their own instantiation (32x32 search and the coefficient cost model switched by the model)
@@ -472,6 +526,20 @@ int kvz_hip_intra_frames(kvz_hip_batch *b, const kvz_hip_intra_cost_model *model
   KVZ_HIP_CHECK(hipGetLastError());
   KVZ_HIP_CHECK(hipEventRecord(b->ev1, b->stream));
   return launches;
+}
+
+int kvz_hip_intra_frames(kvz_hip_batch *b, const kvz_hip_intra_cost_model *model)
+{
+  if (!b || !kvz::cost_model_known(model, "kvz_hip_intra_frames")) return -1;
+  return kvz_intra_frames_queue(b, model, false, model->coeff_cabac != 0);
+}
+
+int kvz_hip_intra_frames_models(kvz_hip_batch *b, const kvz_hip_picture_models *pm)
+{
+  if (!b || !kvz::picture_models_known(pm, b->n_frames, b->sched_ticket != 0, "kvz_hip_intra_frames_models")) return -1;
+  kvz::batch_enter(b);
+  kvz::picture_models_stage(b, pm);
+  return kvz_intra_frames_queue(b, &pm->models[0], true, kvz::picture_models_any_cabac(pm));
 }
 
 int kvz_hip_batch_sync(kvz_hip_batch *b)

@@ -235,6 +235,13 @@ KVZ_HD void ctu_model_from(const kvz_hip_intra_cost_model *src, CtuModel *dst)
   dst->entropy_fbits = src->entropy_fbits;
   dst->ctx_init = src->ctx_init;
 }
+// The models of a launch whose pictures do not share one (kvz_hip_picture_models): rows of the compact form, each with ctx_init pointing at its own row of
+// initial states, and the row of every picture.  models == nullptr: the launch has ONE model, handed over by value.
+struct CtuModelTable {
+  const CtuModel *models = nullptr;            // [n_models]
+  const uint16_t *model_of_picture = nullptr;  // [frames]
+};
+KVZ_HD const CtuModel *picture_model(const CtuModelTable &t, long picture) { return t.models + picture_model(t.model_of_picture, picture); }
 
 // Frame-level device buffers of one batch (all frames share the geometry).
 struct CtuFrames {

@@ -55,13 +55,14 @@ template <bool CABAC> __global__ void __launch_bounds__(KVZ_CTU_THREADS) __attri
 // drains its stores, one lane releases at agent scope and stores the flag; consumer polls relaxed, one lane acquires,
 // then the workgroup barrier.  Compared with one launch per diagonal this removes the per-launch tail (a diagonal of
 // n CTUs x F frames rarely is a multiple of the resident workgroup count) and 61 of 62 launches.
+enum { KVZ_SCHED_MODEL_TABLE = 2 /* bit of CtuSched::no_wpp */, KVZ_SCHED_TABLE_AT = 4 /* words behind CtuSched::ticket */, KVZ_SCHED_TICKET_WORDS = 8 };
 struct CtuSched {
   const uint32_t *items;  // [total]: frame << 16 | y << 8 | x  (CTU coordinates)
-  unsigned *ticket;       // atomic ticket counter, zeroed before every launch
+  unsigned *ticket;       // atomic ticket counter, zeroed before every launch; at ticket + KVZ_SCHED_TABLE_AT a CtuModelTable when no_wpp has KVZ_SCHED_MODEL_TABLE
   unsigned *done;         // [frames * ctus_per_frame]: epoch of the last call that completed the CTU
   unsigned *error;        // set when a wait exceeds its spin bound (never in a healthy run)
   unsigned total, epoch;
-  int no_wpp;             // items in raster order per picture; a row's first CTU also waits for the last CTU of the row above
+  int no_wpp;             // bit 0: items in raster order per picture; a row's first CTU also waits for the last CTU of the row above
   unsigned long long wait_ticks;  // bound of one wait in ticks of the 100 MHz constant clock (s_memrealtime): wall-clock, so that counter
                                   // serialisation under rocprof, time slicing or preemption cannot turn a healthy run into a timeout
 };
@@ -98,6 +99,9 @@ __device__ __forceinline__ bool wait_done(unsigned *flag, unsigned epoch, unsign
 }
 
 // The persistent loop of the ticket schedule; the kernels below differ in their register budget only.
+// sched.no_wpp & KVZ_SCHED_MODEL_TABLE: the pictures of the launch have models of their own (kvz_hip_intra_frames_models) -- `m` is loaded per CTU from the drawn picture's
+// row of the table behind the ticket words.  (A bit of a word the loop keeps anyway and a pointer it keeps anyway: a kernel argument of its own stayed live across the
+// whole program and cost the instantiations that spill a register more.)
 template <bool CABAC, bool S32, bool RDOQ> __device__ __forceinline__ void ticket_loop(const CtuFrames &F, const CtuModel &model, const Tables *tb, const CtuSched &sched)
 {
   __shared__ CtuSharedT<CABAC> shared;
@@ -107,7 +111,7 @@ template <bool CABAC, bool S32, bool RDOQ> __device__ __forceinline__ void ticke
 #ifndef KVZ_CTU_PROFILE
   static_assert(sizeof(CtuSharedT<CABAC>) + sizeof(CtuModel) <= 20480, "eight workgroups per CU");
 #endif
-  if (threadIdx.x == 0) m = model;
+  if (threadIdx.x == 0 && !(sched.no_wpp & KVZ_SCHED_MODEL_TABLE)) m = model;
   const int ctus = F.wc * F.hc;
   for (;;) {
     __syncthreads();  // previous item fully retired (and m visible on the first trip)
@@ -119,13 +123,14 @@ template <bool CABAC, bool S32, bool RDOQ> __device__ __forceinline__ void ticke
     const int frame = item >> 16, y = (item >> 8) & 0xff, x = item & 0xff;
     KVZ_TRACE(1);  // ticket drawn
     if (threadIdx.x == 0) {
+      if (sched.no_wpp & KVZ_SCHED_MODEL_TABLE) m = *picture_model(*reinterpret_cast<const CtuModelTable *>(sched.ticket + KVZ_SCHED_TABLE_AT), frame);  // no lane reads m between the barrier above and the one below; the table is constant during the launch
       unsigned *done = sched.done + (long)frame * ctus;
       // a hand-off that timed out anywhere (this launch or an earlier one: the word is sticky until kvz_hip_batch_reset) poisons the pass: from then on
       // tickets are only drained -- no search on stale neighbour data, no further 30-second waits -- and every CTU still publishes its flag
       bool ok = __hip_atomic_load(sched.error, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0;
       if (ok && x > 0) ok = wait_done(&done[y * F.wc + x - 1], sched.epoch, sched.error, sched.wait_ticks, ((unsigned)frame << 16 | (unsigned)y << 8 | (unsigned)(x - 1)) & 0x1fffffffu);
       if (ok && y > 0) ok = wait_done(&done[(y - 1) * F.wc + (x + 1 < F.wc ? x + 1 : x)], sched.epoch, sched.error, sched.wait_ticks, 0x20000000u | (((unsigned)frame << 16 | (unsigned)(y - 1) << 8 | (unsigned)(x + 1 < F.wc ? x + 1 : x)) & 0x1fffffffu));  // above-right implies above and above-left
-      if (ok && sched.no_wpp && x == 0 && y > 0) ok = wait_done(&done[(y - 1) * F.wc + F.wc - 1], sched.epoch, sched.error, sched.wait_ticks, 0x40000000u | (((unsigned)frame << 16 | (unsigned)(y - 1) << 8 | (unsigned)(F.wc - 1)) & 0x1fffffffu));  // its contexts come from there
+      if (ok && (sched.no_wpp & 1) && x == 0 && y > 0) ok = wait_done(&done[(y - 1) * F.wc + F.wc - 1], sched.epoch, sched.error, sched.wait_ticks, 0x40000000u | (((unsigned)frame << 16 | (unsigned)(y - 1) << 8 | (unsigned)(F.wc - 1)) & 0x1fffffffu));  // its contexts come from there
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
       shared.best_mode = ok ? 1 : 0;
     }

@@ -591,7 +591,26 @@ inline void launch_sao(hipStream_t stream, const u8 *in, u8 *out, int W, int H, 
   }
 }
 
-struct DeblockGeom { int W, H, beta, tc, tc_c; long frame_bytes; const u8 *cu_depth; const kvz_hip_cu_dbk *info; int slice_b, tc1; /* inter pictures: per-4x4 records, tc at strength 1 */ };
+// beta / tc / tc_c / tc1: the thresholds of the launch's one QP.  qp_of_picture != nullptr (device, a QP per picture: kvz_hip_batch_loop_filters_models): every picture's
+// own, derived where they are used from beta_off / tc_off
+struct DeblockThresholds { int beta, tc, tc_c, tc1; };
+struct DeblockGeom { int W, H, beta, tc, tc_c; long frame_bytes; const u8 *cu_depth; const kvz_hip_cu_dbk *info; int slice_b, tc1; /* inter pictures: per-4x4 records, tc at strength 1 */
+                     const int32_t *qp_of_picture; int beta_off, tc_off; };
+KVZ_HD DeblockThresholds deblock_thresholds(int qp, int beta_off, int tc_off)
+{
+  DeblockThresholds t;
+  t.tc1 = deblock_tc(iclip(0, 53, qp + 2 * tc_off));  // filter.c:496-497 with strength 1
+  t.beta = deblock_beta(iclip(0, 51, qp + 2 * beta_off));
+  t.tc = deblock_tc(iclip(0, 53, qp + 2 + 2 * tc_off));                  // filter.c:496-497 with strength 2
+  t.tc_c = deblock_tc(iclip(0, 53, chroma_qp(qp) + 2 + 2 * tc_off));  // filter.c:592-595
+  return t;
+}
+__device__ __forceinline__ DeblockThresholds deblock_thresholds_of(const DeblockGeom &g, long frame)
+{
+  if (g.qp_of_picture) return deblock_thresholds(g.qp_of_picture[frame], g.beta_off, g.tc_off);
+  const DeblockThresholds t = { g.beta, g.tc, g.tc_c, g.tc1 };
+  return t;
+}
 
 __device__ __forceinline__ bool deblock_edge_on(const DeblockGeom &g, long frame, int x, int y, bool vertical)  // filter.c:202-216
 {
@@ -702,14 +721,15 @@ template <bool VERTICAL> __global__ void __launch_bounds__(256) dev_deblock_luma
   const int r = (int)(p % ((long)nx * ny)), ix = r % nx, iy = r / nx;
   const int x = VERTICAL ? 8 * ix : 4 * ix, y = VERTICAL ? 4 * iy : 8 * iy;
   if ((VERTICAL ? x : y) == 0) return;
-  int tc = g.tc;
+  const DeblockThresholds thr = deblock_thresholds_of(g, frame);
+  int tc = thr.tc;
   if (g.info) {  // inter picture: edge test on the 8x8 unit, strength per 4-sample part
     const int ux = x & ~7, uy = y & ~7;
     if (!dbk_edge_on_inter(g, frame, ux, uy, VERTICAL)) return;
     const kvz_hip_cu_dbk *u = dbk_unit(g, frame, ux, uy);
     const int strength = dbk_strength(g, frame, x, y, VERTICAL, (((VERTICAL ? ux : uy)) & ((64 >> u->tr_depth) - 1)) == 0);
     if (!strength) return;
-    if (strength == 1) tc = g.tc1;
+    if (strength == 1) tc = thr.tc1;
   } else if (!deblock_edge_on(g, frame, x, y, VERTICAL)) return;
   u8 *Y = frames + frame * g.frame_bytes;
   dev_pk16 P[2][8];
@@ -732,7 +752,7 @@ template <bool VERTICAL> __global__ void __launch_bounds__(256) dev_deblock_luma
       P[1][k] = __builtin_bit_cast(dev_pk16, __builtin_amdgcn_perm(v, v, 0x0c030c02u));
     }
   }
-  deblock_luma_lines_pk(P, g.beta, tc);
+  deblock_luma_lines_pk(P, thr.beta, tc);
   if (VERTICAL) {
     for (int p = 0; p < 2; p++) {
       // halves (k0 | k1 << 8) and (k2 | k3 << 8) of both lines, then one dword per line
@@ -764,11 +784,11 @@ template <bool VERTICAL> __global__ void __launch_bounds__(256) dev_deblock_chro
     if (q->type != 1 && pp->type != 1) return;
   } else if (!deblock_edge_on(g, frame, 2 * xc, 2 * yc, VERTICAL)) return;
   u8 *P = frames + frame * g.frame_bytes + (long)g.W * g.H + (long)plane * cw * ch;
-  const int across = VERTICAL ? 1 : cw, along = VERTICAL ? cw : 1;
+  const int across = VERTICAL ? 1 : cw, along = VERTICAL ? cw : 1, tc_c = deblock_thresholds_of(g, frame).tc_c;
   for (int i = 0; i < 4; i++) {
     u8 *s = P + (long)yc * cw + xc + i * along;
     const int m2 = s[-2 * across], m3 = s[-across], m4 = s[0], m5 = s[across];
-    const int delta = iclip(-g.tc_c, g.tc_c, (((m4 - m3) * 4) + m2 - m5 + 4) >> 3);
+    const int delta = iclip(-tc_c, tc_c, (((m4 - m3) * 4) + m2 - m5 + 4) >> 3);
     s[-across] = (u8)iclip(0, 255, m3 + delta);
     s[0] = (u8)iclip(0, 255, m4 - delta);
   }
@@ -776,16 +796,15 @@ template <bool VERTICAL> __global__ void __launch_bounds__(256) dev_deblock_chro
 
 // passes: 1 = the vertical edges, 2 = the horizontal edges, 3 = both (in that order)
 inline void deblock_frames_on(hipStream_t stream, u8 *frames, int width, int height, int n_frames, const u8 *cu_depth, int qp, int beta_off, int tc_off, int passes = 3,
-                              const kvz_hip_cu_dbk *info = nullptr, int slice_b = 0)
+                              const kvz_hip_cu_dbk *info = nullptr, int slice_b = 0, const int32_t *qp_of_picture = nullptr /* device: a QP per picture instead of `qp` */)
 {
   if (n_frames <= 0) return;
   DeblockGeom g;
   g.W = width; g.H = height; g.cu_depth = cu_depth; g.frame_bytes = (long)width * height * 3 / 2;
   g.info = info; g.slice_b = slice_b;
-  g.tc1 = deblock_tc(iclip(0, 53, qp + 2 * tc_off));  // filter.c:496-497 with strength 1
-  g.beta = deblock_beta(iclip(0, 51, qp + 2 * beta_off));
-  g.tc = deblock_tc(iclip(0, 53, qp + 2 + 2 * tc_off));                  // filter.c:496-497 with strength 2
-  g.tc_c = deblock_tc(iclip(0, 53, chroma_qp(qp) + 2 + 2 * tc_off));  // filter.c:592-595
+  const DeblockThresholds t = deblock_thresholds(qp, beta_off, tc_off);
+  g.tc1 = t.tc1; g.beta = t.beta; g.tc = t.tc; g.tc_c = t.tc_c;
+  g.qp_of_picture = qp_of_picture; g.beta_off = beta_off; g.tc_off = tc_off;
   const int cw = width >> 1, ch = height >> 1;
   auto grid = [](long n) { return dim3((unsigned)((n + 255) / 256)); };
   const long lv = (long)n_frames * (width >> 3) * (height >> 2), lh = (long)n_frames * (width >> 2) * (height >> 3);
@@ -966,11 +985,18 @@ __global__ void __launch_bounds__(256) dev_sao_stats_kernel(const u8 *src, const
 }
 // ... and the chain over the LCUs of a picture: one lane per picture
 __global__ void __launch_bounds__(64) dev_sao_chain_kernel(const SaoStats *stats, const SaoCand *cand, const SaoGeom g, const int n_frames, const float *fbits, const Tables *tb,
-                                                           const double lambda, const int init_merge, const int init_type, const int no_wpp, SaoRec *recs, u8 *merge)
+                                                           const double lambda, const int init_merge, const int init_type, const int no_wpp, SaoRec *recs, u8 *merge,
+                                                           const CtuModelTable pm = CtuModelTable())
 {
   const int f = blockIdx.x * 64 + threadIdx.x;
   if (f >= n_frames) return;
   const long base = (long)f * g.wl * g.hl;
+  if (pm.models) {  // the picture's own lambda and SAO context states, from its row of the model table (kvz_hip_batch_loop_filters_models)
+    const CtuModel *m = picture_model(pm, f);
+    sao_chain_picture(fbits, tb->ctx_next[0], tb->ctx_next[1], m->lambda, m->ctx_init[KVZ_HIP_CX_SAO_MERGE], m->ctx_init[KVZ_HIP_CX_SAO_TYPE], no_wpp, g.wl, g.hl, stats + base * 3, cand + base * 3,
+                      recs + base * 3, merge + base);
+    return;
+  }
   sao_chain_picture(fbits, tb->ctx_next[0], tb->ctx_next[1], lambda, (u8)init_merge, (u8)init_type, no_wpp, g.wl, g.hl, stats + base * 3, cand + base * 3, recs + base * 3,
                     merge + base);
 }
@@ -1557,14 +1583,14 @@ void kvz_hip_batch_deblock(kvz_hip_batch *b, int qp, int beta_offset_div2, int t
   kvz::deblock_frames_on(b->stream, b->d_rec, b->F.W, b->F.H, b->n_frames, b->d_depth, qp, beta_offset_div2, tc_offset_div2);
 }
 
-void kvz_hip_batch_loop_filters(kvz_hip_batch *b, const kvz_hip_intra_cost_model *model, int deblock, int beta_offset_div2, int tc_offset_div2, int sao)
+// kvz_hip_batch_loop_filters (v == nullptr: `model` for every picture) and kvz_hip_batch_loop_filters_models (`model` = the table's first: price table and no_wpp)
+static void kvz_batch_loop_filters_queue(kvz_hip_batch *b, const kvz_hip_intra_cost_model *model, const kvz::ModelTableView *v, int deblock, int beta_offset_div2, int tc_offset_div2, int sao)
 {
-  if (!kvz::cost_model_known(model, "kvz_hip_batch_loop_filters")) { b->failed = 1; return; }  // no return value: the batch reports it (kvz_hip_batch_sync -> -1)
-  kvz::batch_enter(b);
   const kvz::CtuFrames &F = b->F;
   const int n = b->n_frames;
+  const int32_t *qps = v ? v->qp_of_picture : nullptr;
   if (!sao) {
-    if (deblock) kvz::deblock_frames_on(b->stream, b->d_rec, F.W, F.H, n, b->d_depth, model->qp, beta_offset_div2, tc_offset_div2);
+    if (deblock) kvz::deblock_frames_on(b->stream, b->d_rec, F.W, F.H, n, b->d_depth, model->qp, beta_offset_div2, tc_offset_div2, 3, nullptr, 0, qps);
     return;
   }
   const size_t pic_bytes = (size_t)F.frame_px * n, lcus = (size_t)F.wc * F.hc * n;
@@ -1579,17 +1605,33 @@ void kvz_hip_batch_loop_filters(kvz_hip_batch *b, const kvz_hip_intra_cost_model
   }
   // R = d_rec (kept), V = d_ver, D = d_dbk
   KVZ_HIP_CHECK(hipMemcpyAsync(b->d_ver, b->d_rec, pic_bytes, hipMemcpyDeviceToDevice, b->stream));
-  if (deblock) kvz::deblock_frames_on(b->stream, b->d_ver, F.W, F.H, n, b->d_depth, model->qp, beta_offset_div2, tc_offset_div2, 1);
+  if (deblock) kvz::deblock_frames_on(b->stream, b->d_ver, F.W, F.H, n, b->d_depth, model->qp, beta_offset_div2, tc_offset_div2, 1, nullptr, 0, qps);
   KVZ_HIP_CHECK(hipMemcpyAsync(b->d_dbk, b->d_ver, pic_bytes, hipMemcpyDeviceToDevice, b->stream));
-  if (deblock) kvz::deblock_frames_on(b->stream, b->d_dbk, F.W, F.H, n, b->d_depth, model->qp, beta_offset_div2, tc_offset_div2, 2);
+  if (deblock) kvz::deblock_frames_on(b->stream, b->d_dbk, F.W, F.H, n, b->d_depth, model->qp, beta_offset_div2, tc_offset_div2, 2, nullptr, 0, qps);
   KVZ_HIP_CHECK(hipMemcpyAsync(b->d_sao_fbits, model->entropy_fbits, 128 * sizeof(float), hipMemcpyHostToDevice, b->stream));
   const kvz::SaoGeom g{ F.W, F.H, F.wc, F.hc, F.frame_px };
   hipLaunchKernelGGL(kvz::dev_sao_stats_kernel, dim3((unsigned)(lcus * 3)), dim3(256), 0, b->stream, b->d_src, b->d_rec, b->d_ver, b->d_dbk, g, (kvz::SaoStats *)b->d_sao_stats, (kvz::SaoCand *)b->d_sao_cand);
   hipLaunchKernelGGL(kvz::dev_sao_chain_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, b->stream, (const kvz::SaoStats *)b->d_sao_stats, (const kvz::SaoCand *)b->d_sao_cand, g, n, b->d_sao_fbits, kvz::device_tables(),
-                     model->lambda, (int)model->ctx_init[KVZ_HIP_CX_SAO_MERGE], (int)model->ctx_init[KVZ_HIP_CX_SAO_TYPE], model->no_wpp, b->d_sao_recs, b->d_sao_merge);
+                     model->lambda, (int)model->ctx_init[KVZ_HIP_CX_SAO_MERGE], (int)model->ctx_init[KVZ_HIP_CX_SAO_TYPE], model->no_wpp, b->d_sao_recs, b->d_sao_merge, v ? v->ctu : kvz::CtuModelTable());
   // the SAO'd picture becomes the batch's reconstruction (R is not needed any more)
   kvz::launch_sao(b->stream, b->d_dbk, b->d_rec, F.W, F.H, n, b->d_sao_recs, nullptr, nullptr);
   KVZ_HIP_CHECK(hipGetLastError());
+}
+
+void kvz_hip_batch_loop_filters(kvz_hip_batch *b, const kvz_hip_intra_cost_model *model, int deblock, int beta_offset_div2, int tc_offset_div2, int sao)
+{
+  if (!kvz::cost_model_known(model, "kvz_hip_batch_loop_filters")) { b->failed = 1; return; }  // no return value: the batch reports it (kvz_hip_batch_sync -> -1)
+  kvz::batch_enter(b);
+  kvz_batch_loop_filters_queue(b, model, nullptr, deblock, beta_offset_div2, tc_offset_div2, sao);
+}
+
+int kvz_hip_batch_loop_filters_models(kvz_hip_batch *b, const kvz_hip_picture_models *pm, int deblock, int beta_offset_div2, int tc_offset_div2, int sao)
+{
+  if (!b || !kvz::picture_models_known(pm, b->n_frames, b->sched_ticket != 0, "kvz_hip_batch_loop_filters_models")) return -1;
+  kvz::batch_enter(b);
+  const kvz::ModelTableView v = kvz::picture_models_stage(b, pm);
+  kvz_batch_loop_filters_queue(b, &pm->models[0], &v, deblock, beta_offset_div2, tc_offset_div2, sao);
+  return 0;
 }
 
 int kvz_hip_batch_sao_params(kvz_hip_batch *b, int frame, kvz_hip_sao_params *luma, kvz_hip_sao_params *chroma, uint8_t *merge)
@@ -1809,14 +1851,40 @@ long kvz_hip_batch_entropy_code_tiles(kvz_hip_batch *b, const kvz_hip_intra_cost
 {
   return kvz_hip_batch_entropy_code_then(b, model, sao, not_last, out, capacity, substream_bytes, nullptr, nullptr);
 }
+// The coder of kvz_hip_batch_entropy_code_then (v == nullptr: `model`'s initial states for every picture) and of kvz_hip_batch_entropy_code_then_models (`model` = the
+// table's first: no_wpp, search_nxn).  start_next queues `next`'s pass, once; null when there is none.
+static long kvz_batch_entropy_code_queue(kvz_hip_batch *b, const kvz_hip_intra_cost_model *model, const kvz::ModelTableView *v, int sao, const uint8_t *not_last, uint8_t *out,
+                                         size_t capacity, uint32_t *substream_bytes, const std::function<void()> &start_next)
+{
+  const kvz::CtuFrames &F = b->F;
+  const int ctus = F.wc * F.hc;
+  if (sao && !b->d_sao_recs) { fprintf(stderr, "kvz_hip_batch_entropy_code: kvz_hip_batch_loop_filters(..., sao = 1) has not run on this batch\n"); return -1; }
+  if (model->search_nxn && !b->d_part) { fprintf(stderr, "kvz_hip_batch_entropy_code: the batch has no NxN partition maps\n"); return -1; }
+  KVZ_HIP_CHECK(hipStreamSynchronize(b->stream));
+  if (kvz::batch_check(b) != 0) return -1;
+  const long cells8 = (long)(F.H >> 3) * (F.W >> 3), cells4 = (long)(F.H >> 2) * (F.W >> 2);
+  auto job = [&](int f0, int nf) {
+    kvz::EntropyJob J;
+    memset(&J, 0, sizeof J);
+    J.W = F.W; J.H = F.H; J.wc = F.wc; J.hc = F.hc; J.n_frames = nf; J.no_wpp = model->no_wpp;
+    J.depth = b->d_depth + f0 * cells8; J.mode = b->d_mode + f0 * cells8;
+    J.part = model->search_nxn ? b->d_part + f0 * cells8 : nullptr; J.mode4 = model->search_nxn ? b->d_mode4 + f0 * cells4 : nullptr;
+    J.coeff = b->d_coeff + (size_t)f0 * ctus * KVZ_HIP_CTU_COEFFS;
+    J.sao = sao ? (const kvz::SaoRec *)b->d_sao_recs + (size_t)f0 * ctus * 3 : nullptr; J.sao_merge = sao ? b->d_sao_merge + (size_t)f0 * ctus : nullptr;
+    memcpy(J.ctx_init, model->ctx_init, sizeof model->ctx_init < sizeof J.ctx_init ? sizeof model->ctx_init : sizeof J.ctx_init);
+    if (v) { J.ctx_rows = v->ctx_rows; J.model_of_picture = v->ctu.model_of_picture + f0; }
+    return J;
+  };
+  return kvz::entropy_code_pictures(b->stream, b->device, b->n_frames, F.wc, F.hc, model->no_wpp, not_last, job, out, capacity, substream_bytes,
+                                    start_next ? start_next : std::function<void()>(), b->entropy_deferred ? &b->entropy_out : nullptr, b->entropy_deferred != 0);
+}
+
 long kvz_hip_batch_entropy_code_then(kvz_hip_batch *b, const kvz_hip_intra_cost_model *model, int sao, const uint8_t *not_last, uint8_t *out, size_t capacity,
                                      uint32_t *substream_bytes, kvz_hip_batch *next, const kvz_hip_intra_cost_model *next_model)
 {
   if (!b || !kvz::cost_model_known(model, "kvz_hip_batch_entropy_code")) return -1;
   if (next && !kvz::cost_model_known(next_model, "kvz_hip_batch_entropy_code_then (next_model)")) return -3;  // nothing has been queued anywhere
   kvz::batch_enter(b);
-  const kvz::CtuFrames &F = b->F;
-  const int ctus = F.wc * F.hc;
   // `next`'s pass is queued exactly once on every path below (the caller synchronises `next` whatever this call returns): by the coder at its quiet moment, or here
   int launched = 0;
   bool started = false;
@@ -1832,26 +1900,37 @@ long kvz_hip_batch_entropy_code_then(kvz_hip_batch *b, const kvz_hip_intra_cost_
     }
   };
   struct StartOnExit { decltype(start_next) &f; ~StartOnExit() { f(); } } start_on_exit{ start_next };
-  if (sao && !b->d_sao_recs) { fprintf(stderr, "kvz_hip_batch_entropy_code: kvz_hip_batch_loop_filters(..., sao = 1) has not run on this batch\n"); return -1; }
-  if (model->search_nxn && !b->d_part) { fprintf(stderr, "kvz_hip_batch_entropy_code: the batch has no NxN partition maps\n"); return -1; }
-  KVZ_HIP_CHECK(hipStreamSynchronize(b->stream));
-  if (kvz::batch_check(b) != 0) return -1;
-  const long cells8 = (long)(F.H >> 3) * (F.W >> 3), cells4 = (long)(F.H >> 2) * (F.W >> 2);
-  auto job = [&](int f0, int nf) {
-    kvz::EntropyJob J;
-    memset(&J, 0, sizeof J);
-    J.W = F.W; J.H = F.H; J.wc = F.wc; J.hc = F.hc; J.n_frames = nf; J.no_wpp = model->no_wpp;
-    J.depth = b->d_depth + f0 * cells8; J.mode = b->d_mode + f0 * cells8;
-    J.part = model->search_nxn ? b->d_part + f0 * cells8 : nullptr; J.mode4 = model->search_nxn ? b->d_mode4 + f0 * cells4 : nullptr;
-    J.coeff = b->d_coeff + (size_t)f0 * ctus * KVZ_HIP_CTU_COEFFS;
-    J.sao = sao ? (const kvz::SaoRec *)b->d_sao_recs + (size_t)f0 * ctus * 3 : nullptr; J.sao_merge = sao ? b->d_sao_merge + (size_t)f0 * ctus : nullptr;
-    memcpy(J.ctx_init, model->ctx_init, sizeof model->ctx_init < sizeof J.ctx_init ? sizeof model->ctx_init : sizeof J.ctx_init);
-    return J;
-  };
-  const long total = kvz::entropy_code_pictures(b->stream, b->device, b->n_frames, F.wc, F.hc, model->no_wpp, not_last, job, out, capacity, substream_bytes,
-                                                next ? std::function<void()>(start_next) : std::function<void()>(),
-                                                b->entropy_deferred ? &b->entropy_out : nullptr, b->entropy_deferred != 0);
+  const long total = kvz_batch_entropy_code_queue(b, model, nullptr, sao, not_last, out, capacity, substream_bytes, next ? std::function<void()>(start_next) : std::function<void()>());
   start_next();  // the coder failed before its last chunk: the pass starts now
+  return next && launched < 0 ? -2 : total;
+}
+
+long kvz_hip_batch_entropy_code_models(kvz_hip_batch *b, const kvz_hip_picture_models *pm, int sao, const uint8_t *not_last, uint8_t *out, size_t capacity, uint32_t *substream_bytes)
+{
+  return kvz_hip_batch_entropy_code_then_models(b, pm, sao, not_last, out, capacity, substream_bytes, nullptr, nullptr);
+}
+long kvz_hip_batch_entropy_code_then_models(kvz_hip_batch *b, const kvz_hip_picture_models *pm, int sao, const uint8_t *not_last, uint8_t *out, size_t capacity,
+                                            uint32_t *substream_bytes, kvz_hip_batch *next, const kvz_hip_picture_models *next_pm)
+{
+  if (!b) return -1;
+  if (next && !kvz::picture_models_known(next_pm, next->n_frames, next->sched_ticket != 0, "kvz_hip_batch_entropy_code_then_models (next_models)")) return -3;  // nothing has been queued anywhere
+  // as in kvz_hip_batch_entropy_code_then: `next`'s pass is queued exactly once on every path below, the refusal of b's own table included
+  int launched = 0;
+  bool started = false;
+  auto start_next = [&] {
+    if (next && !started) {
+      started = true;
+      launched = kvz_hip_intra_frames_models(next, next_pm);
+      kvz::batch_enter(b);
+      if (launched > 0) KVZ_HIP_CHECK(hipStreamWaitEvent(b->stream, next->ev1, 0));
+    }
+  };
+  struct StartOnExit { decltype(start_next) &f; ~StartOnExit() { f(); } } start_on_exit{ start_next };
+  if (!kvz::picture_models_known(pm, b->n_frames, b->sched_ticket != 0, "kvz_hip_batch_entropy_code_models")) return -1;  // (nothing queued on b)
+  kvz::batch_enter(b);
+  const kvz::ModelTableView v = kvz::picture_models_stage(b, pm);
+  const long total = kvz_batch_entropy_code_queue(b, &pm->models[0], &v, sao, not_last, out, capacity, substream_bytes, next ? std::function<void()>(start_next) : std::function<void()>());
+  start_next();
   return next && launched < 0 ? -2 : total;
 }
 

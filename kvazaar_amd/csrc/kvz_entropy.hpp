@@ -51,7 +51,14 @@ struct EntropyJob {
   const kvz_hip_cu_info *cu, *ref_cu;  // [frames][(H/4)*(W/4)]
   int poc;                     // temporal MV predictors need poc > 1 (inter.c:1290)
   u8 ctx_init[KVZ_ENTROPY_CTXS];  // the slice's initial states: kvz_hip_intra_cost_model::ctx_init (KVZ_HIP_CX_* order); B slices: + the KVZ_EB_CX_* contexts
+  // pictures under models of their own (kvz_hip_batch_entropy_code_models): ctx_rows != nullptr holds a row of KVZ_ENTROPY_CTX_ROW bytes per model (the model's ctx_init,
+  // zeros behind it) and model_of_picture the row of every picture of the job; ctx_init above is then unused
+  const u8 *ctx_rows;
+  const uint16_t *model_of_picture;
 };
+#define KVZ_ENTROPY_CTX_ROW 176
+// the initial context states of picture f of the job
+KVZ_HD const u8 *entropy_ctx_init(const EntropyJob &J, int f) { return J.ctx_rows ? J.ctx_rows + (long)picture_model(J.model_of_picture, f) * KVZ_ENTROPY_CTX_ROW : J.ctx_init; }
 #define KVZ_EB_CTX(ctx, v) ((u32)(ctx) | ((u32)(v) << 8))
 #define KVZ_EB_EP(value, n) (0x40000000u | ((u32)(n) << 16) | ((u32)(value) & 0xffffu))
 #define KVZ_EB_TRM(v) (0x80000000u | ((u32)(v) << 8) | 168u)  /* the value where a context-coded bin has it, on the coder's pseudo-context (KVZ_ENTROPY_CTX_NEUTRAL) */
@@ -627,7 +634,8 @@ KVZ_DEV void entropy_row_contexts(const EntropyJob &J, const EntropyTabs T, int 
 {
   const int ctus = J.wc * J.hc;
   u8 *out = J.row_ctx + (long)f * J.hc * KVZ_ENTROPY_CTXS;
-  for (int i = 0; i < KVZ_ENTROPY_CTXS; i++) { ctx[i] = J.ctx_init[i]; out[i] = ctx[i]; }
+  const u8 *init = entropy_ctx_init(J, f);
+  for (int i = 0; i < KVZ_ENTROPY_CTXS; i++) { ctx[i] = init[i]; out[i] = ctx[i]; }
   for (int r = 0; r + 1 < J.hc; r++) {
     if (J.wc >= 2) {  // a picture one CTU wide never reaches "lcu->index == 1": its rows keep the slice's initial states
       for (int x = 0; x < 2; x++) {
@@ -649,7 +657,7 @@ KVZ_DEV void entropy_row_contexts(const EntropyJob &J, const EntropyTabs T, int 
         }
       }
     } else {
-      for (int i = 0; i < KVZ_ENTROPY_CTXS; i++) ctx[i] = J.ctx_init[i];
+      for (int i = 0; i < KVZ_ENTROPY_CTXS; i++) ctx[i] = init[i];
     }
     for (int i = 0; i < KVZ_ENTROPY_CTXS; i++) out[(r + 1) * KVZ_ENTROPY_CTXS + i] = ctx[i];
   }
@@ -798,7 +806,7 @@ template <int W> KVZ_DEV u32 entropy_code_row_wide(const EntropyJob &J, const un
   const int ctus = J.wc * J.hc;
   const int f = J.no_wpp ? (int)item : (int)(item / J.hc), row = J.no_wpp ? 0 : (int)(item - (long)f * J.hc);
   const long first = (long)f * ctus + (long)row * J.wc, count = J.no_wpp ? ctus : J.wc;
-  const u8 *start = J.no_wpp ? J.ctx_init : J.row_ctx + ((long)f * J.hc + row) * KVZ_ENTROPY_CTXS;
+  const u8 *start = J.no_wpp ? entropy_ctx_init(J, f) : J.row_ctx + ((long)f * J.hc + row) * KVZ_ENTROPY_CTXS;
   for (int i = 0; i < KVZ_ENTROPY_CTXS; i++) ctx[i] = start[i];
   ctx[KVZ_ENTROPY_CTX_NEUTRAL] = 126;
   WideCoder<W> a;

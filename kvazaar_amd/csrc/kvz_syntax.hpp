@@ -87,6 +87,10 @@ template <class T> KVZ_HD void intra_mpm(int l, int a, T preds[3])
   }
 }
 
+// ---- pictures of one launch under different cost models (kvz_hip_picture_models): the row of the launch's model table that a picture uses.  The CTU pass, the
+// loop filters and the entropy coder all select through this; a null map is the single-model launch (row 0).
+KVZ_HD int picture_model(const uint16_t *model_of_picture, long picture) { return model_of_picture ? (int)model_of_picture[picture] : 0; }
+
 // ---- quantisation, flat scaling lists
 // kvz_g_chroma_scale (transform.c:56-62, H.265 table 8-10): the chroma QP of a luma QP, clipped to the table
 KVZ_HD int chroma_qp(int qp)

@@ -50,16 +50,16 @@ inline u16 half_bits_of_int(int v)
 }
 
 // Deblocking thresholds, H.265 Table 8-12 (filter.c:46-65 kvz_g_tc_table_8x8 / kvz_g_beta_table_8x8)
-inline int deblock_tc(int q)  // q in [0, 53]
+KVZ_HD int deblock_tc(int q)  // q in [0, 53]  (host and device: a mixed-QP launch derives the thresholds per picture, kvz_dev.hpp)
 {
-  static const unsigned char first_q_of_next[] = { 18, 27, 31, 35, 38, 40, 42, 43, 44, 45, 46 };  // tc' steps 0 -> 1 -> ... -> 10 -> 11
-  static const unsigned char from_46[] = { 11, 13, 14, 16, 18, 20, 22, 24 };
+  const unsigned char first_q_of_next[] = { 18, 27, 31, 35, 38, 40, 42, 43, 44, 45, 46 };  // tc' steps 0 -> 1 -> ... -> 10 -> 11
+  const unsigned char from_46[] = { 11, 13, 14, 16, 18, 20, 22, 24 };
   if (q >= 46) return from_46[q - 46];
   int v = 0;
   while (q >= first_q_of_next[v]) v++;
   return v;
 }
-inline int deblock_beta(int q) { return q < 16 ? 0 : (q <= 28 ? q - 10 : 2 * q - 38); }  // q in [0, 51]
+KVZ_HD int deblock_beta(int q) { return q < 16 ? 0 : (q <= 28 ? q - 10 : 2 * q - 38); }  // q in [0, 51]
 
 // Entropy bits of the HEVC CABAC state machine, fixed point 1<<15 (HM 12.0 sm_entropyBits, as tabulated in
 // rdo.c:69-80 kvz_entropy_bits); CTX_ENTROPY_FBITS = value / 32768 (rdo.c:83, cabac.h:131).  Standard constant data.
