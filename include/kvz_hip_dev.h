@@ -196,6 +196,24 @@ int kvz_hip_dev_inter_slots_per_cu(void);
  * a thread that never filtered gets -1. */
 long kvz_hip_dev_entropy_code_inter(const kvz_hip_cu_info *cu, const kvz_hip_cu_info *ref_cu, const int16_t *coeff, int width, int height, int n_pictures,
                                     const kvz_hip_inter_params *params, uint8_t *out, size_t capacity, uint32_t *substream_bytes);
+/* Pictures with a QP and a POC of their own in one launch (kvz_hip_inter_pictures, kvz_hip_types.h): sequences at different --qp, or at different positions of the
+ * low-delay GOP (whose layer moves the picture QP on every picture), fill one launch instead of one small launch per (QP, POC).  The three entry points mirror
+ * kvz_hip_dev_inter_ctu_pass_tiles, kvz_hip_dev_loop_filters_inter and kvz_hip_dev_entropy_code_inter, which stay what they are:
+ *  - `pictures` given: params->qp and params->poc are ignored, picture i runs at pictures->qp[i] / pictures->poc[i]; every other member of params is the launch's.
+ *    The launch takes the kernel build with the residual coder's contexts when ANY picture's QP reaches params->fast_residual_cost.
+ *  - `pictures` NULL: exactly kvz_hip_dev_inter_ctu_pass_tiles / kvz_hip_dev_entropy_code_inter.
+ *  - the loop filters take the QPs alone: qp_of_picture, a HOST array of n_pictures values.
+ * Refused with -1 and a message before anything is queued: a struct_size that is not this library's, pictures->n_pictures != n_pictures, a NULL array, a QP outside
+ * 0 .. 51, a POC below 1. */
+int  kvz_hip_dev_inter_ctu_pass_pictures(const uint8_t *src, const uint8_t *ref, const kvz_hip_cu_info *ref_cu, uint8_t *rec, kvz_hip_cu_info *cu, int16_t *coeff, int width,
+                                         int height, int n_pictures, const kvz_hip_inter_params *params, const int32_t *tile_xy, int n_references,
+                                         const kvz_hip_inter_pictures *pictures);
+int  kvz_hip_dev_loop_filters_inter_pictures(const uint8_t *src, uint8_t *rec, int width, int height, int n_pictures, const kvz_hip_cu_dbk *info, const int32_t *qp_of_picture,
+                                             int slice_is_b, int deblock, int beta_offset_div2, int tc_offset_div2, int sao, int no_wpp, kvz_hip_sao_params *luma,
+                                             kvz_hip_sao_params *chroma, uint8_t *merge);
+long kvz_hip_dev_entropy_code_inter_pictures(const kvz_hip_cu_info *cu, const kvz_hip_cu_info *ref_cu, const int16_t *coeff, int width, int height, int n_pictures,
+                                             const kvz_hip_inter_params *params, uint8_t *out, size_t capacity, uint32_t *substream_bytes,
+                                             const kvz_hip_inter_pictures *pictures);
 /* what the deblocking filter reads (kvz_hip_cu_dbk) of `count` CU records: type, depth, tr_depth, the luma coded block flag at tr_depth, motion */
 void kvz_hip_dev_cu_dbk_from_info(const kvz_hip_cu_info *cu, int count, kvz_hip_cu_dbk *out);
 

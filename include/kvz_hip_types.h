@@ -152,6 +152,17 @@ typedef struct kvz_hip_picture_models {
   const uint16_t *model_of_picture;         /* [n_frames of the batch]: each < n_models */
 } kvz_hip_picture_models;
 
+/* The pictures of ONE launch of the inter CTU pass (kvz_hip_dev.h, the kvz_hip_dev_*_pictures entry points) that do not share a QP and a POC: picture k of sequences
+ * that run at different --qp or stand at different positions of their GOP.  Every picture stays an ordinary constant-QP picture: what the single-QP entry point makes
+ * of it in a launch of its own, byte for byte.  Everything else of kvz_hip_inter_params (preset, switches, geometry) stays the launch's.  HOST arrays.
+ * struct_size: sizeof of the caller's headers; an unknown size is refused with -1. */
+typedef struct kvz_hip_inter_pictures {
+  uint32_t struct_size;
+  int32_t  n_pictures;   /* the n_pictures of the call */
+  const int32_t *qp;     /* [n_pictures]: 0 .. 51 */
+  const int32_t *poc;    /* [n_pictures]: >= 1; temporal AMVP candidates need poc > 1 */
+} kvz_hip_inter_pictures;
+
 /* Per-CTU result record of the batched pass: what kvazaar keeps in cu_array / lcu_t for the CTU. */
 #define KVZ_HIP_CTU_COEFFS 6144 /* 64*64 Y + 32*32 U + 32*32 V coefficients, each plane in lcu_t z-order (cu.h:385-421) */
 

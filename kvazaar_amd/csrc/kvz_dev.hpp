@@ -983,14 +983,23 @@ __global__ void __launch_bounds__(256) dev_sao_stats_kernel(const u8 *src, const
     cand[item] = c;
   }
 }
+// what the SAO decision takes from a picture's QP: lambda (pow stays on the host) and the two context states it prices with.  kvz_hip_dev_loop_filters_inter_pictures
+// builds a row per QP 0 .. 51 and the kernel indexes it by the picture's QP
+struct SaoQpRow { double lambda; int init_merge, init_type; };
 // ... and the chain over the LCUs of a picture: one lane per picture
 __global__ void __launch_bounds__(64) dev_sao_chain_kernel(const SaoStats *stats, const SaoCand *cand, const SaoGeom g, const int n_frames, const float *fbits, const Tables *tb,
                                                            const double lambda, const int init_merge, const int init_type, const int no_wpp, SaoRec *recs, u8 *merge,
-                                                           const CtuModelTable pm = CtuModelTable())
+                                                           const CtuModelTable pm = CtuModelTable(), const SaoQpRow *qp_rows = nullptr, const int32_t *qp_of_picture = nullptr)
 {
   const int f = blockIdx.x * 64 + threadIdx.x;
   if (f >= n_frames) return;
   const long base = (long)f * g.wl * g.hl;
+  if (qp_rows) {  // inter pictures with QPs of their own
+    const SaoQpRow r = qp_rows[qp_of_picture[f]];
+    sao_chain_picture(fbits, tb->ctx_next[0], tb->ctx_next[1], r.lambda, (u8)r.init_merge, (u8)r.init_type, no_wpp, g.wl, g.hl, stats + base * 3, cand + base * 3, recs + base * 3,
+                      merge + base);
+    return;
+  }
   if (pm.models) {  // the picture's own lambda and SAO context states, from its row of the model table (kvz_hip_batch_loop_filters_models)
     const CtuModel *m = picture_model(pm, f);
     sao_chain_picture(fbits, tb->ctx_next[0], tb->ctx_next[1], m->lambda, m->ctx_init[KVZ_HIP_CX_SAO_MERGE], m->ctx_init[KVZ_HIP_CX_SAO_TYPE], no_wpp, g.wl, g.hl, stats + base * 3, cand + base * 3,
@@ -1029,7 +1038,8 @@ struct InterScratch {
   InterSlab *slabs = nullptr; int n_slabs = 0;
   ICtx *ctx = nullptr; unsigned *done = nullptr; uint32_t *items = nullptr; long n_ctus = 0;
   unsigned *ticket = nullptr;  // [0] ticket, [1] error
-  InterModel *model = nullptr;
+  void *model = nullptr; size_t model_bytes = 0;  // the launch's InterModel, or its picture table (InterFrames::pictures)
+  uint8_t *entropy_table = nullptr; size_t entropy_table_bytes = 0;  // kvz_hip_dev_entropy_code_inter_pictures: context rows, POCs and rows of the pictures
 };
 // One set per calling thread and device, like the stream the work is queued on (be() is thread_local): two threads, or two devices of one process, never share
 // ticket / done / slab buffers, and a buffer is only ever freed by the thread whose (synchronised) stream used it.
@@ -1046,7 +1056,7 @@ inline InterScratch &inter_scratch()
         InterScratch &x = all[d];
         if (!x.slabs && !x.ctx && !x.ticket) continue;
         (void)hipSetDevice(d);
-        (void)hipFree(x.slabs); (void)hipFree(x.ctx); (void)hipFree(x.done); (void)hipFree(x.items); (void)hipFree(x.ticket); (void)hipFree(x.model);
+        (void)hipFree(x.slabs); (void)hipFree(x.ctx); (void)hipFree(x.done); (void)hipFree(x.items); (void)hipFree(x.ticket); (void)hipFree(x.model); (void)hipFree(x.entropy_table);
         x = InterScratch();
       }
     });
@@ -1265,6 +1275,8 @@ struct LoopScratch {
   u8 *ver = nullptr, *dbk = nullptr; size_t pic_bytes = 0;
   SaoStats *stats = nullptr; SaoCand *cand = nullptr; SaoRec *recs = nullptr; u8 *merge = nullptr; size_t lcus = 0;
   float *fbits = nullptr;
+  int32_t *qps = nullptr; size_t n_qps = 0;  // kvz_hip_dev_loop_filters_inter_pictures: the pictures' QPs
+  SaoQpRow *sao_rows = nullptr;              // ... and the SAO decision's row per QP 0 .. 51
 };
 // per calling thread and device (see inter_scratch): kvz_hip_dev_entropy_code_inter reads the SAO decisions the LAST kvz_hip_dev_loop_filters_inter of the same thread
 // left on the same device
@@ -1280,7 +1292,7 @@ inline LoopScratch &loop_scratch()
         LoopScratch &x = all[d];
         if (!x.ver && !x.stats && !x.fbits) continue;
         (void)hipSetDevice(d);
-        (void)hipFree(x.ver); (void)hipFree(x.dbk); (void)hipFree(x.stats); (void)hipFree(x.cand); (void)hipFree(x.recs); (void)hipFree(x.merge); (void)hipFree(x.fbits);
+        (void)hipFree(x.ver); (void)hipFree(x.dbk); (void)hipFree(x.stats); (void)hipFree(x.cand); (void)hipFree(x.recs); (void)hipFree(x.merge); (void)hipFree(x.fbits); (void)hipFree(x.qps); (void)hipFree(x.sao_rows);
         x = LoopScratch();
       }
     });
@@ -1288,14 +1300,43 @@ inline LoopScratch &loop_scratch()
   return s[current_device() & 63];
 }
 }  // namespace kvz
+// kvz_hip_dev_loop_filters_inter (qp_host == nullptr: `qp` for every picture) and kvz_hip_dev_loop_filters_inter_pictures (qp_host: a checked HOST array, `qp` unused)
+static int kvz_loop_filters_inter_run(const uint8_t *src, uint8_t *rec, int width, int height, int n_pictures, const kvz_hip_cu_dbk *info, int qp, const int32_t *qp_host, int slice_is_b,
+                                      int deblock, int beta_offset_div2, int tc_offset_div2, int sao, int no_wpp, kvz_hip_sao_params *luma, kvz_hip_sao_params *chroma, uint8_t *merge);
 int kvz_hip_dev_loop_filters_inter(const uint8_t *src, uint8_t *rec, int width, int height, int n_pictures, const kvz_hip_cu_dbk *info, int qp, int slice_is_b, int deblock,
                                    int beta_offset_div2, int tc_offset_div2, int sao, int no_wpp, kvz_hip_sao_params *luma, kvz_hip_sao_params *chroma, uint8_t *merge)
 {
   if (n_pictures <= 0) return 0;
   if (!src || !rec || !info || width <= 0 || height <= 0 || (width & 7) || (height & 7) || qp < 0 || qp > 51) { fprintf(stderr, "kvz_hip_dev_loop_filters_inter: bad argument\n"); return -1; }
+  return kvz_loop_filters_inter_run(src, rec, width, height, n_pictures, info, qp, nullptr, slice_is_b, deblock, beta_offset_div2, tc_offset_div2, sao, no_wpp, luma, chroma, merge);
+}
+int kvz_hip_dev_loop_filters_inter_pictures(const uint8_t *src, uint8_t *rec, int width, int height, int n_pictures, const kvz_hip_cu_dbk *info, const int32_t *qp_of_picture,
+                                            int slice_is_b, int deblock, int beta_offset_div2, int tc_offset_div2, int sao, int no_wpp, kvz_hip_sao_params *luma,
+                                            kvz_hip_sao_params *chroma, uint8_t *merge)
+{
+  if (n_pictures <= 0) return 0;
+  if (!src || !rec || !info || width <= 0 || height <= 0 || (width & 7) || (height & 7)) { fprintf(stderr, "kvz_hip_dev_loop_filters_inter_pictures: bad argument\n"); return -1; }
+  if (!kvz::inter_picture_qps_known(qp_of_picture, n_pictures, "kvz_hip_dev_loop_filters_inter_pictures")) return -1;
+  return kvz_loop_filters_inter_run(src, rec, width, height, n_pictures, info, 0, qp_of_picture, slice_is_b, deblock, beta_offset_div2, tc_offset_div2, sao, no_wpp, luma, chroma, merge);
+}
+static int kvz_loop_filters_inter_run(const uint8_t *src, uint8_t *rec, int width, int height, int n_pictures, const kvz_hip_cu_dbk *info, int qp, const int32_t *qp_host, int slice_is_b,
+                                      int deblock, int beta_offset_div2, int tc_offset_div2, int sao, int no_wpp, kvz_hip_sao_params *luma, kvz_hip_sao_params *chroma, uint8_t *merge)
+{
   hipStream_t st = be().stream;
+  const int32_t *qps = nullptr;  // device: the pictures' QPs
+  if (qp_host) {
+    kvz::LoopScratch &lq = kvz::loop_scratch();
+    if ((size_t)n_pictures > lq.n_qps) {
+      if (lq.qps) KVZ_HIP_CHECK(hipFree(lq.qps));
+      KVZ_HIP_CHECK(hipMalloc((void **)&lq.qps, (size_t)n_pictures * sizeof(int32_t)));
+      lq.n_qps = (size_t)n_pictures;
+    }
+    KVZ_HIP_CHECK(hipMemcpyAsync(lq.qps, qp_host, (size_t)n_pictures * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    KVZ_HIP_CHECK(hipStreamSynchronize(st));  // the caller's array
+    qps = lq.qps;
+  }
   if (!sao) {
-    if (deblock) kvz::deblock_frames_on(st, rec, width, height, n_pictures, nullptr, qp, beta_offset_div2, tc_offset_div2, 3, info, slice_is_b);
+    if (deblock) kvz::deblock_frames_on(st, rec, width, height, n_pictures, nullptr, qp, beta_offset_div2, tc_offset_div2, 3, info, slice_is_b, qps);
     return 0;
   }
   const int wc = (width + 63) >> 6, hc = (height + 63) >> 6;
@@ -1324,16 +1365,25 @@ int kvz_hip_dev_loop_filters_inter(const uint8_t *src, uint8_t *rec, int width, 
   }
   // R = rec (kept until the SAO kernel has read D), V = after the vertical edges, D = after all edges (sao.c:632-735 reads all three around an LCU's borders)
   KVZ_HIP_CHECK(hipMemcpyAsync(sc.ver, rec, pic_bytes, hipMemcpyDeviceToDevice, st));
-  if (deblock) kvz::deblock_frames_on(st, sc.ver, width, height, n_pictures, nullptr, qp, beta_offset_div2, tc_offset_div2, 1, info, slice_is_b);
+  if (deblock) kvz::deblock_frames_on(st, sc.ver, width, height, n_pictures, nullptr, qp, beta_offset_div2, tc_offset_div2, 1, info, slice_is_b, qps);
   KVZ_HIP_CHECK(hipMemcpyAsync(sc.dbk, sc.ver, pic_bytes, hipMemcpyDeviceToDevice, st));
-  if (deblock) kvz::deblock_frames_on(st, sc.dbk, width, height, n_pictures, nullptr, qp, beta_offset_div2, tc_offset_div2, 2, info, slice_is_b);
+  if (deblock) kvz::deblock_frames_on(st, sc.dbk, width, height, n_pictures, nullptr, qp, beta_offset_div2, tc_offset_div2, 2, info, slice_is_b, qps);
   const kvz::SaoGeom g{ width, height, wc, hc, frame_px };
-  const double lambda = 0.57 * pow(2.0, (qp - 12) / 3.0);  // rate_control.c:678-691 at the picture's QP
-  // context.c:38-39 INIT_SAO_MERGE_FLAG / INIT_SAO_TYPE_IDX of the slice type (B: 153 / 160, I: 153 / 200)
-  const int cx_merge = kvz::ctx_state(qp, 153), cx_type = kvz::ctx_state(qp, slice_is_b ? 160 : 200);
+  // rate_control.c:678-691 at the picture's QP; context.c:38-39 INIT_SAO_MERGE_FLAG / INIT_SAO_TYPE_IDX of the slice type (B: 153 / 160, I: 153 / 200)
+  auto sao_row = [&](int q) { return kvz::SaoQpRow{ 0.57 * pow(2.0, (q - 12) / 3.0), kvz::ctx_state(q, 153), kvz::ctx_state(q, slice_is_b ? 160 : 200) }; };
+  const kvz::SaoQpRow row = sao_row(qp);
+  const double lambda = row.lambda;
+  const int cx_merge = row.init_merge, cx_type = row.init_type;
+  if (qps) {  // a row per QP: the kernel takes the picture's
+    kvz::SaoQpRow rows[52];
+    for (int q = 0; q < 52; q++) rows[q] = sao_row(q);
+    if (!sc.sao_rows) KVZ_HIP_CHECK(hipMalloc((void **)&sc.sao_rows, sizeof rows));
+    KVZ_HIP_CHECK(hipMemcpyAsync(sc.sao_rows, rows, sizeof rows, hipMemcpyHostToDevice, st));
+    KVZ_HIP_CHECK(hipStreamSynchronize(st));  // `rows` is a stack object
+  }
   hipLaunchKernelGGL(kvz::dev_sao_stats_kernel, dim3((unsigned)(lcus * 3)), dim3(256), 0, st, src, rec, sc.ver, sc.dbk, g, sc.stats, sc.cand);
   hipLaunchKernelGGL(kvz::dev_sao_chain_kernel, dim3((unsigned)((n_pictures + 63) / 64)), dim3(64), 0, st, (const kvz::SaoStats *)sc.stats, (const kvz::SaoCand *)sc.cand, g, n_pictures, sc.fbits,
-                     kvz::device_tables(), lambda, cx_merge, cx_type, no_wpp, sc.recs, sc.merge);
+                     kvz::device_tables(), lambda, cx_merge, cx_type, no_wpp, sc.recs, sc.merge, kvz::CtuModelTable(), qps ? (const kvz::SaoQpRow *)sc.sao_rows : nullptr, qps);
   kvz::launch_sao(st, sc.dbk, rec, width, height, n_pictures, sc.recs, nullptr, nullptr);
   KVZ_HIP_CHECK(hipGetLastError());
   if (luma || chroma || merge) {  // host copies of the decisions (what the encoder writes as SAO syntax)
@@ -1400,6 +1450,13 @@ int kvz_hip_dev_inter_ctu_pass(const uint8_t *src, const uint8_t *ref, const kvz
 int kvz_hip_dev_inter_ctu_pass_tiles(const uint8_t *src, const uint8_t *ref, const kvz_hip_cu_info *ref_cu, uint8_t *rec, kvz_hip_cu_info *cu, int16_t *coeff, int width,
                                      int height, int n_pictures, const kvz_hip_inter_params *p, const int32_t *tile_xy, int n_references)
 {
+  return kvz_hip_dev_inter_ctu_pass_pictures(src, ref, ref_cu, rec, cu, coeff, width, height, n_pictures, p, tile_xy, n_references, nullptr);
+}
+// pictures == nullptr: p->qp / p->poc for every picture (kvz_hip_dev_inter_ctu_pass[_tiles])
+int kvz_hip_dev_inter_ctu_pass_pictures(const uint8_t *src, const uint8_t *ref, const kvz_hip_cu_info *ref_cu, uint8_t *rec, kvz_hip_cu_info *cu, int16_t *coeff, int width,
+                                        int height, int n_pictures, const kvz_hip_inter_params *p, const int32_t *tile_xy, int n_references,
+                                        const kvz_hip_inter_pictures *pictures)
+{
   if (n_pictures <= 0) return 0;
   if (!p || p->struct_size != sizeof(kvz_hip_inter_params)) {
     fprintf(stderr, "kvz_hip_dev_inter_ctu_pass: kvz_hip_inter_params.struct_size %u is not this library's %zu (zero the struct, set struct_size = sizeof, build against the library's headers)\n", p ? p->struct_size : 0u, sizeof(kvz_hip_inter_params));
@@ -1407,8 +1464,9 @@ int kvz_hip_dev_inter_ctu_pass_tiles(const uint8_t *src, const uint8_t *ref, con
   }
   const int refused = kvz::inter_pass_geometry_refused(width, height, n_pictures, p->ref_width, p->ref_height, p->tile_x, p->tile_y);
   if (refused == 1) { fprintf(stderr, "kvz_hip_dev_inter_ctu_pass: bad geometry\n"); return -1; }
-  if (p->qp < 0 || p->qp > 51) { fprintf(stderr, "kvz_hip_dev_inter_ctu_pass: picture QP %d outside 0..51\n", p->qp); return -1; }
-  if (p->fme_level < 0 || p->fme_level > 4 || p->pu_depth_inter_max < 1 || p->pu_depth_inter_max > 3 || p->poc < 1 || p->fast_residual_cost < 0 || p->fast_residual_cost > 51) { fprintf(stderr, "kvz_hip_dev_inter_ctu_pass: unsupported parameters\n"); return -1; }
+  if (pictures && !kvz::inter_pictures_known(pictures, n_pictures, "kvz_hip_dev_inter_ctu_pass_pictures")) return -1;
+  if (!pictures && (p->qp < 0 || p->qp > 51)) { fprintf(stderr, "kvz_hip_dev_inter_ctu_pass: picture QP %d outside 0..51\n", p->qp); return -1; }
+  if (p->fme_level < 0 || p->fme_level > 4 || p->pu_depth_inter_max < 1 || p->pu_depth_inter_max > 3 || (!pictures && p->poc < 1) || p->fast_residual_cost < 0 || p->fast_residual_cost > 51) { fprintf(stderr, "kvz_hip_dev_inter_ctu_pass: unsupported parameters\n"); return -1; }
   if (refused) {  // the pictures are tiles of a ref_width x ref_height frame
     fprintf(stderr, "kvz_hip_dev_inter_ctu_pass: the %dx%d tile at (%d, %d) does not lie in the %dx%d reference frame, or that frame is beyond what the pass addresses\n", width, height, p->tile_x, p->tile_y, p->ref_width, p->ref_height);
     return -1;
@@ -1422,7 +1480,16 @@ int kvz_hip_dev_inter_ctu_pass_tiles(const uint8_t *src, const uint8_t *ref, con
   KVZ_HIP_CHECK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev_id));
   const char *env = getenv("KVZ_HIP_INTER_WG_PER_CU");
   // the kernel's build: with the residual coder's contexts in the LDS context sets only where the picture's coefficients are priced with them (kvz_inter_ctu.hpp)
-  const bool cabac_build = !(p->qp < p->fast_residual_cost && p->qp < 50);
+  // (pictures with QPs of their own: when any of them is; the others run that build with coeff_cabac == 0)
+  float fbits[128];
+  for (int i = 0; i < 128; i++) fbits[i] = (float)kvz::kEntropyBits[i] / 32768.0f;
+  auto model_at_qp = [&](kvz::InterModel *row, int qp) {
+    kvz::inter_model_init(row, qp, p->poc, kvz_hip_default_coeff_weights(qp) /* 0 from QP 50 on, where kvz_fast_coeff_cost is never used (rdo.c:311-340) */, fbits, p->mv_constraint, p->sao, p->deblock, p->fme_level, p->pu_depth_inter_max, p->no_wpp, p->fast_residual_cost,
+                          width, height, p->ref_width, p->ref_height, p->tile_x, p->tile_y, p->no_tmvp);
+  };
+  kvz::InterPictureTable table;
+  if (pictures) table = kvz::inter_picture_table(pictures->qp, pictures->poc, n_pictures, model_at_qp);
+  const bool cabac_build = pictures ? table.any_cabac : kvz::inter_qp_prices_with_cabac(p->qp, p->fast_residual_cost);
   const void *kernel = cabac_build ? (const void *)kvz::inter_ctu_ticket_kernel_cabac : (const void *)kvz::inter_ctu_ticket_kernel_fast;
   // resident workgroups (= wavefronts) per CU: what the kernel's registers and LDS allow -- a persistent grid, one workgroup per slot
   int fit = 0;
@@ -1447,32 +1514,33 @@ int kvz_hip_dev_inter_ctu_pass_tiles(const uint8_t *src, const uint8_t *ref, con
     KVZ_HIP_CHECK(hipMalloc((void **)&sc.items, (size_t)total * sizeof(uint32_t)));
     sc.n_ctus = total;
   }
-  if (!sc.ticket) { KVZ_HIP_CHECK(hipMalloc((void **)&sc.ticket, 2 * sizeof(unsigned))); KVZ_HIP_CHECK(hipMalloc((void **)&sc.model, sizeof(kvz::InterModel))); }
-  // the ticket list: anti-diagonals x + 2 y ascending (raster order per picture without WPP), pictures interleaved
-  std::vector<uint32_t> items;
-  items.reserve((size_t)total);
-  if (p->no_wpp) {
-    for (int y = 0; y < hc; y++) for (int x = 0; x < wc; x++) for (int f = 0; f < n_pictures; f++) items.push_back((uint32_t)f << 16 | (uint32_t)y << 8 | (uint32_t)x);
-  } else {
-    for (int d = 0; d <= (wc - 1) + 2 * (hc - 1); d++)
-      for (int y = 0; y < hc; y++) { const int x = d - 2 * y; if (x < 0 || x >= wc) continue; for (int f = 0; f < n_pictures; f++) items.push_back((uint32_t)f << 16 | (uint32_t)y << 8 | (uint32_t)x); }
-  }
+  if (!sc.ticket) KVZ_HIP_CHECK(hipMalloc((void **)&sc.ticket, 2 * sizeof(unsigned)));
+  // the model of the launch, or the table of a launch whose pictures have their own (records, then a row per distinct QP: kvz_inter_host.hpp inter_picture_table)
   kvz::InterModel m;
-  float fbits[128];
-  for (int i = 0; i < 128; i++) fbits[i] = (float)kvz::kEntropyBits[i] / 32768.0f;
-  kvz::inter_model_init(&m, p->qp, p->poc, kvz_hip_default_coeff_weights(p->qp) /* 0 from QP 50 on, where kvz_fast_coeff_cost is never used (rdo.c:311-340) */, fbits, p->mv_constraint, p->sao, p->deblock, p->fme_level, p->pu_depth_inter_max, p->no_wpp, p->fast_residual_cost,
-                        width, height, p->ref_width, p->ref_height, p->tile_x, p->tile_y, p->no_tmvp);
+  if (!pictures) model_at_qp(&m, p->qp);
+  const void *model_image = pictures ? (const void *)table.image.data() : (const void *)&m;
+  const size_t model_bytes = pictures ? table.bytes() : sizeof m;
+  if (model_bytes > sc.model_bytes) {
+    if (sc.model) KVZ_HIP_CHECK(hipFree(sc.model));
+    KVZ_HIP_CHECK(hipMalloc((void **)&sc.model, model_bytes));
+    sc.model_bytes = model_bytes;
+  }
+  std::vector<uint32_t> items;
+  kvz::inter_ticket_items(wc, hc, n_pictures, p->no_wpp, items);
   KVZ_HIP_CHECK(hipMemcpyAsync(sc.items, items.data(), (size_t)total * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-  KVZ_HIP_CHECK(hipMemcpyAsync(sc.model, &m, sizeof m, hipMemcpyHostToDevice, st));
+  KVZ_HIP_CHECK(hipMemcpyAsync(sc.model, model_image, model_bytes, hipMemcpyHostToDevice, st));
   KVZ_HIP_CHECK(hipMemsetAsync(sc.done, 0, (size_t)total * sizeof(unsigned), st));
   KVZ_HIP_CHECK(hipMemsetAsync(sc.ticket, 0, 2 * sizeof(unsigned), st));
-  KVZ_HIP_CHECK(hipStreamSynchronize(st));  // `items` and `m` are stack / heap objects of this call
+  KVZ_HIP_CHECK(hipStreamSynchronize(st));  // `items`, `m` and `table` are stack / heap objects of this call
   kvz::InterFrames F;
   F.W = width; F.H = height; F.wc = wc; F.hc = hc; F.frame_px = (long)width * height * 3 / 2; F.cells = (long)(width / 4) * (height / 4);
   F.src = src; F.ref = ref; F.ref_cu = ref_cu; F.rec = rec; F.cu = cu; F.coeff = coeff; F.ctx_out = sc.ctx; F.slabs = sc.slabs;
   F.prof = nullptr;
   F.tile_xy = (p->ref_width || p->ref_height) ? tile_xy : nullptr;
   F.ref_count = n_references > 0 ? n_references : 0;
+  F.pictures = pictures ? (const kvz::InterPicture *)sc.model : nullptr;
+  // the kernel's model argument: what every workgroup loads once per launch -- with a table, picture 0's row (begin_ctu replaces what depends on the picture)
+  const kvz::InterModel *d_model = pictures ? table.model_of_picture(sc.model, 0) : (const kvz::InterModel *)sc.model;
 #ifdef KVZ_ICTU_PROFILE
   static unsigned long long *d_prof = nullptr;
   if (!d_prof) KVZ_HIP_CHECK(hipMalloc((void **)&d_prof, kvz::IP_COUNT * sizeof(unsigned long long)));
@@ -1485,8 +1553,8 @@ int kvz_hip_dev_inter_ctu_pass_tiles(const uint8_t *src, const uint8_t *ref, con
   kvz::DevTimer &tm = kvz::inter_timer();
   if (!tm.e0) { KVZ_HIP_CHECK(hipEventCreate(&tm.e0)); KVZ_HIP_CHECK(hipEventCreate(&tm.e1)); }
   KVZ_HIP_CHECK(hipEventRecord(tm.e0, st));
-  if (cabac_build) hipLaunchKernelGGL(kvz::inter_ctu_ticket_kernel_cabac, dim3((unsigned)n_wg), dim3(KVZ_ICTU_THREADS), 0, st, F, sc.model, kvz::device_tables(), sched);
-  else hipLaunchKernelGGL(kvz::inter_ctu_ticket_kernel_fast, dim3((unsigned)n_wg), dim3(KVZ_ICTU_THREADS), 0, st, F, sc.model, kvz::device_tables(), sched);
+  if (cabac_build) hipLaunchKernelGGL(kvz::inter_ctu_ticket_kernel_cabac, dim3((unsigned)n_wg), dim3(KVZ_ICTU_THREADS), 0, st, F, d_model, kvz::device_tables(), sched);
+  else hipLaunchKernelGGL(kvz::inter_ctu_ticket_kernel_fast, dim3((unsigned)n_wg), dim3(KVZ_ICTU_THREADS), 0, st, F, d_model, kvz::device_tables(), sched);
   KVZ_HIP_CHECK(hipGetLastError());
   KVZ_HIP_CHECK(hipEventRecord(tm.e1, st));
   unsigned flags[2] = { 0, 0 };
@@ -1938,20 +2006,50 @@ long kvz_hip_batch_entropy_code_then_models(kvz_hip_batch *b, const kvz_hip_pict
 long kvz_hip_dev_entropy_code_inter(const kvz_hip_cu_info *cu, const kvz_hip_cu_info *ref_cu, const int16_t *coeff, int width, int height, int n_pictures,
                                     const kvz_hip_inter_params *params, uint8_t *out, size_t capacity, uint32_t *substream_bytes)
 {
+  return kvz_hip_dev_entropy_code_inter_pictures(cu, ref_cu, coeff, width, height, n_pictures, params, out, capacity, substream_bytes, nullptr);
+}
+// pictures == nullptr: params->qp / params->poc for every picture (kvz_hip_dev_entropy_code_inter)
+long kvz_hip_dev_entropy_code_inter_pictures(const kvz_hip_cu_info *cu, const kvz_hip_cu_info *ref_cu, const int16_t *coeff, int width, int height, int n_pictures,
+                                             const kvz_hip_inter_params *params, uint8_t *out, size_t capacity, uint32_t *substream_bytes,
+                                             const kvz_hip_inter_pictures *pictures)
+{
   if (n_pictures <= 0) return 0;
   if (params && params->struct_size != sizeof(kvz_hip_inter_params)) { fprintf(stderr, "kvz_hip_dev_entropy_code_inter: kvz_hip_inter_params.struct_size %u is not this library's %zu\n", params->struct_size, sizeof(kvz_hip_inter_params)); return -1; }
-  if (!cu || !ref_cu || !coeff || !params || width <= 0 || height <= 0 || (width & 7) || (height & 7) || params->qp < 0 || params->qp > 51 || params->poc < 1) {
+  if (!cu || !ref_cu || !coeff || !params || width <= 0 || height <= 0 || (width & 7) || (height & 7) || (!pictures && (params->qp < 0 || params->qp > 51 || params->poc < 1))) {
     fprintf(stderr, "kvz_hip_dev_entropy_code_inter: bad argument\n");
     return -1;
   }
+  if (pictures && !kvz::inter_pictures_known(pictures, n_pictures, "kvz_hip_dev_entropy_code_inter_pictures")) return -1;
   const int wc = (width + 63) >> 6, hc = (height + 63) >> 6, ctus = wc * hc;
   const long cells4 = (long)(height >> 2) * (width >> 2);
   kvz::LoopScratch &ls = kvz::loop_scratch();
   if (params->sao && (!ls.recs || ls.lcus < (size_t)ctus * n_pictures)) { fprintf(stderr, "kvz_hip_dev_entropy_code_inter: kvz_hip_dev_loop_filters_inter(..., sao = 1) has not run on these pictures\n"); return -1; }
   uint8_t init[KVZ_ENTROPY_CTXS];
-  kvz::entropy_b_slice_contexts(params->qp, init);
+  if (!pictures) kvz::entropy_b_slice_contexts(params->qp, init);
   int device = 0;
   KVZ_HIP_CHECK(hipGetDevice(&device));
+  // pictures with a QP and a POC of their own: a row of B-slice context states per distinct QP | every picture's POC (0: no temporal predictors) | every picture's row
+  const uint8_t *d_rows = nullptr; const int32_t *d_poc = nullptr; const uint16_t *d_row_of = nullptr;
+  if (pictures) {
+    int row_of_qp[52], qp_of_row[52];
+    const int n_rows = kvz::inter_qp_rows(pictures->qp, n_pictures, row_of_qp, qp_of_row);
+    const size_t at_poc = (size_t)n_rows * KVZ_ENTROPY_CTX_ROW, at_row = at_poc + (size_t)n_pictures * sizeof(int32_t), bytes = at_row + (size_t)n_pictures * sizeof(uint16_t);
+    static_assert(KVZ_ENTROPY_CTX_ROW % 4 == 0 && KVZ_ENTROPY_CTX_ROW >= KVZ_ENTROPY_CTXS, "the POCs behind the rows are 4-byte aligned");
+    std::vector<uint8_t> image(bytes, 0);
+    for (int r = 0; r < n_rows; r++) kvz::entropy_b_slice_contexts(qp_of_row[r], &image[(size_t)r * KVZ_ENTROPY_CTX_ROW]);
+    for (int i = 0; i < n_pictures; i++) {
+      ((int32_t *)&image[at_poc])[i] = params->no_tmvp ? 0 : pictures->poc[i];
+      ((uint16_t *)&image[at_row])[i] = (uint16_t)row_of_qp[pictures->qp[i]];
+    }
+    kvz::InterScratch &isc = kvz::inter_scratch();
+    if (bytes > isc.entropy_table_bytes) {
+      if (isc.entropy_table) KVZ_HIP_CHECK(hipFree(isc.entropy_table));
+      KVZ_HIP_CHECK(hipMalloc((void **)&isc.entropy_table, bytes));
+      isc.entropy_table_bytes = bytes;
+    }
+    KVZ_HIP_CHECK(hipMemcpy(isc.entropy_table, image.data(), bytes, hipMemcpyHostToDevice));
+    d_rows = isc.entropy_table; d_poc = (const int32_t *)(isc.entropy_table + at_poc); d_row_of = (const uint16_t *)(isc.entropy_table + at_row);
+  }
   auto job = [&](int f0, int nf) {
     kvz::EntropyJob J;
     memset(&J, 0, sizeof J);
@@ -1959,7 +2057,8 @@ long kvz_hip_dev_entropy_code_inter(const kvz_hip_cu_info *cu, const kvz_hip_cu_
     J.cu = cu + f0 * cells4; J.ref_cu = ref_cu + f0 * cells4; J.poc = params->no_tmvp ? 0 : params->poc;  // (the coder only asks the POC whether temporal predictors exist)
     J.coeff = coeff + (size_t)f0 * ctus * KVZ_HIP_CTU_COEFFS;
     J.sao = params->sao ? ls.recs + (size_t)f0 * ctus * 3 : nullptr; J.sao_merge = params->sao ? ls.merge + (size_t)f0 * ctus : nullptr;
-    memcpy(J.ctx_init, init, sizeof init);
+    if (pictures) { J.ctx_rows = d_rows; J.model_of_picture = d_row_of + f0; J.poc_of_picture = d_poc + f0; }
+    else memcpy(J.ctx_init, init, sizeof init);
     return J;
   };
   return kvz::entropy_code_pictures(be().stream, device, n_pictures, wc, hc, params->no_wpp, nullptr, job, out, capacity, substream_bytes);

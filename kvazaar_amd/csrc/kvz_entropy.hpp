@@ -55,10 +55,13 @@ struct EntropyJob {
   // zeros behind it) and model_of_picture the row of every picture of the job; ctx_init above is then unused
   const u8 *ctx_rows;
   const uint16_t *model_of_picture;
+  const int32_t *poc_of_picture;  // B pictures with a POC of their own (kvz_hip_dev_entropy_code_inter_pictures): [frames], 0 where temporal predictors are off; `poc` is then unused
 };
 #define KVZ_ENTROPY_CTX_ROW 176
 // the initial context states of picture f of the job
 KVZ_HD const u8 *entropy_ctx_init(const EntropyJob &J, int f) { return J.ctx_rows ? J.ctx_rows + (long)picture_model(J.model_of_picture, f) * KVZ_ENTROPY_CTX_ROW : J.ctx_init; }
+// the POC of picture f of the job, as far as the coder asks (do temporal MV predictors exist?)
+KVZ_HD int entropy_picture_poc(const EntropyJob &J, int f) { return J.poc_of_picture ? (int)J.poc_of_picture[f] : J.poc; }
 #define KVZ_EB_CTX(ctx, v) ((u32)(ctx) | ((u32)(v) << 8))
 #define KVZ_EB_EP(value, n) (0x40000000u | ((u32)(n) << 16) | ((u32)(value) & 0xffffu))
 #define KVZ_EB_TRM(v) (0x80000000u | ((u32)(v) << 8) | 168u)  /* the value where a context-coded bin has it, on the coder's pseudo-context (KVZ_ENTROPY_CTX_NEUTRAL) */
@@ -304,6 +307,7 @@ struct EntropyCtuB {
   const kvz_hip_cu_info *cu, *ref_cu;  // the picture's, the reference picture's
   const i16 *ctu;
   int w4, cx, cy;
+  int poc;  // the picture's (entropy_picture_poc)
   KVZ_DEV const kvz_hip_cu_info &at(int x, int y) const { return cu[(y >> 2) * w4 + (x >> 2)]; }
   KVZ_DEV static bool a0_coded(int x, int y, int width, int height)  // inter.c:686-741 is_a0_cand_coded
   {
@@ -356,7 +360,7 @@ struct EntropyCtuB {
       if (b1.type == 2) { b[1] = b1; vb[1] = true; }
       if (x != 0) { const kvz_hip_cu_info &b2 = at(x - 1, y - 1); if (b2.type == 2) { b[2] = b2; vb[2] = true; } }
     }
-    if (J.poc >= 1) {  // inter.c:1204-1260: H (below right, not across the CTU row) before C3 (centre), at 16-sample granularity in the reference picture
+    if (poc >= 1) {  // inter.c:1204-1260: H (below right, not across the CTU row) before C3 (centre), at 16-sample granularity in the reference picture
       const int xbr = x + w, ybr = y + h, xc = x + w / 2, yc = y + h / 2;
       bool vh = false;
       if (xbr < J.W && ybr < J.H && ybr % 64 != 0) { const kvz_hip_cu_info &c = ref_cu[(((ybr >> 4) << 4) >> 2) * w4 + (((xbr >> 4) << 4) >> 2)]; if (c.type == 2) { col = c; vh = true; } }
@@ -371,7 +375,7 @@ struct EntropyCtuB {
     if (va[0] || va[1]) nb_b = 1; else if (n != 2) nb_b = 0;
     if (!nb_b) for (int i = 0; i < 3; i++) if (add_mvp(b[i], vb[i], reflist, mv_cand[n < 2 ? n : 1])) { n++; break; }
     if (n == 2 && mv_cand[0][0] == mv_cand[1][0] && mv_cand[0][1] == mv_cand[1][1]) n = 1;
-    if (J.poc > 1 && n < 2 && vcol) {
+    if (poc > 1 && n < 2 && vcol) {
       int col_list = reflist;
       if ((col.mv_dir & (col_list + 1)) == 0) col_list = 1 - col_list;
       mv_cand[n][0] = col_list ? col.mv[1][0] : col.mv[0][0]; mv_cand[n][1] = col_list ? col.mv[1][1] : col.mv[0][1];
@@ -524,7 +528,7 @@ KVZ_DEV void entropy_ctu_bins(const EntropyJob &J, const Tables *tb, long item)
     }
   }
   if (J.cu) {  // a B picture: the inter syntax from the CU records
-    const EntropyCtuB cb{ J, tb, J.cu + f * cells4, J.ref_cu + f * cells4, J.coeff + item * KVZ_HIP_CTU_COEFFS, J.W >> 2, lx * 64, ly * 64 };
+    const EntropyCtuB cb{ J, tb, J.cu + f * cells4, J.ref_cu + f * cells4, J.coeff + item * KVZ_HIP_CTU_COEFFS, J.W >> 2, lx * 64, ly * 64, entropy_picture_poc(J, f) };
     cb.coding_tree(s);
   } else {
     const EntropyCtu c{ J, tb, J.depth + f * cells8, J.mode + f * cells8, J.part ? J.part + f * cells8 : nullptr, J.mode4 ? J.mode4 + f * cells4 : nullptr,
@@ -575,7 +579,7 @@ KVZ_DEV void entropy_ctu_bins_phased(const EntropyJob &J, const Tables *tb, long
     }
   }
   const i16 *ctu = J.coeff + item * KVZ_HIP_CTU_COEFFS;
-  const EntropyCtuB cb{ J, tb, J.cu ? J.cu + f * cells4 : nullptr, J.cu ? J.ref_cu + f * cells4 : nullptr, ctu, J.W >> 2, lx * 64, ly * 64 };
+  const EntropyCtuB cb{ J, tb, J.cu ? J.cu + f * cells4 : nullptr, J.cu ? J.ref_cu + f * cells4 : nullptr, ctu, J.W >> 2, lx * 64, ly * 64, J.cu ? entropy_picture_poc(J, f) : 0 };
   const EntropyCtu ci{ J, tb, J.cu ? nullptr : J.depth + f * cells8, J.cu ? nullptr : J.mode + f * cells8, J.part ? J.part + f * cells8 : nullptr,
                        J.mode4 ? J.mode4 + f * cells4 : nullptr, ctu, J.W >> 3, J.W >> 2 };
   LaneStack stack{ stack_mem, stride };

@@ -170,6 +170,13 @@ struct InterModel {  // per picture
   float fbits[128];                 // kvz_f_entropy_bits
 };
 
+// Pictures with a QP and a POC of their own in one launch (kvz_hip_dev_inter_ctu_pass_pictures): the launch keeps one InterModel row per distinct QP and this record
+// per picture, in ONE device buffer -- [pictures] records, then the rows (kvz_inter_host.hpp inter_picture_table) -- so that the one pointer InterFrames holds finds both
+struct InterPicture {
+  uint32_t model_at;  // bytes from the first record to the picture's InterModel row
+  int32_t poc;
+};
+
 struct InterSlab {  // HBM scratch of one resident workgroup: the quantised levels of the candidates of depth 1 and 2 (Y | U | V, raster inside each plane's block), written
                     // when the CU is quantised and copied to the output block if it wins; `out` stands in for the output block when the caller wants no coefficients
   i16 cand1[32 * 32 + 2 * 16 * 16];
@@ -190,6 +197,7 @@ struct InterFrames {
   InterSlab *slabs;      // one per resident workgroup
   const int *tile_xy;    // NULL, or [n][2]: every picture's own origin in its reference frame (tiles of one size from different places of the grid in one launch)
   int ref_count;         // 0, or the number of reference frames: picture p predicts from frame p % ref_count (several tiles of one frame in the launch)
+  const InterPicture *pictures;  // NULL (the kernel's model argument for every picture), or [n]: every picture's own model row and POC
   unsigned long long *prof;  // [IP_COUNT] or NULL (KVZ_ICTU_PROFILE)
 };
 
@@ -546,9 +554,29 @@ struct InterCtu {
     IC_SYNC();
     load_constants(model, tb);
   }
+  // the model of picture frame_ of a launch whose pictures have their own (F.pictures)
+  IC_DEV const KVZ_GLB InterModel *picture_model_row(int frame_, int *poc)
+  {
+    const KVZ_GLB InterPicture *rec = (const KVZ_GLB InterPicture *)F.pictures + frame_;
+    *poc = rec->poc;
+    return (const KVZ_GLB InterModel *)((const KVZ_GLB uint8_t *)F.pictures + rec->model_at);
+  }
   IC_DEV void begin_ctu(int frame_, int cx_, int cy_)
   {
-    IC_FOR(tid) { if (tid == 0) { frame = frame_; cx = cx_; cy = cy_; g_ic.ref_idx = F.ref_count ? frame_ % F.ref_count : frame_; g_ic.cu_frame = (const CuInfo *)F.cu + (long)frame_ * F.cells;
+    IC_FOR(tid) { if (tid == 0) { frame = frame_; cx = cx_; cy = cy_;
+      if (F.pictures) {
+        // a persistent workgroup moves between pictures: what load_constants took from the launch's one model and depends on the picture's QP or POC is the drawn
+        // picture's from here on, and so is the model the coders' initial context states are read from (run: g_ic.model->ctx_init)
+        int poc_;
+        const KVZ_GLB InterModel *pm = picture_model_row(frame_, &poc_);
+        g_ic.model = (const InterModel *)pm;
+        K->lambda = pm->lambda; K->lambda_sqrt = pm->lambda_sqrt; K->coeff_weights = pm->coeff_weights; K->qp = pm->qp; K->poc = poc_; K->coeff_cabac = pm->coeff_cabac;
+        for (int i = 0; i < 8; i++) {
+          const KVZ_GLB QuantScalars *f = &pm->qf[i >> 2][i & 3], *iv = &pm->qi[i >> 2][i & 3];
+          K->q[i >> 2][i & 3] = QScal{ f->flat_q, f->add, f->q_bits, iv->dq_scale, iv->dq_shift };
+        }
+      }
+      g_ic.ref_idx = F.ref_count ? frame_ % F.ref_count : frame_; g_ic.cu_frame = (const CuInfo *)F.cu + (long)frame_ * F.cells;
       g_ic.ref_base = (const uint8_t *)F.ref + g_ic.ref_idx * ((long)K->ref_w * K->ref_h * 3 / 2); g_ic.ref_cu_base = F.ref_cu + g_ic.ref_idx * ((long)(K->ref_w >> 2) * (K->ref_h >> 2)); g_ic.src_base = (const uint8_t *)F.src + frame_ * F.frame_px; g_ic.rec_base = (uint8_t *)F.rec + frame_ * F.frame_px;
       g_ic.coef_out = F.coeff ? (int16_t *)F.coeff + ((long)frame_ * F.wc * F.hc + (cy_ >> 6) * F.wc + (cx_ >> 6)) * 6144 : (int16_t *)S->out;
       if (F.tile_xy) {

@@ -3,8 +3,10 @@
 #pragma once
 #include <math.h>
 #include <string.h>
+#include <vector>
 
 #include "kvz_inter_ctu.hpp"
+#include "kvz_inter_pictures.hpp"
 #include "kvz_tables.hpp"
 
 namespace kvz {
@@ -67,7 +69,7 @@ inline void inter_model_init(InterModel *m, int qp, int poc, uint64_t coeff_weig
   m->lambda = 0.57 * pow(2.0, (qp - 12) / 3.0);  // rate_control.c:678-691
   m->lambda_sqrt = sqrt(m->lambda);
   m->coeff_weights = coeff_weights;
-  m->coeff_cabac = !(qp < fast_residual_cost && qp < 50);  // rdo.c:311-340: cfg.fast_residual_cost_limit (28 `ultrafast` .. `veryfast`, 0 `faster`), MAX_FAST_COEFF_COST_QP
+  m->coeff_cabac = inter_qp_prices_with_cabac(qp, fast_residual_cost);  // rdo.c:311-340: cfg.fast_residual_cost_limit (28 `ultrafast` .. `veryfast`, 0 `faster`), MAX_FAST_COEFF_COST_QP
   m->ref_w = ref_w > 0 ? ref_w : pic_w; m->ref_h = ref_h > 0 ? ref_h : pic_h; m->tile_x = ref_w > 0 ? tile_x : 0; m->tile_y = ref_h > 0 ? tile_y : 0;
   m->no_tmvp = no_tmvp;
   m->mv_constraint = mv_constraint; m->sao = sao; m->deblock = deblock; m->fme_level = fme_level; m->pu_depth_inter_max = pu_depth_inter_max; m->no_wpp = no_wpp;
@@ -88,6 +90,49 @@ inline void inter_model_init(InterModel *m, int qp, int poc, uint64_t coeff_weig
       m->qi[c][l2 - 2] = quant_scalars(qp, 8, 0, 0, 1 << l2, c ? 2 : 0);
     }
   memcpy(m->fbits, fbits, sizeof m->fbits);
+}
+
+// The ticket list of a launch (kvz_inter_kernels.hpp InterSched::items, picture << 16 | y << 8 | x): anti-diagonals x + 2 y ascending (raster order per picture
+// without WPP), pictures interleaved -- consecutive tickets belong to different pictures
+inline void inter_ticket_items(int wc, int hc, int n_pictures, int no_wpp, std::vector<uint32_t> &items)
+{
+  items.clear();
+  items.reserve((size_t)wc * hc * n_pictures);
+  if (no_wpp) {
+    for (int y = 0; y < hc; y++) for (int x = 0; x < wc; x++) for (int f = 0; f < n_pictures; f++) items.push_back((uint32_t)f << 16 | (uint32_t)y << 8 | (uint32_t)x);
+  } else {
+    for (int d = 0; d <= (wc - 1) + 2 * (hc - 1); d++)
+      for (int y = 0; y < hc; y++) { const int x = d - 2 * y; if (x < 0 || x >= wc) continue; for (int f = 0; f < n_pictures; f++) items.push_back((uint32_t)f << 16 | (uint32_t)y << 8 | (uint32_t)x); }
+  }
+}
+
+// The table of a launch whose pictures have a QP and a POC of their own, as the device holds it (InterFrames::pictures): n InterPicture records, then one InterModel
+// row per distinct QP.  init_row(m, qp): the launch's model at that QP (inter_model_init with the launch's parameters).  The caller copies `image` to the device as
+// it is: the records address their rows relative to the image's first byte.
+struct InterPictureTable {
+  std::vector<uint64_t> image;
+  int n_rows = 0;
+  bool any_cabac = false;  // some picture prices coefficients with the residual coder: the launch takes the kernel build that holds its contexts
+  size_t bytes() const { return image.size() * sizeof(uint64_t); }
+  // the row of a picture in a copy of the image that starts at `base` (the device's, or the image itself)
+  const InterModel *model_of_picture(const void *base, int picture) const { return (const InterModel *)((const uint8_t *)base + ((const InterPicture *)image.data())[picture].model_at); }
+};
+template <class InitRow> inline InterPictureTable inter_picture_table(const int32_t *qp, const int32_t *poc, int n_pictures, const InitRow &init_row)
+{
+  static_assert(sizeof(InterPicture) == 8 && alignof(InterModel) <= 8 && sizeof(InterModel) % 8 == 0, "records and rows share a buffer of 8-byte words");
+  InterPictureTable t;
+  int row_of_qp[52], qp_of_row[52];
+  t.n_rows = inter_qp_rows(qp, n_pictures, row_of_qp, qp_of_row);
+  const size_t rows_at = (size_t)n_pictures * sizeof(InterPicture);
+  t.image.assign((rows_at + (size_t)t.n_rows * sizeof(InterModel)) / sizeof(uint64_t), 0);
+  uint8_t *base = (uint8_t *)t.image.data();
+  for (int r = 0; r < t.n_rows; r++) {
+    InterModel *m = (InterModel *)(base + rows_at) + r;
+    init_row(m, qp_of_row[r]);
+    t.any_cabac = t.any_cabac || m->coeff_cabac;
+  }
+  for (int i = 0; i < n_pictures; i++) ((InterPicture *)base)[i] = InterPicture{ (uint32_t)(rows_at + (size_t)row_of_qp[qp[i]] * sizeof(InterModel)), poc[i] };
+  return t;
 }
 
 }  // namespace kvz

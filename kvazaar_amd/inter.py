@@ -22,6 +22,28 @@ class InterParams(C.Structure):  # kvz_hip_inter_params
             self.struct_size = C.sizeof(InterParams)  # the version of the struct this binding was written against (include/kvz_hip_dev.h)
 
 
+class InterPicturesStruct(C.Structure):  # kvz_hip_inter_pictures
+    _fields_ = [("struct_size", C.c_uint32), ("n_pictures", C.c_int32), ("qp", C.c_void_p), ("poc", C.c_void_p)]
+
+
+class InterPictureParams:
+    """a QP and a POC per picture of one launch (kvz_hip_inter_pictures): the `pictures=` of InterPictures.run / .loop_filters / .entropy_code.  Everything else --
+    preset, switches, geometry -- stays the launch's InterParams, whose qp and poc are then ignored"""
+
+    def __init__(self, qps, pocs):
+        self.qps, self.pocs = np.ascontiguousarray(qps, np.int32).reshape(-1), np.ascontiguousarray(pocs, np.int32).reshape(-1)
+        if self.qps.size != self.pocs.size:
+            raise ValueError(f"{self.qps.size} QPs for {self.pocs.size} POCs")
+        self.struct = InterPicturesStruct(struct_size=C.sizeof(InterPicturesStruct), n_pictures=self.qps.size, qp=self.qps.ctypes.data, poc=self.pocs.ctypes.data)  # (the arrays live as long as self)
+
+    def __len__(self):
+        return int(self.qps.size)
+
+    @property
+    def ptr(self):
+        return C.addressof(self.struct)
+
+
 def veryfast_params(qp, poc, mv_constraint=True):
     """`--preset veryfast` (cfg.c:541-568) for a B picture of the low-delay GOP"""
     p = InterParams(qp=qp, poc=poc, mv_constraint=int(mv_constraint), sao=1, deblock=1, fme_level=2, pu_depth_inter_max=3, no_wpp=0, fast_residual_cost=28)
@@ -98,6 +120,12 @@ class InterPictures:
         lib.kvz_hip_dev_cu_dbk_from_info.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         lib.kvz_hip_dev_loop_filters_inter.restype = C.c_int
         lib.kvz_hip_dev_loop_filters_inter.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p] * 3
+        lib.kvz_hip_dev_inter_ctu_pass_pictures.restype = C.c_int
+        lib.kvz_hip_dev_inter_ctu_pass_pictures.argtypes = [C.c_void_p] * 6 + [C.c_int] * 3 + [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        lib.kvz_hip_dev_loop_filters_inter_pictures.restype = C.c_int
+        lib.kvz_hip_dev_loop_filters_inter_pictures.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 3
+        lib.kvz_hip_dev_entropy_code_inter_pictures.restype = C.c_long
+        lib.kvz_hip_dev_entropy_code_inter_pictures.argtypes = [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         self.d_dbk = None
         lib.kvz_hip_dev_entropy_code_inter.restype = C.c_long
         lib.kvz_hip_dev_entropy_code_inter.argtypes = [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
@@ -115,7 +143,14 @@ class InterPictures:
             assert a.nbytes == size
             up(base + i * size, a.ctypes.data, size)
 
-    def run(self, params):
+    def run(self, params, pictures=None):
+        """the CTU pass of the n pictures; pictures (InterPictureParams): every picture at its own QP and POC instead of params.qp / params.poc"""
+        if pictures is not None:
+            rc = self.lib.kvz_hip_dev_inter_ctu_pass_pictures(self.d_src, self.d_ref, self.d_ref_cu, self.d_rec, self.d_cu, self.d_coeff, self.w, self.h, self.n, C.addressof(params), None, 0,
+                                                              pictures.ptr)
+            if rc != 0:
+                raise RuntimeError(f"kvz_hip_dev_inter_ctu_pass_pictures returned {rc}")
+            return
         rc = self.lib.kvz_hip_dev_inter_ctu_pass(self.d_src, self.d_ref, self.d_ref_cu, self.d_rec, self.d_cu, self.d_coeff, self.w, self.h, self.n, C.addressof(params))
         if rc != 0:
             raise RuntimeError(f"kvz_hip_dev_inter_ctu_pass returned {rc}")
@@ -135,18 +170,28 @@ class InterPictures:
         self._source_sets = getattr(self, "_source_sets", [self.d_src])
         self.d_src = self._source_sets[k]
 
-    def loop_filters(self, params, slice_is_b=True):
-        """deblocking and SAO of the pictures the pass just produced, in place (kvz_hip_dev_loop_filters_inter): d_rec becomes what the next picture predicts from"""
+    def loop_filters(self, params, slice_is_b=True, pictures=None):
+        """deblocking and SAO of the pictures the pass just produced, in place (kvz_hip_dev_loop_filters_inter): d_rec becomes what the next picture predicts from.
+        pictures (InterPictureParams): every picture at its own QP (kvz_hip_dev_loop_filters_inter_pictures)"""
         if self.d_dbk is None:
             self.d_dbk = self.dev.empty(self.n * self.cells * 20)  # kvz_hip_cu_dbk
         self.lib.kvz_hip_dev_cu_dbk_from_info(self.d_cu, self.n * self.cells, self.d_dbk)
+        if pictures is not None:
+            if len(pictures) != self.n:
+                raise ValueError(f"{len(pictures)} picture QPs for {self.n} pictures")
+            rc = self.lib.kvz_hip_dev_loop_filters_inter_pictures(self.d_src, self.d_rec, self.w, self.h, self.n, self.d_dbk, pictures.qps.ctypes.data, int(slice_is_b), params.deblock, 0, 0,
+                                                                  params.sao, params.no_wpp, None, None, None)
+            if rc != 0:
+                raise RuntimeError(f"kvz_hip_dev_loop_filters_inter_pictures returned {rc}")
+            return
         rc = self.lib.kvz_hip_dev_loop_filters_inter(self.d_src, self.d_rec, self.w, self.h, self.n, self.d_dbk, params.qp, int(slice_is_b), params.deblock, 0, 0, params.sao,
                                                      params.no_wpp, None, None, None)
         if rc != 0:
             raise RuntimeError(f"kvz_hip_dev_loop_filters_inter returned {rc}")
 
-    def entropy_code(self, params):
+    def entropy_code(self, params, pictures=None):
         """kvz_hip_dev_entropy_code_inter: the slice data of the pictures the pass just produced (after loop_filters when params.sao: their SAO decisions are coded).
+        pictures (InterPictureParams): every picture at its own QP and POC (kvz_hip_dev_entropy_code_inter_pictures).
         -> (bytes of all substreams back to back, sizes [sequence][substream])"""
         if self.d_coeff is None:
             raise RuntimeError("InterPictures(..., with_levels=True) keeps the levels the entropy coder needs")
@@ -157,8 +202,12 @@ class InterPictures:
             from .batch import pinned_bytes
             self._entropy_ptr, self._entropy_out = pinned_bytes(self.lib, capacity)  # pinned: the call downloads the slice data straight into it
         sizes = np.zeros((self.n, rows), np.uint32)
-        total = self.lib.kvz_hip_dev_entropy_code_inter(self.d_cu, self.d_ref_cu, self.d_coeff, self.w, self.h, self.n, C.addressof(params), self._entropy_out.ctypes.data,
-                                                        capacity, sizes.ctypes.data)
+        if pictures is not None:
+            total = self.lib.kvz_hip_dev_entropy_code_inter_pictures(self.d_cu, self.d_ref_cu, self.d_coeff, self.w, self.h, self.n, C.addressof(params), self._entropy_out.ctypes.data,
+                                                                     capacity, sizes.ctypes.data, pictures.ptr)
+        else:
+            total = self.lib.kvz_hip_dev_entropy_code_inter(self.d_cu, self.d_ref_cu, self.d_coeff, self.w, self.h, self.n, C.addressof(params), self._entropy_out.ctypes.data,
+                                                            capacity, sizes.ctypes.data)
         if total < 0:
             raise RuntimeError("kvz_hip_dev_entropy_code_inter failed")
         return self._entropy_out[:total], sizes
