@@ -128,7 +128,8 @@ typedef struct kvz_hip_intra_cost_model {
    * 32x32 CU first, then -- unless it has no coefficients (cu-split-termination zero, search.c:975-984) -- its four 16x16 children with early termination.
    * 0: --pu-depth-intra 2-3 (ultrafast ... faster): 32x32 CUs only arise by merging four 16x16 CUs under the top-left one's mode (search.c:996-1044). */
   int32_t  search_32x32;
-  /* != 0: every transform block is quantised by rate-distortion optimised quantisation (kvazaar's --rdoq with --rdoq-skip 0 and --signhide 0, preset `medium`;
+  /* != 0: every transform block is quantised by rate-distortion optimised quantisation (kvazaar's --rdoq with --rdoq-skip 0, preset `medium`; not together with
+   * signhide below: kvz_rdoq's own hiding step, rdo.c:971, is not on the device;
    * kvz_rdoq, rdo.c:661-1000, on the contexts of the row's real coder as they stand when the CTU's search begins: state->cabac) instead of kvz_quant.  Needs
    * coeff_cabac (the presets that switch RDOQ on have --fast-residual-cost 0) and search_32x32 is independent of it. */
   int32_t  rdoq;
@@ -138,12 +139,17 @@ typedef struct kvz_hip_intra_cost_model {
   int32_t  search_nxn;
   uint8_t  ctx_init[160];     /* uc_state at slice start (kvz_init_contexts, context.c:202-305) of the KVZ_HIP_CX_* contexts; the rest unused */
   float    entropy_fbits[128];/* kvz_f_entropy_bits (rdo.c:69-83) */
+  /* != 0: sign data hiding (kvazaar's --signhide, sign_data_hiding_enabled_flag of the PPS): after kvz_quant a coefficient group whose first and last levels lie at
+   * least four scan positions apart gets the parity of its level sum made equal to the sign bit of its first level, by the cheapest change of one level by one
+   * (quant-generic.c:84-176), and the residual syntax leaves that sign out (encode_coding_tree-generic.c:199, 240-247).  The pass, its coefficient prices and the
+   * entropy coder all follow the switch of the picture's model.  Not together with rdoq or search_nxn, and not under KVZ_HIP_SCHED=wave: such a launch returns -1. */
+  int32_t  signhide;
 } kvz_hip_intra_cost_model;
 
 /* The cost models of ONE batched launch whose pictures do not share a model (kvz_hip_batch.h, the kvz_hip_*_models entry points): pictures of streams that run at
  * different QPs in one batch.  Every picture stays an ordinary constant-QP picture under the model model_of_picture names -- what the single-model entry point
- * makes of it in a batch of its own, byte for byte.  The models of one table may differ in qp, lambda, lambda_sqrt, coeff_weights, ctx_init and (without rdoq)
- * coeff_cabac; they must agree in adaptive, no_wpp, search_32x32, rdoq, search_nxn and entropy_fbits, which select the kernel, the order of the CTUs and the one
+ * makes of it in a batch of its own, byte for byte.  The models of one table may differ in qp, lambda, lambda_sqrt, coeff_weights, ctx_init, signhide and (without
+ * rdoq) coeff_cabac; they must agree in adaptive, no_wpp, search_32x32, rdoq, search_nxn and entropy_fbits, which select the kernel, the order of the CTUs and the one
  * price table of the launch.  struct_size as in kvz_hip_intra_cost_model: sizeof of the caller's headers. */
 typedef struct kvz_hip_picture_models {
   uint32_t struct_size;

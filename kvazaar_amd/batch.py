@@ -14,7 +14,7 @@ class CostModel(C.Structure):
                 ("part_size", C.c_float * 2), ("intra_mode", C.c_float * 2), ("chroma_mode", C.c_float * 2),
                 ("cbf_luma", (C.c_float * 2) * 2), ("cbf_chroma", (C.c_float * 2) * 2), ("coeff_weights", C.c_uint64),
                 ("qp", C.c_int32), ("adaptive", C.c_int32), ("coeff_cabac", C.c_int32), ("no_wpp", C.c_int32), ("search_32x32", C.c_int32), ("rdoq", C.c_int32), ("search_nxn", C.c_int32), ("ctx_init", C.c_uint8 * 160),
-                ("entropy_fbits", C.c_float * 128)]
+                ("entropy_fbits", C.c_float * 128), ("signhide", C.c_int32)]
 
     def key(self):
         return bytes(self)
@@ -44,8 +44,9 @@ class PictureModelsStruct(C.Structure):
 class PictureModels:
     """A cost model per picture of a batch (kvz_hip_picture_models): pictures of streams at different QPs in one launch.  qps: the QP of every picture of the batch, in
     order; the table holds one model per distinct QP.  weights: fast-coefficient-cost weights for every QP (an int), per QP (a dict or a callable), or None for kvazaar's
-    built-in table.  switches: CostModel fields set on every model (adaptive, no_wpp, search_32x32, rdoq, search_nxn, coeff_cabac) -- the first five must be the same for
-    all models of a table, which this guarantees.  HipBatch.launch / run / loop_filters / entropy_code take it wherever they take a CostModel.  The object owns the ctypes
+    built-in table.  switches: CostModel fields set on every model (adaptive, no_wpp, search_32x32, rdoq, search_nxn, coeff_cabac, signhide) -- the first five must be the
+    same for all models of a table, which this guarantees.  signhide may also be a sequence with a value per picture (sign data hiding for some streams of the batch):
+    the table then holds a model per distinct (QP, signhide).  HipBatch.launch / run / loop_filters / entropy_code take it wherever they take a CostModel.  The object owns the ctypes
     arrays the struct points into: keep it alive while a call uses it."""
 
     def __init__(self, lib, qps, weights=None, **switches):
@@ -53,18 +54,24 @@ class PictureModels:
         if not qps:
             raise ValueError("PictureModels: no pictures")
         self.qps = qps
-        distinct = sorted(set(qps))
-        row = {q: i for i, q in enumerate(distinct)}
+        hide = switches.pop("signhide", 0)
+        hide = [int(bool(v)) for v in hide] if isinstance(hide, (list, tuple, np.ndarray)) else [int(bool(hide))] * len(qps)
+        if len(hide) != len(qps):
+            raise ValueError("PictureModels: signhide per picture needs a value for every picture")
+        self.signhide = hide
+        distinct = sorted(set(zip(qps, hide)))
+        row = {k: i for i, k in enumerate(distinct)}
         self.models = (CostModel * len(distinct))()
-        for i, q in enumerate(distinct):
+        for i, (q, sh) in enumerate(distinct):
             w = weights(q) if callable(weights) else (weights[q] if isinstance(weights, dict) else weights)
             m = cost_model(lib, q, w)
             for k, v in switches.items():
                 if k not in ("adaptive", "no_wpp", "search_32x32", "rdoq", "search_nxn", "coeff_cabac"):
                     raise TypeError(f"PictureModels: {k} is not a switch of the cost model")
                 setattr(m, k, int(v))
+            m.signhide = sh
             self.models[i] = m
-        self.index = (C.c_uint16 * len(qps))(*[row[q] for q in qps])
+        self.index = (C.c_uint16 * len(qps))(*[row[k] for k in zip(qps, hide)])
         self.struct = PictureModelsStruct(C.sizeof(PictureModelsStruct), len(distinct), self.models, self.index)
 
     def model_of(self, picture):

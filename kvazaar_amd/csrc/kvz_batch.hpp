@@ -200,6 +200,8 @@ inline ModelTableView picture_models_stage(kvz_hip_batch *b, const kvz_hip_pictu
     cm.ctx_init = d + at_ctx + i * ctx_bytes;
     memcpy(image.data() + at_rows + i * sizeof(CtuModel), &cm, sizeof cm);
     memcpy(image.data() + at_ctx + i * ctx_bytes, pm->models[i].ctx_init, sizeof pm->models[i].ctx_init);
+    static_assert(sizeof pm->models[i].ctx_init <= KVZ_ENTROPY_ROW_SIGNHIDE && KVZ_ENTROPY_CTXS <= KVZ_ENTROPY_ROW_SIGNHIDE, "the switch sits behind the states");
+    image[at_ctx + i * ctx_bytes + KVZ_ENTROPY_ROW_SIGNHIDE] = pm->models[i].signhide != 0;  // what the entropy coder reads of the model besides its states (entropy_signhide)
   }
   for (size_t f = 0; f < nf; f++) {
     const int32_t qp = pm->models[pm->model_of_picture[f]].qp;
@@ -453,8 +455,9 @@ void kvz_hip_batch_order_after(kvz_hip_batch *b, kvz_hip_batch *other)
 }
 
 // The pass of kvz_hip_intra_frames (!table: `model` for every picture) and of kvz_hip_intra_frames_models (table: picture_models_stage has put it on the device; `model` = its first: the switches and
-// the price table every model shares; any_cabac: some model prices coefficients with the CABAC model -- that instantiation then prices the others' through its run-time switch)
-static int kvz_intra_frames_queue(kvz_hip_batch *b, const kvz_hip_intra_cost_model *model, bool table, bool any_cabac)
+// the price table every model shares; any_cabac: some model prices coefficients with the CABAC model -- that instantiation then prices the others' through its run-time switch;
+// any_signhide: some model hides sign bits -- the launch takes a sign-hiding instantiation, which reads the switch of the drawn picture's model)
+static int kvz_intra_frames_queue(kvz_hip_batch *b, const kvz_hip_intra_cost_model *model, bool table, bool any_cabac, bool any_signhide)
 {
   kvz::batch_enter(b);
   const kvz::CtuFrames &F = b->F;
@@ -497,6 +500,9 @@ static int kvz_intra_frames_queue(kvz_hip_batch *b, const kvz_hip_intra_cost_mod
       kvz::CtuFrames Fr = F;
       Fr.cu_part = b->d_part; Fr.cu_mode4 = b->d_mode4;
       hipLaunchKernelGGL(kvz::intra_ctu_ticket_kernel_rdoq, dim3(b->grid_ticket), dim3(KVZ_CTU_THREADS), 0, b->stream, Fr, cm, kvz::device_tables(), sc);
+    } else if (any_signhide) {  // sign data hiding: its own instantiations, with the CABAC coefficient model inside (pictures priced by the fast estimate switch it off at run time, as in a mixed launch)
+      if (cm.search_32x32) hipLaunchKernelGGL(kvz::intra_ctu_ticket_kernel_signhide<true>, dim3(b->grid_ticket), dim3(KVZ_CTU_THREADS), 0, b->stream, F, cm, kvz::device_tables(), sc);
+      else hipLaunchKernelGGL(kvz::intra_ctu_ticket_kernel_signhide<false>, dim3(b->grid_ticket), dim3(KVZ_CTU_THREADS), 0, b->stream, F, cm, kvz::device_tables(), sc);
     } else if (cm.search_32x32) {
       if (cm.coeff_cabac) hipLaunchKernelGGL((kvz::intra_ctu_ticket_kernel<true, true>), dim3(b->grid_ticket), dim3(KVZ_CTU_THREADS), 0, b->stream, F, cm, kvz::device_tables(), sc);
       else hipLaunchKernelGGL((kvz::intra_ctu_ticket_kernel<false, true>), dim3(b->grid_ticket), dim3(KVZ_CTU_THREADS), 0, b->stream, F, cm, kvz::device_tables(), sc);
@@ -531,7 +537,8 @@ static int kvz_intra_frames_queue(kvz_hip_batch *b, const kvz_hip_intra_cost_mod
 int kvz_hip_intra_frames(kvz_hip_batch *b, const kvz_hip_intra_cost_model *model)
 {
   if (!b || !kvz::cost_model_known(model, "kvz_hip_intra_frames")) return -1;
-  return kvz_intra_frames_queue(b, model, false, model->coeff_cabac != 0);
+  if (!kvz::signhide_known(model, b->sched_ticket != 0, "kvz_hip_intra_frames")) return -1;
+  return kvz_intra_frames_queue(b, model, false, model->coeff_cabac != 0, model->signhide != 0);
 }
 
 int kvz_hip_intra_frames_models(kvz_hip_batch *b, const kvz_hip_picture_models *pm)
@@ -539,7 +546,7 @@ int kvz_hip_intra_frames_models(kvz_hip_batch *b, const kvz_hip_picture_models *
   if (!b || !kvz::picture_models_known(pm, b->n_frames, b->sched_ticket != 0, "kvz_hip_intra_frames_models")) return -1;
   kvz::batch_enter(b);
   kvz::picture_models_stage(b, pm);
-  return kvz_intra_frames_queue(b, &pm->models[0], true, kvz::picture_models_any_cabac(pm));
+  return kvz_intra_frames_queue(b, &pm->models[0], true, kvz::picture_models_any_cabac(pm), kvz::picture_models_any_signhide(pm));
 }
 
 int kvz_hip_batch_sync(kvz_hip_batch *b)

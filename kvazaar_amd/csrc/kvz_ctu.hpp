@@ -225,6 +225,7 @@ struct CtuModel {
   uint64_t coeff_weights;
   int qp;
   u8 adaptive, coeff_cabac, no_wpp, search_32x32, rdoq, search_nxn;  // switches (bytes: the struct lives in LDS next to a block that is sized to the last word)
+  u8 signhide;                 // sign data hiding (one of the two bytes the switches left of their word: the row keeps its size)
   const float *entropy_fbits;  // [128]
   const u8 *ctx_init;          // [KVZ_CX_COUNT]
 };
@@ -232,6 +233,7 @@ KVZ_HD void ctu_model_from(const kvz_hip_intra_cost_model *src, CtuModel *dst)
 {
   dst->lambda = src->lambda; dst->lambda_sqrt = src->lambda_sqrt; dst->coeff_weights = src->coeff_weights; dst->qp = src->qp; dst->adaptive = src->adaptive != 0;
   dst->coeff_cabac = src->coeff_cabac != 0; dst->no_wpp = src->no_wpp != 0; dst->search_32x32 = src->search_32x32 != 0; dst->rdoq = src->rdoq != 0; dst->search_nxn = src->search_nxn != 0;
+  dst->signhide = src->signhide != 0;
   dst->entropy_fbits = src->entropy_fbits;
   dst->ctx_init = src->ctx_init;
 }
@@ -379,7 +381,10 @@ struct RdoqLds {
 // RDOQ: the instantiation that quantises with kvz_rdoq (kvz_hip_intra_cost_model::rdoq, preset `medium`) and / or tries NxN partitions (search_nxn); the
 // others carry none of that code
 // S32: the instantiation that can also SEARCH 32x32 CUs (kvz_hip_intra_cost_model::search_32x32, --pu-depth-intra 1-3); the others carry none of its code
-template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
+// SH: the instantiation that can hide sign bits (kvz_hip_intra_cost_model::signhide, --signhide): a stage between kvz_quant and everything that reads levels
+// (hide_signs), for the pictures whose model has the switch; the others carry none of its code.  Not with RDOQ (kvz_picture_models.hpp signhide_known).
+template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false> struct CtuProgramT {
+  static_assert(!(SH && RDOQ), "kvz_rdoq's own sign hiding is not built");
   using CtxSet = CtxSetT<CABAC>;
   const CtuModel *m;
   const Tables *tb;
@@ -389,6 +394,7 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
   static constexpr bool NXN = RDOQ;
   KVZ_DEV bool nxn_on() const { return NXN && m->search_nxn; }
   KVZ_DEV bool cabac_on() const { return CABAC && m->coeff_cabac; }  // coefficients priced with the CABAC model (rdo.c:311-340)
+  KVZ_DEV bool hide_on() const { return SH && m->signhide; }         // the picture's levels go through sign data hiding (uniform: the model is the picture's)
   int frame, cx, cy;  // CTU origin (luma px)
   int a1x, a1y, a2x, a2y;  // CTU-local luma origin of the depth-1 / depth-2 CU whose candidates are live (uniform)
   // The thread that runs a CU's scalar bookkeeping inside the first phase of its reference build (cu_header, price_modes: a serial chain of LDS lookups and
@@ -647,8 +653,8 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
   // ---------------------------------------------------------------- residual coding in counting mode
   // kvz_encode_coeff_nxn (strategies/generic/encode_coding_tree-generic.c:40-283) as get_coeff_cabac_cost runs it (rdo.c:220-263):
   // the bits of one transform block's residual syntax priced on context set *c, whose states move only with `update` (the coder works
-  // on a copy of the search contexts, `update` flag included).  Sign data hiding, transform skip and encryption are off in this
-  // configuration.  coeff: log2w x log2w levels, row-major, in LDS; type 0 luma / 2 chroma; scan 0 diagonal, 1 horizontal, 2 vertical.
+  // on a copy of the search contexts, `update` flag included).  Transform skip and encryption are off in this configuration; with sign data
+  // hiding (hide_on()) a group whose first and last level lie four scan positions apart codes one sign fewer.  coeff: log2w x log2w levels, row-major, in LDS; type 0 luma / 2 chroma; scan 0 diagonal, 1 horizontal, 2 vertical.
   // The scans, context increments and the last position's layout are kvz_syntax.hpp's.
   // Tables::diag8 for scan_group(): RDOQ instantiations have it staged per CTU in LDS (run()) -- a load from global memory in front of every group of a 32x32 block otherwise
   KVZ_DEV const u8 *diag8() const
@@ -678,7 +684,7 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
     for (int i = 0; i < (1 << (2 * log2w)); i++) any |= coeff[i] != 0;
     if (!any) return 0;  // get_coeff_cabac_cost: no coefficient, no bits
     CoeffPriceSink sink{ this, c, update && m->adaptive, 0.0 };
-    entropy_coeff_nxn(sink, tb, coeff, log2w, type, scan);
+    entropy_coeff_nxn(sink, tb, coeff, log2w, type, scan, hide_on());
     return sink.bits;
   }
 #else
@@ -688,6 +694,9 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
     const int length = 31 - __builtin_clz((unsigned)imax(symbol - (2 << r_param), 1));
     return symbol < (3 << r_param) ? (symbol >> r_param) + 1 + r_param : 4 + 2 * length - r_param;
   }
+  // encode_coding_tree-generic.c:199: the group's first level (lowest scan position) has its sign hidden when the last one lies four positions or more behind it.
+  // nzmask: bit k = scan position k of the group holds a level, at least one set.
+  KVZ_DEV static bool sign_hidden(unsigned nzmask) { return (31 - __builtin_clz(nzmask)) - __builtin_ctz(nzmask) >= 4; }
   // Escape codes of one coded group, every level on its own lane (k = scan position = lane < 16, q = levels coded before it): the Rice
   // parameter only ever moves up, by one after an escape-coded level above 3 << parameter (encode_coding_tree.c:224-246), so the up to
   // four positions where it moves are the first level above 3, the first one above 6 after that, ... -- four ballots and a few scalar
@@ -825,6 +834,7 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
           if (lane == kk) acc += price((type == 0 ? KVZ_HIP_CX_ABS_LUMA : KVZ_HIP_CX_ABS_CHROMA) + ctx_set, absval > 2);
         }
         bypass += (unsigned long long)num;  // signs
+        if constexpr (SH) { if (hide_on() && sign_hidden(nzmask)) bypass -= 1; }
         if (gt1 || num > 8) byp += escape_bins_lane(mine, k, q, absval);
         prev_c1_zero = gt1 ? 1 : 0;
       }
@@ -957,6 +967,7 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
       if (num > 0) prev_gt1 = gt1 != 0;
       if (part != 1 && num > 0) {
         q15 += (unsigned long long)num << 15;  // signs
+        if constexpr (SH) { if (hide_on() && sign_hidden(nzmask)) q15 -= 1ull << 15; }
         if (gt1 || num > 8) byp_par += escape_bins_lane(lane < 16 && level != 0, k, q, absval);
       }
     }
@@ -1781,6 +1792,45 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
       }
     }
   }
+  // Sign data hiding (quant-generic.c:84-176; the rule is kvz_recon.hpp's sign_hide_group) on the three blocks of a unit, between kvz_quant and everything that reads
+  // levels: ONE LANE PER COEFFICIENT GROUP, lane = the group's place in scan order.  The wavefront playing threads 0..63 takes the luma block (up to 64 groups: a
+  // 32x32 block), the other one U on lanes 0.. and V on lanes 16.. (up to 16 groups each) -- the split recon_cu8 has anyway, so there a wavefront-level barrier on
+  // either side is enough.  What a group needs of the rest of its block is one bit, "no group behind me holds a level": a ballot (the host simulation, whose threads
+  // run one after the other in rising order, looks the later groups up: they have not been touched yet).  cf_*: the transform coefficients, lv_*: kvz_quant's levels,
+  // both row-major in LDS; a lane changes at most one level, inside its own group.  Every thread comes here.
+  KVZ_DEV void hide_signs(int tid, int log2y, int log2c, int scan, const i16 *cf_y, i16 *lv_y, const i16 *cf_u, i16 *lv_u, const i16 *cf_v, i16 *lv_v) const
+  {
+    if constexpr (SH) {
+      const int wv = tid >> 6, lane = tid & 63;
+      const int c = wv == 0 ? 0 : 1 + (lane >> 4), i = wv == 0 ? lane : (lane & 15), l2 = wv == 0 ? log2y : log2c, groups = 1 << (2 * l2 - 4);
+      const bool live = c < 3 && i < groups;
+      const i16 *cf = c == 0 ? cf_y : (c == 1 ? cf_u : cf_v);
+      i16 *lv = c == 0 ? lv_y : (c == 1 ? lv_u : lv_v);
+      auto group_base = [&](int gi) { const int g = scan_group(l2, scan, gi, diag8()); return (((g >> (l2 - 2)) * 4) << l2) + (g & ((1 << (l2 - 2)) - 1)) * 4; };
+      auto group_any = [&](int base) {
+        unsigned long long acc4 = 0;
+        for (int r = 0; r < 4; r++) { unsigned long long four; __builtin_memcpy(&four, lv + base + (r << l2), 8); acc4 |= four; }
+        return acc4 != 0;
+      };
+      const int base = live ? group_base(i) : 0;
+      const bool any = live && group_any(base);
+#ifdef KVZ_HOSTSIM
+      bool first_visited = true;
+      for (int j = i + 1; live && j < groups; j++) first_visited = first_visited && !group_any(group_base(j));
+#else
+      unsigned long long behind = __ballot(any);  // bit = lane = place in scan order (the chroma planes: sixteen lanes each)
+      if (wv != 0) behind = (behind >> (16 * ((c - 1) & 1))) & 0xffffull;
+      const bool first_visited = ((behind >> i) >> 1) == 0;
+#endif
+      if (any) {
+        // (read from LDS as the rule asks for them: with the group's rows loaded once and looked up in registers by selects -- CgRows, kvz_residual.hpp -- the pass
+        // was slower, 470.7 against 425.9 ms for 1 536 1080p pictures: profiles/experiments/signhide_group_rows_in_registers_slower.patch)
+        auto at = [&](int n) { const int r = scan_in_group(scan, n); return base + ((r >> 2) << l2) + (r & 3); };
+        const SignHideChange ch = sign_hide_group([&](int n) { return (int)lv[at(n)]; }, [&](int n) { return (int)cf[at(n)]; }, s->qs[l2 - 2][c ? 1 : 0], first_visited);
+        if (ch.pos >= 0) { const int o = at(ch.pos); lv[o] = (i16)sign_hide_apply(lv[o], cf[o], ch.step); }
+      }
+    }
+  }
   // The 8x8 CU -- an 8x8 luma and two 4x4 chroma units, 96 samples -- with every stage of recon_tus() in ONE pass, one lane per
   // sample of any plane: three quarters of the CUs the search evaluates are these, and a loop per plane runs each stage's code
   // three times for a handful of lanes.  Wavefront-uniform by construction: the wavefront playing threads 0..63 is all luma
@@ -1831,6 +1881,7 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
     KVZ_PROF(KVZ_P_FDCT);
     // second pass, and -- the coefficient a lane produces is the one it quantises -- straight on: quantise (quant-generic.c:57-81)
     // -> coefficient store + cost sums; dequantise (:335-339)
+    const bool hide = hide_on();  // sign data hiding: the levels wait for hide_signs() before anything is made of them (false where !SH)
     KVZ_FOR_THREADS(tid) {
       u32 packed = 0;
       auto stage3 = [&](auto luma, int tid_) {
@@ -1845,13 +1896,32 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
         const QuantScalars q = s->qs[l2 - 2][LUMA ? 0 : 1];
         const int level = quant_level(cf, q);
         levels_lds(lv, c)[e] = (i16)level;  // lv == 3 here
+        if constexpr (SH) { if (hide) { tbuf(t, 0, c)[e] = (i16)cf; return; } }  // the coefficient stays for the hiding stage, where the dequantised one will go
         tbuf(t, 0, c)[e] = dequant_level(level, q);
         packed = level_cost(level, m->coeff_weights).word();
       };
       if (tid < 64) stage3(std::true_type(), tid); else if (tid < 96) stage3(std::false_type(), tid);
       // the plane's weight sum (< 2^22) and its count of levels travel in ONE word: one reduction instead of two.  (Per-lane LDS atomics instead of the DPP
       // reduction -- profiles/experiments, r05_g -- take 7 k instructions per CTU off the vector pipe and cost 6 % throughput: 64 lanes on one address.)
-      plane_sums(ROWS_CU8, tid, tid < 64 ? 0 : (tid < 80 ? 1 : (tid < 96 ? 2 : -1)), packed, true, 3);
+      if (!hide) plane_sums(ROWS_CU8, tid, tid < 64 ? 0 : (tid < 80 ? 1 : (tid < 96 ? 2 : -1)), packed, true, 3);
+    }
+    if constexpr (SH) {
+      if (hide) {  // hiding, then the rest of stage 3 on the final levels; luma and chroma still each on their own wavefront
+        KVZ_WAVE_SYNC();
+        KVZ_FOR_THREADS(tid) { hide_signs(tid, 3, 2, intra_scan_order(mode, depth), tbuf(t, 0, 0), levels_lds(lv, 0), tbuf(t, 0, 1), levels_lds(lv, 1), tbuf(t, 0, 2), levels_lds(lv, 2)); }
+        KVZ_WAVE_SYNC();
+        KVZ_FOR_THREADS(tid) {
+          u32 packed = 0;
+          auto stage3b = [&](auto luma, int tid_) {
+            KVZ_CU8_ROLE(tid_);
+            const int level = levels_lds(lv, c)[e];
+            tbuf(t, 0, c)[e] = dequant_level(level, s->qs[l2 - 2][LUMA ? 0 : 1]);
+            packed = level_cost(level, m->coeff_weights).word();
+          };
+          if (tid < 64) stage3b(std::true_type(), tid); else if (tid < 96) stage3b(std::false_type(), tid);
+          plane_sums(ROWS_CU8, tid, tid < 64 ? 0 : (tid < 80 ? 1 : (tid < 96 ? 2 : -1)), packed, true, 3);
+        }
+      }
     }
     KVZ_WAVE_SYNC();
     KVZ_PROF(KVZ_P_QUANT);
@@ -2091,7 +2161,52 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> struct CtuProgramT {
       KVZ_SYNC();
       KVZ_PROF(KVZ_P_RDOQ);
     }
-    if (!RDOQ && wide) {
+    if (SH && !RDOQ && wide && hide_on()) {
+      // Sign data hiding: the stage below in three steps -- kvz_quant's levels into LDS, hide_signs() on them, then cost sums and dequantisation from the final
+      // levels.  The levels' place in LDS is the unit's own (16x16 CUs, 32x32 CUs and merges) or, for the 32x32 units of the 64x64 attempt, whose levels live in
+      // the CTU's scratch block in HBM, the staging copy the CABAC coefficient cost reads (levels_lds(); idle during that attempt whatever prices the levels);
+      // the coefficients stay where they are, in transform buffer 0.
+      auto held = [&](int c) { return lv == 0 ? levels_lds(lv, c) : coeff_dst(lv, c, xl, yl); };
+      KVZ_FOR_THREADS(tid) {
+        for (int trip = 0; trip < wide_trips(t.lw); trip++) {
+          int seg;
+          const int c = wide_task(t.lw, trip, mover_lane(tid), &seg);
+          if (c < 0) continue;
+          const QuantScalars q = s->qs[tu_log2(t, c) - 2][c ? 1 : 0];
+          i16 cf[8], lvl[8];
+          __builtin_memcpy(cf, KVZ_ALIGNED(tbuf(t, 0, c) + (seg << 3), 16), 16);
+          for (int k = 0; k < 8; k++) lvl[k] = (i16)quant_level(cf[k], q);
+          __builtin_memcpy(KVZ_ALIGNED(held(c) + (seg << 3), 16), lvl, 16);
+        }
+      }
+      KVZ_SYNC();
+      KVZ_FOR_THREADS(tid) { hide_signs(tid, t.lw, tu_log2(t, 1), intra_scan_order(mode, depth), tbuf(t, 0, 0), held(0), tbuf(t, 0, 1), held(1), tbuf(t, 0, 2), held(2)); }
+      KVZ_SYNC();
+      KVZ_FOR_THREADS(tid) {
+        const u32 cw_lo = (u32)uni((int)(u32)m->coeff_weights), cw_hi = (u32)uni((int)(u32)(m->coeff_weights >> 32));
+        for (int trip = 0; trip < wide_trips(t.lw); trip++) {
+          int seg;
+          const int c = wide_task(t.lw, trip, mover_lane(tid), &seg);
+          u32 packed = 0;
+          if (c >= 0) {
+            const QuantScalars q = s->qs[tu_log2(t, c) - 2][c ? 1 : 0];
+            i16 lvl[8], dq[8];
+            __builtin_memcpy(lvl, KVZ_ALIGNED(held(c) + (seg << 3), 16), 16);
+            u32 wsum = 0, nz = 0;
+            for (int k = 0; k < 8; k++) {
+              const LevelCost lc = level_cost(lvl[k], cw_lo, cw_hi);
+              wsum += lc.weight;
+              nz += lc.nonzero;
+              dq[k] = dequant_level(lvl[k], q);
+            }
+            packed = wsum | (nz << 24);
+            if (lv == 0) __builtin_memcpy(KVZ_ALIGNED(coeff_dst(lv, c, xl, yl) + (seg << 3), 16), lvl, 16);
+            __builtin_memcpy(KVZ_ALIGNED(tbuf(t, 1, c) + (seg << 3), 16), dq, 16);
+          }
+          plane_sums(wide_rows(t.lw, trip), tid, c, packed, true, 3);
+        }
+      }
+    } else if (!RDOQ && wide) {
       const bool to_stage = cabac_on() && lv == 0;  // see levels_lds()
       KVZ_FOR_THREADS(tid) {
         const u32 cw_lo = (u32)uni((int)(u32)m->coeff_weights), cw_hi = (u32)uni((int)(u32)(m->coeff_weights >> 32));  // scalars for the call

@@ -1,7 +1,7 @@
 // kvz_ctu_kernels.hpp -- the __global__ entry points of the batched CTU pass (the program itself is kvz_ctu.hpp) and their scheduling protocol.
 //
-// Build layout: the six instantiations are the bulk of the library's compile time, so kvazaar_amd/build.py compiles each of them in a translation unit of
-// its own (kvz_ctu_tu.hip with -DKVZ_CTU_KERNEL_TU=<k>), in parallel, next to kvz_hip.hip compiled with -DKVZ_CTU_SEPARATE_TUS -- which then only sees
+// Build layout: the eight instantiations are the bulk of the library's compile time, so kvazaar_amd/build.py compiles each of them in a translation unit of
+// its own (kvz_ctu_tu.hip with -DKVZ_CTU_KERNEL_TU=<k>, k = 0..7), in parallel, next to kvz_hip.hip compiled with -DKVZ_CTU_SEPARATE_TUS -- which then only sees
 // DECLARATIONS here and launches the kernels through their host stubs.  Without that define kvz_hip.hip is self-contained as before (tools/build_variants.sh).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -102,7 +102,7 @@ __device__ __forceinline__ bool wait_done(unsigned *flag, unsigned epoch, unsign
 // sched.no_wpp & KVZ_SCHED_MODEL_TABLE: the pictures of the launch have models of their own (kvz_hip_intra_frames_models) -- `m` is loaded per CTU from the drawn picture's
 // row of the table behind the ticket words.  (A bit of a word the loop keeps anyway and a pointer it keeps anyway: a kernel argument of its own stayed live across the
 // whole program and cost the instantiations that spill a register more.)
-template <bool CABAC, bool S32, bool RDOQ> __device__ __forceinline__ void ticket_loop(const CtuFrames &F, const CtuModel &model, const Tables *tb, const CtuSched &sched)
+template <bool CABAC, bool S32, bool RDOQ, bool SH = false> __device__ __forceinline__ void ticket_loop(const CtuFrames &F, const CtuModel &model, const Tables *tb, const CtuSched &sched)
 {
   __shared__ CtuSharedT<CABAC> shared;
   __shared__ CtuModel m;  // scalars in LDS; its price table stays in HBM (kvz_hip_batch::d_entropy)
@@ -138,7 +138,7 @@ template <bool CABAC, bool S32, bool RDOQ> __device__ __forceinline__ void ticke
     KVZ_TRACE(2);  // neighbours there
     const bool run_it = shared.best_mode != 0;  // uniform.  (run() first writes the field behind several barriers of its own: no lane can still be reading it here)
     if (run_it) {
-      CtuProgramT<CABAC, S32, RDOQ> p;
+      CtuProgramT<CABAC, S32, RDOQ, SH> p;
       p.m = &m; p.tb = tb; p.F = F; p.s = &shared;
       if constexpr (RDOQ) { __shared__ RdoqLds rdoq_lds; p.rl = &rdoq_lds; }
       p.frame = frame; p.cx = x * 64; p.cy = y * 64;
@@ -168,6 +168,18 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false> __global__ void __lau
 #else
 {
   ticket_loop<CABAC, S32, RDOQ>(F, model, tb, sched);
+}
+#endif
+// Sign data hiding (kvz_hip_intra_cost_model::signhide): the program with the hiding stage between kvz_quant and whatever reads levels (kvz_ctu.hpp hide_signs), with
+// and without the 32x32 search.  Both carry the CABAC coefficient model; what prices a picture's levels -- and whether its signs are hidden at all -- is its model's
+// business at run time, so the pictures of a mixed launch (kvz_hip_picture_models) each come out as in a launch of their own.
+template <bool S32> __global__ void __launch_bounds__(KVZ_CTU_THREADS) __attribute__((amdgpu_waves_per_eu(KVZ_CTU_WAVES_PER_EU))) KVZ_CTU_VGPR_ATTR intra_ctu_ticket_kernel_signhide(const CtuFrames F, const CtuModel model, const Tables *tb,
+                                                                        const CtuSched sched)
+#if !KVZ_CTU_KERNEL_BODIES
+;
+#else
+{
+  ticket_loop<true, S32, false, true>(F, model, tb, sched);
 }
 #endif
 // --rdoq / NxN partitions: its own register budget.  Round 3: kvz_rdoq runs as ONE out-of-line wavefront-cooperative routine (kvz_rdoq.hpp rdoq_block_wave), so the

@@ -1,9 +1,9 @@
-// kvz_ctu_tu.hip -- one CTU kernel instantiation per translation unit (see kvz_ctu_kernels.hpp): compiled six times by kvazaar_amd/build.py with
-// -DKVZ_CTU_KERNEL_TU=0..5, in parallel with kvz_hip.hip.
+// kvz_ctu_tu.hip -- one CTU kernel instantiation per translation unit (see kvz_ctu_kernels.hpp): compiled eight times by kvazaar_amd/build.py with
+// -DKVZ_CTU_KERNEL_TU=0..7, in parallel with kvz_hip.hip.
 #include <hip/hip_runtime.h>
 
 #ifndef KVZ_CTU_KERNEL_TU
-#error "compile with -DKVZ_CTU_KERNEL_TU=<0..5>"
+#error "compile with -DKVZ_CTU_KERNEL_TU=<0..7>"
 #endif
 #include "kvz_ctu_kernels.hpp"
 
@@ -21,6 +21,10 @@ template __global__ void intra_ctu_ticket_kernel<false, true, false>(KVZ_TICKET_
 #elif KVZ_CTU_KERNEL_TU == 4
 template __global__ void intra_ctu_ticket_kernel<true, true, false>(KVZ_TICKET_ARGS);
 #elif KVZ_CTU_KERNEL_TU == 5  // RDOQ / NxN: intra_ctu_ticket_kernel_rdoq's body (kvz_ctu_kernels.hpp)
+#elif KVZ_CTU_KERNEL_TU == 6  // sign data hiding
+template __global__ void intra_ctu_ticket_kernel_signhide<false>(KVZ_TICKET_ARGS);
+#elif KVZ_CTU_KERNEL_TU == 7  // ... with 32x32 CUs searched
+template __global__ void intra_ctu_ticket_kernel_signhide<true>(KVZ_TICKET_ARGS);
 #else
 #error "KVZ_CTU_KERNEL_TU out of range"
 #endif

@@ -1941,6 +1941,7 @@ static long kvz_batch_entropy_code_queue(kvz_hip_batch *b, const kvz_hip_intra_c
     J.sao = sao ? (const kvz::SaoRec *)b->d_sao_recs + (size_t)f0 * ctus * 3 : nullptr; J.sao_merge = sao ? b->d_sao_merge + (size_t)f0 * ctus : nullptr;
     memcpy(J.ctx_init, model->ctx_init, sizeof model->ctx_init < sizeof J.ctx_init ? sizeof model->ctx_init : sizeof J.ctx_init);
     if (v) { J.ctx_rows = v->ctx_rows; J.model_of_picture = v->ctu.model_of_picture + f0; }
+    J.signhide = model->signhide != 0;  // (with a table: every picture by its own model's row)
     return J;
   };
   return kvz::entropy_code_pictures(b->stream, b->device, b->n_frames, F.wc, F.hc, model->no_wpp, not_last, job, out, capacity, substream_bytes,

@@ -56,10 +56,20 @@ struct EntropyJob {
   const u8 *ctx_rows;
   const uint16_t *model_of_picture;
   const int32_t *poc_of_picture;  // B pictures with a POC of their own (kvz_hip_dev_entropy_code_inter_pictures): [frames], 0 where temporal predictors are off; `poc` is then unused
+  // I pictures coded with sign data hiding (kvz_hip_intra_cost_model::signhide): every picture of the job, or -- with ctx_rows -- those whose model's row says so in
+  // its last byte (KVZ_ENTROPY_ROW_SIGNHIDE; the contexts end at KVZ_ENTROPY_CTXS)
+  int signhide;
 };
 #define KVZ_ENTROPY_CTX_ROW 176
+#define KVZ_ENTROPY_ROW_SIGNHIDE (KVZ_ENTROPY_CTX_ROW - 1)
 // the initial context states of picture f of the job
 KVZ_HD const u8 *entropy_ctx_init(const EntropyJob &J, int f) { return J.ctx_rows ? J.ctx_rows + (long)picture_model(J.model_of_picture, f) * KVZ_ENTROPY_CTX_ROW : J.ctx_init; }
+// does the residual syntax of picture f of the job hide signs?  (B pictures never: the inter pass has no hiding step)
+KVZ_HD bool entropy_signhide(const EntropyJob &J, int f)
+{
+  if (J.cu) return false;
+  return J.ctx_rows ? J.ctx_rows[(long)picture_model(J.model_of_picture, f) * KVZ_ENTROPY_CTX_ROW + KVZ_ENTROPY_ROW_SIGNHIDE] != 0 : J.signhide != 0;
+}
 // the POC of picture f of the job, as far as the coder asks (do temporal MV predictors exist?)
 KVZ_HD int entropy_picture_poc(const EntropyJob &J, int f) { return J.poc_of_picture ? (int)J.poc_of_picture[f] : J.poc; }
 #define KVZ_EB_CTX(ctx, v) ((u32)(ctx) | ((u32)(v) << 8))
@@ -73,6 +83,7 @@ struct BinSink {
   // kvz_cabac_encode_bins_ep of a run codes the same bytes however the run is cut (low' = (low << n) + range * value is exact), and the coder's serial chain is one step
   // per record.  pend_v / pend_n: the run being gathered.
   u32 pend_v = 0; int pend_n = 0;
+  bool signhide = false;  // the picture's residual syntax hides signs (entropy_signhide)
   KVZ_DEV void put(u32 r) { if (n < cap) out[n] = r; n++; }
   KVZ_DEV void finish() { if (pend_n > 0) { put(KVZ_EB_EP(pend_v, pend_n)); pend_n = 0; pend_v = 0; } }
   KVZ_DEV void ctx(int c, int v) { finish(); put(KVZ_EB_CTX(c, v ? 1 : 0)); bits += 6; }
@@ -90,7 +101,7 @@ struct BinSink {
   }
   KVZ_DEV void trm(int v) { finish(); put(KVZ_EB_TRM(v)); bits += 7; }
   // the residual of the transform block whose levels start `off` into the CTU's block: here and now
-  KVZ_DEV void tu(const Tables *tb, const i16 *ctu, int off, int log2_size, int type, int scan_mode) { entropy_coeff_nxn(*this, tb, ctu + off, log2_size, type, scan_mode); }
+  KVZ_DEV void tu(const Tables *tb, const i16 *ctu, int off, int log2_size, int type, int scan_mode) { entropy_coeff_nxn(*this, tb, ctu + off, log2_size, type, scan_mode, signhide); }
 };
 // ... or later: a sink that queues what follows the first transform block of a CU -- records as they are, blocks as descriptors (kind 3: offset | log2 - 2 << 13 |
 // chroma << 15 | scan << 16) -- so that the bin stage can run the blocks of all its lanes a coefficient group at a time (entropy_ctu_bins_phased).  A CU queues at most
@@ -516,6 +527,7 @@ KVZ_DEV void entropy_ctu_bins(const EntropyJob &J, const Tables *tb, long item)
   const int ctus = J.wc * J.hc, f = (int)(item / ctus), k = (int)(item - (long)f * ctus), lx = k % J.wc, ly = k / J.wc;
   const long cells8 = (long)(J.H >> 3) * (J.W >> 3), cells4 = (long)(J.H >> 2) * (J.W >> 2);
   BinSink s{ J.bins + item * J.cap, 0, J.cap, 0 };
+  s.signhide = entropy_signhide(J, f);
   if (J.sao) {  // encode_sao (encoderstate.c:519-552)
     const int merge = J.sao_merge[item];
     if (lx > 0) s.ctx(KVZ_HIP_CX_SAO_MERGE, merge == 1);
@@ -587,6 +599,7 @@ KVZ_DEV void entropy_ctu_bins_phased(const EntropyJob &J, const Tables *tb, long
   if (live) stack[sp++] = 0;
   TuWalk t;
   t.i = -1;
+  t.signhide = entropy_signhide(J, f);
   bool open = false;
   // every lane takes a step of whatever it is at in every round: the wavefront runs the three pieces one after the other, each for the lanes that are there
   for (;;) {

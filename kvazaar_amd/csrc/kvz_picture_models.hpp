@@ -16,6 +16,16 @@ inline bool cost_model_known(const kvz_hip_intra_cost_model *m, const char *who)
           who, m ? m->struct_size : 0u, sizeof(kvz_hip_intra_cost_model));
   return false;
 }
+// Sign data hiding (kvz_hip_intra_cost_model::signhide) exists for kvz_quant's levels under the ticket schedule: kvz_rdoq's own hiding step (rdo.c:971) works on the
+// rate deltas of its chain and is not on the device, and NxN partitions only occur in the preset that has RDOQ.
+inline bool signhide_known(const kvz_hip_intra_cost_model *m, bool ticket_schedule, const char *who)
+{
+  if (!m->signhide) return true;
+  if (m->rdoq) { fprintf(stderr, "%s: signhide together with rdoq is not supported (kvz_rdoq's own sign hiding is not on the device)\n", who); return false; }
+  if (m->search_nxn) { fprintf(stderr, "%s: signhide together with search_nxn is not supported\n", who); return false; }
+  if (!ticket_schedule) { fprintf(stderr, "%s: signhide needs the ticket schedule (not KVZ_HIP_SCHED=wave)\n", who); return false; }
+  return true;
+}
 
 // Is this a table a batch of n_frames pictures can run (ticket_schedule: the batch does not run under KVZ_HIP_SCHED=wave)?  Everything an entry point refuses is refused here, before anything is queued.
 inline bool picture_models_known(const kvz_hip_picture_models *pm, int n_frames, bool ticket_schedule, const char *who)
@@ -37,6 +47,7 @@ inline bool picture_models_known(const kvz_hip_picture_models *pm, int n_frames,
       return false;
     }
     if (m.rdoq && !m.coeff_cabac) { fprintf(stderr, "%s: model %d has rdoq without coeff_cabac\n", who, i); return false; }
+    if (!signhide_known(&m, true, who)) return false;  // (the schedule is asked about below, for every table)
   }
   for (int f = 0; f < n_frames; f++)
     if (pm->model_of_picture[f] >= pm->n_models) { fprintf(stderr, "%s: model_of_picture[%d] = %u of %d models\n", who, f, (unsigned)pm->model_of_picture[f], pm->n_models); return false; }
@@ -46,6 +57,11 @@ inline bool picture_models_known(const kvz_hip_picture_models *pm, int n_frames,
 inline bool picture_models_any_cabac(const kvz_hip_picture_models *pm)
 {
   for (int i = 0; i < pm->n_models; i++) if (pm->models[i].coeff_cabac) return true;
+  return false;
+}
+inline bool picture_models_any_signhide(const kvz_hip_picture_models *pm)
+{
+  for (int i = 0; i < pm->n_models; i++) if (pm->models[i].signhide) return true;
   return false;
 }
 }  // namespace kvz

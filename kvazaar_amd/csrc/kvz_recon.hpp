@@ -1,8 +1,10 @@
 // kvz_recon.hpp -- the integer arithmetic of one sample on its way through intra_recon_tb_leaf (intra.c:561-608) + kvz_quantize_residual (quant-generic.c:198-292),
 // each step stated ONCE: the lane decompositions of the intra CTU pass (kvz_ctu.hpp recon_cu8, recon_tus, eval_pu) differ in which samples a lane takes, never in
-// what happens to a sample.  Plain functions without state, the same text for the device and the host simulation.  8 bit, flat scaling lists.
+// what happens to a sample.  Plain functions without state, the same text for the device and the host simulation.  8 bit, flat scaling lists; sign data hiding
+// (quant-generic.c:84-176) as a step of its own between quant_level and dequant_level, for the pictures whose model asks for it (sign_hide_group).
 #pragma once
 #include "kvz_ops.hpp"
+#include "kvz_syntax.hpp"
 
 namespace kvz {
 
@@ -36,6 +38,73 @@ KVZ_HD int quant_level(int cf, const QuantScalars &q)
   if (cf < 0) level = -level;
   return iclip(-32768, 32767, level);
 }
+
+// ---- sign data hiding (quant-generic.c:84-176, --signhide): the decoder infers the sign of a coefficient group's first level (lowest scan position) from the parity
+// of the group's level sum whenever the first and the last level lie at least four scan positions apart, so the encoder makes the parity fit, by the one change of
+// one level by one that costs least.
+// quant-generic.c:94 delta_u: what rounding left of the coefficient beyond `level` (the level kvz_quant gave it, before any hiding), in 1/256 of a quantisation
+// step: -86 .. 170 in an I slice (add = 171/512 of a step).  |cf| * q and level << q_bits stay below 2^31 (quant_level), their difference lies in [-add, 2^q_bits - add).
+KVZ_HD int quant_delta_u(int cf, int level, const QuantScalars &q)
+{
+  return (int)((u32)iabs(cf) * (u32)q.flat_q - ((u32)iabs(level) << q.q_bits)) >> (q.q_bits - 8);
+}
+// The rule for ONE coefficient group.  level_at(n) / coeff_at(n): kvz_quant's level and the transform coefficient at scan position n of the group, 0 .. 15.
+// first_visited: no group behind this one in scan order holds a level (the reference visits groups last to first: this is the first it meets with a level, and its
+// candidate walk starts at the last level instead of position 15).  Returns the change: the scan position whose level moves, -1 for none, and the step, which the
+// caller applies with the sign of the COEFFICIENT (sign_hide_apply) -- a zero level leaves zero in the direction its coefficient points.
+// The block-level condition of the reference (sum of absolute levels >= 2) needs no statement: a group that takes part holds two levels.  Its +-32767 clamp cannot
+// be reached at 8 bit: the largest level is 1638 (QP 0, 4x4 block).
+struct SignHideChange { int pos, step; };
+template <class LevelAt, class CoeffAt> KVZ_HD SignHideChange sign_hide_group(LevelAt level_at, CoeffAt coeff_at, const QuantScalars &q, bool first_visited)
+{
+  int first_nz = 16, last_nz = -1, sum = 0;
+  for (int n = 0; n < 16; n++) {
+    const int l = level_at(n);
+    if (l) { if (first_nz == 16) first_nz = n; last_nz = n; }
+    sum += l;  // (= the sum from first_nz to last_nz)
+  }
+  SignHideChange best{ -1, 0 };
+  if (last_nz - first_nz < 4) return best;
+  const int signbit = level_at(first_nz) > 0 ? 0 : 1;
+  if (signbit == (sum & 1)) return best;
+  int min_cost = 0x7fffffff;
+  for (int n = first_visited ? last_nz : 15; n >= 0; n--) {  // downwards, and only a strictly smaller cost wins: of equal costs the highest position
+    const int l = level_at(n), cf = coeff_at(n);
+    int cost = 0x7fffffff, step = 0;
+    if (l != 0) {
+      const int du = quant_delta_u(cf, l, q);
+      if (du > 0) { cost = -du; step = 1; }
+      else if (n == first_nz && iabs(l) == 1) {}  // would move first_nz
+      else { cost = du; step = -1; }
+    } else if (n < first_nz && (cf >= 0 ? 0 : 1) != signbit) {}  // would become the first level, with the wrong sign
+    else { cost = -quant_delta_u(cf, 0, q); step = 1; }
+    if (cost < min_cost) { min_cost = cost; best.pos = n; best.step = step; }
+  }
+  return best;
+}
+KVZ_HD int sign_hide_apply(int level, int cf, int step) { return cf >= 0 ? level + step : level - step; }
+// Where scan position n of group i (scan order) of a 2^log2w block sits in the row-major block
+template <class PtrU8> KVZ_HD int scan_offset(int log2w, int scan_mode, int i, int n, PtrU8 diag8)
+{
+  const int g = scan_group(log2w, scan_mode, i, diag8), gy = g >> (log2w - 2), gx = g & ((1 << (log2w - 2)) - 1), r = scan_in_group(scan_mode, n);
+  return ((gy * 4 + (r >> 2)) << log2w) + gx * 4 + (r & 3);
+}
+// ... and for a whole block, serially, groups last to first: coeff -> the levels kvz_quant left in `level` (row-major, 2^log2w wide).  What the lanes of the CTU
+// pass do a group each (kvz_ctu.hpp hide_signs) and what the tests compare with the per-call oracle.
+template <class PtrU8> KVZ_HD void sign_hide_block(const i16 *coeff, i16 *level, int log2w, int scan_mode, const QuantScalars &q, PtrU8 diag8)
+{
+  bool seen = false;
+  for (int i = (1 << (2 * log2w - 4)) - 1; i >= 0; i--) {
+    bool any = false;
+    for (int n = 0; n < 16; n++) any |= level[scan_offset(log2w, scan_mode, i, n, diag8)] != 0;
+    if (!any) continue;
+    const SignHideChange ch = sign_hide_group([&](int n) { return (int)level[scan_offset(log2w, scan_mode, i, n, diag8)]; },
+                                              [&](int n) { return (int)coeff[scan_offset(log2w, scan_mode, i, n, diag8)]; }, q, !seen);
+    seen = true;
+    if (ch.pos >= 0) { const int o = scan_offset(log2w, scan_mode, i, ch.pos, diag8); level[o] = (i16)sign_hide_apply(level[o], coeff[o], ch.step); }
+  }
+}
+
 // quant-generic.c:335-339
 KVZ_HD i16 dequant_level(int level, const QuantScalars &q) { return (i16)iclip(-32768, 32767, (level * q.dq_scale + (1 << (q.dq_shift - 1))) >> q.dq_shift); }
 

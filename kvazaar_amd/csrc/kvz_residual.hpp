@@ -10,13 +10,16 @@
 
 namespace kvz {
 
-// kvz_encode_coeff_nxn_generic: the residual syntax of one transform block (sign hiding, transform skip, encryption off), cut at the coefficient group so that a caller can
+// kvz_encode_coeff_nxn_generic: the residual syntax of one transform block (transform skip, encryption off; sign data hiding by TuWalk::signhide: the walk of a picture
+// coded with sign_data_hiding_enabled_flag leaves out the sign of a group's first level when its last level lies four scan positions or more behind it -- the levels
+// then carry it in their parity, kvz_recon.hpp sign_hide_group), cut at the coefficient group so that a caller can
 // run it a group at a time (the entropy coder's bin stage keeps the lanes of a wavefront in the same piece of code that way): entropy_tu_begin -- which groups are
 // significant, the last position and its syntax -- then entropy_tu_cg once per group, last to first, while t.i >= 0.
 struct TuWalk {
   const i16 *coeff; int log2_size, type, scan_mode;
   unsigned long long sig_cg;  // bit cy * nbs + cx
   int i, scan_pos_sig, scan_pos_last, pos_last, c1;
+  bool signhide = false;  // set before entropy_tu_begin, like the block's own fields
 };
 KVZ_DEV int entropy_cg_of(const u32 *scan, int i, int log2_size)  // g_sig_last_scan_cg: the scan is group-major
 {
@@ -95,7 +98,8 @@ template <class Sink> KVZ_DEV void entropy_tu_cg(Sink &s, const Tables *tb, TuWa
     const unsigned long long pat = scan_pattern16(scan_mode);
     CgRows rows{ 0, 0, 0, 0 };  // (an insignificant group is all zero: the first group's flag is inferred, its levels are still walked)
     if ((sig_cg >> cg_blk_pos) & 1) rows.load(coeff, width, cg_pos_x, cg_pos_y);
-    if (scan_pos_sig == scan_pos_last) { const int v = rows.at((int)((pat >> (4 * (scan_pos_last & 15))) & 15)); abs_coeff[0] = iabs(v); coeff_signs = v < 0; num_non_zero = 1; scan_pos_sig--; }
+    int last_nz = -1, first_nz = 16;  // scan positions of the group's levels that come first and last in CODING order: the highest and the lowest
+    if (scan_pos_sig == scan_pos_last) { const int v = rows.at((int)((pat >> (4 * (scan_pos_last & 15))) & 15)); abs_coeff[0] = iabs(v); coeff_signs = v < 0; num_non_zero = 1; last_nz = first_nz = scan_pos_sig; scan_pos_sig--; }
     const int right = cg_pos_x < nbs - 1 && ((sig_cg >> (cg_pos_y * nbs + cg_pos_x + 1)) & 1);
     const int lower = cg_pos_y < nbs - 1 && ((sig_cg >> ((cg_pos_y + 1) * nbs + cg_pos_x)) & 1);
     if (i == scan_cg_last || i == 0) sig_cg |= 1ull << cg_blk_pos;
@@ -105,7 +109,7 @@ template <class Sink> KVZ_DEV void entropy_tu_cg(Sink &s, const Tables *tb, TuWa
       for (; scan_pos_sig >= sub_pos; scan_pos_sig--) {
         const int p = (int)((pat >> (4 * (scan_pos_sig & 15))) & 15), pos_y = cg_pos_y * 4 + (p >> 2), pos_x = cg_pos_x * 4 + (p & 3), v = rows.at(p);
         if (scan_pos_sig > sub_pos || i == 0 || num_non_zero) s.ctx(base_sig + sig_ctx_inc(pattern, scan_mode, pos_x, pos_y, log2_size, type), v != 0);
-        if (v) { abs_coeff[num_non_zero++] = iabs(v); coeff_signs = 2 * coeff_signs + (v < 0); }
+        if (v) { abs_coeff[num_non_zero++] = iabs(v); coeff_signs = 2 * coeff_signs + (v < 0); if (last_nz < 0) last_nz = scan_pos_sig; first_nz = scan_pos_sig; }
       }
     } else scan_pos_sig = sub_pos - 1;
     if (num_non_zero > 0) {
@@ -121,7 +125,8 @@ template <class Sink> KVZ_DEV void entropy_tu_cg(Sink &s, const Tables *tb, TuWa
         else if (c1 < 3 && c1 > 0) c1++;
       }
       if (c1 == 0 && first_c2 != -1) s.ctx((type == 0 ? KVZ_HIP_CX_ABS_LUMA : KVZ_HIP_CX_ABS_CHROMA) + ctx_set, abs_coeff[first_c2] > 2);
-      s.ep(coeff_signs, num_non_zero);
+      if (t.signhide && last_nz - first_nz >= 4) s.ep(coeff_signs >> 1, num_non_zero - 1);  // encode_coding_tree-generic.c:199, 240-247: the last sign coded is the first level's
+      else s.ep(coeff_signs, num_non_zero);
       if (c1 == 0 || num_non_zero > 8) {
         int first_coeff2 = 1;
         for (int idx = 0; idx < num_non_zero; idx++) {
@@ -148,10 +153,10 @@ template <class Sink> KVZ_DEV void entropy_tu_cg(Sink &s, const Tables *tb, TuWa
   }
   t.sig_cg = sig_cg; t.scan_pos_sig = scan_pos_sig; t.c1 = c1; t.i = i - 1;
 }
-template <class Sink> KVZ_DEV void entropy_coeff_nxn(Sink &s, const Tables *tb, const i16 *coeff, int log2_size, int type, int scan_mode)
+template <class Sink> KVZ_DEV void entropy_coeff_nxn(Sink &s, const Tables *tb, const i16 *coeff, int log2_size, int type, int scan_mode, bool signhide = false)
 {
   TuWalk t;
-  t.coeff = coeff; t.log2_size = log2_size; t.type = type; t.scan_mode = scan_mode;
+  t.coeff = coeff; t.log2_size = log2_size; t.type = type; t.scan_mode = scan_mode; t.signhide = signhide;
   entropy_tu_begin(s, tb, t);
   while (t.i >= 0) entropy_tu_cg(s, tb, t);
 }
