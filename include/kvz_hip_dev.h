@@ -49,6 +49,12 @@ int  kvz_hip_dev_transform(int kind, const int16_t *in, int16_t *tmp, int16_t *o
  * into out + i * w * w.  (4w + 2) + w^2 bytes per block. */
 int  kvz_hip_dev_angular_pred(int log2_width, int mode, const uint8_t *ref_above, const uint8_t *ref_left, int count, uint8_t *out);
 
+/* The mode selection of search_intra_rough (search_intra.c:433-530) as the intra CTU pass runs it, on `count` tables, one wavefront per table: winner[i] = the mode
+ * the reference's order picks.  Table i is raw + i * 35 * nblk: 35 modes x nblk 8x8-block SATDs (a mode's SATD is the sum of (block + 2) >> 2; nblk 1 with log2w 3,
+ * 4 with log2w 4), preds + 3 i: its three most probable modes, mode_bits + 3 i: lambda_sqrt * kvz_luma_mode_bits of "no most probable mode", "the first", "the
+ * second or third".  A developer entry point: the pass itself takes these from LDS.  -1: a shape the pass does not have. */
+int  kvz_hip_dev_intra_select(int log2w, int nblk, const uint32_t *raw, const int8_t *preds, const double *mode_bits, int count, int32_t *winner);
+
 /* Deblocking of all-intra, constant-QP pictures in place: kvz_filter_deblock_lcu (filter.c:783) over every LCU of every
  * frame.  frames = n_frames x [Y | U | V] tight planar 4:2:0 (the batch layout), cu_depth = n_frames x [H/8][W/8] CU depths
  * as the CTU pass returns them; beta / tc offsets are cfg.deblock_beta / cfg.deblock_tc (cfg.c: 0, 0).  Not a strategy in

@@ -37,6 +37,7 @@
 #include "kvz_rdoq.hpp"
 #include "kvz_recon.hpp"
 #include "kvz_residual.hpp"
+#include "kvz_select.hpp"
 
 namespace kvz {
 
@@ -69,6 +70,19 @@ static unsigned long long g_kvz_syncs;
 #define KVZ_WAVE_SYNC()
 #else
 #define KVZ_WAVE_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
+#endif
+
+// KVZ_TOGETHER(a, b, ...) (2, 5 or 10 variables that were just loaded): every one of them is needed HERE, all at once -- an opaque use that keeps the compiler from
+// sinking each load of a one-lane chain to its own first use, where every one of them would be issued and waited for by itself.  Changes no value: nothing on the host.
+#ifdef KVZ_HOSTSIM
+#define KVZ_TOGETHER(...)
+#else
+#define KVZ_TG1(v) "+v"(v)
+#define KVZ_TG_PICK(_1, _2, _3, _4, _5, _6, _7, _8, _9, _10, NAME, ...) NAME
+#define KVZ_TG_2(a, b) KVZ_TG1(a), KVZ_TG1(b)
+#define KVZ_TG_5(a, b, c, d, e) KVZ_TG1(a), KVZ_TG1(b), KVZ_TG1(c), KVZ_TG1(d), KVZ_TG1(e)
+#define KVZ_TG_10(a, b, c, d, e, f, g, h, i, j) KVZ_TG_5(a, b, c, d, e), KVZ_TG_5(f, g, h, i, j)
+#define KVZ_TOGETHER(...) asm volatile("" : KVZ_TG_PICK(__VA_ARGS__, KVZ_TG_10, _9, _8, _7, _6, KVZ_TG_5, _4, _3, KVZ_TG_2, _1)(__VA_ARGS__))
 #endif
 
 // Sum of `v` over the workgroup added to the LDS word *dst.  Must be reached by every lane of the wave (uniform control
@@ -333,7 +347,7 @@ template <bool CABAC> struct CtuSharedT {
   // neighbour CTUs' data, staged once per CTU: reconstructed border pixels and CU info of the left column / top row
   u8 bpx_left[3][66];        // x = ox-1, y = oy-1 .. oy+63   (index 0 = corner)
   u8 bpx_top[3][98];         // y = oy-1, x = ox-1 .. ox+95   (index 0 = corner)
-  u8 nb_depth[2][8], nb_mode[2][8];  // [0 left / 1 top][8x8 index]
+  uint16_t nb_cu[2][8];      // [0 left / 1 top][8x8 index]: the CU behind the CTU's edge in the format of neighbour_cu() -- the low half of a CtuCu with type 1 --, 0 = no such CTU
   u8 dcval[3];               // DC value of the current references per plane
   int8_t mode_disp[35];      // angular parameters per mode (intra-generic.c:59-60, 70-76): signed sample displacement,
   int16_t mode_inv[35];      //   inverse angle, and whether the mode projects on the top reference
@@ -489,17 +503,39 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false> stru
     if constexpr (NXN) { if (m->search_nxn) { const u32 v = (u32)mode * 0x01010101u; __builtin_memcpy(rl->mode4[lv][cell], &v, 4); } }
   }
 
-  // CU info at luma frame position (fx, fy) as seen from work-tree level lv; false = not available
-  // CU info at luma frame position (fx, fy) as seen from work-tree level lv, as a VALUE: -1 = not available, else
-  // type | depth << 1 | mode << 8 (KVZ_NB_*).  (Handing out a CtuCu through a pointer put the struct on the stack: every neighbour
-  // lookup of the thread-0 blocks went through scratch memory.)
+  // CU info at luma frame position (fx, fy) as seen from work-tree level lv, as a VALUE: type | depth << 1 | mode << 8 (KVZ_NB_*; the bits in between are not
+  // defined), 0 = not available -- an untouched cell of the work tree (CU_NOTSET) and a position outside the picture look alike to every caller: one asks for
+  // type 1, the other for a depth above its own.  (Handing out a CtuCu through a pointer put the struct on the stack: every neighbour lookup of the thread-0
+  // blocks went through scratch memory.)  Only the left column (fx == cx - 1) and the top row (fy == cy - 1) are ever asked for outside the CTU, and those are
+  // staged by init() in the same format as the low half of a CtuCu: the lookup is a choice between two LDS offsets and ONE 16-bit load, as rec_off() is for
+  // samples -- the left and the above neighbour of a CU can be in flight together.
 #define KVZ_NB_TYPE(v) ((v) & 1)
 #define KVZ_NB_DEPTH(v) (((v) >> 1) & 3)
 #define KVZ_NB_MODE(v) (((v) >> 8) & 0xff)
   KVZ_DEV int neighbour_cu(int lv, int fx, int fy) const
   {
-    if (fx < 0 || fy < 0 || fx >= F.W || fy >= F.H) return -1;
-    const int pu = ((fy >> 2) & 1) * 2 + ((fx >> 2) & 1);  // which 4x4 unit of its 8x8 cell (search_nxn: modes are 4x4-granular)
+    if constexpr (NXN) { if (nxn_on()) return neighbour_cu_nxn(lv, fx, fy); }
+    static_assert(sizeof(CtuCu) == 4 && __builtin_offsetof(CtuCu, mode) == 1, "type | depth << 1 | ... | mode << 8 are the first two bytes of a CtuCu");
+    const int xl = fx - cx, yl = fy - cy;
+    const u8 *base = (const u8 *)s;
+    const lds_off o_in = (lds_off)((const u8 *)&s->cu[lv][0] - base) + 4 * ((yl >> 3) * 8 + (xl >> 3));
+    const lds_off o_nb = (lds_off)((const u8 *)&s->nb_cu[0][0] - base) + 2 * (xl < 0 ? (yl >> 3) : 8 + (xl >> 3));
+    uint16_t v;
+    __builtin_memcpy(&v, base + (((unsigned)xl < 64u && (unsigned)yl < 64u) ? o_in : o_nb), 2);
+    return v;
+  }
+  // The left and the above neighbour of the block at (x, y), both lookups in flight together
+  KVZ_DEV void neighbour_pair(int lv, int x, int y, int *left, int *above) const
+  {
+    int l = neighbour_cu(lv, x - 1, y), a = neighbour_cu(lv, x, y - 1);
+    KVZ_TOGETHER(l, a);
+    *left = l; *above = a;
+  }
+  // ... with search_nxn, where modes are 4x4-granular (mode4, nb_mode4_left) and an 8x8 CU being tried as NxN sees its own PUs at level 4
+  KVZ_DEV int neighbour_cu_nxn(int lv, int fx, int fy) const
+  {
+    if (fx < 0 || fy < 0 || fx >= F.W || fy >= F.H) return 0;
+    const int pu = ((fy >> 2) & 1) * 2 + ((fx >> 2) & 1);  // which 4x4 unit of its 8x8 cell
     if (fx >= cx && fx < cx + 64 && fy >= cy && fy < cy + 64) {
       const int cell = ((fy - cy) >> 3) * 8 + ((fx - cx) >> 3);
       if (NXN && lv == 4) {
@@ -509,13 +545,10 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false> stru
         lv = 3;
       }
       const CtuCu c = s->cu[lv][cell];
-      const int mode = nxn_on() ? (int)rl->mode4[lv][cell][pu] : (int)c.mode;
-      return (int)c.type | ((int)c.depth << 1) | (mode << 8);
+      return (int)c.type | ((int)c.depth << 1) | ((int)rl->mode4[lv][cell][pu] << 8);
     }
-    // outside the CTU only the left column (fx == cx-1) and the top row (fy == cy-1) are ever asked for
-    const int side = fx < cx ? 0 : 1, i = side == 0 ? (fy - cy) >> 3 : (fx - cx) >> 3;
-    const int mode = (nxn_on() && side == 0) ? (int)rl->nb_mode4_left[(fy - cy) >> 2] : (int)s->nb_mode[side][i];
-    return 1 | ((int)s->nb_depth[side][i] << 1) | (mode << 8);
+    const int side = fx < cx ? 0 : 1, i = side == 0 ? (fy - cy) >> 3 : (fx - cx) >> 3, e = s->nb_cu[side][i];
+    return side == 0 ? (e & 0xff) | ((int)rl->nb_mode4_left[(fy - cy) >> 2] << 8) : e;
   }
   // Where the reconstructed sample (px, py) of plane c (plane coordinates of the frame) lives as work-tree level lv sees it, as a byte offset into CtuShared: the
   // decided picture (which also holds the 8x8 candidates of the 16x16 CU being split) or the left / top border of the neighbour CTUs.  The choice is made on the
@@ -550,8 +583,8 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false> stru
   KVZ_DEV static void mpm_candidates(int y, int left /* neighbour_cu() values */, int above, int8_t preds[3])
   {
     int l = 1, a = 1;
-    if (left >= 0 && KVZ_NB_TYPE(left) == 1) l = KVZ_NB_MODE(left);
-    if (above >= 0 && KVZ_NB_TYPE(above) == 1 && (y & 63) != 0) a = KVZ_NB_MODE(above);
+    if (KVZ_NB_TYPE(left) == 1) l = KVZ_NB_MODE(left);
+    if (KVZ_NB_TYPE(above) == 1 && (y & 63) != 0) a = KVZ_NB_MODE(above);
     intra_mpm(l, a, preds);
   }
   // CABAC_FBITS_UPDATE (cabac.h:133-139) on context idx of `c`: the price of `bin` (CTX_ENTROPY_FBITS, cabac.h:131), then -- if
@@ -565,9 +598,11 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false> stru
     return bits;
   }
   // kvz_g_auc_next_state_mps / _lps (cabac.c:40-62) on the packed state
-  KVZ_DEV int ctx_next(int st, int bin) const
+  KVZ_DEV int ctx_next(int st, int bin) const { return ctx_next_with(st, bin, s->ctx_lps[st >> 1]); }
+  // ... with the table entry s->ctx_lps[st >> 1] brought by the caller, who may have several lookups in flight together
+  KVZ_DEV static int ctx_next_with(int st, int bin, int lps_entry)
   {
-    const int mps = st + ((st < 124) << 1), lps = (int)s->ctx_lps[st >> 1] ^ (st & 1);  // branch-free: both are a handful of ALU ops + one LDS byte
+    const int mps = st + ((st < 124) << 1), lps = lps_entry ^ (st & 1);  // branch-free: both are a handful of ALU ops + one LDS byte
     return bin == (st & 1) ? mps : lps;
   }
   // Copy / exchange of context sets (search.c:655, 956-959, 1051): the residual-coding part only matters (and only moves) when coefficients are priced
@@ -604,12 +639,13 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false> stru
     if (in) bits += (mode == preds[0]) ? 1 : 2; else bits += 5;
     return bits;
   }
+  // the context of a split flag (encode_coding_tree.c:1060-1080) from the two neighbours' neighbour_cu() values: how many of them are deeper
+  KVZ_DEV static int split_model_of(int left, int above, int depth) { return (KVZ_NB_DEPTH(left) > depth) + (KVZ_NB_DEPTH(above) > depth); }
   KVZ_DEV int split_model(int lv, int x, int y, int depth) const
   {
-    int model = 0, n;
-    if (x > 0 && (n = neighbour_cu(lv, x - 1, y)) >= 0 && KVZ_NB_DEPTH(n) > depth) model++;
-    if (y > 0 && (n = neighbour_cu(lv, x, y - 1)) >= 0 && KVZ_NB_DEPTH(n) > depth) model++;
-    return model;
+    int left, above;
+    neighbour_pair(lv, x, y, &left, &above);  // (0 beyond the picture's left and upper edge)
+    return split_model_of(left, above, depth);
   }
   // `known_preds`: the CU's most probable modes when the caller already has them (rough_search derives the same three from
   // the same neighbours: for the 8-aligned CU origins x >= 4 <=> x > 0 and yl > 0 <=> (y & 63) > 0).
@@ -622,9 +658,9 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false> stru
     const bool no_left = mock && (x & 63) == 0;
     if (known_preds && !(no_left && x > 0)) { preds[0] = known_preds[0]; preds[1] = known_preds[1]; preds[2] = known_preds[2]; }
     else {
-      const int left = (x > 0 && !no_left) ? neighbour_cu(lv, x - 1, y) : -1;
-      const int above = ((y & 63) > 0 && y > 0) ? neighbour_cu(lv, x, y - 1) : -1;
-      mpm_candidates(y, left, above, preds);
+      int left, above;
+      neighbour_pair(lv, x, y, &left, &above);
+      mpm_candidates(y, no_left ? 0 : left, above, preds);  // (mpm_candidates itself takes DC across a CTU row)
     }
     double bits = luma_mode_bits(c, mode, preds, update);
     bits += ctx_price(c, KVZ_CX_CHROMA, 0, update);
@@ -1442,140 +1478,73 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false> stru
   {
     if (S32 && nblk == 16) return s->satd_raw[mode][0];  // a 32x32 CU's sum over its sixteen blocks, already rounded per block (rough_search)
     if (NXN && nblk == 0) return s->satd_raw[mode][0];   // a 4x4 PU: the finished 4x4 SATD (eval_pu)
-    u32 v = 0;
-    for (int b = 0; b < nblk; b++) v += (s->satd_raw[mode][b] + 2) >> 2;
-    return v;
+    return select_satd_sum(s->satd_raw[mode], nblk);
   }
 
-  // search_intra.c:391-530 search_intra_rough: all 35 modes predicted + SATD-scored, then the reference's selection
-  // order replayed on the cost table by one lane.  Leaves the winner in s->best_mode and the CU's info entries filled.
-  // Also builds the chroma references of the CU (they only depend on neighbouring chroma reconstruction).
-#ifndef KVZ_HOSTSIM
-  // Wavefront minima by DPP row shifts (a lane without a source keeps its own value) + the four row results by lane index
-  KVZ_DEV static unsigned long long wave_min_u64(unsigned long long v)
-  {
-#define KVZ_MIN64_STEP(ctrl)                                                                                         \
-    {                                                                                                                \
-      const int lo_ = (int)(unsigned)v, hi_ = (int)(unsigned)(v >> 32);                                              \
-      const unsigned olo = (unsigned)__builtin_amdgcn_update_dpp(lo_, lo_, ctrl, 0xF, 0xF, false);                    \
-      const unsigned ohi = (unsigned)__builtin_amdgcn_update_dpp(hi_, hi_, ctrl, 0xF, 0xF, false);                    \
-      const unsigned long long o = ((unsigned long long)ohi << 32) | olo;                                            \
-      v = o < v ? o : v;                                                                                             \
-    }
-    KVZ_MIN64_STEP(0x111) KVZ_MIN64_STEP(0x112) KVZ_MIN64_STEP(0x114) KVZ_MIN64_STEP(0x118)
-#undef KVZ_MIN64_STEP
-    unsigned long long r = ~0ull;
-    for (int row = 0; row < 4; row++) {
-      const unsigned long long o = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), 16 * row + 15) << 32) |
-                                   (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, 16 * row + 15);
-      r = o < r ? o : r;
-    }
-    return r;
-  }
-  KVZ_DEV static unsigned wave_min_u32(unsigned v)
-  {
-    int x = (int)v;
-#define KVZ_MIN32_STEP(ctrl) { const unsigned o = (unsigned)__builtin_amdgcn_update_dpp(x, x, ctrl, 0xF, 0xF, false); x = (int)(o < (unsigned)x ? o : (unsigned)x); }
-    KVZ_MIN32_STEP(0x111) KVZ_MIN32_STEP(0x112) KVZ_MIN32_STEP(0x114) KVZ_MIN32_STEP(0x118)
-#undef KVZ_MIN32_STEP
-    const unsigned a = (unsigned)__builtin_amdgcn_readlane(x, 15), b = (unsigned)__builtin_amdgcn_readlane(x, 31), c = (unsigned)__builtin_amdgcn_readlane(x, 47), d = (unsigned)__builtin_amdgcn_readlane(x, 63);
-    const unsigned ab = a < b ? a : b, cd = c < d ? c : d;
-    return ab < cd ? ab : cd;
-  }
-#endif
   // The selection order of search_intra_rough (search_intra.c:433-530) replayed on the cost table of all 35 modes (s->satd_raw; nblk 8x8 blocks per mode, 0: a 4x4
   // PU whose entry is the finished SATD).  Returns the winner on the lanes that ran the replay -- the host build: thread 0; the device: the wavefront playing
   // threads 0..63, all its lanes together -- and -1 on the others.
   KVZ_DEV int replay_selection(int tid, int log2w, int nblk) const
   {
-    // The replay below is serial and uniform.  On the device the first wavefront's worth of thread ids runs it together:
-    // lane m first works out mode m's SATD and cost, the replay then picks values out of those registers by lane index
-    // (v_readlane) instead of recomputing them from LDS.  The host build computes them on demand -- same formulas.
-#ifdef KVZ_HOSTSIM
-      if (tid != 0) return -1;
-      {
+#ifndef KVZ_HOSTSIM
+    // On the device the first wavefront's worth of thread ids runs it together: lane m works out mode m's SATD and cost, the selection then runs on those
+    // registers with wavefront reductions (select_on_wave, kvz_select.hpp) -- same formulas, same winner as the serial order below.
+    if (tid >= 64) return -1;
+    const int my_mode = tid < 35 ? tid : 0, p0 = s->preds[0], p1 = s->preds[1], p2 = s->preds[2];
+    const u32 my_raw = mode_satd(my_mode, nblk);
+    return select_on_wave(tid, my_raw, select_mode_cost(my_raw, my_mode, p0, p1, p2, s->mode_bits_cost), p0, p1, p2, log2w);
+#else
+    // The statement of the reference's order: serial, by thread 0.
+    if (tid != 0) return -1;
+    // The list kvazaar builds (modes[], costs[]) is only ever read back as "first minimum in append order", so it is
+    // replayed with a visited mask and running minima instead of arrays.
+    unsigned long long visited = 0;
+    double final_cost = 0;
+    int final_mode = -1;
+    const int8_t p0 = s->preds[0], p1 = s->preds[1], p2 = s->preds[2];
 #define KVZ_RAW(md) mode_satd((md), nblk)
-#define KVZ_COST(md, raw) ((double)(raw) + s->mode_bits_cost[(md) == p0 ? 1 : (((md) == p1 || (md) == p2) ? 2 : 0)])
-#else
-      if (tid >= 64) return -1;
-      {
-        const int my_mode = tid < 35 ? tid : 0;
-        const u32 my_raw = mode_satd(my_mode, nblk);
-        const double my_cost = (double)my_raw + s->mode_bits_cost[my_mode == s->preds[0] ? 1 : ((my_mode == s->preds[1] || my_mode == s->preds[2]) ? 2 : 0)];
-        const int my_cost_lo = __double2loint(my_cost), my_cost_hi = __double2hiint(my_cost);
-#define KVZ_RAW(md) ((u32)__builtin_amdgcn_readlane((int)my_raw, __builtin_amdgcn_readfirstlane(md)))
-        // On the device an append only records WHEN a mode was appended (in the lane that holds the mode); "first minimum in append
-        // order" is then one wavefront minimum of the costs -- non-negative doubles order like their bit patterns -- and one of
-        // the append positions among the lanes that reach it, instead of two v_readlane and a double compare per append.
-        int my_pos = 0, n_app = 0;
-#endif
-        // The list kvazaar builds (modes[], costs[]) is only ever read back as "first minimum in append order", so it is
-        // replayed with a visited mask and running minima instead of arrays.
-        unsigned long long visited = 0;
-        double final_cost = 0;
-        int final_mode = -1;
-        const int8_t p0 = s->preds[0], p1 = s->preds[1], p2 = s->preds[2];
-#ifdef KVZ_HOSTSIM
 #define KVZ_APPEND(md, raw)                                                                                         \
-        {                                                                                                           \
-          const int md_ = (md);                                                                                     \
-          visited |= 1ull << md_;                                                                                   \
-          const double c_ = KVZ_COST(md_, raw);                                                                     \
-          if (final_mode < 0 || c_ < final_cost) { final_cost = c_; final_mode = md_; }                             \
+    {                                                                                                               \
+      const int md_ = (md);                                                                                         \
+      visited |= 1ull << md_;                                                                                       \
+      const double c_ = select_mode_cost((raw), md_, p0, p1, p2, s->mode_bits_cost);                                \
+      if (final_mode < 0 || c_ < final_cost) { final_cost = c_; final_mode = md_; }                                 \
+    }
+    int offset = log2w == 2 ? 2 : (log2w == 3 ? 4 : 8);
+    int32_t min_cost = 0x7fffffff, max_cost = -0x7fffffff - 1;
+    int best_mode = -1;
+    u32 first_min = 0;
+    for (int mode = 2; mode <= 34; mode += 2 * offset)
+      for (int i = 0; i < 2; i++) if (mode + i * offset <= 34) {
+        const u32 raw = KVZ_RAW(mode + i * offset);
+        KVZ_APPEND(mode + i * offset, raw);
+        if ((int32_t)raw < min_cost) min_cost = (int32_t)raw;
+        if ((int32_t)raw > max_cost) max_cost = (int32_t)raw;
+        if (best_mode < 0 || raw < first_min) { first_min = raw; best_mode = mode + i * offset; }
+      }
+    double best_cost = min_cost;
+    if (min_cost != max_cost) {
+      while (offset > 1) {
+        offset >>= 1;
+        const int tm[2] = { best_mode - offset, best_mode + offset };
+        for (int i = 0; i < 2; i++) if (tm[i] >= 2 && tm[i] <= 34) {
+          const u32 raw = KVZ_RAW(tm[i]);
+          KVZ_APPEND(tm[i], raw);
+          if ((double)raw < best_cost) { best_cost = (double)raw; best_mode = tm[i]; }
         }
-#else
-#define KVZ_APPEND(md, raw)                                                                                         \
-        {                                                                                                           \
-          const int md_ = __builtin_amdgcn_readfirstlane(md);                                                       \
-          visited |= 1ull << md_;                                                                                   \
-          if (tid == md_) my_pos = n_app;                                                                           \
-          n_app++;                                                                                                  \
-        }
-#endif
-        int offset = log2w == 2 ? 2 : (log2w == 3 ? 4 : 8);
-        int32_t min_cost = 0x7fffffff, max_cost = -0x7fffffff - 1;
-        int best_mode = -1;
-        u32 first_min = 0;
-        for (int mode = 2; mode <= 34; mode += 2 * offset)
-          for (int i = 0; i < 2; i++) if (mode + i * offset <= 34) {
-            const u32 raw = KVZ_RAW(mode + i * offset);
-            KVZ_APPEND(mode + i * offset, raw);
-            if ((int32_t)raw < min_cost) min_cost = (int32_t)raw;
-            if ((int32_t)raw > max_cost) max_cost = (int32_t)raw;
-            if (best_mode < 0 || raw < first_min) { first_min = raw; best_mode = mode + i * offset; }
-          }
-        double best_cost = min_cost;
-        if (min_cost != max_cost) {
-          while (offset > 1) {
-            offset >>= 1;
-            const int tm[2] = { best_mode - offset, best_mode + offset };
-            for (int i = 0; i < 2; i++) if (tm[i] >= 2 && tm[i] <= 34) {
-              const u32 raw = KVZ_RAW(tm[i]);
-              KVZ_APPEND(tm[i], raw);
-              if ((double)raw < best_cost) { best_cost = (double)raw; best_mode = tm[i]; }
-            }
-          }
-        }
-        const int add_modes[5] = { p0, p1, p2, 0, 1 };
-        for (int p = 0; p < 5; p++)
-          if (!((visited >> add_modes[p]) & 1)) { const u32 raw = KVZ_RAW(add_modes[p]); KVZ_APPEND(add_modes[p], raw); }
+      }
+    }
+    const int add_modes[5] = { p0, p1, p2, 0, 1 };
+    for (int p = 0; p < 5; p++)
+      if (!((visited >> add_modes[p]) & 1)) { const u32 raw = KVZ_RAW(add_modes[p]); KVZ_APPEND(add_modes[p], raw); }
 #undef KVZ_APPEND
 #undef KVZ_RAW
-#ifdef KVZ_HOSTSIM
-#undef KVZ_COST
-#else
-        {
-          const bool mine = tid < 35 && ((visited >> tid) & 1);
-          const unsigned long long key = mine ? (((unsigned long long)(unsigned)my_cost_hi << 32) | (unsigned)my_cost_lo) : ~0ull;
-          const unsigned long long kmin = wave_min_u64(key);
-          final_mode = (int)(wave_min_u32((mine && key == kmin) ? (unsigned)((my_pos << 6) | tid) : ~0u) & 63);
-          (void)final_cost;
-        }
+    return final_mode;
 #endif
-        (void)p0; (void)p1; (void)p2;
-        return final_mode;
-      }
   }
+  // search_intra.c:391-530 search_intra_rough: all 35 modes predicted + SATD-scored, then the reference's selection
+  // order replayed on the cost table (replay_selection).  Leaves the winner in s->best_mode and the CU's info entries filled.
+  // Also builds the chroma references of the CU (they only depend on neighbouring chroma reconstruction).
   template <class First>
   KVZ_DEV void rough_search(int lv, int x, int y, int depth, First first)
   {
@@ -1598,7 +1567,8 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false> stru
         for (int e = tid; e < 1024; e += KVZ_CTU_THREADS) ot[e] = *org_at(0, xl + (e >> 5), yl + (e & 31));
         for (int v = tid; v < 35; v += KVZ_CTU_THREADS) s->satd_raw[v][0] = 0;
         if (tid == KVZ_CTU_THREADS - 1) {
-          const int left = x >= 4 ? neighbour_cu(lv, x - 1, y) : -1, above = (y >= 4 && yl > 0) ? neighbour_cu(lv, x, y - 1) : -1;
+          int left, above;
+          neighbour_pair(lv, x, y, &left, &above);
           mpm_candidates(y, left, above, s->preds);
         }
       }
@@ -1631,7 +1601,8 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false> stru
         s->org_t[e] = *org_at(0, xl + ex, yl + ey);
       }
       if (tid == KVZ_CTU_THREADS - 1) {
-        const int left = x >= 4 ? neighbour_cu(lv, x - 1, y) : -1, above = (y >= 4 && yl > 0) ? neighbour_cu(lv, x, y - 1) : -1;
+        int left, above;
+        neighbour_pair(lv, x, y, &left, &above);
         mpm_candidates(y, left, above, s->preds);
       }
     }
@@ -1677,9 +1648,14 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false> stru
       const int final_mode = replay_selection(tid, log2w, nblk);
       if (final_mode >= 0) {
         if (tid == 0) s->best_mode = final_mode;
-        // lcu_fill_cu_info (search.c:137-159) for the searched CU: at most 2x2 entries
-        for (int i = 0; tid == 0 && i < (w >> 3) * (w >> 3); i++) {
-          const int cell = ((yl >> 3) + i / (w >> 3)) * 8 + (xl >> 3) + i % (w >> 3);
+        // lcu_fill_cu_info (search.c:137-159) for the searched CU, an entry per lane that holds the winner (the host build: thread 0, all of them)
+#ifdef KVZ_HOSTSIM
+        const int holders = 1;
+#else
+        const int holders = 64;
+#endif
+        for (int i = tid; i < (w >> 3) * (w >> 3); i += holders) {
+          const int cell = ((yl >> 3) + (i >> (log2w - 3))) * 8 + (xl >> 3) + (i & ((w >> 3) - 1));
           CtuCu *cu = &s->cu[lv][cell];
           cu->type = 1; cu->depth = (u8)depth; cu->mode = (u8)final_mode; cu->tr_depth = (u8)depth;
           set_mode4(lv, cell, final_mode);
@@ -2391,60 +2367,78 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false> stru
 
   // cu_bits() * lambda + leaf_rd_cost() of the CU just evaluated at its own depth (eval_cu: search.c:895-940 + 425-541), bin for bin the same
   // prices and transitions on the search contexts -- but the six bins sit on five different contexts (only U's and V's coded-block flags share
-  // one), so all states are read first, all prices and successors looked up next, and everything is written back at the end: three LDS round
-  // trips on thread 0's critical path instead of one read-price-write chain per bin.  The sums of prices are exact in any order (multiples
-  // of 2^-15 below 2^10), the cost expressions are the callees' own.
+  // one), so thread 0's critical path is made of as few dependent LDS round trips as the data allow: (1) the ten syntax contexts as one 8-byte and one
+  // 2-byte read, together with the CU's coded-block flags, the sums of the reconstruction and lambda; (2) five prices and five successor-table entries;
+  // (3) the price and the successor of V's flag on U's successor state, the one true dependence; then everything is written back at once (KVZ_TOGETHER
+  // holds the loads of a round trip together).  The sums of prices are exact in any order
+  // (multiples of 2^-15 below 2^10), the cost expressions are the callees' own.
   KVZ_DEV double cu_cost_batched(int lv, int x, int y, int depth, int mode, const int8_t *known_preds, const double *known_coeff_bits) const
   {
     const int xl = x - cx, yl = y - cy, w = 64 >> depth;
     u8 *cs = s->cab.s;
     const bool adaptive = m->adaptive != 0;
+    // (1) what does not depend on another read
+    u32 st03, st47, st89 = 0;  // contexts 0..3 (the split flag's three and the part size's), 4..7 (intra mode, chroma mode, luma flags), 8..9 (chroma flags)
+    __builtin_memcpy(&st03, cs, 4); __builtin_memcpy(&st47, cs + 4, 4); __builtin_memcpy(&st89, cs + 8, 2);
+    u32 cbf = s->cu[lv][(yl >> 3) * 8 + (xl >> 3)].cbf;
+    // the two neighbours, once: the split flag's context of a 16x16 CU looks at both, the most probable modes on the CTU's left edge at the one above
+    const bool no_left = (x & 63) == 0;  // the mock encode's left neighbour (intra_mode_syntax_bits)
+    const bool own_preds = !known_preds || (no_left && x > 0);
+    int left = 0, above = 0;
+    if (depth != 3 || own_preds) neighbour_pair(lv, x, y, &left, &above);
+    u32 luma_ssd = s->acc[0], ssd_u = s->acc[1], ssd_v = s->acc[2], wy = 0, wu = 0, wv = 0;
+    double coeff_bits = 0, lambda = m->lambda;
+    if (known_coeff_bits) coeff_bits += *known_coeff_bits;
+    else { wy = s->acc[3]; wu = s->acc[4]; wv = s->acc[5]; }
+    KVZ_TOGETHER(st03, st47, st89, cbf, luma_ssd, ssd_u, ssd_v, wy, wu, wv);
+    KVZ_TOGETHER(coeff_bits, lambda);
     // which contexts, which bins
     const bool has_sp = depth == 3 || !(F.W < x + w || F.H < y + w);
-    const int i_sp = depth == 3 ? KVZ_CX_PART : KVZ_CX_SPLIT + (has_sp ? split_model(lv, x, y, depth) : 0), b_sp = depth == 3 ? 1 : 0;
+    const int i_sp = depth == 3 ? KVZ_CX_PART : KVZ_CX_SPLIT + (has_sp ? split_model_of(left, above, depth) : 0), b_sp = depth == 3 ? 1 : 0;
     int8_t preds[3];
-    const bool no_left = (x & 63) == 0;  // the mock encode's left neighbour (intra_mode_syntax_bits)
-    if (known_preds && !(no_left && x > 0)) { preds[0] = known_preds[0]; preds[1] = known_preds[1]; preds[2] = known_preds[2]; }
-    else {
-      const int left = (x > 0 && !no_left) ? neighbour_cu(lv, x - 1, y) : -1;
-      const int above = ((y & 63) > 0 && y > 0) ? neighbour_cu(lv, x, y - 1) : -1;
-      mpm_candidates(y, left, above, preds);
-    }
+    if (!own_preds) { preds[0] = known_preds[0]; preds[1] = known_preds[1]; preds[2] = known_preds[2]; }
+    else mpm_candidates(y, no_left ? 0 : left, above, preds);
     const int b_in = (mode == preds[0] || mode == preds[1] || mode == preds[2]) ? 1 : 0;
-    const CtuCu *tr_cu = &s->cu[lv][(yl >> 3) * 8 + (xl >> 3)];
-    const int cb_u = cbf_is_set(tr_cu->cbf, depth, 1), cb_v = cbf_is_set(tr_cu->cbf, depth, 2), cb_y = cbf_is_set(tr_cu->cbf, depth, 0);
-    const int i_cc = KVZ_CX_CBF_CHROMA, i_cl = KVZ_CX_CBF_LUMA + 1;
-    // states, then prices and successors, then the second bin on the chroma flag's context
-    const int s_sp = cs[i_sp], s_in = cs[KVZ_CX_INTRA], s_ch = cs[KVZ_CX_CHROMA], s_cu = cs[i_cc], s_cl = cs[i_cl];
-    const float f_sp = s->entropy_fbits[s_sp ^ b_sp], f_in = s->entropy_fbits[s_in ^ b_in], f_ch = s->entropy_fbits[s_ch ^ 0];
-    const float f_cu = s->entropy_fbits[s_cu ^ cb_u], f_cl = s->entropy_fbits[s_cl ^ cb_y];
-    const int n_sp = ctx_next(s_sp, b_sp), n_in = ctx_next(s_in, b_in), n_ch = ctx_next(s_ch, 0), n_cu = ctx_next(s_cu, cb_u), n_cl = ctx_next(s_cl, cb_y);
+    const int cb_u = cbf_is_set((uint16_t)cbf, depth, 1), cb_v = cbf_is_set((uint16_t)cbf, depth, 2), cb_y = cbf_is_set((uint16_t)cbf, depth, 0);
+    static_assert(KVZ_CX_SPLIT == 0 && KVZ_CX_PART == 3 && KVZ_CX_INTRA == 4 && KVZ_CX_CHROMA == 5 && KVZ_CX_CBF_LUMA == 6 && KVZ_CX_CBF_CHROMA == 8, "the bytes picked out of st03 / st47 / st89 below");
+    const int s_sp = (int)((st03 >> (8 * i_sp)) & 255), s_in = (int)(st47 & 255), s_ch = (int)((st47 >> 8) & 255), s_cl = (int)(st47 >> 24), s_cu = (int)(st89 & 255);
+    // (2) prices and successor-table entries of the five states
+    float f_sp = s->entropy_fbits[s_sp ^ b_sp], f_in = s->entropy_fbits[s_in ^ b_in], f_ch = s->entropy_fbits[s_ch ^ 0];
+    float f_cu = s->entropy_fbits[s_cu ^ cb_u], f_cl = s->entropy_fbits[s_cl ^ cb_y];
+    int l_sp = s->ctx_lps[s_sp >> 1], l_in = s->ctx_lps[s_in >> 1], l_ch = s->ctx_lps[s_ch >> 1], l_cu = s->ctx_lps[s_cu >> 1], l_cl = s->ctx_lps[s_cl >> 1];
+    KVZ_TOGETHER(f_sp, f_in, f_ch, f_cu, f_cl, l_sp, l_in, l_ch, l_cu, l_cl);
+    const int n_sp = ctx_next_with(s_sp, b_sp, l_sp), n_in = ctx_next_with(s_in, b_in, l_in), n_ch = ctx_next_with(s_ch, 0, l_ch);
+    const int n_cu = ctx_next_with(s_cu, cb_u, l_cu), n_cl = ctx_next_with(s_cl, cb_y, l_cl);
+    // (3) the second bin on the chroma flag's context
     const int s_cv = adaptive ? n_cu : s_cu;
-    const float f_cv = s->entropy_fbits[s_cv ^ cb_v];
-    const int n_cv = ctx_next(s_cv, cb_v);
+    float f_cv = s->entropy_fbits[s_cv ^ cb_v];
+    int l_cv = s->ctx_lps[s_cv >> 1];
+    KVZ_TOGETHER(f_cv, l_cv);
+    const int n_cv = ctx_next_with(s_cv, cb_v, l_cv);
     if (adaptive) {
-      if (has_sp) cs[i_sp] = (u8)n_sp;
-      cs[KVZ_CX_INTRA] = (u8)n_in; cs[KVZ_CX_CHROMA] = (u8)n_ch; cs[i_cc] = (u8)n_cv; cs[i_cl] = (u8)n_cl;
+      if (has_sp) st03 = (st03 & ~(255u << (8 * i_sp))) | ((u32)n_sp << (8 * i_sp));
+      st47 = (st47 & 0x00ff0000u) | (u32)n_in | ((u32)n_ch << 8) | ((u32)n_cl << 24);
+      st89 = (st89 & 0xff00u) | (u32)n_cv;
+      __builtin_memcpy(cs, &st03, 4); __builtin_memcpy(cs + 4, &st47, 4); __builtin_memcpy(cs + 8, &st89, 2);
     }
     // cu_bits
     double bits = 0;
     if (has_sp) bits += (double)f_sp;
     bits += ((double)f_in + (b_in ? ((mode == preds[0]) ? 1 : 2) : 5)) + (double)f_ch;
-    double cost = bits * m->lambda;
+    double cost = bits * lambda;
     // leaf_rd_cost
-    double tr_tree_bits = 0, coeff_bits = 0;
+    double tr_tree_bits = 0;
     tr_tree_bits += (double)f_cu;
     tr_tree_bits += (double)f_cv;
     tr_tree_bits += (double)f_cl;
-    if (known_coeff_bits) coeff_bits += *known_coeff_bits;
-    else {
-      if (cb_y) coeff_bits += (double)s->acc[3] / 256.0;
-      if (cb_u) coeff_bits += (double)s->acc[4] / 256.0;
-      if (cb_v) coeff_bits += (double)s->acc[5] / 256.0;
+    if (!known_coeff_bits) {  // kvz_fast_coeff_cost (rdo.c:311-326): the weight sums of the quantisation stage
+      if (cb_y) coeff_bits += (double)wy / 256.0;
+      if (cb_u) coeff_bits += (double)wu / 256.0;
+      if (cb_v) coeff_bits += (double)wv / 256.0;
     }
-    const unsigned luma_ssd = s->acc[0], chroma_ssd = s->acc[1] + s->acc[2];
+    const unsigned chroma_ssd = ssd_u + ssd_v;
     const double lbits = tr_tree_bits + coeff_bits;
-    cost += luma_ssd * 0.8 + chroma_ssd * 1.5 + lbits * m->lambda;
+    cost += luma_ssd * 0.8 + chroma_ssd * 1.5 + lbits * lambda;
     return cost;
   }
 
@@ -2715,7 +2709,8 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false> stru
       }
       if (tid == 32) price_modes();
       if (tid == 33) {
-        const int left = x >= 4 ? neighbour_cu(4, x - 1, y) : -1, above = (y >= 4 && yl > 0) ? neighbour_cu(4, x, y - 1) : -1;
+        int left, above;
+        neighbour_pair(4, x, y, &left, &above);
         mpm_candidates(y, left, above, s->preds);
       }
       if (tid == 34) { s->acc[0] = 0; s->acc[3] = 0; s->acc[6] = 0; }
@@ -2938,7 +2933,7 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false> stru
         // One lane per dword of a record, 95 lanes at once.  Lanes 0..79, border pixels -- per plane (Y 40 | U 20 | V 20 lanes), w4 = a quarter of the CTU's width in
         // it: w4 dwords of the left CTU's right column -> bpx_left[c][1..], w4 of the upper CTU's bottom row and w4 / 2 of the upper-right CTU's -> bpx_top[c][1..]
         // (index i <-> y = oy - 1 + i / x = ox - 1 + i: the corner in front puts these four bytes on an odd address).  Lanes 80..82: the corner of a plane, the last
-        // sample of the upper-left CTU's bottom row.  Lanes 83..90: the eight dwords of nb_depth | nb_mode.
+        // sample of the upper-left CTU's bottom row.  Lanes 83..90: the eight dwords of nb_cu.
         if (tid < 80) {
           const int c = tid < 40 ? 0 : (tid < 60 ? 1 : 2), t = tid - (c == 0 ? 0 : (c == 1 ? 40 : 60)), w4 = c ? 8 : 16, po = c == 0 ? 0 : (c == 1 ? 64 : 96);  // po: the plane inside a 128-byte row / column record
           const int part = t < w4 ? 0 : (t < 2 * w4 ? 1 : 2), j = 4 * (t - part * w4);
@@ -2950,12 +2945,17 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false> stru
           const u8 v = r_tl ? (u8)(load_shared_dword(r_tl + po + lw - 4) >> 24) : 0;
           s->bpx_left[c][0] = v; s->bpx_top[c][0] = v;
         } else if (tid < 91) {
-          // record [256..287]: depth, mode of the bottom 8x8 row, depth, mode of the right 8x8 column, 8 bytes each
-          const int k = tid - 83, side = (k >> 1) & 1, what = k >> 2;  // what: 0 depth, 1 mode; side: 0 left, 1 top
+          // record [256..287]: depth, mode of the bottom 8x8 row, depth, mode of the right 8x8 column, 8 bytes each -> nb_cu, a lane per pair of entries
+          const int k = tid - 83, side = k < 4 ? 0 : 1, j = k & 3;  // side: 0 left, 1 top; entries 2 j and 2 j + 1 of it
           const u8 *r = side == 0 ? r_left : r_top;
-          const u32 v = r ? load_shared_dword(r + 256 + (side == 0 ? 16 : 0) + what * 8 + (k & 1) * 4) : 0;
-          static_assert(__builtin_offsetof(CtuSharedT<CABAC>, nb_mode) == __builtin_offsetof(CtuSharedT<CABAC>, nb_depth) + 16 && __builtin_offsetof(CtuSharedT<CABAC>, nb_depth) % 4 == 0, "nb_depth | nb_mode as eight dwords");
-          wide_store<4>(&s->nb_depth[0][0] + 4 * k, WideBytes<4>{ { v } });
+          u32 v = 0;
+          if (r) {
+            const int at = 256 + (side == 0 ? 16 : 0) + (j >> 1) * 4, sh = 16 * (j & 1);
+            const u32 d = load_shared_dword(r + at) >> sh, md = load_shared_dword(r + at + 8) >> sh;
+            v = (1u | ((d & 3u) << 1) | ((md & 255u) << 8)) | ((1u | (((d >> 8) & 3u) << 1) | (((md >> 8) & 255u) << 8)) << 16);
+          }
+          static_assert(__builtin_offsetof(CtuSharedT<CABAC>, nb_cu) % 4 == 0 && sizeof(((CtuSharedT<CABAC> *)0)->nb_cu) == 32, "nb_cu as eight dwords");
+          wide_store<4>(reinterpret_cast<u8 *>(&s->nb_cu[0][0]) + 4 * k, WideBytes<4>{ { v } });
         } else if (tid < 94) {  // one entry behind each: nothing behind the left column, the next sample of the upper-right CTU's row
           const int c = tid - 91, po = c == 0 ? 0 : (c == 1 ? 64 : 96), lw = c ? 32 : 64;
           s->bpx_left[c][lw + 1] = 0;
@@ -3087,7 +3087,8 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false> stru
         // split-unit context (encode_coding_tree.c:148-163, 205-225)
         for (int j = 0; j < 4; j++) {
           const int px = x + 4 * (j & 1), py = y + 4 * (j >> 1), pm = rl->mode4[0][(yl >> 3) * 8 + (xl >> 3)][j];
-          const int left = px > 0 ? neighbour_cu(0, px - 1, py) : -1, above = (py & 63) > 0 ? neighbour_cu(0, px, py - 1) : -1;
+          int left, above;
+          neighbour_pair(0, px, py, &left, &above);
           int8_t preds[3];
           mpm_candidates(py, left, above, preds);
           ctx_code(KVZ_CX_INTRA, pm == preds[0] || pm == preds[1] || pm == preds[2]);
@@ -3100,7 +3101,8 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false> stru
         continue;
       }
       {
-        const int left = x > 0 ? neighbour_cu(0, x - 1, y) : -1, above = (y & 63) > 0 ? neighbour_cu(0, x, y - 1) : -1;
+        int left, above;
+        neighbour_pair(0, x, y, &left, &above);
         int8_t preds[3];
         mpm_candidates(y, left, above, preds);
         ctx_code(KVZ_CX_INTRA, cu->mode == preds[0] || cu->mode == preds[1] || cu->mode == preds[2]);  // prev_intra_luma_pred_flag; mpm_idx / rem mode are bypass

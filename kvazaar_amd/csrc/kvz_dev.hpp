@@ -17,6 +17,7 @@
 #include "kvz_ops.hpp"
 #include "kvz_sao.hpp"
 #include "kvz_entropy.hpp"
+#include "kvz_select.hpp"
 
 namespace kvz {
 
@@ -300,6 +301,21 @@ dev_transform_small_mfma_kernel(const i16 *in, i16 *out, const int count, const 
 // from the side reference (intra-generic.c:82-104); the others read the staged bytes directly.
 // Bytes per block: 2 (2 W + 1) read, W^2 written.
 constexpr int kAngularGroupsPerLane = 8;  // 2048 groups = 8 KB of output per workgroup: enough bytes in flight per barrier phase to cover the load latency
+// kvz_hip_dev_intra_select: the CTU pass's selection (select_on_wave) on tables in memory, a wavefront per table -- lane m brings mode m's SATD and cost as
+// CtuProgramT::replay_selection does from LDS
+__global__ void __launch_bounds__(256) dev_intra_select_kernel(const u32 *raw, const int8_t *preds, const double *mode_bits, const int count, const int log2w, const int nblk,
+                                                               int32_t *winner)
+{
+  const long table = (long)blockIdx.x * 4 + (threadIdx.x >> 6);  // wavefront-uniform: all 64 lanes stay or leave together
+  if (table >= count) return;
+  const int lane = threadIdx.x & 63, my_mode = lane < 35 ? lane : 0;
+  const int p0 = preds[3 * table], p1 = preds[3 * table + 1], p2 = preds[3 * table + 2];
+  const double bits[3] = { mode_bits[3 * table], mode_bits[3 * table + 1], mode_bits[3 * table + 2] };
+  const u32 my_raw = select_satd_sum(raw + (table * 35 + my_mode) * nblk, nblk);
+  const int w = select_on_wave(lane, my_raw, select_mode_cost(my_raw, my_mode, p0, p1, p2, bits), p0, p1, p2, log2w);
+  if (lane == 0) winner[table] = w;
+}
+
 template <int L2> __global__ void __launch_bounds__(256) dev_angular_kernel(const u8 *above, const u8 *left, const int count, const int mode, u8 *out)
 {
   constexpr int W = 1 << L2, NG = kAngularGroupsPerLane, GPB = W * W / 4, BLOCKS = 256 * NG / GPB, RS = 2 * W + 1, ES = (2 * W + 1 + 8 + 3) & ~3;
@@ -1253,6 +1269,14 @@ int kvz_hip_dev_angular_pred(int log2_width, int mode, const uint8_t *ref_above,
   case 5: KVZ_DEV_LAUNCH(kvz::dev_angular_kernel<5>, threads, ref_above, ref_left, count, mode, out); break;
   default: fprintf(stderr, "kvz_hip_dev_angular_pred: unsupported log2_width=%d\n", log2_width); return -1;
   }
+  return 0;
+}
+
+int kvz_hip_dev_intra_select(int log2w, int nblk, const uint32_t *raw, const int8_t *preds, const double *mode_bits, int count, int32_t *winner)
+{
+  if (!((log2w == 3 && nblk == 1) || (log2w == 4 && nblk == 4))) { fprintf(stderr, "kvz_hip_dev_intra_select: unsupported log2w=%d nblk=%d\n", log2w, nblk); return -1; }
+  if (count <= 0) return 0;
+  KVZ_DEV_LAUNCH(kvz::dev_intra_select_kernel, ((long)count + 3) / 4 * 256, raw, preds, mode_bits, count, log2w, nblk, winner);
   return 0;
 }
 

@@ -22,6 +22,7 @@ class Dev:
             f.restype = None; f.argtypes = [ci, vp, vp, ci, vp]
         l.kvz_hip_dev_transform.restype = None; l.kvz_hip_dev_transform.argtypes = [ci, vp, vp, vp, ci, ci]
         l.kvz_hip_dev_angular_pred.restype = None; l.kvz_hip_dev_angular_pred.argtypes = [ci, ci, vp, vp, ci, vp]
+        l.kvz_hip_dev_intra_select.restype = ci; l.kvz_hip_dev_intra_select.argtypes = [ci, ci, vp, vp, vp, ci, vp]
 
     def put(self, a):
         a = np.ascontiguousarray(a)
