@@ -209,6 +209,27 @@ long kvz_hip_batch_entropy_code_models(kvz_hip_batch *b, const kvz_hip_picture_m
 long kvz_hip_batch_entropy_code_then_models(kvz_hip_batch *b, const kvz_hip_picture_models *models, int sao, const uint8_t *not_last, uint8_t *out, size_t capacity,
                                             uint32_t *substream_bytes, kvz_hip_batch *next, const kvz_hip_picture_models *next_models);
 
+/* ---- Per-coefficient scaling lists (kvz_hip_scaling_lists, kvz_hip_types.h) ----
+ * kvazaar's --scaling-list default: H.265 tables 7-5 and 7-6 (scalinglist.c:266-282), every DC term 16. */
+void kvz_hip_scaling_lists_default(kvz_hip_scaling_lists *lists);
+/* Gives the batch n_sets list sets and each picture one of them: set_of_picture[n_frames of the batch] (HOST) holds an index below n_sets, or 0xffff for a picture
+ * that stays flat; NULL: every picture uses set 0.  n_sets == 0 clears the state: the batch is then what it was before the first such call.  The arrays are copied
+ * (the forward factors (quant_scale << 4) / entry and the inverse ones inv_quant_scale * entry are derived here, once per set and qp % 6).  State of the batch like
+ * kvz_hip_batch_set_device_share: it holds for every later kvz_hip_intra_frames and kvz_hip_intra_frames_models on the batch (also the passes
+ * kvz_hip_batch_entropy_code_then[_models] start on it as `next`), with each picture's luma factors taken at its model's qp % 6 and its chroma factors at its chroma QP's.
+ * Pictures with lists and pictures without share one launch; a flat picture of such a launch comes out byte for byte as in a launch on a batch without lists, and a
+ * batch without lists launches the kernels it launched before.  Loop filters, SAO, hashes, distortion and the entropy coder do not depend on lists (the lists
+ * themselves are SPS / PPS syntax and stay with the host).
+ * The factor rows and one word per picture (its two rows at its QP) are kept in a device buffer of the batch and staged by the pass like the model table of
+ * kvz_hip_intra_frames_models: compared with what the device holds on every launch and copied -- a small copy the call waits for -- only when the sets, a picture's set or a
+ * picture's QP changed since the last launch; a steady chain of launches pays one copy.  (A pass started as `next` by kvz_hip_batch_entropy_code_then pays that wait inside
+ * the overlap when its QPs change from launch to launch.)
+ * Returns 0, or -1 -- with a message on stderr and the batch's previous state kept -- for: a struct_size this library does not know; an entry or a non-zero DC term
+ * outside 13 .. 255; a set index that is neither below n_sets nor 0xffff; n_sets < 0 or > 65535, or sets == NULL with n_sets > 0; a batch under KVZ_HIP_SCHED=wave.
+ * While a batch has lists, a pass whose model (any model of a table) has rdoq, search_nxn or signhide is refused: -1, a message that names scaling lists, nothing
+ * queued.  (kvz_rdoq with lists needs the per-coefficient error scales of scalinglist.c:351-367, the hiding rule a factor per position: neither is built.) */
+int  kvz_hip_batch_set_scaling_lists(kvz_hip_batch *b, const kvz_hip_scaling_lists *sets, int n_sets, const uint16_t *set_of_picture);
+
 #ifdef __cplusplus
 }
 #endif

@@ -87,6 +87,33 @@ class PictureModels:
         return len(self.qps)
 
 
+class ScalingListsStruct(C.Structure):
+    """kvz_hip_scaling_lists (include/kvz_hip_types.h)"""
+    _fields_ = [("struct_size", C.c_uint32), ("coeff", ((C.c_int32 * 64) * 6) * 4), ("dc", (C.c_int32 * 6) * 4)]
+
+
+class ScalingLists:
+    """One set of per-coefficient scaling lists (kvz_hip_scaling_lists; kvazaar's --scaling-list / --cqmfile): coeff [4][6][64] as the encoder holds
+    scaling_list_coeff[size_id][list_id] (16 entries at 4x4, 64 above, raster order, 13 .. 255), dc [4][6] (0 = 16).  HipBatch.set_scaling_lists takes a sequence of them."""
+
+    def __init__(self, coeff, dc=None):
+        self.struct = ScalingListsStruct()
+        self.struct.struct_size = C.sizeof(ScalingListsStruct)
+        self.coeff = np.ascontiguousarray(coeff, np.int32).reshape(4, 6, 64)
+        self.dc = np.zeros((4, 6), np.int32) if dc is None else np.ascontiguousarray(dc, np.int32).reshape(4, 6)
+        C.memmove(self.struct.coeff, self.coeff.ctypes.data, self.coeff.nbytes)
+        C.memmove(self.struct.dc, self.dc.ctypes.data, self.dc.nbytes)
+
+    @classmethod
+    def default(cls, lib):
+        """--scaling-list default (kvz_hip_scaling_lists_default): H.265 tables 7-5 / 7-6, DC 16"""
+        st = ScalingListsStruct()
+        lib.kvz_hip_scaling_lists_default.argtypes = [C.POINTER(ScalingListsStruct)]
+        lib.kvz_hip_scaling_lists_default.restype = None
+        lib.kvz_hip_scaling_lists_default(C.byref(st))
+        return cls(np.ctypeslib.as_array(st.coeff), np.ctypeslib.as_array(st.dc))
+
+
 def _is_table(model):
     return isinstance(model, PictureModels)
 
@@ -176,6 +203,29 @@ class HipBatch:
         self.lib.kvz_hip_batch_set_device_share.argtypes = [C.c_void_p, C.c_int, C.c_int]
         self.lib.kvz_hip_batch_set_device_share.restype = None
         self.lib.kvz_hip_batch_set_device_share(self.handle, num, den)
+
+    FLAT = 0xffff  # set_of_picture: the picture stays without lists
+
+    def set_scaling_lists(self, sets, set_of_picture=None):
+        """kvz_hip_batch_set_scaling_lists: the batch's later passes quantise picture i under sets[set_of_picture[i]] (HipBatch.FLAT: flat; None: every picture under
+        sets[0]).  sets: a sequence of ScalingLists.  State of the batch until changed or cleared; raises BatchError when the library refuses (see stderr), and the
+        previous state stays"""
+        sets = list(sets)
+        arr = (ScalingListsStruct * max(len(sets), 1))(*[s.struct for s in sets])
+        index = None
+        if set_of_picture is not None:
+            if len(set_of_picture) != self.n:
+                raise ValueError(f"set_of_picture of {len(set_of_picture)} pictures for a batch of {self.n}")
+            index = (C.c_uint16 * self.n)(*[int(v) for v in set_of_picture])
+        f = self.lib.kvz_hip_batch_set_scaling_lists
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        f.restype = C.c_int
+        if f(self.handle, C.addressof(arr) if sets else None, len(sets), C.addressof(index) if index is not None else None) != 0:
+            raise BatchError("kvz_hip_batch_set_scaling_lists: refused (see stderr)")
+
+    def clear_scaling_lists(self):
+        """the batch is again what it was before the first set_scaling_lists"""
+        self.set_scaling_lists([])
 
     def sync(self):
         if self.lib.kvz_hip_batch_sync(self.handle) != 0:

@@ -1,7 +1,7 @@
 """Builds libkvz_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
-The library is eleven translation units compiled in parallel: kvz_hip.hip (C ABI, per-call ops, streaming kernels, host side of the batch; with
--DKVZ_CTU_SEPARATE_TUS it only declares the CTU kernels) and kvz_ctu_tu.hip eight times, one CTU kernel instantiation each (-DKVZ_CTU_KERNEL_TU=0..7,
+The library is fifteen translation units compiled in parallel: kvz_hip.hip (C ABI, per-call ops, streaming kernels, host side of the batch; with
+-DKVZ_CTU_SEPARATE_TUS it only declares the CTU kernels) and kvz_ctu_tu.hip twelve times, one CTU kernel instantiation each (-DKVZ_CTU_KERNEL_TU=0..11; 8..11 are the scaling-list ones,
 csrc/kvz_ctu_kernels.hpp).  Objects are rebuilt when one of the files they include (hipcc -MD) is newer."""
 import os
 import subprocess
@@ -18,7 +18,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
 # (object name, source, extra defines)
 MFMA_VGPR_FORM = ["-mllvm", "-amdgpu-mfma-vgpr-form"]  # an internal LLVM option, only a tuning of the streaming transform kernels: dropped where hipcc does not know it (_probe_flags)
 UNITS = ([("kvz_hip", "kvz_hip.hip", ["-DKVZ_CTU_SEPARATE_TUS"] + MFMA_VGPR_FORM)]  # (the streaming transform kernels: accumulators in VGPRs, no v_accvgpr moves around the bias pass)
-         + [(f"kvz_ctu_tu{k}", "kvz_ctu_tu.hip", [f"-DKVZ_CTU_KERNEL_TU={k}"]) for k in range(8)]
+         + [(f"kvz_ctu_tu{k}", "kvz_ctu_tu.hip", [f"-DKVZ_CTU_KERNEL_TU={k}"]) for k in range(12)]
          + [("kvz_inter_tu0", "kvz_inter_tu.hip", ["-DKVZ_ICTU_CABAC=0"]), ("kvz_inter_tu1", "kvz_inter_tu.hip", ["-DKVZ_ICTU_CABAC=1"])])  # the inter CTU pass's two builds (csrc/kvz_inter_kernels.hpp)
 
 

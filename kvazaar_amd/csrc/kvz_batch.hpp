@@ -11,6 +11,7 @@
 #include "kvz_entropy.hpp"  // KVZ_ENTROPY_CTX_ROW: the rows of a model table
 #include "kvz_picture_models.hpp"
 #include "kvz_runtime.hpp"
+#include "kvz_scaling_lists.hpp"
 
 #include "kvz_ctu_kernels.hpp"
 
@@ -53,6 +54,13 @@ struct kvz_hip_batch {
   // and the host image it was copied from: a call with the same table skips the copy, like last_entropy
   kvz::DevBuf d_models;
   std::vector<uint8_t> h_models;
+  // scaling lists (kvz_hip_batch_set_scaling_lists; n_list_sets == 0: none): the factor rows of every set and, behind them, of the flat list (kvz_scaling_lists.hpp),
+  // and every picture's set.  On the device, staged per launch like the model table (scaling_lists_stage): the rows | every picture's two rows at its QP
+  int n_list_sets = 0;
+  std::vector<uint32_t> list_rows;
+  std::vector<uint16_t> list_set_of_picture;
+  kvz::DevBuf d_lists;
+  std::vector<uint32_t> h_lists;
   int device;   // the batch's buffers and stream live here; every entry point binds the calling thread to it
   int failed;   // sticky: a CTU hand-off wait of some run timed out, the results of that run are invalid
   unsigned long long wait_ticks;
@@ -224,9 +232,52 @@ inline ModelTableView picture_models_stage(kvz_hip_batch *b, const kvz_hip_pictu
   return v;
 }
 
+
+// The factor table of a launch on a batch that has lists: the batch's rows and every picture's two rows at the QP of its model (pm: the launch's table, or nullptr
+// and `qp` for all), copied when it differs from what the device holds; the two pointers go behind the ticket words (kvz_ctu_kernels.hpp KVZ_SCHED_LISTS_AT).
+inline void scaling_lists_stage(kvz_hip_batch *b, const kvz_hip_picture_models *pm, int qp)
+{
+  const size_t n_rows = b->list_rows.size(), nf = (size_t)b->n_frames, bytes = (n_rows + nf) * sizeof(uint32_t);
+  bool fresh = false;
+  if (bytes > b->d_lists.bytes) {
+    KVZ_HIP_CHECK(hipStreamSynchronize(b->stream));  // a launch in flight may still read the old one
+    if (b->d_lists.p) KVZ_HIP_CHECK(hipFree(b->d_lists.p));
+    b->d_lists.bytes = bytes;
+    KVZ_HIP_CHECK(hipMalloc(&b->d_lists.p, b->d_lists.bytes));
+    fresh = true;
+  }
+  std::vector<uint32_t> image(b->list_rows);
+  image.resize(n_rows + nf);
+  for (size_t f = 0; f < nf; f++) image[n_rows + f] = scaling_list_rows_of_picture(b->list_set_of_picture[f], b->n_list_sets, pm ? pm->models[pm->model_of_picture[f]].qp : qp);
+  if (fresh || image != b->h_lists) {
+    CtuListTable lt;
+    lt.rows = (const uint32_t *)b->d_lists.p;
+    lt.rows_of_picture = lt.rows + n_rows;
+    static_assert(sizeof(CtuListTable) <= (KVZ_SCHED_TICKET_WORDS - KVZ_SCHED_LISTS_AT) * sizeof(unsigned), "d_ticket");
+    KVZ_HIP_CHECK(hipMemcpyAsync(b->d_lists.p, image.data(), bytes, hipMemcpyHostToDevice, b->stream));
+    KVZ_HIP_CHECK(hipMemcpyAsync(b->d_ticket + KVZ_SCHED_LISTS_AT, &lt, sizeof lt, hipMemcpyHostToDevice, b->stream));
+    KVZ_HIP_CHECK(hipStreamSynchronize(b->stream));
+    b->h_lists.swap(image);
+  }
+}
+
 }  // namespace kvz
 
 extern "C" {
+
+void kvz_hip_scaling_lists_default(kvz_hip_scaling_lists *lists) { kvz::scaling_lists_default(lists); }
+
+int kvz_hip_batch_set_scaling_lists(kvz_hip_batch *b, const kvz_hip_scaling_lists *sets, int n_sets, const uint16_t *set_of_picture)
+{
+  if (!b || !kvz::scaling_list_sets_known(sets, n_sets, set_of_picture, b->n_frames, b->sched_ticket != 0, "kvz_hip_batch_set_scaling_lists")) return -1;
+  b->n_list_sets = n_sets;
+  b->list_rows.assign(n_sets ? (size_t)(n_sets + 1) * 6 * kvz::KVZ_LIST_ROW : 0, 0);
+  b->list_set_of_picture.assign(n_sets ? (size_t)b->n_frames : 0, 0);
+  for (int k = 0; k < n_sets; k++) kvz::scaling_list_rows(&sets[k], b->list_rows.data() + (size_t)k * 6 * kvz::KVZ_LIST_ROW);
+  if (n_sets) kvz::scaling_list_rows(nullptr, b->list_rows.data() + (size_t)n_sets * 6 * kvz::KVZ_LIST_ROW);
+  if (n_sets && set_of_picture) b->list_set_of_picture.assign(set_of_picture, set_of_picture + b->n_frames);
+  return 0;
+}
 
 void kvz_hip_intra_cost_model_init(int qp, uint64_t coeff_weights, kvz_hip_intra_cost_model *model) { kvz::cost_model_init(qp, coeff_weights, model); }
 uint64_t kvz_hip_default_coeff_weights(int qp) { return qp >= 0 && qp < 50 ? kvz::kDefaultCoeffWeights[qp] : 0; }
@@ -338,7 +389,7 @@ void kvz_hip_batch_destroy(kvz_hip_batch *b)
   if (b->entropy_out.p) (void)hipFree(b->entropy_out.p);
   if (b->ev_up) { (void)hipEventSynchronize(b->ev_up); (void)hipEventDestroy(b->ev_up); }
   if (b->ev_src_read) (void)hipEventDestroy(b->ev_src_read);
-  (void)hipFree(b->d_sse); (void)hipFree(b->d_models.p);
+  (void)hipFree(b->d_sse); (void)hipFree(b->d_models.p); (void)hipFree(b->d_lists.p);
   (void)hipStreamDestroy(b->stream);
   delete b;
 }
@@ -456,9 +507,11 @@ void kvz_hip_batch_order_after(kvz_hip_batch *b, kvz_hip_batch *other)
 
 // The pass of kvz_hip_intra_frames (!table: `model` for every picture) and of kvz_hip_intra_frames_models (table: picture_models_stage has put it on the device; `model` = its first: the switches and
 // the price table every model shares; any_cabac: some model prices coefficients with the CABAC model -- that instantiation then prices the others' through its run-time switch;
-// any_signhide: some model hides sign bits -- the launch takes a sign-hiding instantiation, which reads the switch of the drawn picture's model)
-static int kvz_intra_frames_queue(kvz_hip_batch *b, const kvz_hip_intra_cost_model *model, bool table, bool any_cabac, bool any_signhide)
+// any_signhide: some model hides sign bits -- the launch takes a sign-hiding instantiation, which reads the switch of the drawn picture's model; pm: the table, or nullptr).
+// A batch that has scaling lists takes the instantiations that quantise under a factor per position (the entry points have refused rdoq, search_nxn and signhide).
+static int kvz_intra_frames_queue(kvz_hip_batch *b, const kvz_hip_intra_cost_model *model, const kvz_hip_picture_models *pm, bool any_cabac, bool any_signhide)
 {
+  const bool table = pm != nullptr, lists = b->n_list_sets > 0;
   kvz::batch_enter(b);
   const kvz::CtuFrames &F = b->F;
   int launches = 0;
@@ -485,6 +538,7 @@ static int kvz_intra_frames_queue(kvz_hip_batch *b, const kvz_hip_intra_cost_mod
   if (!b->sched_ticket && (cm.search_32x32 || cm.rdoq || cm.search_nxn)) { fprintf(stderr, "kvz_hip_intra_frames: search_32x32 / rdoq / search_nxn need the ticket schedule\n"); return -1; }
   if (!b->sched_ticket && cm.no_wpp) { fprintf(stderr, "kvz_hip_intra_frames: the one-launch-per-diagonal schedule (KVZ_HIP_SCHED=wave) needs WPP\n"); return -1; }
   if (cm.rdoq && !cm.coeff_cabac) { fprintf(stderr, "kvz_hip_intra_frames: rdoq needs coeff_cabac (kvazaar's presets with --rdoq have --fast-residual-cost 0)\n"); return -1; }
+  if (lists) kvz::scaling_lists_stage(b, pm, model->qp);  // (a batch under the other schedule has none)
   if (b->sched_ticket) {
     b->epoch++;
     KVZ_HIP_CHECK(hipMemsetAsync(b->d_ticket, 0, sizeof(unsigned), b->stream));  // the error word behind it stays: sticky across runs
@@ -492,7 +546,13 @@ static int kvz_intra_frames_queue(kvz_hip_batch *b, const kvz_hip_intra_cost_mod
     kvz::CtuSched sc{ cm.no_wpp ? b->d_items_raster : b->d_items, b->d_ticket, b->d_done, b->d_error, b->total_items, b->epoch, cm.no_wpp | (table ? kvz::KVZ_SCHED_MODEL_TABLE : 0), b->wait_ticks };
     // two instantiations: the one without the CABAC coefficient model carries none of its code, registers or context storage
     // (the instantiations that search 32x32 CUs, --pu-depth-intra 1-3, are separate ones too: the others stay as they were)
-    if (cm.rdoq || cm.search_nxn) {  // --rdoq and / or NxN partitions (preset `medium`): their own instantiation (32x32 search and the coefficient cost model switched by the model)
+    if (lists) {
+      if (cm.search_32x32) {
+        if (cm.coeff_cabac) hipLaunchKernelGGL((kvz::intra_ctu_ticket_kernel_lists<true, true>), dim3(b->grid_ticket), dim3(KVZ_CTU_THREADS), 0, b->stream, F, cm, kvz::device_tables(), sc);
+        else hipLaunchKernelGGL((kvz::intra_ctu_ticket_kernel_lists<false, true>), dim3(b->grid_ticket), dim3(KVZ_CTU_THREADS), 0, b->stream, F, cm, kvz::device_tables(), sc);
+      } else if (cm.coeff_cabac) hipLaunchKernelGGL((kvz::intra_ctu_ticket_kernel_lists<true, false>), dim3(b->grid_ticket), dim3(KVZ_CTU_THREADS), 0, b->stream, F, cm, kvz::device_tables(), sc);
+      else hipLaunchKernelGGL((kvz::intra_ctu_ticket_kernel_lists<false, false>), dim3(b->grid_ticket), dim3(KVZ_CTU_THREADS), 0, b->stream, F, cm, kvz::device_tables(), sc);
+    } else if (cm.rdoq || cm.search_nxn) {  // --rdoq and / or NxN partitions (preset `medium`): their own instantiation (32x32 search and the coefficient cost model switched by the model)
       if (cm.search_nxn && !b->d_part) {
         KVZ_HIP_CHECK(hipMalloc((void **)&b->d_part, (size_t)(F.W / 8) * (F.H / 8) * b->n_frames));
         KVZ_HIP_CHECK(hipMalloc((void **)&b->d_mode4, (size_t)(F.W / 4) * (F.H / 4) * b->n_frames));
@@ -538,15 +598,17 @@ int kvz_hip_intra_frames(kvz_hip_batch *b, const kvz_hip_intra_cost_model *model
 {
   if (!b || !kvz::cost_model_known(model, "kvz_hip_intra_frames")) return -1;
   if (!kvz::signhide_known(model, b->sched_ticket != 0, "kvz_hip_intra_frames")) return -1;
-  return kvz_intra_frames_queue(b, model, false, model->coeff_cabac != 0, model->signhide != 0);
+  if (!kvz::scaling_lists_known(model, b->n_list_sets > 0, "kvz_hip_intra_frames")) return -1;
+  return kvz_intra_frames_queue(b, model, nullptr, model->coeff_cabac != 0, model->signhide != 0);
 }
 
 int kvz_hip_intra_frames_models(kvz_hip_batch *b, const kvz_hip_picture_models *pm)
 {
   if (!b || !kvz::picture_models_known(pm, b->n_frames, b->sched_ticket != 0, "kvz_hip_intra_frames_models")) return -1;
+  if (!kvz::scaling_lists_known(pm, b->n_list_sets > 0, "kvz_hip_intra_frames_models")) return -1;
   kvz::batch_enter(b);
   kvz::picture_models_stage(b, pm);
-  return kvz_intra_frames_queue(b, &pm->models[0], true, kvz::picture_models_any_cabac(pm), kvz::picture_models_any_signhide(pm));
+  return kvz_intra_frames_queue(b, &pm->models[0], pm, kvz::picture_models_any_cabac(pm), kvz::picture_models_any_signhide(pm));
 }
 
 int kvz_hip_batch_sync(kvz_hip_batch *b)

@@ -397,14 +397,23 @@ struct RdoqLds {
 // S32: the instantiation that can also SEARCH 32x32 CUs (kvz_hip_intra_cost_model::search_32x32, --pu-depth-intra 1-3); the others carry none of its code
 // SH: the instantiation that can hide sign bits (kvz_hip_intra_cost_model::signhide, --signhide): a stage between kvz_quant and everything that reads levels
 // (hide_signs), for the pictures whose model has the switch; the others carry none of its code.  Not with RDOQ (kvz_picture_models.hpp signhide_known).
-template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false> struct CtuProgramT {
+// LISTS: the instantiation of the batches that were given scaling lists (kvz_hip_batch_set_scaling_lists, --scaling-list): every level is quantised and dequantised
+// under the factors of its position (kvz_recon.hpp list_index), read from the picture's two rows of the batch's factor table -- lf_y at its luma qp % 6, lf_c at
+// its chroma one; a picture without lists has the rows of a flat list and comes out as from the other instantiations.  The table stays in memory (a few hundred
+// bytes per picture that the caches keep; the workgroup's LDS block has no room for it).  Not with RDOQ (its error scales per coefficient are not built) and not
+// with SH (the hiding rule prices a change with ONE factor): kvz_picture_models.hpp scaling_lists_known.
+template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false, bool LISTS = false> struct CtuProgramT {
   static_assert(!(SH && RDOQ), "kvz_rdoq's own sign hiding is not built");
+  static_assert(!(LISTS && (RDOQ || SH)), "scaling lists with kvz_rdoq or sign data hiding are not built");
   using CtxSet = CtxSetT<CABAC>;
   const CtuModel *m;
   const Tables *tb;
   CtuFrames F;
   CtuSharedT<CABAC> *s;
   RdoqLds *rl = nullptr;  // RDOQ instantiation only
+  const u32 *lf_y = nullptr, *lf_c = nullptr;  // LISTS instantiations only: the picture's factor rows (uniform)
+  // the factors of element e of a 2^l2 block of plane c
+  KVZ_DEV ListFactor factor_at(int c, int l2, int e) const { return list_factor(((c ? lf_c : lf_y) + c * KVZ_LIST_PLANE)[list_index(l2, e)]); }
   static constexpr bool NXN = RDOQ;
   KVZ_DEV bool nxn_on() const { return NXN && m->search_nxn; }
   KVZ_DEV bool cabac_on() const { return CABAC && m->coeff_cabac; }  // coefficients priced with the CABAC model (rdo.c:311-340)
@@ -1870,10 +1879,12 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false> stru
         for (int i = 0; i < n; i++) a += dct_at(l2, k, i) * (int)src[(j << l2) + i];
         const int cf = (i16)((a + add) >> shift);
         const QuantScalars q = s->qs[l2 - 2][LUMA ? 0 : 1];
-        const int level = quant_level(cf, q);
+        ListFactor f{ 0, 0 };
+        if constexpr (LISTS) f = factor_at(c, l2, e);
+        const int level = LISTS ? quant_level(cf, q, f.fwd) : quant_level(cf, q);
         levels_lds(lv, c)[e] = (i16)level;  // lv == 3 here
         if constexpr (SH) { if (hide) { tbuf(t, 0, c)[e] = (i16)cf; return; } }  // the coefficient stays for the hiding stage, where the dequantised one will go
-        tbuf(t, 0, c)[e] = dequant_level(level, q);
+        tbuf(t, 0, c)[e] = LISTS ? dequant_level(level, q, f.inv) : dequant_level(level, q);
         packed = level_cost(level, m->coeff_weights).word();
       };
       if (tid < 64) stage3(std::true_type(), tid); else if (tid < 96) stage3(std::false_type(), tid);
@@ -2197,12 +2208,14 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false> stru
             __builtin_memcpy(cf, KVZ_ALIGNED(tbuf(t, 0, c) + (seg << 3), 16), 16);
             u32 wsum = 0, nz = 0;
             for (int k = 0; k < 8; k++) {
-              const int level = quant_level(cf[k], q);
+              ListFactor f{ 0, 0 };
+              if constexpr (LISTS) f = factor_at(c, l2, (seg << 3) + k);  // (eight samples of one row: 8, 4 or 2 different list entries at 8, 16 or 32 samples a row)
+              const int level = LISTS ? quant_level(cf[k], q, f.fwd) : quant_level(cf[k], q);
               lvl[k] = (i16)level;
               const LevelCost lc = level_cost(level, cw_lo, cw_hi);
               wsum += lc.weight;
               nz += lc.nonzero;
-              dq[k] = dequant_level(level, q);
+              dq[k] = LISTS ? dequant_level(level, q, f.inv) : dequant_level(level, q);
             }
             packed = wsum | (nz << 24);
             __builtin_memcpy(KVZ_ALIGNED(coeff_dst(lv, c, xl, yl) + (seg << 3), 16), lvl, 16);
@@ -2225,12 +2238,14 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false> stru
         for (int e = tid; e < n2; e += KVZ_CTU_THREADS) {
           int level;
           if (RDOQ && m->rdoq) { level = (stage ? stage : cout)[e]; if (stage) cout[e] = (i16)level; }  // kvz_rdoq left them in LDS (above)
+          else if constexpr (LISTS) { level = quant_level(src[e], q, factor_at(c, l2, e).fwd); cout[e] = (i16)level; }
           else { level = quant_level(src[e], q); cout[e] = (i16)level; }
           if (stage && !(RDOQ && m->rdoq)) stage[e] = (i16)level;
           const LevelCost lc = level_cost(level, m->coeff_weights);
           wsum += lc.weight;
           nz += lc.nonzero;
-          dq[e] = dequant_level(level, q);
+          if constexpr (LISTS) dq[e] = dequant_level(level, q, factor_at(c, l2, e).inv);
+          else dq[e] = dequant_level(level, q);
         }
         block_add(&s->acc[3 + c], wsum);
         block_add(&s->acc[6 + c], nz);
@@ -2976,7 +2991,7 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false> stru
         s->mode_disp[mode] = (int8_t)(mode < 2 ? 0 : (md < 0 ? -disp_tab[ad] : disp_tab[ad]));
         s->mode_inv[mode] = (int16_t)(mode < 2 ? 0 : inv_tab[ad]);
       }
-      if (v >= 128 && v < 136) s->qs[(v - 128) >> 1][v & 1] = quant_scalars(m->qp, 8, 1, 0, 4 << ((v - 128) >> 1), (v & 1) ? 2 : 0);  // 8 bit, I slice, flat lists
+      if (v >= 128 && v < 136) s->qs[(v - 128) >> 1][v & 1] = quant_scalars(m->qp, 8, 1, LISTS ? 1 : 0, 4 << ((v - 128) >> 1), (v & 1) ? 2 : 0);  // 8 bit, I slice; flat lists, or the shifts of the rule that takes a factor per position
       if (v < 128) s->entropy_fbits[v] = m->entropy_fbits[v];
       if (v < 64) s->ctx_lps[v] = tb->ctx_next[1][2 * v];
       }

@@ -1,7 +1,7 @@
 // kvz_ctu_kernels.hpp -- the __global__ entry points of the batched CTU pass (the program itself is kvz_ctu.hpp) and their scheduling protocol.
 //
-// Build layout: the eight instantiations are the bulk of the library's compile time, so kvazaar_amd/build.py compiles each of them in a translation unit of
-// its own (kvz_ctu_tu.hip with -DKVZ_CTU_KERNEL_TU=<k>, k = 0..7), in parallel, next to kvz_hip.hip compiled with -DKVZ_CTU_SEPARATE_TUS -- which then only sees
+// Build layout: the twelve instantiations are the bulk of the library's compile time, so kvazaar_amd/build.py compiles each of them in a translation unit of
+// its own (kvz_ctu_tu.hip with -DKVZ_CTU_KERNEL_TU=<k>, k = 0..11), in parallel, next to kvz_hip.hip compiled with -DKVZ_CTU_SEPARATE_TUS -- which then only sees
 // DECLARATIONS here and launches the kernels through their host stubs.  Without that define kvz_hip.hip is self-contained as before (tools/build_variants.sh).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -55,7 +55,13 @@ template <bool CABAC> __global__ void __launch_bounds__(KVZ_CTU_THREADS) __attri
 // drains its stores, one lane releases at agent scope and stores the flag; consumer polls relaxed, one lane acquires,
 // then the workgroup barrier.  Compared with one launch per diagonal this removes the per-launch tail (a diagonal of
 // n CTUs x F frames rarely is a multiple of the resident workgroup count) and 61 of 62 launches.
-enum { KVZ_SCHED_MODEL_TABLE = 2 /* bit of CtuSched::no_wpp */, KVZ_SCHED_TABLE_AT = 4 /* words behind CtuSched::ticket */, KVZ_SCHED_TICKET_WORDS = 8 };
+enum { KVZ_SCHED_MODEL_TABLE = 2 /* bit of CtuSched::no_wpp */, KVZ_SCHED_TABLE_AT = 4 /* words behind CtuSched::ticket */, KVZ_SCHED_LISTS_AT = 8 /* likewise */, KVZ_SCHED_TICKET_WORDS = 12 };
+// The scaling-list factors of a launch on a batch that has lists (kvz_batch.hpp scaling_lists_stage), read by the LISTS instantiations alone, behind the ticket
+// words like the model table: rows of KVZ_LIST_ROW words (kvz_recon.hpp), one per list set and qp % 6, and for every picture its luma row | its chroma row << 16.
+struct CtuListTable {
+  const uint32_t *rows = nullptr;
+  const uint32_t *rows_of_picture = nullptr;  // [frames]
+};
 struct CtuSched {
   const uint32_t *items;  // [total]: frame << 16 | y << 8 | x  (CTU coordinates)
   unsigned *ticket;       // atomic ticket counter, zeroed before every launch; at ticket + KVZ_SCHED_TABLE_AT a CtuModelTable when no_wpp has KVZ_SCHED_MODEL_TABLE
@@ -102,7 +108,7 @@ __device__ __forceinline__ bool wait_done(unsigned *flag, unsigned epoch, unsign
 // sched.no_wpp & KVZ_SCHED_MODEL_TABLE: the pictures of the launch have models of their own (kvz_hip_intra_frames_models) -- `m` is loaded per CTU from the drawn picture's
 // row of the table behind the ticket words.  (A bit of a word the loop keeps anyway and a pointer it keeps anyway: a kernel argument of its own stayed live across the
 // whole program and cost the instantiations that spill a register more.)
-template <bool CABAC, bool S32, bool RDOQ, bool SH = false> __device__ __forceinline__ void ticket_loop(const CtuFrames &F, const CtuModel &model, const Tables *tb, const CtuSched &sched)
+template <bool CABAC, bool S32, bool RDOQ, bool SH = false, bool LISTS = false> __device__ __forceinline__ void ticket_loop(const CtuFrames &F, const CtuModel &model, const Tables *tb, const CtuSched &sched)
 {
   __shared__ CtuSharedT<CABAC> shared;
   __shared__ CtuModel m;  // scalars in LDS; its price table stays in HBM (kvz_hip_batch::d_entropy)
@@ -138,8 +144,14 @@ template <bool CABAC, bool S32, bool RDOQ, bool SH = false> __device__ __forcein
     KVZ_TRACE(2);  // neighbours there
     const bool run_it = shared.best_mode != 0;  // uniform.  (run() first writes the field behind several barriers of its own: no lane can still be reading it here)
     if (run_it) {
-      CtuProgramT<CABAC, S32, RDOQ, SH> p;
+      CtuProgramT<CABAC, S32, RDOQ, SH, LISTS> p;
       p.m = &m; p.tb = tb; p.F = F; p.s = &shared;
+      if constexpr (LISTS) {  // the picture's two factor rows, as scalars (the table is constant during the launch)
+        const CtuListTable lt = *reinterpret_cast<const CtuListTable *>(sched.ticket + KVZ_SCHED_LISTS_AT);
+        const uint32_t rows = (uint32_t)__builtin_amdgcn_readfirstlane((int)lt.rows_of_picture[frame]);
+        p.lf_y = lt.rows + (size_t)(rows & 0xffffu) * KVZ_LIST_ROW;
+        p.lf_c = lt.rows + (size_t)(rows >> 16) * KVZ_LIST_ROW;
+      }
       if constexpr (RDOQ) { __shared__ RdoqLds rdoq_lds; p.rl = &rdoq_lds; }
       p.frame = frame; p.cx = x * 64; p.cy = y * 64;
       p.lane_rot = (t * 64) & (KVZ_CTU_THREADS - 1);
@@ -180,6 +192,17 @@ template <bool S32> __global__ void __launch_bounds__(KVZ_CTU_THREADS) __attribu
 #else
 {
   ticket_loop<true, S32, false, true>(F, model, tb, sched);
+}
+#endif
+// Scaling lists (kvz_hip_batch_set_scaling_lists): the program that quantises and dequantises under a factor per coefficient position (kvz_ctu.hpp LISTS), for the
+// two coefficient cost models with and without the 32x32 search.  Launched only on a batch that has lists: every other launch takes the kernels above, unchanged.
+template <bool CABAC, bool S32> __global__ void __launch_bounds__(KVZ_CTU_THREADS) __attribute__((amdgpu_waves_per_eu(KVZ_CTU_WAVES_PER_EU))) KVZ_CTU_VGPR_ATTR intra_ctu_ticket_kernel_lists(const CtuFrames F, const CtuModel model, const Tables *tb,
+                                                                        const CtuSched sched)
+#if !KVZ_CTU_KERNEL_BODIES
+;
+#else
+{
+  ticket_loop<CABAC, S32, false, false, true>(F, model, tb, sched);
 }
 #endif
 // --rdoq / NxN partitions: its own register budget.  Round 3: kvz_rdoq runs as ONE out-of-line wavefront-cooperative routine (kvz_rdoq.hpp rdoq_block_wave), so the

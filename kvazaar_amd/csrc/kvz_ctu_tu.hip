@@ -1,9 +1,9 @@
-// kvz_ctu_tu.hip -- one CTU kernel instantiation per translation unit (see kvz_ctu_kernels.hpp): compiled eight times by kvazaar_amd/build.py with
-// -DKVZ_CTU_KERNEL_TU=0..7, in parallel with kvz_hip.hip.
+// kvz_ctu_tu.hip -- one CTU kernel instantiation per translation unit (see kvz_ctu_kernels.hpp): compiled twelve times by kvazaar_amd/build.py with
+// -DKVZ_CTU_KERNEL_TU=0..11, in parallel with kvz_hip.hip.
 #include <hip/hip_runtime.h>
 
 #ifndef KVZ_CTU_KERNEL_TU
-#error "compile with -DKVZ_CTU_KERNEL_TU=<0..7>"
+#error "compile with -DKVZ_CTU_KERNEL_TU=<0..11>"
 #endif
 #include "kvz_ctu_kernels.hpp"
 
@@ -25,6 +25,14 @@ template __global__ void intra_ctu_ticket_kernel<true, true, false>(KVZ_TICKET_A
 template __global__ void intra_ctu_ticket_kernel_signhide<false>(KVZ_TICKET_ARGS);
 #elif KVZ_CTU_KERNEL_TU == 7  // ... with 32x32 CUs searched
 template __global__ void intra_ctu_ticket_kernel_signhide<true>(KVZ_TICKET_ARGS);
+#elif KVZ_CTU_KERNEL_TU == 8  // scaling lists: fast estimate
+template __global__ void intra_ctu_ticket_kernel_lists<false, false>(KVZ_TICKET_ARGS);
+#elif KVZ_CTU_KERNEL_TU == 9  // ... CABAC coefficient model
+template __global__ void intra_ctu_ticket_kernel_lists<true, false>(KVZ_TICKET_ARGS);
+#elif KVZ_CTU_KERNEL_TU == 10  // ... and both with 32x32 CUs searched
+template __global__ void intra_ctu_ticket_kernel_lists<false, true>(KVZ_TICKET_ARGS);
+#elif KVZ_CTU_KERNEL_TU == 11
+template __global__ void intra_ctu_ticket_kernel_lists<true, true>(KVZ_TICKET_ARGS);
 #else
 #error "KVZ_CTU_KERNEL_TU out of range"
 #endif

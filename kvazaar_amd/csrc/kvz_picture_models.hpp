@@ -26,6 +26,21 @@ inline bool signhide_known(const kvz_hip_intra_cost_model *m, bool ticket_schedu
   if (!ticket_schedule) { fprintf(stderr, "%s: signhide needs the ticket schedule (not KVZ_HIP_SCHED=wave)\n", who); return false; }
   return true;
 }
+// Scaling lists are state of the batch (kvz_hip_batch_set_scaling_lists); while it has them (`lists`) the pass quantises with kvz_quant under a factor per position:
+// kvz_rdoq would need the per-coefficient error scales (scalinglist.c:351-367) and the hiding rule a factor per position in its rounding remainders -- not built.
+inline bool scaling_lists_known(const kvz_hip_intra_cost_model *m, bool lists, const char *who)
+{
+  if (!lists) return true;
+  if (m->rdoq) { fprintf(stderr, "%s: the batch has scaling lists: rdoq is not supported with them (kvz_rdoq's per-coefficient error scales are not on the device)\n", who); return false; }
+  if (m->search_nxn) { fprintf(stderr, "%s: the batch has scaling lists: search_nxn is not supported with them\n", who); return false; }
+  if (m->signhide) { fprintf(stderr, "%s: the batch has scaling lists: signhide is not supported with them (the hiding rule takes one quantiser factor per block)\n", who); return false; }
+  return true;
+}
+inline bool scaling_lists_known(const kvz_hip_picture_models *pm, bool lists, const char *who)
+{
+  for (int i = 0; lists && i < pm->n_models; i++) if (!scaling_lists_known(&pm->models[i], true, who)) return false;
+  return true;
+}
 
 // Is this a table a batch of n_frames pictures can run (ticket_schedule: the batch does not run under KVZ_HIP_SCHED=wave)?  Everything an entry point refuses is refused here, before anything is queued.
 inline bool picture_models_known(const kvz_hip_picture_models *pm, int n_frames, bool ticket_schedule, const char *who)

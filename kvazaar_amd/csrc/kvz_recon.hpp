@@ -1,6 +1,7 @@
 // kvz_recon.hpp -- the integer arithmetic of one sample on its way through intra_recon_tb_leaf (intra.c:561-608) + kvz_quantize_residual (quant-generic.c:198-292),
 // each step stated ONCE: the lane decompositions of the intra CTU pass (kvz_ctu.hpp recon_cu8, recon_tus, eval_pu) differ in which samples a lane takes, never in
-// what happens to a sample.  Plain functions without state, the same text for the device and the host simulation.  8 bit, flat scaling lists; sign data hiding
+// what happens to a sample.  Plain functions without state, the same text for the device and the host simulation.  8 bit; flat scaling lists, or -- for the batches
+// that were given lists (kvz_hip_batch_set_scaling_lists) -- a forward and an inverse factor per coefficient position (list_index, ListFactor); sign data hiding
 // (quant-generic.c:84-176) as a step of its own between quant_level and dequant_level, for the pictures whose model asks for it (sign_hide_group).
 #pragma once
 #include "kvz_ops.hpp"
@@ -31,13 +32,16 @@ template <class Mat> KVZ_DEV i16 inv_point(int n, Mat m, const i16 *in, int at, 
   return (i16)iclip(-32768, 32767, (a + (1 << (shift - 1))) >> shift);
 }
 
-// quant-generic.c:57-81: the level of one coefficient.  |cf| * q + add < 2^31 for 8-bit flat lists (32767 * 26214 + (171 << 18)), so 32-bit arithmetic is exact.
-KVZ_HD int quant_level(int cf, const QuantScalars &q)
+// quant-generic.c:57-81: the level of one coefficient under the forward factor of its position (quant_coeff[n]).  |cf| * q + add < 2^31 for 8-bit flat lists
+// (32767 * 26214 + (171 << 18)) and for every list the library accepts: entries >= 13 keep the factor (quant_scale << 4) / entry <= 32263, and
+// 32767 * 32263 + (171 << 18) = 1 101 988 445 -- so 32-bit arithmetic is exact.  (A full 32-bit multiply: the factor has 15 bits, the product 30.)
+KVZ_HD int quant_level(int cf, const QuantScalars &q, int fwd)
 {
-  int level = (int)(((u32)iabs(cf) * (u32)q.flat_q + (u32)q.add) >> q.q_bits);
+  int level = (int)(((u32)iabs(cf) * (u32)fwd + (u32)q.add) >> q.q_bits);
   if (cf < 0) level = -level;
   return iclip(-32768, 32767, level);
 }
+KVZ_HD int quant_level(int cf, const QuantScalars &q) { return quant_level(cf, q, q.flat_q); }  // flat lists: one factor for the block
 
 // ---- sign data hiding (quant-generic.c:84-176, --signhide): the decoder infers the sign of a coefficient group's first level (lowest scan position) from the parity
 // of the group's level sum whenever the first and the last level lie at least four scan positions apart, so the encoder makes the parity fit, by the one change of
@@ -107,6 +111,30 @@ template <class PtrU8> KVZ_HD void sign_hide_block(const i16 *coeff, i16 *level,
 
 // quant-generic.c:335-339
 KVZ_HD i16 dequant_level(int level, const QuantScalars &q) { return (i16)iclip(-32768, 32767, (level * q.dq_scale + (1 << (q.dq_shift - 1))) >> q.dq_shift); }
+// quant-generic.c:309-333: ... under the inverse factor of its position (de_quant_coeff[n] = inv_quant_scale * entry <= 72 * 255; q from quant_scalars with
+// scaling_list set: dq_shift = 20 - 14 - transform_shift + 4, dq_qp_per = qp_scaled / 6).  While the shift exceeds qp / 6 the product is rounded and shifted right;
+// from qp / 6 == shift on (5 at 4x4, 6 at 8x8, 7 at 16x16, 8 at 32x32) it is clipped, shifted LEFT by the difference and clipped again.  |level * inv| <=
+// 32768 * 18360 < 2^30.  With the factor of a flat list (inv_quant_scale * 16) both sides give what the rule above gives.
+KVZ_HD i16 dequant_level(int level, const QuantScalars &q, int inv)
+{
+  const int prod = level * inv, down = q.dq_shift - q.dq_qp_per;
+  if (down > 0) return (i16)iclip(-32768, 32767, (prod + (1 << (down - 1))) >> down);
+  return (i16)iclip(-32768, 32767, iclip(-32768, 32767, prod) * (1 << -down));
+}
+
+// ---- per-coefficient scaling lists (scalinglist.c:289-342, 375-391) in compact form: what kvz_scalinglist_set upsamples into a table per block size is indexed
+// here the way it is upsampled.  A plane's factors: 16 for 4x4, 64 for 8x8, 64 + the DC term for 16x16 and for 32x32 -- KVZ_LIST_PLANE words, padded to 16 bytes;
+// a row = the three planes' factors at one qp % 6.  A word holds the forward factor (quant_level) in its low half and the inverse one (dequant_level) in its high half.
+enum { KVZ_LIST_PLANE = 212, KVZ_LIST_ROW = 3 * KVZ_LIST_PLANE };
+// where the factors of element e (row-major) of a 2^l2 block are in its plane's part of a row: list entry 8 * (y >> ratio) + (x >> ratio), the DC term for (0, 0)
+KVZ_HD int list_index(int l2, int e)
+{
+  if (l2 == 2) return e;
+  const int r = l2 - 3, x = e & ((1 << l2) - 1), y = e >> l2;
+  return (l2 == 3 ? 16 : (l2 == 4 ? 80 : 145)) + ((e == 0 && r > 0) ? 64 : 8 * (y >> r) + (x >> r));
+}
+struct ListFactor { int fwd, inv; };
+KVZ_HD ListFactor list_factor(u32 word) { return ListFactor{ (int)(word & 0xffffu), (int)(word >> 16) }; }
 
 // What a level adds to its plane's cost sums: its weight -- `weights`: kvz_hip_intra_cost_model::coeff_weights, four 16-bit prices for |level| = 0, 1, 2, >= 3 -- and
 // whether it counts.  word(): both in one, weight | (nonzero << 24), for the stages that reduce one word per plane; such words add up without carrying into the
