@@ -55,6 +55,13 @@ int  kvz_hip_dev_angular_pred(int log2_width, int mode, const uint8_t *ref_above
  * second or third".  A developer entry point: the pass itself takes these from LDS.  -1: a shape the pass does not have. */
 int  kvz_hip_dev_intra_select(int log2w, int nblk, const uint32_t *raw, const int8_t *preds, const double *mode_bits, int count, int32_t *winner);
 
+/* Stages 2-5 of the CTU pass's 8x8 CU (forward transform, quantise / dequantise, inverse transform: the device functions of kvz_recon.hpp that kvz_ctu.hpp recon_cu8
+ * calls, in its lane roles and buffer layout) on `count` units in device memory.  A unit is an 8x8 luma and two 4x4 chroma blocks, 96 int16 (Y 64 | U 16 | V 16,
+ * row-major), with a QP (qp[i]; 8 bit, I slice, flat lists, no sign hiding).  from_coeffs 0: `in` holds residuals -> levels, dequantised coefficients and the
+ * reconstructed residual, each laid out like `in`; 1: `in` holds dequantised coefficients, only the two inverse passes run (levels come back zero, dequant = in).
+ * A developer entry point: the pass itself works in LDS.  -1: arguments it does not take. */
+int  kvz_hip_dev_cu8_units(int count, int from_coeffs, const int16_t *in, const int32_t *qp, int16_t *levels, int16_t *dequant, int16_t *resid);
+
 /* Deblocking of all-intra, constant-QP pictures in place: kvz_filter_deblock_lcu (filter.c:783) over every LCU of every
  * frame.  frames = n_frames x [Y | U | V] tight planar 4:2:0 (the batch layout), cu_depth = n_frames x [H/8][W/8] CU depths
  * as the CTU pass returns them; beta / tc offsets are cfg.deblock_beta / cfg.deblock_tc (cfg.c: 0, 0).  Not a strategy in

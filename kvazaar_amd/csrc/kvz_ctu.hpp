@@ -72,6 +72,16 @@ static unsigned long long g_kvz_syncs;
 #define KVZ_WAVE_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
 #endif
 
+// What a lane works out in one phase and uses in a later one stays in its registers: declared outside the phases.  The host simulation, whose threads run one after
+// the other, keeps one per thread.
+#ifdef KVZ_HOSTSIM
+#define KVZ_LANE_VAR(type, name) type name[KVZ_CTU_THREADS] = {}
+#define KVZ_LANE(name, tid) name[tid]
+#else
+#define KVZ_LANE_VAR(type, name) type name = {}
+#define KVZ_LANE(name, tid) name
+#endif
+
 // KVZ_TOGETHER(a, b, ...) (2, 5 or 10 variables that were just loaded): every one of them is needed HERE, all at once -- an opaque use that keeps the compiler from
 // sinking each load of a one-lane chain to its own first use, where every one of them would be issued and waited for by itself.  Changes no value: nothing on the host.
 #ifdef KVZ_HOSTSIM
@@ -1103,7 +1113,8 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false, bool
           s->fref[side][k] = v;
         }
       }
-      const int c = tid - (KVZ_CTU_THREADS - 3);  // the last three lanes: one DC value each
+      const int c = mover_lane(tid) - (KVZ_CTU_THREADS - 3);  // the last three lanes: one DC value each (opaque: what follows from c is the same in every call, and the
+      // 32x32 units of the 64x64 attempt kept a shift count made of it in a register across their loop, spilled)
       if (c >= 0 && ((c == 0 && luma) || (c > 0 && chroma))) {
         const int l2 = c ? log2w_c : log2w_y, w = 1 << l2;
 #ifdef KVZ_HOSTSIM
@@ -1730,25 +1741,31 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false, bool
   // plane, so it adds the word as it is to acc[3 + plane] and finish_planes() takes it apart when the unit is done.  The wide layouts (eight words a lane, a
   // row stays below 128 levels and 2^23) add from both wavefronts and take the word apart here, before rows are added up.
   // Every lane of a wavefront that has tasks in the trip comes here, lanes without a task with c = -1 and v = 0.
+  // Returns, on the device and for ROWS_CU8, the sum of the lane's own plane (V's on the chroma wavefront's lanes without a task) -- every lane of the wavefront has it
+  // in registers here, where the next stage would otherwise read acc[] back and wait; 0 otherwise (the host's sums are complete when the phase is).
   enum RowPlan { ROWS_CU8, ROWS_W16, ROWS_W32_Y, ROWS_W32_C };
-  KVZ_DEV void plane_sums(RowPlan plan, int tid, int c, u32 v, bool packed, int base) const
+  KVZ_DEV u32 plane_sums(RowPlan plan, int tid, int c, u32 v, bool packed, int base) const
   {
 #ifdef KVZ_HOSTSIM
     (void)tid;
-    if (c < 0) return;
+    if (c < 0) return 0;
     if (packed && plan != ROWS_CU8) { s->acc[3 + c] += v & 0xffffffu; s->acc[6 + c] += v >> 24; }
     else s->acc[base + c] += v;
+    return 0;
 #else
     (void)c;
-    if ((plan == ROWS_W16 || plan == ROWS_W32_C) && tid >= 64) return;  // wavefront-uniform: the other wavefront has no tasks in this trip
+    if ((plan == ROWS_W16 || plan == ROWS_W32_C) && tid >= 64) return 0;  // wavefront-uniform: the other wavefront has no tasks in this trip
     const int x = row16_sum((int)v);
     const u32 r0 = (u32)__builtin_amdgcn_readlane(x, 15), r1 = (u32)__builtin_amdgcn_readlane(x, 31), r2 = (u32)__builtin_amdgcn_readlane(x, 47), r3 = (u32)__builtin_amdgcn_readlane(x, 63);
-    if ((tid & 63) != 0) return;
     if (plan == ROWS_CU8) {
-      if (tid < 64) s->acc[base] += r0 + r1 + r2 + r3;
-      else { s->acc[base + 1] += r0; s->acc[base + 2] += r1; }
-      return;
+      const u32 luma = r0 + r1 + r2 + r3;
+      if ((tid & 63) == 0) {
+        if (tid < 64) s->acc[base] += luma;
+        else { s->acc[base + 1] += r0; s->acc[base + 2] += r1; }
+      }
+      return tid < 64 ? luma : (tid < 80 ? r0 : r1);
     }
+    if ((tid & 63) != 0) return 0;
     auto put = [&](int plane, u32 a, u32 b) {
       if (packed) {
         const u32 ws = (a & 0xffffffu) + (b & 0xffffffu), n = (a >> 24) + (b >> 24);
@@ -1759,6 +1776,7 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false, bool
     if (plan == ROWS_W16) { put(0, r0, r1); put(1, r2, 0); put(2, r3, 0); }
     else if (plan == ROWS_W32_Y) { put(0, r0, r1); put(0, r2, r3); }
     else { put(1, r0, r1); put(2, r2, r3); }
+    return 0;
 #endif
   }
   // The end of a unit, for planes c0 .. c1 - 1, by the one thread that owns them: a packed sum of LevelCost words is taken apart (weight sum, count: what the
@@ -1839,58 +1857,56 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false, bool
       if (tid < 2) s->acc[3 * tid] = 0;
       if (tid >= 64 && tid < 68) s->acc[1 + (tid - 64) + ((tid - 64) >> 1)] = 0;  // 1, 2, 4, 5
     }
+    // A pass of the transforms is one output per lane: the lane's N inputs as ONE 16-byte (chroma: 8-byte) LDS read, against its row of the matrix as int16 pairs, on
+    // v_dot2_i32_i16 (cu8_fwd_first .. cu8_inv_second, kvz_recon.hpp: the stages' arithmetic and index rules, shared with kvz_hip_dev_cu8_units and its host twin).  The forward passes read rows anyway; the inverse ones read columns, so the stage in front of
+    // each stores TRANSPOSED (the dequantised coefficients of stage 3, the output of stage 4): only these two intermediates, which nothing outside this function
+    // reads -- the coefficient that hide_signs() looks up by scan position, the levels and the candidate keep their layout.  A lane's matrix rows are fixed -- row
+    // e >> l2 of M for the forward passes, row e & (n - 1) of M^T for the inverse ones -- and come from Tables::small_pairs here, so that stage 1 hides the loads.
+    KVZ_LANE_VAR(WideBytes<16>, mat_f);
+    KVZ_LANE_VAR(WideBytes<16>, mat_i);
+    KVZ_LANE_VAR(u32, pred_org);  // stage 1's predicted and source sample, for stage 5: sample e is lane e's in both
+    KVZ_LANE_VAR(u32, plane_word);  // the lane's plane's packed sum of stage 3 (plane_sums), whose count decides whether stages 4 and 5 have anything to do
     auto stage1 = [&](auto luma, int tid) {
       KVZ_CU8_ROLE(tid);
       const int px = e & (n - 1), py = e >> l2;
+      cu8_matrix_rows<l2>(tb, e, KVZ_LANE(mat_f, tid), KVZ_LANE(mat_i, tid));
       const u8 p = predict_pixel(l2, mode, c, px, py);
       cv.at(c, (xl >> sh) + px, (yl >> sh) + py) = p;
-      tbuf(t, 0, c)[e] = (i16)((int)*org_at(c, (xl >> sh) + px, (yl >> sh) + py) - (int)p);
+      const u8 o = *org_at(c, (xl >> sh) + px, (yl >> sh) + py);
+      KVZ_LANE(pred_org, tid) = (u32)p | ((u32)o << 8);
+      tbuf(t, 0, c)[e] = (i16)((int)o - (int)p);
     };
     KVZ_CU8_STAGE(stage1)
     KVZ_WAVE_SYNC();
     KVZ_PROF(KVZ_P_RPRED);
-    // The four transform passes below are fwd_point / inv_point (kvz_recon.hpp) spelled out: called through the helpers the same values come out, but the
-    // 32x32-search kernel then spills five more VGPRs (scratch 48 -> 68 B per lane).  Everything else of a sample's arithmetic is the shared text.
     auto stage2 = [&](auto luma, int tid) {  // forward transform (dct-generic.c:559-568), first pass
       KVZ_CU8_ROLE(tid);
-      const int k = e >> l2, j = e & (n - 1);
-      constexpr int shift = l2 - 1, add = 1 << (shift - 1);
-      const i16 *src = tbuf(t, 0, c);
-      int a = 0;
-#pragma unroll
-      for (int i = 0; i < n; i++) a += dct_at(l2, k, i) * (int)src[(j << l2) + i];
-      tbuf(t, 1, c)[e] = (i16)((a + add) >> shift);
+      tbuf(t, 1, c)[e] = cu8_fwd_first<l2>(tbuf(t, 0, c), e, KVZ_LANE(mat_f, tid));
     };
     KVZ_CU8_STAGE(stage2)
     KVZ_WAVE_SYNC();
     KVZ_PROF(KVZ_P_FDCT);
     // second pass, and -- the coefficient a lane produces is the one it quantises -- straight on: quantise (quant-generic.c:57-81)
-    // -> coefficient store + cost sums; dequantise (:335-339)
+    // -> coefficient store + cost sums; dequantise (:335-339), stored transposed for the inverse passes
     const bool hide = hide_on();  // sign data hiding: the levels wait for hide_signs() before anything is made of them (false where !SH)
     KVZ_FOR_THREADS(tid) {
       u32 packed = 0;
       auto stage3 = [&](auto luma, int tid_) {
         KVZ_CU8_ROLE(tid_);
-        const int k = e >> l2, j = e & (n - 1);
-        constexpr int shift = l2 + 6, add = 1 << (shift - 1);
-        const i16 *src = tbuf(t, 1, c);
-        int a = 0;
-#pragma unroll
-        for (int i = 0; i < n; i++) a += dct_at(l2, k, i) * (int)src[(j << l2) + i];
-        const int cf = (i16)((a + add) >> shift);
+        const int cf = cu8_fwd_second<l2>(tbuf(t, 1, c), e, KVZ_LANE(mat_f, tid_));
         const QuantScalars q = s->qs[l2 - 2][LUMA ? 0 : 1];
         ListFactor f{ 0, 0 };
         if constexpr (LISTS) f = factor_at(c, l2, e);
         const int level = LISTS ? quant_level(cf, q, f.fwd) : quant_level(cf, q);
         levels_lds(lv, c)[e] = (i16)level;  // lv == 3 here
-        if constexpr (SH) { if (hide) { tbuf(t, 0, c)[e] = (i16)cf; return; } }  // the coefficient stays for the hiding stage, where the dequantised one will go
-        tbuf(t, 0, c)[e] = LISTS ? dequant_level(level, q, f.inv) : dequant_level(level, q);
+        if constexpr (SH) { if (hide) { tbuf(t, 0, c)[e] = (i16)cf; return; } }  // the coefficient stays for the hiding stage (in the standard layout: it goes by scan position)
+        tbuf(t, 0, c)[cu8_transposed<l2>(e)] = LISTS ? dequant_level(level, q, f.inv) : dequant_level(level, q);
         packed = level_cost(level, m->coeff_weights).word();
       };
       if (tid < 64) stage3(std::true_type(), tid); else if (tid < 96) stage3(std::false_type(), tid);
       // the plane's weight sum (< 2^22) and its count of levels travel in ONE word: one reduction instead of two.  (Per-lane LDS atomics instead of the DPP
       // reduction -- profiles/experiments, r05_g -- take 7 k instructions per CTU off the vector pipe and cost 6 % throughput: 64 lanes on one address.)
-      if (!hide) plane_sums(ROWS_CU8, tid, tid < 64 ? 0 : (tid < 80 ? 1 : (tid < 96 ? 2 : -1)), packed, true, 3);
+      if (!hide) KVZ_LANE(plane_word, tid) = plane_sums(ROWS_CU8, tid, tid < 64 ? 0 : (tid < 80 ? 1 : (tid < 96 ? 2 : -1)), packed, true, 3);
     }
     if constexpr (SH) {
       if (hide) {  // hiding, then the rest of stage 3 on the final levels; luma and chroma still each on their own wavefront
@@ -1902,26 +1918,27 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false, bool
           auto stage3b = [&](auto luma, int tid_) {
             KVZ_CU8_ROLE(tid_);
             const int level = levels_lds(lv, c)[e];
-            tbuf(t, 0, c)[e] = dequant_level(level, s->qs[l2 - 2][LUMA ? 0 : 1]);
+            tbuf(t, 0, c)[cu8_transposed<l2>(e)] = dequant_level(level, s->qs[l2 - 2][LUMA ? 0 : 1]);
             packed = level_cost(level, m->coeff_weights).word();
           };
           if (tid < 64) stage3b(std::true_type(), tid); else if (tid < 96) stage3b(std::false_type(), tid);
-          plane_sums(ROWS_CU8, tid, tid < 64 ? 0 : (tid < 80 ? 1 : (tid < 96 ? 2 : -1)), packed, true, 3);
+          KVZ_LANE(plane_word, tid) = plane_sums(ROWS_CU8, tid, tid < 64 ? 0 : (tid < 80 ? 1 : (tid < 96 ? 2 : -1)), packed, true, 3);
         }
       }
     }
     KVZ_WAVE_SYNC();
     KVZ_PROF(KVZ_P_QUANT);
+    // does the lane's plane have levels?  The wavefront's own reduction left the answer in registers; the host simulation reads the finished sum -- so the word
+    // plane_sums() returns (luma: the four rows' sum; the other wavefront: row 0 for U, row 1 for V) is exercised by the device tests only.
+#ifdef KVZ_HOSTSIM
+#define KVZ_CU8_CODED(tid) ((void)KVZ_LANE(plane_word, tid), (s->acc[3 + c] >> 24) != 0)
+#else
+#define KVZ_CU8_CODED(tid) ((KVZ_LANE(plane_word, tid) >> 24) != 0)
+#endif
     auto stage4 = [&](auto luma, int tid) {  // inverse transform (dct-generic.c:570-579), first pass; only observable when the plane has coefficients
       KVZ_CU8_ROLE(tid);
-      if (s->acc[3 + c] >> 24) {
-        const int j = e >> l2, i = e & (n - 1);
-        constexpr int shift = 7, add = 1 << (shift - 1);
-        const i16 *src = tbuf(t, 0, c);
-        int a = 0;
-#pragma unroll
-        for (int k = 0; k < n; k++) a += dct_at(l2, k, i) * (int)src[(k << l2) + j];
-        tbuf(t, 1, c)[e] = (i16)iclip(-32768, 32767, (a + add) >> shift);
+      if (KVZ_CU8_CODED(tid)) {
+        tbuf(t, 1, c)[cu8_transposed<l2>(e)] = cu8_inv_first<l2>(tbuf(t, 0, c), e, KVZ_LANE(mat_i, tid));  // transposed again: the second pass reads its columns
       }
     };
     KVZ_CU8_STAGE(stage4)
@@ -1933,24 +1950,17 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false, bool
       u32 ssd = 0;
       auto stage5 = [&](auto luma, int tid_) {
         KVZ_CU8_ROLE(tid_);
-        u8 *rp = &cv.at(c, (xl >> sh) + (e & (n - 1)), (yl >> sh) + (e >> l2));
-        int v = *rp;
-        if (s->acc[3 + c] >> 24) {
-          const int j = e >> l2, i = e & (n - 1);
-          constexpr int shift = 12, add = 1 << (shift - 1);
-          const i16 *src = tbuf(t, 1, c);
-          int a = 0;
-#pragma unroll
-          for (int k = 0; k < n; k++) a += dct_at(l2, k, i) * (int)src[(k << l2) + j];
-          const i16 res = (i16)iclip(-32768, 32767, (a + add) >> shift);
-          v = recon_sample(v, res);
-          *rp = (u8)v;
+        int v = (int)(KVZ_LANE(pred_org, tid_) & 0xffu);
+        if (KVZ_CU8_CODED(tid_)) {
+          v = recon_sample(v, cu8_inv_second<l2>(tbuf(t, 1, c), e, KVZ_LANE(mat_i, tid_)));
+          cv.at(c, (xl >> sh) + (e & (n - 1)), (yl >> sh) + (e >> l2)) = (u8)v;
         }
-        ssd = sq_err(*org_at(c, (xl >> sh) + (e & (n - 1)), (yl >> sh) + (e >> l2)), v);
+        ssd = sq_err((int)(KVZ_LANE(pred_org, tid_) >> 8), v);
       };
       if (tid < 64) stage5(std::true_type(), tid); else if (tid < 96) stage5(std::false_type(), tid);
       plane_sums(ROWS_CU8, tid, tid < 64 ? 0 : (tid < 80 ? 1 : (tid < 96 ? 2 : -1)), ssd, false, 0);
     }
+#undef KVZ_CU8_CODED
     KVZ_SYNC();
     KVZ_FOR_THREADS(tid) {
       // all three planes' counts, so behind the barrier; only thread 0 reads the results next (eval_cu's cost phase, same thread: no barrier in between)

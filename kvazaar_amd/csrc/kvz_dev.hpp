@@ -18,6 +18,8 @@
 #include "kvz_sao.hpp"
 #include "kvz_entropy.hpp"
 #include "kvz_select.hpp"
+#include "kvz_recon.hpp"
+#include "kvz_tables.hpp"
 
 namespace kvz {
 
@@ -314,6 +316,48 @@ __global__ void __launch_bounds__(256) dev_intra_select_kernel(const u32 *raw, c
   const u32 my_raw = select_satd_sum(raw + (table * 35 + my_mode) * nblk, nblk);
   const int w = select_on_wave(lane, my_raw, select_mode_cost(my_raw, my_mode, p0, p1, p2, bits), p0, p1, p2, log2w);
   if (lane == 0) winner[table] = w;
+}
+
+// kvz_hip_dev_cu8_units: stages 2-5 of the CTU pass's 8x8 CU (kvz_recon.hpp cu8_*: what kvz_ctu.hpp recon_cu8 calls) on units in memory, two wavefronts
+// per unit with recon_cu8's roles: threads 0..63 the luma samples, 64..79 / 80..95 the U / V samples.  A unit: Y 64 | U 16 | V 16 int16, row-major.
+struct Cu8MatRow { u32 w[4]; };
+template <int L2> KVZ_DEV void dev_cu8_lane(int stage, int c, int e, i16 (*t)[96], int from_coeffs, int qp, const Cu8MatRow &fwd, const Cu8MatRow &inv, const i16 *in, i16 *levels, i16 *dequant,
+                                            i16 *resid)
+{
+  const int po = c == 0 ? 0 : (c == 1 ? 64 : 80);
+  i16 *t0 = t[0] + po, *t1 = t[1] + po;
+  if (stage == 1) { if (!from_coeffs) t0[e] = in[po + e]; }
+  else if (stage == 2) { if (!from_coeffs) t1[e] = cu8_fwd_first<L2>(t0, e, fwd); }
+  else if (stage == 3) {
+    int level = 0, dq = in[po + e];
+    if (!from_coeffs) {
+      const QuantScalars q = quant_scalars(qp, 8, 1, 0, 1 << L2, c ? 2 : 0);
+      level = quant_level(cu8_fwd_second<L2>(t1, e, fwd), q);
+      dq = dequant_level(level, q);
+    }
+    levels[po + e] = (i16)level;
+    dequant[po + e] = (i16)dq;
+    t0[cu8_transposed<L2>(e)] = (i16)dq;
+  }
+  else if (stage == 4) t1[cu8_transposed<L2>(e)] = cu8_inv_first<L2>(t0, e, inv);
+  else resid[po + e] = cu8_inv_second<L2>(t1, e, inv);
+}
+__global__ void __launch_bounds__(256) dev_cu8_units_kernel(const i16 *in, const int32_t *qp, const int count, const int from_coeffs, const Tables *tb, i16 *levels, i16 *dequant, i16 *resid)
+{
+  __shared__ alignas(16) i16 t[2][2][96];  // two units per workgroup, each on its own pair of wavefronts
+  const int half = threadIdx.x >> 7, tid = threadIdx.x & 127;
+  const long unit = 2l * blockIdx.x + half, o = 96 * unit;
+  const bool live = unit < count && tid < 96;  // (every thread stays for the barriers)
+  const int c = tid < 64 ? 0 : (tid < 80 ? 1 : 2), e = tid < 64 ? tid : (tid & 15), q = live ? qp[unit] : 0;
+  Cu8MatRow fwd = {}, inv = {};
+  if (tid < 64) cu8_matrix_rows<3>(tb, e, fwd, inv); else cu8_matrix_rows<2>(tb, e, fwd, inv);
+  for (int stage = 1; stage <= 5; stage++) {
+    if (live) {
+      if (tid < 64) dev_cu8_lane<3>(stage, c, e, t[half], from_coeffs, q, fwd, inv, in + o, levels + o, dequant + o, resid + o);
+      else dev_cu8_lane<2>(stage, c, e, t[half], from_coeffs, q, fwd, inv, in + o, levels + o, dequant + o, resid + o);
+    }
+    __syncthreads();
+  }
 }
 
 template <int L2> __global__ void __launch_bounds__(256) dev_angular_kernel(const u8 *above, const u8 *left, const int count, const int mode, u8 *out)
@@ -1277,6 +1321,14 @@ int kvz_hip_dev_intra_select(int log2w, int nblk, const uint32_t *raw, const int
   if (!((log2w == 3 && nblk == 1) || (log2w == 4 && nblk == 4))) { fprintf(stderr, "kvz_hip_dev_intra_select: unsupported log2w=%d nblk=%d\n", log2w, nblk); return -1; }
   if (count <= 0) return 0;
   KVZ_DEV_LAUNCH(kvz::dev_intra_select_kernel, ((long)count + 3) / 4 * 256, raw, preds, mode_bits, count, log2w, nblk, winner);
+  return 0;
+}
+
+int kvz_hip_dev_cu8_units(int count, int from_coeffs, const int16_t *in, const int32_t *qp, int16_t *levels, int16_t *dequant, int16_t *resid)
+{
+  if (count < 0 || (from_coeffs != 0 && from_coeffs != 1)) { fprintf(stderr, "kvz_hip_dev_cu8_units: count=%d from_coeffs=%d\n", count, from_coeffs); return -1; }
+  if (count == 0) return 0;
+  KVZ_DEV_LAUNCH(kvz::dev_cu8_units_kernel, ((long)count + 1) / 2 * 256, in, qp, count, from_coeffs, kvz::device_tables(), levels, dequant, resid);
   return 0;
 }
 

@@ -164,14 +164,7 @@ template <int MAXN> __global__ void __launch_bounds__(256) dev_inter_pred_kernel
 // four adjacent outputs from four dwords -- the 8 (4) taps of the horizontal pass are two (one) v_dot4_i32_i8 on pixels biased by -128 (+ 128 * 64 afterwards:
 // every filter sums to 64), the vertical pass on the 14-bit intermediates, kept TRANSPOSED in LDS so that a column's samples are adjacent, is v_dot2_i32_i16 --
 // and the finished block leaves through LDS as one dword per lane.  Same integers as the kernel above, whatever the order of the sums.
-typedef short kvz_short2 __attribute__((ext_vector_type(2)));
-KVZ_DEV int dot4_i8(int a, int b, int c) { return __builtin_amdgcn_sdot4(a, b, c, false); }
-KVZ_DEV int dot2_i16(unsigned a, unsigned b, int c)
-{
-  kvz_short2 va, vb;
-  __builtin_memcpy(&va, &a, 4); __builtin_memcpy(&vb, &b, 4);
-  return __builtin_amdgcn_sdot2(va, vb, c, false);
-}
+KVZ_DEV int dot4_i8(int a, int b, int c) { return __builtin_amdgcn_sdot4(a, b, c, false); }  // (dot2_i16: kvz_ops.hpp)
 struct McWaveLds {
   alignas(16) u8 win[23 * 32];        // luma window: 23 rows of up to 28 bytes from a dword-aligned column; chroma: two windows of 11 rows x 16 bytes behind each other
   alignas(16) i16 gT[16 * 24];        // horizontal pass, transposed: [column][row], rows padded to 24; chroma: two planes of [8][12]

@@ -41,6 +41,18 @@ KVZ_HD int iclip(int lo, int hi, int v) { return v < lo ? lo : (v > hi ? hi : v)
 KVZ_HD int imin(int a, int b) { return a < b ? a : b; }
 KVZ_HD int imax(int a, int b) { return a > b ? a : b; }
 KVZ_DEV u8 clip_pixel(int v) { return (u8)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
+// c + a.lo * b.lo + a.hi * b.hi on two packed pairs of int16 (v_dot2_i32_i16; the host simulation states the same sum).  No saturation: the callers' sums fit 32 bits.
+#ifdef KVZ_HOSTSIM
+KVZ_DEV int dot2_i16(unsigned a, unsigned b, int c) { return c + (int)(i16)(a & 0xffffu) * (int)(i16)(b & 0xffffu) + (int)(i16)(a >> 16) * (int)(i16)(b >> 16); }
+#else
+typedef short kvz_short2 __attribute__((ext_vector_type(2)));
+KVZ_DEV int dot2_i16(unsigned a, unsigned b, int c)
+{
+  kvz_short2 va, vb;
+  __builtin_memcpy(&va, &a, 4); __builtin_memcpy(&vb, &b, 4);
+  return __builtin_amdgcn_sdot2(va, vb, c, false);
+}
+#endif
 #ifndef KVZ_HOSTSIM
 // Sums along the rows of 16 lanes of a wavefront: DPP row_shr 8 / 4 / 2 / 1 (lanes shifted in from outside the row read 0), so lane k of a row ends up with the sum of
 // the row's lanes 0..k and lane 15 with the row's total -- read the four totals with v_readlane 15 / 31 / 47 / 63.  No LDS traffic, no dependent shuffles.

@@ -32,6 +32,52 @@ template <class Mat> KVZ_DEV i16 inv_point(int n, Mat m, const i16 *in, int at, 
   return (i16)iclip(-32768, 32767, (a + (1 << (shift - 1))) >> shift);
 }
 
+// The same points where the N inputs and the N matrix entries that multiply them are each N / 2 adjacent pairs of int16 (x.w[], m.w[]: Tables::small_pairs holds the
+// rows of M and of M^T that way; the inverse passes get their column as a row by reading a buffer that was stored transposed): N / 2 v_dot2_i32_i16.  The sum is the
+// exact 32-bit integer in any order (|entry| <= 90, |input| <= 32 768, eight terms).
+template <int N, class Row, class MatRow> KVZ_DEV int row_dot(const Row &x, const MatRow &m)
+{
+  int a = 0;
+  for (int i = 0; i < N / 2; i++) a = dot2_i16(x.w[i], m.w[i], a);
+  return a;
+}
+template <int N, class Row, class MatRow> KVZ_DEV i16 fwd_row_point(const Row &x, const MatRow &m, int shift) { return (i16)((row_dot<N>(x, m) + (1 << (shift - 1))) >> shift); }
+template <int N, class Row, class MatRow> KVZ_DEV i16 inv_row_point(const Row &x, const MatRow &m, int shift)
+{
+  return (i16)iclip(-32768, 32767, (row_dot<N>(x, m) + (1 << (shift - 1))) >> shift);
+}
+
+// ---- stages 2-5 of the 8x8 CU (kvz_ctu.hpp recon_cu8: one lane per sample e of a 2^L2 block, 8-point luma / 4-point chroma), stated once for the CTU pass, for the
+// developer entry point that runs them on blocks without a picture (kvz_dev.hpp kvz_hip_dev_cu8_units) and for its serial host twin (tests/hostsim/hostsim_cu8.cpp).
+// t0 / t1: the plane's two scratch buffers of 2^(2 L2) int16, 2^(L2 + 1)-byte aligned.  The lane's inputs are one row of a buffer, read as ONE load; its matrix rows
+// (cu8_matrix_rows: row e >> L2 of M for the forward passes, row e & (n - 1) of M^T for the inverse ones, from Tables::small_pairs) stay in registers.  The inverse passes
+// read columns, so what they read is stored TRANSPOSED by the stage in front: the caller stores stage 3's dequantised value and cu8_inv_first's result at
+// cu8_transposed(e); everything else -- cu8_fwd_first's result, the coefficient, the level, the residual -- belongs to element e.
+template <int N> struct alignas(2 * N) Int16Row { u32 w[N / 2]; };
+template <int N> KVZ_DEV Int16Row<N> int16_row(const i16 *p)
+{
+  Int16Row<N> r;
+#ifdef KVZ_HOSTSIM
+  __builtin_memcpy(&r, p, 2 * N);
+#else
+  __builtin_memcpy(&r, __builtin_assume_aligned(p, 2 * N), 2 * N);
+#endif
+  return r;
+}
+template <int L2> KVZ_HD int cu8_transposed(int e) { return ((e & ((1 << L2) - 1)) << L2) + (e >> L2); }
+template <int L2, class MatRow> KVZ_DEV void cu8_matrix_rows(const Tables *tb, int e, MatRow &fwd, MatRow &inv)
+{
+  constexpr int n = 1 << L2;
+  __builtin_memcpy(&fwd, &tb->small_pairs[L2 == 3 ? 1 : 0][0][e >> L2][0], 2 * n);
+  __builtin_memcpy(&inv, &tb->small_pairs[L2 == 3 ? 1 : 0][1][e & (n - 1)][0], 2 * n);
+}
+// forward transform (dct-generic.c:559-568): first pass -> t1[e]; second pass -> the coefficient of element e
+template <int L2, class MatRow> KVZ_DEV i16 cu8_fwd_first(const i16 *t0, int e, const MatRow &fwd) { return fwd_row_point<(1 << L2)>(int16_row<(1 << L2)>(t0 + ((e & ((1 << L2) - 1)) << L2)), fwd, L2 - 1); }
+template <int L2, class MatRow> KVZ_DEV i16 cu8_fwd_second(const i16 *t1, int e, const MatRow &fwd) { return fwd_row_point<(1 << L2)>(int16_row<(1 << L2)>(t1 + ((e & ((1 << L2) - 1)) << L2)), fwd, L2 + 6); }
+// inverse transform (dct-generic.c:570-579) on the transposed intermediates: first pass -> t1[cu8_transposed(e)]; second pass -> the residual of sample e
+template <int L2, class MatRow> KVZ_DEV i16 cu8_inv_first(const i16 *t0, int e, const MatRow &inv) { return inv_row_point<(1 << L2)>(int16_row<(1 << L2)>(t0 + ((e >> L2) << L2)), inv, 7); }
+template <int L2, class MatRow> KVZ_DEV i16 cu8_inv_second(const i16 *t1, int e, const MatRow &inv) { return inv_row_point<(1 << L2)>(int16_row<(1 << L2)>(t1 + ((e >> L2) << L2)), inv, 12); }
+
 // quant-generic.c:57-81: the level of one coefficient under the forward factor of its position (quant_coeff[n]).  |cf| * q + add < 2^31 for 8-bit flat lists
 // (32767 * 26214 + (171 << 18)) and for every list the library accepts: entries >= 13 keep the factor (quant_scale << 4) / entry <= 32263, and
 // 32767 * 32263 + (171 << 18) = 1 101 988 445 -- so 32-bit arithmetic is exact.  (A full 32-bit multiply: the factor has 15 bits, the product 30.)
