@@ -227,6 +227,19 @@ int  kvz_hip_dev_loop_filters_inter_pictures(const uint8_t *src, uint8_t *rec, i
 long kvz_hip_dev_entropy_code_inter_pictures(const kvz_hip_cu_info *cu, const kvz_hip_cu_info *ref_cu, const int16_t *coeff, int width, int height, int n_pictures,
                                              const kvz_hip_inter_params *params, uint8_t *out, size_t capacity, uint32_t *substream_bytes,
                                              const kvz_hip_inter_pictures *pictures);
+/* The inter CTU pass with per-coefficient scaling lists (kvz_hip_scaling_lists, kvz_hip_types.h; kvazaar --scaling-list / --cqmfile): a superset of
+ * kvz_hip_dev_inter_ctu_pass_pictures.  Picture i is quantised and dequantised under sets[set_of_picture[i]]: inter CUs under the inter lists 3-5 (32x32: the inter
+ * list of that size), the intra CUs of the B slice under the intra lists 0-2 with the B slice's rounding.  sets / set_of_picture are HOST arrays; set_of_picture NULL:
+ * set 0 for every picture; 0xffff: the picture stays flat, byte for byte what a launch without lists makes of it.  Pictures with different sets, QPs and POCs share
+ * the launch.  n_sets == 0: exactly kvz_hip_dev_inter_ctu_pass_pictures (its kernels, its bytes); `pictures` NULL: params->qp / params->poc for every picture.
+ * The factor table derived from the sets is kept on the device per calling thread and device and copied again only when a call's table differs.
+ * The loop filters and the entropy coder need nothing: kvz_hip_dev_loop_filters_inter[_pictures] and kvz_hip_dev_entropy_code_inter[_pictures] take the pass's
+ * outputs as they are (the SPS / PPS signalling of the lists stays with the host encoder).
+ * Refused with -1 and a message before anything is queued, besides what kvz_hip_dev_inter_ctu_pass_pictures refuses: a set whose struct_size is not this library's, an
+ * entry or a non-zero DC term outside 13 .. 255, n_sets outside 0 .. 65535, a set_of_picture value that is neither 0xffff nor below n_sets. */
+int  kvz_hip_dev_inter_ctu_pass_lists(const uint8_t *src, const uint8_t *ref, const kvz_hip_cu_info *ref_cu, uint8_t *rec, kvz_hip_cu_info *cu, int16_t *coeff, int width,
+                                      int height, int n_pictures, const kvz_hip_inter_params *params, const int32_t *tile_xy, int n_references,
+                                      const kvz_hip_inter_pictures *pictures, const kvz_hip_scaling_lists *sets, int n_sets, const uint16_t *set_of_picture);
 /* what the deblocking filter reads (kvz_hip_cu_dbk) of `count` CU records: type, depth, tr_depth, the luma coded block flag at tr_depth, motion */
 void kvz_hip_dev_cu_dbk_from_info(const kvz_hip_cu_info *cu, int count, kvz_hip_cu_dbk *out);
 

@@ -158,12 +158,12 @@ typedef struct kvz_hip_picture_models {
   const uint16_t *model_of_picture;         /* [n_frames of the batch]: each < n_models */
 } kvz_hip_picture_models;
 
-/* Per-coefficient scaling lists (kvazaar's --scaling-list / --cqmfile; scaling_list_enabled_flag of the SPS) of the all-intra CTU pass: state of a batch
- * (kvz_hip_batch_set_scaling_lists, kvz_hip_batch.h), not of a cost model.  The arrays are what kvazaar's scaling_list_t holds after kvz_scalinglist_parse or
+/* Per-coefficient scaling lists (kvazaar's --scaling-list / --cqmfile; scaling_list_enabled_flag of the SPS): state of a batch of the all-intra CTU pass
+ * (kvz_hip_batch_set_scaling_lists, kvz_hip_batch.h), an argument of the inter CTU pass (kvz_hip_dev_inter_ctu_pass_lists, kvz_hip_dev.h); not part of a cost model.  The arrays are what kvazaar's scaling_list_t holds after kvz_scalinglist_parse or
  * kvz_scalinglist_get_default: per size (0: 4x4 .. 3: 32x32) and list (0-2 intra Y, U, V; 3-5 inter; two lists, intra and inter, at 32x32) the 16 entries of a 4x4
  * list or the 64 of a larger one in raster order, and the DC term that replaces entry 0 for the coefficient (0, 0) of 16x16 and 32x32 blocks.  Entries and non-zero DC terms
- * lie in 13 .. 255: the encoder keeps (quant_scale << 4) / entry in 16 bits (scalinglist.h:51), which wraps below 13.  The all-intra pass reads the intra lists only;
- * the inter ones are carried for the inter pass.  struct_size: sizeof of the caller's headers (kvz_hip_scaling_lists_default sets it); an unknown size is refused. */
+ * lie in 13 .. 255: the encoder keeps (quant_scale << 4) / entry in 16 bits (scalinglist.h:51), which wraps below 13.  The all-intra pass reads the intra lists only; the inter
+ * pass reads the inter lists 3-5 (and [3][1] at 32x32) for inter CUs and the intra lists 0-2 for the intra CUs of a B slice.  struct_size: sizeof of the caller's headers (kvz_hip_scaling_lists_default sets it); an unknown size is refused. */
 typedef struct kvz_hip_scaling_lists {
   uint32_t struct_size;
   int32_t  coeff[4][6][64];   /* scaling_list_coeff[size_id][list_id] */

@@ -1,8 +1,8 @@
 """Builds libkvz_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
-The library is fifteen translation units compiled in parallel: kvz_hip.hip (C ABI, per-call ops, streaming kernels, host side of the batch; with
+The library is seventeen translation units compiled in parallel: kvz_hip.hip (C ABI, per-call ops, streaming kernels, host side of the batch; with
 -DKVZ_CTU_SEPARATE_TUS it only declares the CTU kernels) and kvz_ctu_tu.hip twelve times, one CTU kernel instantiation each (-DKVZ_CTU_KERNEL_TU=0..11; 8..11 are the scaling-list ones,
-csrc/kvz_ctu_kernels.hpp).  Objects are rebuilt when one of the files they include (hipcc -MD) is newer."""
+csrc/kvz_ctu_kernels.hpp) and kvz_inter_tu.hip four times (the inter CTU pass with and without the residual coder's contexts, with and without scaling lists).  Objects are rebuilt when one of the files they include (hipcc -MD) is newer."""
 import os
 import subprocess
 from concurrent.futures import ThreadPoolExecutor
@@ -19,7 +19,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
 MFMA_VGPR_FORM = ["-mllvm", "-amdgpu-mfma-vgpr-form"]  # an internal LLVM option, only a tuning of the streaming transform kernels: dropped where hipcc does not know it (_probe_flags)
 UNITS = ([("kvz_hip", "kvz_hip.hip", ["-DKVZ_CTU_SEPARATE_TUS"] + MFMA_VGPR_FORM)]  # (the streaming transform kernels: accumulators in VGPRs, no v_accvgpr moves around the bias pass)
          + [(f"kvz_ctu_tu{k}", "kvz_ctu_tu.hip", [f"-DKVZ_CTU_KERNEL_TU={k}"]) for k in range(12)]
-         + [("kvz_inter_tu0", "kvz_inter_tu.hip", ["-DKVZ_ICTU_CABAC=0"]), ("kvz_inter_tu1", "kvz_inter_tu.hip", ["-DKVZ_ICTU_CABAC=1"])])  # the inter CTU pass's two builds (csrc/kvz_inter_kernels.hpp)
+         + [("kvz_inter_tu0", "kvz_inter_tu.hip", ["-DKVZ_ICTU_CABAC=0"]), ("kvz_inter_tu1", "kvz_inter_tu.hip", ["-DKVZ_ICTU_CABAC=1"])]  # the inter CTU pass's two builds (csrc/kvz_inter_kernels.hpp)
+         + [("kvz_inter_tu2", "kvz_inter_tu.hip", ["-DKVZ_ICTU_LISTS=1", "-DKVZ_ICTU_CABAC=0"]),  # ... and the two for launches with scaling lists
+            ("kvz_inter_tu3", "kvz_inter_tu.hip", ["-DKVZ_ICTU_LISTS=1", "-DKVZ_ICTU_CABAC=1"])])
 
 
 def _deps(dfile):

@@ -1099,6 +1099,8 @@ struct InterScratch {
   ICtx *ctx = nullptr; unsigned *done = nullptr; uint32_t *items = nullptr; long n_ctus = 0;
   unsigned *ticket = nullptr;  // [0] ticket, [1] error
   void *model = nullptr; size_t model_bytes = 0;  // the launch's InterModel, or its picture table (InterFrames::pictures)
+  void *lists = nullptr; size_t lists_bytes = 0;  // kvz_hip_dev_inter_ctu_pass_lists: the picture table with the factor rows behind it (kvz_inter_host.hpp
+  std::vector<uint64_t> h_lists;                  // inter_picture_table_lists), grow-only, and what it holds: copied again only when a call's image differs
   uint8_t *entropy_table = nullptr; size_t entropy_table_bytes = 0;  // kvz_hip_dev_entropy_code_inter_pictures: context rows, POCs and rows of the pictures
 };
 // One set per calling thread and device, like the stream the work is queued on (be() is thread_local): two threads, or two devices of one process, never share
@@ -1116,7 +1118,7 @@ inline InterScratch &inter_scratch()
         InterScratch &x = all[d];
         if (!x.slabs && !x.ctx && !x.ticket) continue;
         (void)hipSetDevice(d);
-        (void)hipFree(x.slabs); (void)hipFree(x.ctx); (void)hipFree(x.done); (void)hipFree(x.items); (void)hipFree(x.ticket); (void)hipFree(x.model); (void)hipFree(x.entropy_table);
+        (void)hipFree(x.slabs); (void)hipFree(x.ctx); (void)hipFree(x.done); (void)hipFree(x.items); (void)hipFree(x.ticket); (void)hipFree(x.model); (void)hipFree(x.lists); (void)hipFree(x.entropy_table);
         x = InterScratch();
       }
     });
@@ -1528,10 +1530,16 @@ int kvz_hip_dev_inter_ctu_pass_tiles(const uint8_t *src, const uint8_t *ref, con
 {
   return kvz_hip_dev_inter_ctu_pass_pictures(src, ref, ref_cu, rec, cu, coeff, width, height, n_pictures, p, tile_xy, n_references, nullptr);
 }
-// pictures == nullptr: p->qp / p->poc for every picture (kvz_hip_dev_inter_ctu_pass[_tiles])
 int kvz_hip_dev_inter_ctu_pass_pictures(const uint8_t *src, const uint8_t *ref, const kvz_hip_cu_info *ref_cu, uint8_t *rec, kvz_hip_cu_info *cu, int16_t *coeff, int width,
                                         int height, int n_pictures, const kvz_hip_inter_params *p, const int32_t *tile_xy, int n_references,
                                         const kvz_hip_inter_pictures *pictures)
+{
+  return kvz_hip_dev_inter_ctu_pass_lists(src, ref, ref_cu, rec, cu, coeff, width, height, n_pictures, p, tile_xy, n_references, pictures, nullptr, 0, nullptr);
+}
+// pictures == nullptr: p->qp / p->poc for every picture (kvz_hip_dev_inter_ctu_pass[_tiles]); n_sets == 0: no scaling lists (kvz_hip_dev_inter_ctu_pass_pictures)
+int kvz_hip_dev_inter_ctu_pass_lists(const uint8_t *src, const uint8_t *ref, const kvz_hip_cu_info *ref_cu, uint8_t *rec, kvz_hip_cu_info *cu, int16_t *coeff, int width,
+                                     int height, int n_pictures, const kvz_hip_inter_params *p, const int32_t *tile_xy, int n_references,
+                                     const kvz_hip_inter_pictures *pictures, const kvz_hip_scaling_lists *sets, int n_sets, const uint16_t *set_of_picture)
 {
   if (n_pictures <= 0) return 0;
   if (!p || p->struct_size != sizeof(kvz_hip_inter_params)) {
@@ -1547,6 +1555,8 @@ int kvz_hip_dev_inter_ctu_pass_pictures(const uint8_t *src, const uint8_t *ref, 
     fprintf(stderr, "kvz_hip_dev_inter_ctu_pass: the %dx%d tile at (%d, %d) does not lie in the %dx%d reference frame, or that frame is beyond what the pass addresses\n", width, height, p->tile_x, p->tile_y, p->ref_width, p->ref_height);
     return -1;
   }
+  if (!kvz::scaling_list_sets_known(sets, n_sets, set_of_picture, n_pictures, true /* the pass has no other schedule */, "kvz_hip_dev_inter_ctu_pass_lists")) return -1;
+  const bool lists = n_sets > 0;
   hipStream_t st = be().stream;
   const int wc = (width + 63) / 64, hc = (height + 63) / 64, ctus = wc * hc;
   const long total = (long)ctus * n_pictures;
@@ -1561,12 +1571,17 @@ int kvz_hip_dev_inter_ctu_pass_pictures(const uint8_t *src, const uint8_t *ref, 
   for (int i = 0; i < 128; i++) fbits[i] = (float)kvz::kEntropyBits[i] / 32768.0f;
   auto model_at_qp = [&](kvz::InterModel *row, int qp) {
     kvz::inter_model_init(row, qp, p->poc, kvz_hip_default_coeff_weights(qp) /* 0 from QP 50 on, where kvz_fast_coeff_cost is never used (rdo.c:311-340) */, fbits, p->mv_constraint, p->sao, p->deblock, p->fme_level, p->pu_depth_inter_max, p->no_wpp, p->fast_residual_cost,
-                          width, height, p->ref_width, p->ref_height, p->tile_x, p->tile_y, p->no_tmvp);
+                          width, height, p->ref_width, p->ref_height, p->tile_x, p->tile_y, p->no_tmvp, lists ? 1 : 0);
   };
   kvz::InterPictureTable table;
-  if (pictures) table = kvz::inter_picture_table(pictures->qp, pictures->poc, n_pictures, model_at_qp);
-  const bool cabac_build = pictures ? table.any_cabac : kvz::inter_qp_prices_with_cabac(p->qp, p->fast_residual_cost);
-  const void *kernel = cabac_build ? (const void *)kvz::inter_ctu_ticket_kernel_cabac : (const void *)kvz::inter_ctu_ticket_kernel_fast;
+  if (lists) {  // every picture has a record: its rows of the factor table travel with it
+    std::vector<int32_t> qp_all, poc_all;
+    if (!pictures) { qp_all.assign((size_t)n_pictures, p->qp); poc_all.assign((size_t)n_pictures, p->poc); }
+    table = kvz::inter_picture_table_lists(pictures ? pictures->qp : qp_all.data(), pictures ? pictures->poc : poc_all.data(), n_pictures, model_at_qp, sets, n_sets, set_of_picture);
+  } else if (pictures) table = kvz::inter_picture_table(pictures->qp, pictures->poc, n_pictures, model_at_qp);
+  const bool cabac_build = (pictures || lists) ? table.any_cabac : kvz::inter_qp_prices_with_cabac(p->qp, p->fast_residual_cost);
+  const void *kernel = lists ? (cabac_build ? (const void *)kvz::inter_ctu_ticket_kernel_lists_cabac : (const void *)kvz::inter_ctu_ticket_kernel_lists_fast)
+                             : (cabac_build ? (const void *)kvz::inter_ctu_ticket_kernel_cabac : (const void *)kvz::inter_ctu_ticket_kernel_fast);
   // resident workgroups (= wavefronts) per CU: what the kernel's registers and LDS allow -- a persistent grid, one workgroup per slot
   int fit = 0;
   KVZ_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&fit, kernel, KVZ_ICTU_THREADS, 0));
@@ -1576,7 +1591,7 @@ int kvz_hip_dev_inter_ctu_pass_pictures(const uint8_t *src, const uint8_t *ref, 
   if (env && atoi(env) > 0) per_cu = atoi(env) < fit ? atoi(env) : fit;
   if (per_cu < 1) per_cu = 1;
   int n_wg = n_cu * per_cu;
-  if (getenv("KVZ_HIP_INTER_VERBOSE")) fprintf(stderr, "kvz_hip inter pass: %s build, %d workgroups per CU x %d CUs\n", cabac_build ? "cabac" : "fast", per_cu, n_cu);
+  if (getenv("KVZ_HIP_INTER_VERBOSE")) fprintf(stderr, "kvz_hip inter pass: %s%s build, %d workgroups per CU x %d CUs\n", lists ? "lists " : "", cabac_build ? "cabac" : "fast", per_cu, n_cu);
   if ((long)n_wg > total) n_wg = (int)total;
   if (n_wg > sc.n_slabs) {
     if (sc.slabs) KVZ_HIP_CHECK(hipFree(sc.slabs));
@@ -1593,9 +1608,24 @@ int kvz_hip_dev_inter_ctu_pass_pictures(const uint8_t *src, const uint8_t *ref, 
   if (!sc.ticket) KVZ_HIP_CHECK(hipMalloc((void **)&sc.ticket, 2 * sizeof(unsigned)));
   // the model of the launch, or the table of a launch whose pictures have their own (records, then a row per distinct QP: kvz_inter_host.hpp inter_picture_table)
   kvz::InterModel m;
-  if (!pictures) model_at_qp(&m, p->qp);
+  if (!pictures && !lists) model_at_qp(&m, p->qp);
   const void *model_image = pictures ? (const void *)table.image.data() : (const void *)&m;
-  const size_t model_bytes = pictures ? table.bytes() : sizeof m;
+  const size_t model_bytes = lists ? 0 : (pictures ? table.bytes() : sizeof m);
+  if (lists) {  // the table with the factor rows has a buffer of its own, which keeps what it holds from call to call
+    bool fresh = false;
+    if (table.bytes() > sc.lists_bytes) {
+      if (sc.lists) KVZ_HIP_CHECK(hipFree(sc.lists));  // (the calling thread's stream is idle: every call ends synchronised)
+      sc.lists = nullptr; sc.lists_bytes = 0;
+      KVZ_HIP_CHECK(hipMalloc(&sc.lists, table.bytes() + table.bytes() / 8));
+      sc.lists_bytes = table.bytes() + table.bytes() / 8;
+      fresh = true;
+    }
+    if (fresh || table.image != sc.h_lists) {
+      KVZ_HIP_CHECK(hipMemcpyAsync(sc.lists, table.image.data(), table.bytes(), hipMemcpyHostToDevice, st));
+      KVZ_HIP_CHECK(hipStreamSynchronize(st));
+      sc.h_lists = table.image;
+    }
+  }
   if (model_bytes > sc.model_bytes) {
     if (sc.model) KVZ_HIP_CHECK(hipFree(sc.model));
     KVZ_HIP_CHECK(hipMalloc((void **)&sc.model, model_bytes));
@@ -1604,7 +1634,7 @@ int kvz_hip_dev_inter_ctu_pass_pictures(const uint8_t *src, const uint8_t *ref, 
   std::vector<uint32_t> items;
   kvz::inter_ticket_items(wc, hc, n_pictures, p->no_wpp, items);
   KVZ_HIP_CHECK(hipMemcpyAsync(sc.items, items.data(), (size_t)total * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-  KVZ_HIP_CHECK(hipMemcpyAsync(sc.model, model_image, model_bytes, hipMemcpyHostToDevice, st));
+  if (model_bytes) KVZ_HIP_CHECK(hipMemcpyAsync(sc.model, model_image, model_bytes, hipMemcpyHostToDevice, st));
   KVZ_HIP_CHECK(hipMemsetAsync(sc.done, 0, (size_t)total * sizeof(unsigned), st));
   KVZ_HIP_CHECK(hipMemsetAsync(sc.ticket, 0, 2 * sizeof(unsigned), st));
   KVZ_HIP_CHECK(hipStreamSynchronize(st));  // `items`, `m` and `table` are stack / heap objects of this call
@@ -1614,9 +1644,9 @@ int kvz_hip_dev_inter_ctu_pass_pictures(const uint8_t *src, const uint8_t *ref, 
   F.prof = nullptr;
   F.tile_xy = (p->ref_width || p->ref_height) ? tile_xy : nullptr;
   F.ref_count = n_references > 0 ? n_references : 0;
-  F.pictures = pictures ? (const kvz::InterPicture *)sc.model : nullptr;
+  F.pictures = lists ? (const kvz::InterPicture *)sc.lists : (pictures ? (const kvz::InterPicture *)sc.model : nullptr);
   // the kernel's model argument: what every workgroup loads once per launch -- with a table, picture 0's row (begin_ctu replaces what depends on the picture)
-  const kvz::InterModel *d_model = pictures ? table.model_of_picture(sc.model, 0) : (const kvz::InterModel *)sc.model;
+  const kvz::InterModel *d_model = lists ? table.model_of_picture(sc.lists, 0) : (pictures ? table.model_of_picture(sc.model, 0) : (const kvz::InterModel *)sc.model);
 #ifdef KVZ_ICTU_PROFILE
   static unsigned long long *d_prof = nullptr;
   if (!d_prof) KVZ_HIP_CHECK(hipMalloc((void **)&d_prof, kvz::IP_COUNT * sizeof(unsigned long long)));
@@ -1629,7 +1659,9 @@ int kvz_hip_dev_inter_ctu_pass_pictures(const uint8_t *src, const uint8_t *ref, 
   kvz::DevTimer &tm = kvz::inter_timer();
   if (!tm.e0) { KVZ_HIP_CHECK(hipEventCreate(&tm.e0)); KVZ_HIP_CHECK(hipEventCreate(&tm.e1)); }
   KVZ_HIP_CHECK(hipEventRecord(tm.e0, st));
-  if (cabac_build) hipLaunchKernelGGL(kvz::inter_ctu_ticket_kernel_cabac, dim3((unsigned)n_wg), dim3(KVZ_ICTU_THREADS), 0, st, F, d_model, kvz::device_tables(), sched);
+  if (lists && cabac_build) hipLaunchKernelGGL(kvz::inter_ctu_ticket_kernel_lists_cabac, dim3((unsigned)n_wg), dim3(KVZ_ICTU_THREADS), 0, st, F, d_model, kvz::device_tables(), sched);
+  else if (lists) hipLaunchKernelGGL(kvz::inter_ctu_ticket_kernel_lists_fast, dim3((unsigned)n_wg), dim3(KVZ_ICTU_THREADS), 0, st, F, d_model, kvz::device_tables(), sched);
+  else if (cabac_build) hipLaunchKernelGGL(kvz::inter_ctu_ticket_kernel_cabac, dim3((unsigned)n_wg), dim3(KVZ_ICTU_THREADS), 0, st, F, d_model, kvz::device_tables(), sched);
   else hipLaunchKernelGGL(kvz::inter_ctu_ticket_kernel_fast, dim3((unsigned)n_wg), dim3(KVZ_ICTU_THREADS), 0, st, F, d_model, kvz::device_tables(), sched);
   KVZ_HIP_CHECK(hipGetLastError());
   KVZ_HIP_CHECK(hipEventRecord(tm.e1, st));

@@ -33,8 +33,22 @@
 #include "kvz_ops.hpp"
 #include "kvz_tables.hpp"
 #include "kvz_residual.hpp"
+#include "kvz_recon.hpp"
 
 namespace kvz {
+
+// The kernel's builds for launches that were given scaling lists (kvz_hip_dev_inter_ctu_pass_lists, kvazaar --scaling-list; kvz_inter_tu.hip -DKVZ_ICTU_LISTS=1): every
+// level is quantised and dequantised under the factors of its position (quantize_tu), read from the picture's two rows of the launch's factor table.  A build
+// constant on the device, so that the builds without lists hold none of it; the host simulation of the lists (tests/hostsim/hostsim_inter_lists.cpp) makes it a
+// variable and has both forms of the program in one library.
+#ifndef KVZ_ICTU_LISTS
+#define KVZ_ICTU_LISTS 0
+#endif
+#ifdef KVZ_HOSTSIM
+#define KVZ_ICTU_LISTS_STATE 1
+#else
+#define KVZ_ICTU_LISTS_STATE KVZ_ICTU_LISTS
+#endif
 
 #ifndef KVZ_ICTU_THREADS
 #define KVZ_ICTU_THREADS 64  // lanes per CTU.  Measured on the MI355X with 256 sequences in flight (416x240): 64 lanes 20.9 k CTUs/s, 128: 18.8 k, 256: 11.9 k
@@ -176,6 +190,14 @@ struct InterPicture {
   uint32_t model_at;  // bytes from the first record to the picture's InterModel row
   int32_t poc;
 };
+// ... and the record of a launch with scaling lists (the LISTS builds read these in InterPicture's place): the picture's two rows of the factor table that follows the
+// model rows in the same buffer -- the row of its set (or of the flat list) at its luma qp % 6 and the one at its chroma qp % 6, KVZ_LIST_ROW_INTER words each
+// (kvz_scaling_lists.hpp scaling_list_rows_inter)
+struct InterPictureLists {
+  uint32_t model_at;
+  int32_t poc;
+  uint32_t lists_y_at, lists_c_at;  // bytes from the first record
+};
 
 struct InterSlab {  // HBM scratch of one resident workgroup: the quantised levels of the candidates of depth 1 and 2 (Y | U | V, raster inside each plane's block), written
                     // when the CU is quantised and copied to the output block if it wins; `out` stands in for the output block when the caller wants no coefficients
@@ -197,7 +219,8 @@ struct InterFrames {
   InterSlab *slabs;      // one per resident workgroup
   const int *tile_xy;    // NULL, or [n][2]: every picture's own origin in its reference frame (tiles of one size from different places of the grid in one launch)
   int ref_count;         // 0, or the number of reference frames: picture p predicts from frame p % ref_count (several tiles of one frame in the launch)
-  const InterPicture *pictures;  // NULL (the kernel's model argument for every picture), or [n]: every picture's own model row and POC
+  const InterPicture *pictures;  // NULL (the kernel's model argument for every picture), or [n]: every picture's own model row and POC (a launch with scaling
+                                 // lists always has them, as InterPictureLists records)
   unsigned long long *prof;  // [IP_COUNT] or NULL (KVZ_ICTU_PROFILE)
 };
 
@@ -213,7 +236,12 @@ struct PView { lu8 *p; int s; };  // a plane of a block in LDS: sample (x, y) at
 
 // Per-picture constants and the small tables, copied into LDS once per workgroup (the kernel is persistent): a table look-up on the decision path is an LDS read, not a
 // round trip to L2 / HBM.
-struct QScal { int flat_q, add, q_bits, dq_scale, dq_shift; };  // kvz_quant / kvz_dequant with flat lists (quant-generic.c:57-81, 335-339)
+struct QScal {  // kvz_quant / kvz_dequant with flat lists (quant-generic.c:57-81, 335-339)
+  int flat_q, add, q_bits, dq_scale, dq_shift;
+#if KVZ_ICTU_LISTS_STATE
+  int dq_qp_per;  // with lists (quant-generic.c:309-333; the model's scalars were made for that rule: kvz_inter_host.hpp inter_model_init): dq_shift includes the + 4
+#endif
+};
 struct InterConst {
   double lambda, lambda_sqrt;
   uint64_t coeff_weights;
@@ -229,6 +257,9 @@ struct InterConst {
   int8_t chroma_filter[8][4];  // filter.c:74-84
   u8 avail_top[16][16], avail_left[16][16];  // intra.c:47-82 as regenerated by kvz_tables.hpp
   u32 div_magic[32];           // 2^20 / d + 1 (div_by's multiplier, kvz_inter_ctu_pix.inc): there is no integer division in hardware, and one per staged window was ~25 instructions
+#if KVZ_ICTU_LISTS_STATE
+  const KVZ_GLB u32 *lf_y, *lf_c;  // the picture's factor rows in HBM, luma and chroma QP (begin_ctu)
+#endif
 };
 
 // A 32x32 block is interpolated, compared and transformed in 16x16 TILES (its four quadrants; smaller blocks are one tile): the sample buffers below are sized for a tile.
@@ -531,6 +562,9 @@ struct InterCtu {
       if (tid < 8) {
         const QuantScalars f = model->qf[tid >> 2][tid & 3], iv = model->qi[tid >> 2][tid & 3];
         K->q[tid >> 2][tid & 3] = QScal{ f.flat_q, f.add, f.q_bits, iv.dq_scale, iv.dq_shift };
+#if KVZ_ICTU_LISTS_STATE
+        K->q[tid >> 2][tid & 3].dq_qp_per = iv.dq_qp_per;
+#endif
       }
       for (int i = tid; i < 128; i += KVZ_ICTU_THREADS) K->fbits[i] = ((const KVZ_GLB float *)model->fbits)[i];
       for (int i = tid; i < 1024; i += KVZ_ICTU_THREADS) K->dct32[i] = (int8_t)((const KVZ_GLB i16 *)tb->dct[3])[i];
@@ -557,6 +591,15 @@ struct InterCtu {
   // the model of picture frame_ of a launch whose pictures have their own (F.pictures)
   IC_DEV const KVZ_GLB InterModel *picture_model_row(int frame_, int *poc)
   {
+#if KVZ_ICTU_LISTS_STATE
+    if (KVZ_ICTU_LISTS) {  // a launch with lists: the wider record, and with it the picture's two factor rows (a picture without a set has the flat list's)
+      const KVZ_GLB InterPictureLists *rec = (const KVZ_GLB InterPictureLists *)F.pictures + frame_;
+      *poc = rec->poc;
+      K->lf_y = (const KVZ_GLB u32 *)((const KVZ_GLB uint8_t *)F.pictures + rec->lists_y_at);
+      K->lf_c = (const KVZ_GLB u32 *)((const KVZ_GLB uint8_t *)F.pictures + rec->lists_c_at);
+      return (const KVZ_GLB InterModel *)((const KVZ_GLB uint8_t *)F.pictures + rec->model_at);
+    }
+#endif
     const KVZ_GLB InterPicture *rec = (const KVZ_GLB InterPicture *)F.pictures + frame_;
     *poc = rec->poc;
     return (const KVZ_GLB InterModel *)((const KVZ_GLB uint8_t *)F.pictures + rec->model_at);
@@ -574,6 +617,9 @@ struct InterCtu {
         for (int i = 0; i < 8; i++) {
           const KVZ_GLB QuantScalars *f = &pm->qf[i >> 2][i & 3], *iv = &pm->qi[i >> 2][i & 3];
           K->q[i >> 2][i & 3] = QScal{ f->flat_q, f->add, f->q_bits, iv->dq_scale, iv->dq_shift };
+#if KVZ_ICTU_LISTS_STATE
+          K->q[i >> 2][i & 3].dq_qp_per = iv->dq_qp_per;
+#endif
         }
       }
       g_ic.ref_idx = F.ref_count ? frame_ % F.ref_count : frame_; g_ic.cu_frame = (const CuInfo *)F.cu + (long)frame_ * F.cells;

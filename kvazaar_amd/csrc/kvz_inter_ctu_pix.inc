@@ -763,17 +763,37 @@ IC_FN bool quantize_tu(int lv, int c, int xl, int yl, int w, bool intra, bool ea
   IC_SYNC();
   transform_pass(dst, l2, l2 - 1, false, tb);
   transform_pass(dst, l2, l2 + 6, false, tb);
-  // kvz_quant (quant-generic.c:68-81, flat lists, no sign hiding) fused with "any level non-zero", kvz_fast_coeff_cost of the levels and -- into the TRANSPOSED position, for the
-  // inverse passes -- kvz_dequant (quant-generic.c:298-340); all reads of the block before its writes
+  // kvz_quant (quant-generic.c:68-81, no sign hiding) fused with "any level non-zero", kvz_fast_coeff_cost of the levels and -- into the TRANSPOSED position, for the
+  // inverse passes -- kvz_dequant (quant-generic.c:298-340); all reads of the block before its writes.
+  // Flat lists: one forward and one inverse factor for the block.  The LISTS builds (kvz_inter_ctu.hpp KVZ_ICTU_LISTS): the two factors of every position (kvz_recon.hpp
+  // list_index, list_factor), from the plane of the block's list -- (intra CU ? 0 : 3) + c, list_plane_of; an intra CU of a B slice takes the intra lists under the
+  // B slice's rounding -- in the picture's row at the block's QP, luma or chroma.  A picture without a set reads the flat list's row: the same path.
   u32 nz = 0, wsum = 0;
   const uint64_t weights = M->coeff_weights;
   IC_KEEP_DECL(deq, 16, 32 * 32);
+#if KVZ_ICTU_LISTS_STATE
+  QuantScalars dq;  // what dequant_product reads
+  dq.dq_shift = qs.dq_shift; dq.dq_qp_per = qs.dq_qp_per;
+  const KVZ_GLB u32 *plane = (c ? K->lf_c : K->lf_y) + list_plane_of(intra, c) * KVZ_LIST_PLANE;
+#endif
   IC_FOR(tid) {
+    // the factor words of the lane's whole trip (up to 16 at 32x32) leave together, ahead of the coefficient reads: HBM loads in flight behind one another and behind
+    // the LDS reads, not one dependent load per coefficient
+    u32 fw[16];
+#if KVZ_ICTU_LISTS_STATE
+    if (KVZ_ICTU_LISTS) {
+#pragma unroll
+      for (int t = 0; t < 16; t++) { const int i = tid + KVZ_ICTU_THREADS * t; fw[t] = i < n ? plane[list_index(l2, i)] : 0u; }
+    }
+#endif
     for (int t = 0; t < 16; t++) {
       const int i = tid + KVZ_ICTU_THREADS * t;
       if (i >= n) break;
       const int cf = tb[i];
-      int level = (int)((umul24((u32)iabs(cf), (u32)qs.flat_q) + (u32)qs.add) >> qs.q_bits);  // 32 bits hold it: |cf| <= 2^15, a flat 8-bit list's multiplier <= 26214, add <= 171 << 18
+      // 32 bits hold it: |cf| <= 2^15, a flat 8-bit list's multiplier <= 26214, add <= 171 << 18; with lists the multiplier is (26214 << 4) / 13 = 32263 at most
+      // (entries >= 13: kvz_scaling_lists.hpp) and the product stays below 2^30 (kvz_recon.hpp quant_level) -- both operands within 24 bits either way
+      const ListFactor lf = KVZ_ICTU_LISTS ? list_factor(fw[t]) : ListFactor{ qs.flat_q, 0 };
+      int level = (int)((umul24((u32)iabs(cf), (u32)lf.fwd) + (u32)qs.add) >> qs.q_bits);
       if (cf < 0) level = -level;
       level = iclip(-32768, 32767, level);
       levels[i] = (i16)level;
@@ -781,6 +801,11 @@ IC_FN bool quantize_tu(int lv, int c, int xl, int yl, int w, bool intra, bool ea
       int a = iabs(level);
       if (a > 3) a = 3;
       wsum += (u32)((weights >> (16 * a)) & 0xffff);
+#if KVZ_ICTU_LISTS_STATE
+      // quant-generic.c:309-333, either side of its branch (dequant_product); |level| <= 2^15 and the inverse factor <= 72 * 255 fit the 24-bit multiply
+      if (KVZ_ICTU_LISTS) IC_KEEP(deq, t, i) = dequant_product(mul24(level, lf.inv), dq);
+      else
+#endif
       IC_KEEP(deq, t, i) = iclip(-32768, 32767, (mul24(level, qs.dq_scale) + (1 << (qs.dq_shift - 1))) >> qs.dq_shift);
     }
   }

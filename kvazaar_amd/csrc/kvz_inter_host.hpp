@@ -7,6 +7,7 @@
 
 #include "kvz_inter_ctu.hpp"
 #include "kvz_inter_pictures.hpp"
+#include "kvz_scaling_lists.hpp"
 #include "kvz_tables.hpp"
 
 namespace kvz {
@@ -62,7 +63,8 @@ inline int inter_pass_geometry_refused(int width, int height, int n_pictures, in
 }
 
 inline void inter_model_init(InterModel *m, int qp, int poc, uint64_t coeff_weights, const float fbits[128], int mv_constraint, int sao, int deblock, int fme_level,
-                             int pu_depth_inter_max, int no_wpp, int fast_residual_cost, int pic_w = 0, int pic_h = 0, int ref_w = 0, int ref_h = 0, int tile_x = 0, int tile_y = 0, int no_tmvp = 0)
+                             int pu_depth_inter_max, int no_wpp, int fast_residual_cost, int pic_w = 0, int pic_h = 0, int ref_w = 0, int ref_h = 0, int tile_x = 0, int tile_y = 0, int no_tmvp = 0,
+                             int scaling_list = 0 /* a launch with scaling lists: the inverse scalars of the rule that takes a factor per position (quant-generic.c:309-333) */)
 {
   memset(m, 0, sizeof *m);
   m->qp = qp; m->poc = poc;
@@ -87,7 +89,7 @@ inline void inter_model_init(InterModel *m, int qp, int poc, uint64_t coeff_weig
   for (int l2 = 2; l2 <= 5; l2++)
     for (int c = 0; c < 2; c++) {
       m->qf[c][l2 - 2] = quant_scalars(qp, 8, 0 /* B slice: rounding 85 */, 0, 1 << l2, c ? 2 : 0);
-      m->qi[c][l2 - 2] = quant_scalars(qp, 8, 0, 0, 1 << l2, c ? 2 : 0);
+      m->qi[c][l2 - 2] = quant_scalars(qp, 8, 0, scaling_list, 1 << l2, c ? 2 : 0);
     }
   memcpy(m->fbits, fbits, sizeof m->fbits);
 }
@@ -113,9 +115,10 @@ struct InterPictureTable {
   std::vector<uint64_t> image;
   int n_rows = 0;
   bool any_cabac = false;  // some picture prices coefficients with the residual coder: the launch takes the kernel build that holds its contexts
+  size_t record_bytes = sizeof(InterPicture);  // (sizeof(InterPictureLists) in a launch with scaling lists; either record starts with model_at)
   size_t bytes() const { return image.size() * sizeof(uint64_t); }
   // the row of a picture in a copy of the image that starts at `base` (the device's, or the image itself)
-  const InterModel *model_of_picture(const void *base, int picture) const { return (const InterModel *)((const uint8_t *)base + ((const InterPicture *)image.data())[picture].model_at); }
+  const InterModel *model_of_picture(const void *base, int picture) const { return (const InterModel *)((const uint8_t *)base + ((const InterPicture *)((const uint8_t *)image.data() + (size_t)picture * record_bytes))->model_at); }
 };
 template <class InitRow> inline InterPictureTable inter_picture_table(const int32_t *qp, const int32_t *poc, int n_pictures, const InitRow &init_row)
 {
@@ -132,6 +135,36 @@ template <class InitRow> inline InterPictureTable inter_picture_table(const int3
     t.any_cabac = t.any_cabac || m->coeff_cabac;
   }
   for (int i = 0; i < n_pictures; i++) ((InterPicture *)base)[i] = InterPicture{ (uint32_t)(rows_at + (size_t)row_of_qp[qp[i]] * sizeof(InterModel)), poc[i] };
+  return t;
+}
+
+// ... and of a launch with scaling lists (kvz_hip_dev_inter_ctu_pass_lists; checked by scaling_list_sets_known): n InterPictureLists records, the InterModel rows, then
+// the factor table -- six rows (qp % 6) of KVZ_LIST_ROW_INTER words per set, the sets in order, the flat list behind them (scaling_list_rows_inter) -- and every
+// record's two rows of it: those of the picture's set, or of the flat list (set 0xffff), at its luma and its chroma QP (scaling_list_row; the byte offsets fit 32 bits for every n_sets the check accepts).
+// set_of_picture == nullptr: set 0 for every picture.  init_row must make its rows for a launch with lists (inter_model_init's scaling_list).
+template <class InitRow> inline InterPictureTable inter_picture_table_lists(const int32_t *qp, const int32_t *poc, int n_pictures, const InitRow &init_row,
+                                                                            const kvz_hip_scaling_lists *sets, int n_sets, const uint16_t *set_of_picture)
+{
+  static_assert(sizeof(InterPictureLists) == 16, "records and rows share a buffer of 8-byte words");
+  InterPictureTable t;
+  t.record_bytes = sizeof(InterPictureLists);
+  int row_of_qp[52], qp_of_row[52];
+  t.n_rows = inter_qp_rows(qp, n_pictures, row_of_qp, qp_of_row);
+  const size_t rows_at = (size_t)n_pictures * sizeof(InterPictureLists), lists_at = rows_at + (size_t)t.n_rows * sizeof(InterModel), row_bytes = KVZ_LIST_ROW_INTER * sizeof(uint32_t);
+  t.image.assign((lists_at + (size_t)(n_sets + 1) * 6 * row_bytes) / sizeof(uint64_t), 0);
+  uint8_t *base = (uint8_t *)t.image.data();
+  for (int r = 0; r < t.n_rows; r++) {
+    InterModel *m = (InterModel *)(base + rows_at) + r;
+    init_row(m, qp_of_row[r]);
+    t.any_cabac = t.any_cabac || m->coeff_cabac;
+  }
+  for (int k = 0; k <= n_sets; k++) scaling_list_rows_inter(k < n_sets ? &sets[k] : nullptr, (uint32_t *)(base + lists_at) + (size_t)k * 6 * KVZ_LIST_ROW_INTER);
+  for (int i = 0; i < n_pictures; i++) {
+    const int set = set_of_picture ? set_of_picture[i] : 0;
+    const size_t row_y = scaling_list_row(set, n_sets, qp[i]), row_c = scaling_list_row(set, n_sets, scaled_qp(2, qp[i], 0));
+    ((InterPictureLists *)base)[i] = InterPictureLists{ (uint32_t)(rows_at + (size_t)row_of_qp[qp[i]] * sizeof(InterModel)), poc[i], (uint32_t)(lists_at + row_y * row_bytes),
+                                                        (uint32_t)(lists_at + row_c * row_bytes) };
+  }
   return t;
 }
 

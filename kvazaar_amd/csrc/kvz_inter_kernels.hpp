@@ -20,13 +20,20 @@ struct InterSched {
 };
 
 // two builds of the kernel (kvz_inter_ctu.hpp KVZ_ICTU_CABAC): `_fast` for pictures whose coefficients are priced by kvz_fast_coeff_cost (small context sets: 20 KB of LDS,
-// eight workgroups per CU), `_cabac` for those priced with the residual coder's contexts
+// eight workgroups per CU), `_cabac` for those priced with the residual coder's contexts; and the same two for launches with scaling lists
+// (-DKVZ_ICTU_LISTS=1, kvz_inter_ctu.hpp: kvz_hip_dev_inter_ctu_pass_lists), `_lists_fast` / `_lists_cabac`
 #define KVZ_ICTU_KERNEL(name) __global__ void __launch_bounds__(KVZ_ICTU_THREADS) __attribute__((amdgpu_waves_per_eu(KVZ_ICTU_WAVES_PER_EU, KVZ_ICTU_WAVES_PER_EU))) name(const InterFrames F, const InterModel *model, const Tables *tb, const InterSched sched)
 #ifndef KVZ_INTER_KERNEL_BODY
 KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_fast);
 KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_cabac);
+KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_lists_fast);
+KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_lists_cabac);
 #else
-#if KVZ_ICTU_CABAC
+#if KVZ_ICTU_LISTS && KVZ_ICTU_CABAC
+KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_lists_cabac)
+#elif KVZ_ICTU_LISTS
+KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_lists_fast)
+#elif KVZ_ICTU_CABAC
 KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_cabac)
 #else
 KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_fast)

@@ -161,17 +161,22 @@ KVZ_HD i16 dequant_level(int level, const QuantScalars &q) { return (i16)iclip(-
 // scaling_list set: dq_shift = 20 - 14 - transform_shift + 4, dq_qp_per = qp_scaled / 6).  While the shift exceeds qp / 6 the product is rounded and shifted right;
 // from qp / 6 == shift on (5 at 4x4, 6 at 8x8, 7 at 16x16, 8 at 32x32) it is clipped, shifted LEFT by the difference and clipped again.  |level * inv| <=
 // 32768 * 18360 < 2^30.  With the factor of a flat list (inv_quant_scale * 16) both sides give what the rule above gives.
-KVZ_HD i16 dequant_level(int level, const QuantScalars &q, int inv)
+// (dequant_product: the rule from the product level * inv on, for the caller that multiplies its own way -- the inter pass's 24-bit multiply)
+KVZ_HD i16 dequant_product(int prod, const QuantScalars &q)
 {
-  const int prod = level * inv, down = q.dq_shift - q.dq_qp_per;
+  const int down = q.dq_shift - q.dq_qp_per;
   if (down > 0) return (i16)iclip(-32768, 32767, (prod + (1 << (down - 1))) >> down);
   return (i16)iclip(-32768, 32767, iclip(-32768, 32767, prod) * (1 << -down));
 }
+KVZ_HD i16 dequant_level(int level, const QuantScalars &q, int inv) { return dequant_product(level * inv, q); }
 
 // ---- per-coefficient scaling lists (scalinglist.c:289-342, 375-391) in compact form: what kvz_scalinglist_set upsamples into a table per block size is indexed
 // here the way it is upsampled.  A plane's factors: 16 for 4x4, 64 for 8x8, 64 + the DC term for 16x16 and for 32x32 -- KVZ_LIST_PLANE words, padded to 16 bytes;
 // a row = the three planes' factors at one qp % 6.  A word holds the forward factor (quant_level) in its low half and the inverse one (dequant_level) in its high half.
-enum { KVZ_LIST_PLANE = 212, KVZ_LIST_ROW = 3 * KVZ_LIST_PLANE };
+// The all-intra pass keeps rows of the three intra lists; the inter pass rows of all six, intra Y, U, V then inter Y, U, V (KVZ_LIST_ROW_INTER; kvz_scaling_lists.hpp
+// scaling_list_rows_inter), and a block of plane c reads list (intra CU ? 0 : 3) + c (quant-generic.c:59, :312).
+enum { KVZ_LIST_PLANE = 212, KVZ_LIST_ROW = 3 * KVZ_LIST_PLANE, KVZ_LIST_ROW_INTER = 6 * KVZ_LIST_PLANE };
+KVZ_HD int list_plane_of(bool intra_cu, int c) { return (intra_cu ? 0 : 3) + c; }
 // where the factors of element e (row-major) of a 2^l2 block are in its plane's part of a row: list entry 8 * (y >> ratio) + (x >> ratio), the DC term for (0, 0)
 KVZ_HD int list_index(int l2, int e)
 {

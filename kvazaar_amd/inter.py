@@ -126,6 +126,9 @@ class InterPictures:
         lib.kvz_hip_dev_loop_filters_inter_pictures.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 3
         lib.kvz_hip_dev_entropy_code_inter_pictures.restype = C.c_long
         lib.kvz_hip_dev_entropy_code_inter_pictures.argtypes = [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        if hasattr(lib, "kvz_hip_dev_inter_ctu_pass_lists"):  # (a library from before the entry point still loads: tools/bench_inter_scaling_lists.py times one)
+            lib.kvz_hip_dev_inter_ctu_pass_lists.restype = C.c_int
+            lib.kvz_hip_dev_inter_ctu_pass_lists.argtypes = [C.c_void_p] * 6 + [C.c_int] * 3 + [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         self.d_dbk = None
         lib.kvz_hip_dev_entropy_code_inter.restype = C.c_long
         lib.kvz_hip_dev_entropy_code_inter.argtypes = [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
@@ -135,6 +138,7 @@ class InterPictures:
         self.ctus = ((width + 63) // 64) * ((height + 63) // 64)
         self.d_coeff = e(n * self.ctus * 6144 * 2) if with_levels else None  # KVZ_HIP_CTU_COEFFS int16 per CTU: what the entropy coder reads
         self._entropy_out = None
+        self._list_sets, self._list_index, self._n_list_sets = None, None, 0  # set_scaling_lists
 
     def upload(self, i, src, ref, ref_cu):
         up = self.lib.kvz_hip_dev_upload
@@ -143,8 +147,38 @@ class InterPictures:
             assert a.nbytes == size
             up(base + i * size, a.ctypes.data, size)
 
+    FLAT = 0xffff  # set_of_picture: the picture stays without lists
+
+    def set_scaling_lists(self, sets, set_of_picture=None):
+        """Later run() calls quantise picture i under sets[set_of_picture[i]] (InterPictures.FLAT: flat; None: every picture under sets[0]) through
+        kvz_hip_dev_inter_ctu_pass_lists.  sets: a sequence of batch.ScalingLists, the conventions of HipBatch.set_scaling_lists; an empty sequence clears.  State of
+        the object until changed or cleared.  The library checks the sets when a launch is made: run() raises when it refuses them (see stderr)"""
+        from .batch import ScalingListsStruct
+        sets = list(sets)
+        if not sets:
+            self._list_sets, self._list_index, self._n_list_sets = None, None, 0
+            return
+        index = None
+        if set_of_picture is not None:
+            if len(set_of_picture) != self.n:
+                raise ValueError(f"set_of_picture of {len(set_of_picture)} pictures for {self.n}")
+            index = (C.c_uint16 * self.n)(*[int(v) for v in set_of_picture])
+        self._list_sets, self._list_index, self._n_list_sets = (ScalingListsStruct * len(sets))(*[s.struct for s in sets]), index, len(sets)
+
+    def clear_scaling_lists(self):
+        """the object is again what it was before the first set_scaling_lists"""
+        self.set_scaling_lists([])
+
     def run(self, params, pictures=None):
-        """the CTU pass of the n pictures; pictures (InterPictureParams): every picture at its own QP and POC instead of params.qp / params.poc"""
+        """the CTU pass of the n pictures; pictures (InterPictureParams): every picture at its own QP and POC instead of params.qp / params.poc.  While the object
+        holds scaling lists (set_scaling_lists) the launch is kvz_hip_dev_inter_ctu_pass_lists"""
+        if self._n_list_sets:
+            rc = self.lib.kvz_hip_dev_inter_ctu_pass_lists(self.d_src, self.d_ref, self.d_ref_cu, self.d_rec, self.d_cu, self.d_coeff, self.w, self.h, self.n, C.addressof(params), None, 0,
+                                                           pictures.ptr if pictures is not None else None, C.addressof(self._list_sets), self._n_list_sets,
+                                                           C.addressof(self._list_index) if self._list_index is not None else None)
+            if rc != 0:
+                raise RuntimeError(f"kvz_hip_dev_inter_ctu_pass_lists returned {rc}")
+            return
         if pictures is not None:
             rc = self.lib.kvz_hip_dev_inter_ctu_pass_pictures(self.d_src, self.d_ref, self.d_ref_cu, self.d_rec, self.d_cu, self.d_coeff, self.w, self.h, self.n, C.addressof(params), None, 0,
                                                               pictures.ptr)
