@@ -159,7 +159,8 @@ namespace kvz {
 // Optional in-kernel timeline (build with -DKVZ_CTU_PROFILE): lane 0 of every workgroup adds the shader-clock cycles
 // spent since the previous mark to a per-category counter in HBM.  Categories are the KVZ_P_* constants.
 #define KVZ_PROF_PU_AT (2 * KVZ_P_COUNT + 16)  /* F.prof: [0, 2 COUNT) stages, then 16 words of rdoq_block_wave (8 sections, 4 + 4 cycles / calls by block size), then the stages inside eval_pu */
-#define KVZ_PROF_WORDS (4 * KVZ_P_COUNT + 16)
+#define KVZ_PROF_W32_AT (4 * KVZ_P_COUNT + 16)  /* ... then the stages of the 32x32 units' reconstructions (the 16x16 CUs' share the table of eval_pu: no instantiation has both) */
+#define KVZ_PROF_WORDS (6 * KVZ_P_COUNT + 16)
 enum { KVZ_P_INIT = 0, KVZ_P_REFS, KVZ_P_PRED35, KVZ_P_SATD, KVZ_P_SELECT, KVZ_P_RPRED, KVZ_P_FDCT, KVZ_P_QUANT, KVZ_P_IDCT, KVZ_P_RECON,
        KVZ_P_COST, KVZ_P_COPY, KVZ_P_FINISH, KVZ_P_MISC, KVZ_P_COEFFBITS, KVZ_P_RDOQ, KVZ_P_COUNT };
 #if defined(KVZ_CTU_PROFILE) && !defined(KVZ_HOSTSIM)
@@ -303,7 +304,7 @@ template <bool CABAC> struct CtuSharedT {
                              // by then the split result has been written to the frame (run()).
 #if defined(KVZ_CTU_PROFILE) && !defined(KVZ_HOSTSIM)
   unsigned long long prof_rq[16];   // rdoq_block_wave's sections and sizes (luma blocks, so one wavefront adds), flushed with prof_acc
-  unsigned long long prof_acc[64];  // [category] cycles, [KVZ_P_COUNT + category] marks; [32 + ...] the same inside the 4x4 PUs of the NxN attempt (eval_pu)
+  unsigned long long prof_acc[96];  // [category] cycles, [KVZ_P_COUNT + category] marks; [32 prof_pu + ...] the same inside the 4x4 PUs of the NxN attempt (eval_pu) or a 16x16 CU's reconstruction (1), a 32x32 unit's (2)
   int prof_pu;
 #endif
   CtuCu cu[4][64];
@@ -441,7 +442,7 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false, bool
   {
     if (threadIdx.x == 0) {
       const unsigned long long t = __builtin_amdgcn_s_memtime();
-      const int at = s->prof_pu ? 32 : 0;
+      const int at = 32 * s->prof_pu;
       s->prof_acc[at + cat] += t - t_last;  // LDS: a global atomic per mark would dominate what is being measured
       s->prof_acc[at + KVZ_P_COUNT + cat] += 1;
       t_last = __builtin_amdgcn_s_memtime();
@@ -1705,16 +1706,19 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false, bool
 #endif
   }
 
-  // Both passes of a 16- or 32-point transform of plane c, in place on x.  Device: luma on the wavefront playing threads 0..63, V too,
-  // U on the other one, chained through MFMA registers (kvz_mfma.hpp).  Host: one thread, scalar loops through a temporary --
-  // the same integers (fwd_point / inv_point).
-  KVZ_DEV void transform_big(int l2, i16 *x, bool inverse, int tid, int c) const
+  // Both passes of a 16- or 32-point transform of plane c, in place on x.  Device: luma on the wavefront playing threads 0..63, chroma
+  // on the other one, chained through MFMA registers (kvz_mfma.hpp); `pair`: the 16x16 block that follows x in memory too (V behind U in tb_big: the table
+  // operands loaded once, the two chains interleaved).  Host: one thread, scalar loops through a temporary -- the same integers (fwd_point / inv_point) --
+  // and a call per plane (big_pairs()).
+  KVZ_DEV void transform_big(int l2, i16 *x, bool inverse, int tid, int c, bool pair = false) const
   {
 #ifndef KVZ_HOSTSIM
-    if ((tid >> 6) != (c & 1)) return;
+    if ((tid >> 6) != (c ? 1 : 0)) return;
     if (l2 == 5) mfma_transform_block<32>(x, x, inverse, tb, tid & 63);
+    else if (pair) mfma_transform_blocks16<2>(x, x, inverse, tb, tid & 63);
     else mfma_transform_block<16>(x, x, inverse, tb, tid & 63);
 #else
+    (void)pair;
     if (tid != 0) return;
     const int n = 1 << l2;
     i16 tmp[32 * 32];
@@ -1730,11 +1734,20 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false, bool
 #endif
   }
 
+  // Does the device take the two 16-point chroma blocks of a 32x32 unit in ONE call of transform_big (plane 1 with `pair`)?
+#ifdef KVZ_HOSTSIM
+  KVZ_DEV static bool big_pairs(const TuSet &) { return false; }
+#else
+  KVZ_DEV static bool big_pairs(const TuSet &t) { return t.lw == 5; }
+#endif
+
   // ---- the per-plane sums of a reconstruction stage (s->acc: [0..2] SSD, [3..5] weight sums, [6..8] counts of levels).  Every lane decomposition below places its
   // lanes so that a DPP row of sixteen lanes never mixes planes: ONE row reduction (row16_sum + four v_readlane) serves all three planes of a stage, and the
   // decompositions differ only in which plane a row belongs to:
   //   ROWS_CU8    recon_cu8, eval_pu: the wavefront playing threads 0..63 is all luma; on the other one row 0 is U and row 1 V
-  //   ROWS_W16    a 16x16 CU, one trip on the first wavefront: rows 0-1 luma, row 2 U, row 3 V
+  //   ROWS_CU16   recon_cu16: one plane per wavefront and call -- luma on the wavefront playing threads 0..63 (rows 0-1; 2-3 idle), U, then V, on all rows of the
+  //               other one.  One writer per slot -- the wavefront that owns the plane -- so the sums are stored, not added; returns the plane's sum (packed: its count)
+  //   ROWS_W16    a 16x16 CU (recon_tus: sign data hiding), one trip on the first wavefront: rows 0-1 luma, row 2 U, row 3 V
   //   ROWS_W32_Y  a 32x32 unit, trip 0: both wavefronts all luma
   //   ROWS_W32_C  ... trip 1: the first wavefront, rows 0-1 U, rows 2-3 V
   // `packed`: v is a sum of LevelCost words.  ROWS_CU8 has one writer per slot and stage -- each wavefront owns its planes' slots -- and at most 64 words per
@@ -1743,7 +1756,7 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false, bool
   // Every lane of a wavefront that has tasks in the trip comes here, lanes without a task with c = -1 and v = 0.
   // Returns, on the device and for ROWS_CU8, the sum of the lane's own plane (V's on the chroma wavefront's lanes without a task) -- every lane of the wavefront has it
   // in registers here, where the next stage would otherwise read acc[] back and wait; 0 otherwise (the host's sums are complete when the phase is).
-  enum RowPlan { ROWS_CU8, ROWS_W16, ROWS_W32_Y, ROWS_W32_C };
+  enum RowPlan { ROWS_CU8, ROWS_CU16, ROWS_W16, ROWS_W32_Y, ROWS_W32_C };
   KVZ_DEV u32 plane_sums(RowPlan plan, int tid, int c, u32 v, bool packed, int base) const
   {
 #ifdef KVZ_HOSTSIM
@@ -1753,7 +1766,6 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false, bool
     else s->acc[base + c] += v;
     return 0;
 #else
-    (void)c;
     if ((plan == ROWS_W16 || plan == ROWS_W32_C) && tid >= 64) return 0;  // wavefront-uniform: the other wavefront has no tasks in this trip
     const int x = row16_sum((int)v);
     const u32 r0 = (u32)__builtin_amdgcn_readlane(x, 15), r1 = (u32)__builtin_amdgcn_readlane(x, 31), r2 = (u32)__builtin_amdgcn_readlane(x, 47), r3 = (u32)__builtin_amdgcn_readlane(x, 63);
@@ -1764,6 +1776,15 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false, bool
         else { s->acc[base + 1] += r0; s->acc[base + 2] += r1; }
       }
       return tid < 64 ? luma : (tid < 80 ? r0 : r1);
+    }
+    if (plan == ROWS_CU16) {  // c: lane 0's, which always has a task.  A row stays below 128 levels (luma: sixteen lanes of eight) and 2^23
+      u32 a = r0 + r1 + r2 + r3, n = 0;
+      if (packed) { a = (r0 & 0xffffffu) + (r1 & 0xffffffu) + (r2 & 0xffffffu) + (r3 & 0xffffffu); n = (r0 >> 24) + (r1 >> 24) + (r2 >> 24) + (r3 >> 24); }
+      if ((tid & 63) == 0) {
+        if (packed) { s->acc[3 + c] = a; s->acc[6 + c] = n; }
+        else s->acc[base + c] = a;
+      }
+      return packed ? n : a;
     }
     if ((tid & 63) != 0) return 0;
     auto put = [&](int plane, u32 a, u32 b) {
@@ -2014,6 +2035,7 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false, bool
   // ---- the arithmetic stages of recon_tus() for units of 16 and 32 samples: a lane task is a row segment of EIGHT samples of one plane (the 8x8 CU has
   // recon_cu8; one sample per lane and trip was three trips on two wavefronts for a 16x16 CU and twelve for a 32x32 unit).  Where the tasks sit:
   //   16x16 CU    32 luma + 8 U + 8 V tasks, ONE trip on the wavefront playing threads 0..63: DPP rows 0-1 luma, the first half of row 2 U, of row 3 V
+  //               (with sign data hiding switched on and in the RDOQ instantiation only: otherwise a 16x16 CU has recon_cu16, a role per wavefront)
   //   32x32 unit  trip 0: 128 luma tasks on both wavefronts; trip 1: 32 U (rows 0-1) + 32 V (rows 2-3) on the first
   // (plane_sums: ROWS_W16, ROWS_W32_Y, ROWS_W32_C).
   // Returns the plane of thread tid's task in `trip` (-1: none) and which eight samples of the plane: elements 8 seg .. 8 seg + 7, row-major.
@@ -2077,6 +2099,201 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false, bool
     }
   }
 
+  // kvz_intra_predict (intra.c:252-301) for sample (x, y) of BOTH chroma planes of a 2^l2 unit -- predict_pixel() for c = 1 and c = 2, which read the unfiltered
+  // references and have no edge filters, with what the planes share worked out once: position, displacement, fraction and where in the (extended) main reference
+  // the two samples lie (angular_ref's choice).
+  KVZ_DEV void predict_chroma_pair(int l2, int mode, int x, int y, u8 *pu, u8 *pv) const
+  {
+    const u8 *top_u = s->ref[1][0], *left_u = s->ref[1][1], *top_v = s->ref[2][0], *left_v = s->ref[2][1];
+    if (mode == 0) { *pu = planar_pixel(l2, x, y, top_u, left_u); *pv = planar_pixel(l2, x, y, top_v, left_v); return; }
+    if (mode == 1) { *pu = s->dcval[1]; *pv = s->dcval[2]; return; }
+    const bool vertical = mode >= 18;
+    const int px = vertical ? x : y, py = vertical ? y : x;
+    const int delta_pos = (py + 1) * s->mode_disp[mode], di = delta_pos >> 5, df = delta_pos & 31, inv = s->mode_inv[mode];  // displacement 0: di = df = 0, the sample itself
+    const int i1 = px + di, i2 = i1 + 1;
+    const bool main1 = i1 >= -1, main2 = i2 >= -1;
+    const int o1 = main1 ? i1 + 1 : (128 + (-1 - i1) * inv) >> 8, o2 = main2 ? i2 + 1 : (128 + (-1 - i2) * inv) >> 8;
+    auto plane = [&](const u8 *top, const u8 *left) {
+      const u8 *main_ref = vertical ? top : left, *side_ref = vertical ? left : top;
+      const int r1 = (main1 ? main_ref : side_ref)[o1], r2 = (main2 ? main_ref : side_ref)[o2];
+      return (u8)(((32 - df) * r1 + df * r2 + 16) >> 5);
+    };
+    *pu = plane(top_u, left_u);
+    *pv = plane(top_v, left_v);
+  }
+
+  // The 16x16 CU -- a 16x16 luma and two 8x8 chroma units -- with the stages of recon_tus() per wavefront ROLE, after the model of recon_cu8.  The wavefront playing
+  // threads 0..63 is all luma: 32 row tasks of eight samples (predict_row8, the wide quantise and reconstruct bodies of recon_tus) around the 16-point passes on the
+  // matrix cores, in place.  The other one is all chroma: lane e takes sample e of U AND of V -- they share position, mode arithmetic and matrix rows -- through the
+  // 8-point row passes of kvz_recon.hpp (cu8_fwd_first<3> .. cu8_inv_second<3>: the lane's eight inputs are one 16-byte LDS read against its row of the matrix as
+  // int16 pairs), the two intermediates in front of the inverse passes stored transposed, and the coefficient a lane produces is the one it quantises.  In recon_tus
+  // all of this sat on the first wavefront -- the chroma passes one output per lane with sixteen 16-bit LDS reads each, U then V behind the luma chain, a workgroup
+  // barrier per pass -- while the second one waited at seven barriers.
+  // Nothing crosses between luma and chroma before the cost, so the five stages synchronise per wavefront (KVZ_WAVE_SYNC) and each wavefront clears and fills only
+  // its own sums: acc[0, 3, 6] luma, acc[1, 2, 4, 5, 7, 8] chroma, one writer each (plane_sums ROWS_CU16).  Levels, candidate and cbf bits go where recon_tus puts
+  // them (coeff_dst, cand_view, finish_planes); only the transposed intermediates are private.  Same arithmetic, same order of the integer operations per sample.
+  // Not for the RDOQ instantiation and not with sign data hiding switched on (recon_tus); the scaling-list instantiations come here (factor_at).
+  KVZ_DEV void recon_cu16(int lv, const TuSet &t, int depth, int mode)
+  {
+    const int xl = t.x - cx, yl = t.y - cy, xc = xl >> 1, yc = yl >> 1;
+    const CandView cv = cand_view(lv);
+    const int umode = uni(mode);
+    const bool to_stage = cabac_on() && lv == 0;  // see levels_lds()
+    KVZ_LANE_VAR(WideBytes<16>, mat_f);  // chroma lanes: row e >> 3 of M, row e & 7 of M^T (cu8_matrix_rows), the same for U and V
+    KVZ_LANE_VAR(WideBytes<16>, mat_i);
+    KVZ_LANE_VAR(u32, pred_org);         // chroma lanes: stage 1's predicted and source samples for stage 5, U in the low half, V in the high one
+    KVZ_LANE_VAR(u32, coded);            // which of the wavefront's planes have levels, from its own reduction in stage 3: luma bit 0; chroma bit 0 U, bit 1 V
+#ifdef KVZ_HOSTSIM
+#define KVZ_CU16_CODED(tid, c) ((void)KVZ_LANE(coded, tid), s->acc[6 + (c)] != 0)  // the finished sum: the word plane_sums() returns is exercised by the device tests only
+#else
+#define KVZ_CU16_CODED(tid, c) (((KVZ_LANE(coded, tid) >> ((c) == 2 ? 1 : 0)) & 1u) != 0)
+#endif
+    // stage 1: prediction -> candidate (as kvazaar blits it before quantising) and residual
+    KVZ_FOR_THREADS(tid) {
+      if (tid < 3) s->acc[3 * tid] = 0;
+      if (tid >= 64 && tid < 70) s->acc[1 + (tid - 64) + ((tid - 64) >> 1)] = 0;  // 1, 2, 4, 5, 7, 8
+      if (tid < 32) {
+        // one b64 write of the row to the candidate, one b128 write of the residual (see recon_tus)
+        const int seg = mover_lane(tid), py = seg >> 1, px0 = (seg << 3) & 15;
+        u8 p[8], o[8];
+        i16 res[8];
+        predict_row8(4, umode, 0, px0, py, p);
+        __builtin_memcpy(o, KVZ_ALIGNED(org_at(0, xl + px0, yl + py), 8), 8);
+        for (int k = 0; k < 8; k++) res[k] = (i16)((int)o[k] - (int)p[k]);
+        __builtin_memcpy(KVZ_ALIGNED(&cv.at(0, xl + px0, yl + py), 8), p, 8);
+        __builtin_memcpy(KVZ_ALIGNED(tbuf(t, 0, 0) + (seg << 3), 16), res, 16);
+      } else if (tid >= 64) {
+        const int e = tid - 64, px = e & 7, py = e >> 3;
+        cu8_matrix_rows<3>(tb, e, KVZ_LANE(mat_f, tid), KVZ_LANE(mat_i, tid));
+        u8 pu, pv;
+        predict_chroma_pair(3, umode, px, py, &pu, &pv);
+        cv.at(1, xc + px, yc + py) = pu;
+        cv.at(2, xc + px, yc + py) = pv;
+        const u8 ou = *org_at(1, xc + px, yc + py), ov = *org_at(2, xc + px, yc + py);
+        KVZ_LANE(pred_org, tid) = (u32)pu | ((u32)ou << 8) | ((u32)pv << 16) | ((u32)ov << 24);
+        tbuf(t, 0, 1)[e] = (i16)((int)ou - (int)pu);
+        tbuf(t, 0, 2)[e] = (i16)((int)ov - (int)pv);
+      }
+    }
+    KVZ_WAVE_SYNC();
+    KVZ_PROF(KVZ_P_RPRED);
+    // stage 2: forward transform (dct-generic.c:559-568).  Luma: both 16-point passes, in place on buffer 0; chroma: the first 8-point pass
+    KVZ_FOR_THREADS(tid) {
+      if (tid < 64) transform_big(4, tbuf(t, 0, 0), false, tid, 0);
+      else {
+        const int e = tid - 64;
+        tbuf(t, 1, 1)[e] = cu8_fwd_first<3>(tbuf(t, 0, 1), e, KVZ_LANE(mat_f, tid));
+        tbuf(t, 1, 2)[e] = cu8_fwd_first<3>(tbuf(t, 0, 2), e, KVZ_LANE(mat_f, tid));
+      }
+    }
+    KVZ_WAVE_SYNC();
+    KVZ_PROF(KVZ_P_FDCT);
+    // stage 3: (chroma: the second pass, and straight on) quantise (quant-generic.c:57-81) -> coefficient store + cost sums; dequantise (:335-339) -> luma:
+    // buffer 1, chroma: buffer 0, transposed for the inverse passes
+    KVZ_FOR_THREADS(tid) {
+      const u32 cw_lo = (u32)uni((int)(u32)m->coeff_weights), cw_hi = (u32)uni((int)(u32)(m->coeff_weights >> 32));  // scalars for the call
+      if (tid < 64) {
+        u32 packed = 0;
+        if (tid < 32) {
+          const int seg = mover_lane(tid);
+          const QuantScalars q = s->qs[2][0];
+          i16 cf[8], lvl[8], dq[8];
+          __builtin_memcpy(cf, KVZ_ALIGNED(tbuf(t, 0, 0) + (seg << 3), 16), 16);
+          u32 wsum = 0, nz = 0;
+          for (int k = 0; k < 8; k++) {
+            ListFactor f{ 0, 0 };
+            if constexpr (LISTS) f = factor_at(0, 4, (seg << 3) + k);
+            const int level = LISTS ? quant_level(cf[k], q, f.fwd) : quant_level(cf[k], q);
+            lvl[k] = (i16)level;
+            const LevelCost lc = level_cost(level, cw_lo, cw_hi);
+            wsum += lc.weight;
+            nz += lc.nonzero;
+            dq[k] = LISTS ? dequant_level(level, q, f.inv) : dequant_level(level, q);
+          }
+          packed = wsum | (nz << 24);
+          __builtin_memcpy(KVZ_ALIGNED(coeff_dst(lv, 0, xl, yl) + (seg << 3), 16), lvl, 16);
+          if (to_stage) __builtin_memcpy(KVZ_ALIGNED(levels_lds(lv, 0) + (seg << 3), 16), lvl, 16);
+          __builtin_memcpy(KVZ_ALIGNED(tbuf(t, 1, 0) + (seg << 3), 16), dq, 16);
+        }
+        KVZ_LANE(coded, tid) = plane_sums(ROWS_CU16, tid, tid < 32 ? 0 : -1, packed, true, 3) != 0;
+      } else {
+        const int e = tid - 64;
+        const QuantScalars q = s->qs[1][1];  // U and V share the plane's scaled QP
+        auto plane = [&](int c) {
+          const int cf = cu8_fwd_second<3>(tbuf(t, 1, c), e, KVZ_LANE(mat_f, tid));
+          ListFactor f{ 0, 0 };
+          if constexpr (LISTS) f = factor_at(c, 3, e);
+          const int level = LISTS ? quant_level(cf, q, f.fwd) : quant_level(cf, q);
+          coeff_dst(lv, c, xl, yl)[e] = (i16)level;
+          if (to_stage) levels_lds(lv, c)[e] = (i16)level;
+          tbuf(t, 0, c)[cu8_transposed<3>(e)] = LISTS ? dequant_level(level, q, f.inv) : dequant_level(level, q);
+          return level_cost(level, cw_lo, cw_hi).word();
+        };
+        const u32 wu = plane(1), wv = plane(2);
+        const u32 nu = plane_sums(ROWS_CU16, tid, 1, wu, true, 3), nv = plane_sums(ROWS_CU16, tid, 2, wv, true, 3);
+        KVZ_LANE(coded, tid) = (u32)(nu != 0) | ((u32)(nv != 0) << 1);
+      }
+    }
+    KVZ_WAVE_SYNC();
+    KVZ_PROF(KVZ_P_QUANT);
+    // stage 4: inverse transform (dct-generic.c:570-579), only observable when the plane has coefficients.  Luma: both passes, in place on buffer 1; chroma: the
+    // first pass, transposed again for the second
+    KVZ_FOR_THREADS(tid) {
+      if (tid < 64) { if (uni((int)KVZ_CU16_CODED(tid, 0))) transform_big(4, tbuf(t, 1, 0), true, tid, 0); }
+      else {
+        const int e = tid - 64;
+        if (KVZ_CU16_CODED(tid, 1)) tbuf(t, 1, 1)[cu8_transposed<3>(e)] = cu8_inv_first<3>(tbuf(t, 0, 1), e, KVZ_LANE(mat_i, tid));
+        if (KVZ_CU16_CODED(tid, 2)) tbuf(t, 1, 2)[cu8_transposed<3>(e)] = cu8_inv_first<3>(tbuf(t, 0, 2), e, KVZ_LANE(mat_i, tid));
+      }
+    }
+    KVZ_WAVE_SYNC();
+    KVZ_PROF(KVZ_P_IDCT);
+    // stage 5: (chroma: the second pass, and straight on with the sample it produces) reconstruction (quant-generic.c:266-277) + SSD against the source
+    // (search.c:500-505, 512-523)
+    KVZ_FOR_THREADS(tid) {
+      if (tid < 64) {
+        u32 ssd = 0;
+        if (tid < 32) {
+          const int seg = mover_lane(tid), py = seg >> 1, px0 = (seg << 3) & 15;
+          u8 *rp = &cv.at(0, xl + px0, yl + py);
+          u8 v[8], o[8];
+          __builtin_memcpy(v, KVZ_ALIGNED(rp, 8), 8);
+          __builtin_memcpy(o, KVZ_ALIGNED(org_at(0, xl + px0, yl + py), 8), 8);
+          if (KVZ_CU16_CODED(tid, 0)) {
+            i16 res[8];
+            __builtin_memcpy(res, KVZ_ALIGNED(tbuf(t, 1, 0) + (seg << 3), 16), 16);
+            for (int k = 0; k < 8; k++) v[k] = (u8)recon_sample(v[k], res[k]);
+            __builtin_memcpy(KVZ_ALIGNED(rp, 8), v, 8);
+          }
+          for (int k = 0; k < 8; k++) ssd += sq_err(o[k], v[k]);
+        }
+        plane_sums(ROWS_CU16, tid, tid < 32 ? 0 : -1, ssd, false, 0);
+      } else {
+        const int e = tid - 64, px = e & 7, py = e >> 3;
+        auto plane = [&](int c) {
+          const u32 po = KVZ_LANE(pred_org, tid) >> (c == 2 ? 16 : 0);
+          int v = (int)(po & 0xffu);
+          if (KVZ_CU16_CODED(tid, c)) {
+            v = recon_sample(v, cu8_inv_second<3>(tbuf(t, 1, c), e, KVZ_LANE(mat_i, tid)));
+            cv.at(c, xc + px, yc + py) = (u8)v;
+          }
+          return sq_err((int)((po >> 8) & 0xffu), v);
+        };
+        const u32 su = plane(1), sv = plane(2);
+        plane_sums(ROWS_CU16, tid, 1, su, false, 0);
+        plane_sums(ROWS_CU16, tid, 2, sv, false, 0);
+      }
+    }
+#undef KVZ_CU16_CODED
+    KVZ_SYNC();
+    KVZ_FOR_THREADS(tid) {
+      // all three planes' counts, so behind the barrier; only thread 0 reads the results next (eval_cu's cost phase, same thread: no barrier in between)
+      if (tid == 0) finish_planes(lv, xl, yl, depth, 0, 3, false);
+    }
+    if (cabac_on()) KVZ_SYNC();  // as in recon_cu8: the counting-mode coder runs on every lane behind this
+    KVZ_PROF(KVZ_P_RECON);
+  }
+
   // intra_recon_tb_leaf (intra.c:561-608) + kvz_quantize_residual (quant-generic.c:198-292) for the three planes of `t` -- a CU of 8, 16 or 32 luma samples with
   // its chroma blocks (4x4 for the 8x8 CU), or a 32x32 unit of a 64x64 CU -- written into work-tree level lv (0..3; the PUs of level 4 have eval_pu).  Sets the cbf
   // bits of the CU's info entry.  One barrier per stage.
@@ -2092,9 +2309,10 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false, bool
     // From here on the stages written one sample per lane and trip (stages 1 and 7 where !wide, stage 4 whenever the levels come from kvz_rdoq) serve the RDOQ
     // instantiation alone, and of these stages 1 and 7 exactly one case: its 8x8 CU.
 #if defined(KVZ_CTU_PROFILE) && !defined(KVZ_HOSTSIM)
-    // the stage clock of the units larger than 8x8 goes to the PU half of prof_acc, idle where no NxN partition is tried: tools/ctu_profile.py prints both paths side by side
-    struct InLarge { CtuSharedT<CABAC> *s; bool on; __device__ InLarge(CtuSharedT<CABAC> *s_, bool on_) : s(s_), on(on_) { if (on && threadIdx.x == 0) s->prof_pu = 1; } __device__ ~InLarge() { if (on && threadIdx.x == 0) s->prof_pu = 0; } } in_large(s, !NXN && t.lw >= 4);
+    // the stage clock of the units larger than 8x8 goes to the PU part of prof_acc (16x16 CUs), idle where no NxN partition is tried, and to a part of its own (32x32 units): tools/ctu_profile.py prints the paths side by side
+    struct InLarge { CtuSharedT<CABAC> *s; int on; __device__ InLarge(CtuSharedT<CABAC> *s_, int on_) : s(s_), on(on_) { if (on && threadIdx.x == 0) s->prof_pu = on; } __device__ ~InLarge() { if (on && threadIdx.x == 0) s->prof_pu = 0; } } in_large(s, (!NXN && t.lw >= 4) ? t.lw - 3 : 0);
 #endif
+    if (!RDOQ && t.lw == 4 && t.lc == 3 && !hide_on()) { recon_cu16(lv, t, depth, mode); return; }
     // stage 1: prediction -> rec (as kvazaar blits it before quantising) and residual
     if (wide) {
       const int umode = uni(mode);
@@ -2139,7 +2357,7 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false, bool
           const i16 *src = tbuf(t, pass, c);
           i16 *dst = tbuf(t, pass ^ 1, c);
           if (l2 >= 4) {  // 16 / 32 points: both passes at once (pass 0 only), in place on buffer 0, by one wavefront per plane
-            if (pass == 0) transform_big(l2, tbuf(t, 0, c), false, tid, c);
+            if (pass == 0 && !(big_pairs(t) && c == 2)) transform_big(l2, tbuf(t, 0, c), false, tid, c, big_pairs(t) && c == 1);
             continue;
           }
           for (int e = tid; e < n * n; e += KVZ_CTU_THREADS) {
@@ -2272,7 +2490,8 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false, bool
           const i16 *src = tbuf(t, pass ^ 1, c);
           i16 *dst = tbuf(t, pass, c);
           if (l2 >= 4) {  // both passes at once, in place on buffer 1 (where the dequantised coefficients are)
-            if (pass == 0) transform_big(l2, tbuf(t, 1, c), true, tid, c);
+            // (a 32x32 unit's chroma: V goes with U where both have levels)
+            if (pass == 0 && !(big_pairs(t) && c == 2 && s->acc[7])) transform_big(l2, tbuf(t, 1, c), true, tid, c, big_pairs(t) && c == 1 && s->acc[8]);
             continue;
           }
           for (int e = tid; e < n * n; e += KVZ_CTU_THREADS) {
@@ -3479,7 +3698,7 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false, bool
   KVZ_DEV void run()
   {
 #if defined(KVZ_CTU_PROFILE) && !defined(KVZ_HOSTSIM)
-    if (threadIdx.x == 0) { for (int i = 0; i < 64; i++) s->prof_acc[i] = 0; for (int i = 0; i < 16; i++) s->prof_rq[i] = 0; s->prof_pu = 0; }
+    if (threadIdx.x == 0) { for (int i = 0; i < 96; i++) s->prof_acc[i] = 0; for (int i = 0; i < 16; i++) s->prof_rq[i] = 0; s->prof_pu = 0; }
     t_last = __builtin_amdgcn_s_memtime();
 #endif
     init();
@@ -3532,7 +3751,7 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false, bool
 #if defined(KVZ_CTU_PROFILE) && !defined(KVZ_HOSTSIM)
     __syncthreads();
     if (threadIdx.x == 0) {
-      for (int i = 0; i < 2 * KVZ_P_COUNT; i++) { atomicAdd(&F.prof[i], s->prof_acc[i]); atomicAdd(&F.prof[KVZ_PROF_PU_AT + i], s->prof_acc[32 + i]); }
+      for (int i = 0; i < 2 * KVZ_P_COUNT; i++) { atomicAdd(&F.prof[i], s->prof_acc[i]); atomicAdd(&F.prof[KVZ_PROF_PU_AT + i], s->prof_acc[32 + i]); atomicAdd(&F.prof[KVZ_PROF_W32_AT + i], s->prof_acc[64 + i]); }
       for (int i = 0; i < 16; i++) atomicAdd(&F.prof[2 * KVZ_P_COUNT + i], s->prof_rq[i]);
     }
 #endif

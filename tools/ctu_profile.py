@@ -41,7 +41,7 @@ def main():
     for i in range(n):
         b.upload(i, frames[i % len(frames)])
     b.run(model)
-    NW = 4 * len(NAMES) + 16
+    NW = 6 * len(NAMES) + 16
     buf = (C.c_ulonglong * NW)()
     n_cat = len(NAMES)
     lib.kvz_hip_batch_profile.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int]
@@ -49,18 +49,20 @@ def main():
     b.run(model)
     lib.kvz_hip_batch_profile(b.handle, buf, NW)
     tot = sum(buf[:len(NAMES)])
-    tot_all = tot + sum(buf[2 * len(NAMES) + 16:3 * len(NAMES) + 16])
+    w32 = 4 * len(NAMES) + 16  # the 32x32 units' reconstructions (kvz_ctu.hpp KVZ_PROF_W32_AT)
+    tot_all = tot + sum(buf[2 * len(NAMES) + 16:3 * len(NAMES) + 16]) + sum(buf[w32:w32 + len(NAMES)])
     nctu = n * 510
     pu = 2 * len(NAMES) + 16
-    # the instantiations without NxN book the reconstructions of units larger than 8x8 in the PU half (recon_tus): the table shows both paths side by side
+    # the instantiations without NxN book the reconstructions of 16x16 CUs in the PU part and those of 32x32 units in a part of their own: the table shows the paths side by side
     split = not (os.environ.get("KVZ_PROFILE_RDOQ") or os.environ.get("KVZ_PROFILE_NXN")) and sum(buf[pu:pu + len(NAMES)]) > 0
     if split:
         print(f"kernel_ms {b.kernel_ms():.2f}  cycles/CTU {tot_all / nctu:.0f}")
-        print(f"{'':11s} {'all':>10s}                 | {'8x8 path + the rest':>28s} | {'larger units (recon_tus, 16x16 / 32x32)':>40s}")
+        print(f"{'':11s} {'all':>10s}                 | {'8x8 path + the rest':>28s} | {'16x16 CUs (reconstruction)':>32s} | {'32x32 units (reconstruction)':>32s}")
         for i, nm in enumerate(NAMES):
-            a, l = buf[i], buf[pu + i]
-            print(f"{nm:11s} {(a + l) / nctu:10.0f} cyc/CTU  {100.0 * (a + l) / tot_all:5.1f}% | {a / nctu:8.0f} {100.0 * a / tot_all:5.1f}% {buf[len(NAMES) + i] / nctu:7.1f} marks/CTU | "
-                  f"{l / nctu:8.0f} {100.0 * l / tot_all:5.1f}% {buf[pu + len(NAMES) + i] / nctu:7.1f} marks/CTU")
+            a, l, g = buf[i], buf[pu + i], buf[w32 + i]
+            print(f"{nm:11s} {(a + l + g) / nctu:10.0f} cyc/CTU  {100.0 * (a + l + g) / tot_all:5.1f}% | {a / nctu:8.0f} {100.0 * a / tot_all:5.1f}% {buf[len(NAMES) + i] / nctu:7.1f} marks/CTU | "
+                  f"{l / nctu:8.0f} {100.0 * l / tot_all:5.1f}% {buf[pu + len(NAMES) + i] / nctu:7.1f} marks/CTU | "
+                  f"{g / nctu:8.0f} {100.0 * g / tot_all:5.1f}% {buf[w32 + len(NAMES) + i] / nctu:7.1f} marks/CTU")
         return
     print(f"kernel_ms {b.kernel_ms():.2f}  cycles/CTU {tot_all / nctu:.0f} (outside the 4x4 PUs {tot / nctu:.0f})")
     for i, nm in enumerate(NAMES):
