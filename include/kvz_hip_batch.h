@@ -230,6 +230,32 @@ void kvz_hip_scaling_lists_default(kvz_hip_scaling_lists *lists);
  * queued.  (kvz_rdoq with lists needs the per-coefficient error scales of scalinglist.c:351-367, the hiding rule a factor per position: neither is built.) */
 int  kvz_hip_batch_set_scaling_lists(kvz_hip_batch *b, const kvz_hip_scaling_lists *sets, int n_sets, const uint16_t *set_of_picture);
 
+/* ---- Batches of different picture sizes in one launch (kvz_hip_batch_group) ----
+ * A batch fixes ONE geometry, and a small batch's pass cannot fill the device: a service with 1080p, 832x480 and 4K streams would run one thin launch per size, or
+ * split the workgroup slots by hand (kvz_hip_batch_set_device_share).  A group joins the CTU passes -- the one kernel that needs everybody's parallelism -- of its
+ * batches into ONE persistent launch over every CTU of every picture of every batch.  Everything else stays per batch and is used as before: buffers, stream,
+ * uploads, downloads, loop filters, entropy coder, hashes, distortion.
+ * n >= 1 distinct batches of one device, any geometries (equal ones too), ticket schedule.  Builds the joint ticket lists (WPP and raster) and the device-side
+ * records once.  NULL + message: n < 1, a NULL or repeated batch, batches on different devices, a batch under KVZ_HIP_SCHED=wave, 65 536 or more pictures in total.
+ * The batches must outlive the group. */
+typedef struct kvz_hip_batch_group kvz_hip_batch_group;
+kvz_hip_batch_group *kvz_hip_batch_group_create(kvz_hip_batch *const *batches, int n);
+void                 kvz_hip_batch_group_destroy(kvz_hip_batch_group *g);
+/* One launch over every CTU of every picture of every batch.  models[i] is batch i's table (one model for all of a batch's pictures is a table with n_models == 1).
+ * Afterwards every batch is in the state its own kvz_hip_intra_frames_models(batch i, models[i]) would have left it in, byte for byte (reconstruction, levels, CU
+ * depths and modes, CTU costs, the border records the coder's row contexts come from), and it is that batch's next pass: the launch starts after whatever each
+ * batch's stream held (a pending kvz_hip_batch_upload_all_async included), everything queued on a batch afterwards starts after the joint pass, and the batch's
+ * next upload starts when the joint pass has ended.  A batch stays usable alone between joint launches.
+ * The launch takes the device's whole occupancy (a batch's kvz_hip_batch_set_device_share is not consulted).  One kernel build serves it: the tables must agree in
+ * search_32x32 and no_wpp; coeff_cabac and signhide may differ from picture to picture and from batch to batch.
+ * Returns 1, or -1 with a message on stderr and NOTHING queued on any batch for: a table kvz_hip_intra_frames_models would refuse for its batch; a table with rdoq or
+ * search_nxn; a batch that has scaling lists; tables that disagree in search_32x32 or no_wpp; a batch that is invalid since a hand-off wait timed out (kvz_hip_batch_reset).
+ * A hand-off wait that times out inside the joint pass poisons the launch as it poisons a batch's own: EVERY batch of the group then reports -1 from sync, download and
+ * checksums until it is reset; the message names the batch beside the picture and the CTU. */
+int   kvz_hip_batch_group_intra_frames(kvz_hip_batch_group *g, const kvz_hip_picture_models *const *models);
+/* device time of the joint launch (milliseconds); call after the batches were synced */
+float kvz_hip_batch_group_last_kernel_ms(kvz_hip_batch_group *g);
+
 #ifdef __cplusplus
 }
 #endif

@@ -382,6 +382,70 @@ class HipBatch:
         self._entropy_ptr = self._entropy_out = None
 
 
+class BatchGroup:
+    """kvz_hip_batch_group: the CTU passes of several HipBatch objects -- any picture sizes -- as ONE persistent launch.  Everything else (uploads, loop filters, entropy
+    coder, downloads, hashes) is called on the batches as before; a batch stays usable alone between joint launches.  The batches must outlive the group: close()
+    the group first."""
+
+    def __init__(self, lib, batches):
+        batches = list(batches)
+        if any(b.handle is None for b in batches):
+            raise ValueError("BatchGroup: a batch of the group has been closed")
+        self.lib, self.batches = lib, batches
+        lib.kvz_hip_batch_group_create.restype = C.c_void_p
+        lib.kvz_hip_batch_group_create.argtypes = [C.c_void_p, C.c_int]
+        lib.kvz_hip_batch_group_destroy.restype = None
+        lib.kvz_hip_batch_group_destroy.argtypes = [C.c_void_p]
+        lib.kvz_hip_batch_group_intra_frames.restype = C.c_int
+        lib.kvz_hip_batch_group_intra_frames.argtypes = [C.c_void_p, C.c_void_p]
+        lib.kvz_hip_batch_group_last_kernel_ms.restype = C.c_float
+        lib.kvz_hip_batch_group_last_kernel_ms.argtypes = [C.c_void_p]
+        handles = (C.c_void_p * max(len(batches), 1))(*[b.handle for b in batches])
+        self.handle = lib.kvz_hip_batch_group_create(handles, len(batches))
+        if not self.handle:
+            raise RuntimeError(f"kvz_hip_batch_group_create({len(batches)} batches) failed (see stderr)")
+
+    def _tables(self, models):
+        """one entry per batch: a PictureModels, or a CostModel for all of that batch's pictures (wrapped into a table of one model)"""
+        models = list(models)
+        if len(models) != len(self.batches):
+            raise ValueError(f"BatchGroup: {len(models)} models for {len(self.batches)} batches")
+        tables = []
+        for b, m in zip(self.batches, models):
+            if b.handle is None:
+                raise ValueError("BatchGroup: a batch of the group has been closed")
+            if _is_table(m):
+                b._check_table(m)
+                tables.append((m, m.struct))
+            else:
+                one = (CostModel * 1)(m)
+                index = (C.c_uint16 * b.n)()
+                tables.append(((one, index), PictureModelsStruct(C.sizeof(PictureModelsStruct), 1, one, index)))
+        return tables
+
+    def launch(self, models):
+        """kvz_hip_batch_group_intra_frames: asynchronous; 1, or -1 when the library refuses (see stderr; nothing is queued on any batch then)"""
+        tables = self._tables(models)
+        ptrs = (C.c_void_p * len(tables))(*[C.addressof(t[1]) for t in tables])
+        return self.lib.kvz_hip_batch_group_intra_frames(self.handle, ptrs)
+
+    def run(self, models):
+        if self.launch(models) < 0:
+            raise BatchError("kvz_hip_batch_group_intra_frames: the group cannot run these models (see stderr)")
+        bad = [i for i, b in enumerate(self.batches) if self.lib.kvz_hip_batch_sync(b.handle) != 0]  # every batch is synced, whatever the first one says
+        if bad:
+            raise BatchError(f"kvz_hip_batch_sync: a CTU hand-off wait of the joint pass timed out; the results of batches {bad} are invalid")
+
+    def kernel_ms(self):
+        """device time of the last joint launch; after the batches were synced"""
+        return float(self.lib.kvz_hip_batch_group_last_kernel_ms(self.handle))
+
+    def close(self):
+        if self.handle:
+            self.lib.kvz_hip_batch_group_destroy(self.handle)
+            self.handle = None
+
+
 def psnr(lib, sse, num_pixels):
     """kvz_hip_psnr: compute_psnr's last step (encmain.c:138-143) -- 999.99 for sse == 0, else 10 log10(num_pixels * 255^2 / sse); on the host, no device involved"""
     lib.kvz_hip_psnr.argtypes = [C.c_uint64, C.c_long]

@@ -9,6 +9,7 @@
 #include "../../include/kvz_hip_batch.h"
 #include "kvz_ctu.hpp"
 #include "kvz_entropy.hpp"  // KVZ_ENTROPY_CTX_ROW: the rows of a model table
+#include "kvz_joint.hpp"
 #include "kvz_picture_models.hpp"
 #include "kvz_runtime.hpp"
 #include "kvz_scaling_lists.hpp"
@@ -64,15 +65,18 @@ struct kvz_hip_batch {
   int device;   // the batch's buffers and stream live here; every entry point binds the calling thread to it
   int failed;   // sticky: a CTU hand-off wait of some run timed out, the results of that run are invalid
   unsigned long long wait_ticks;
+  kvz_hip_batch_group *joint = nullptr;  // the group whose joint pass was the last one queued on this batch (kvz_hip_batch_group_intra_frames): batch_check also reads ITS error word; cleared by kvz_hip_batch_reset
 };
 
 namespace kvz {
+int joint_check(kvz_hip_batch *b);  // (below, with the group)
 // kvazaar worker threads other than the creating one call into a batch (search_lcu_hip.c): bind them to the batch's device
 inline void batch_enter(const kvz_hip_batch *b) { KVZ_HIP_CHECK(hipSetDevice(b->device)); thread_state().bound = true; }
 // after the stream has drained: did a hand-off wait time out?  0 ok, -1 invalid results (reported, never fatal: the embedding
 // encoder decides what to do)
 inline int batch_check(kvz_hip_batch *b)
 {
+  if (b->joint && !b->failed) joint_check(b);
   if (b->sched_ticket && !b->failed) {
     // a synchronous hipMemcpy here waited for everything the copy engine held -- 84 ms of another batch's pictures on their way up in the double-buffered chain
     const unsigned err = *(volatile unsigned *)b->h_error;
@@ -232,6 +236,23 @@ inline ModelTableView picture_models_stage(kvz_hip_batch *b, const kvz_hip_pictu
   return v;
 }
 
+
+// The price table and initial contexts of a launch's (first) model in kvz_hip_batch::d_entropy: copied when they differ from what the device holds (a small
+// host-to-device copy waits behind whatever the copy engine is busy with)
+inline void entropy_table_stage(kvz_hip_batch *b, const kvz_hip_intra_cost_model *model)
+{
+  static_assert(sizeof model->ctx_init <= 40 * sizeof(float), "last_entropy");
+  float now[128 + 40] = { 0 };
+  memcpy(now, model->entropy_fbits, 128 * sizeof(float));
+  memcpy(now + 128, model->ctx_init, sizeof model->ctx_init);
+  if (!b->entropy_valid || memcmp(now, b->last_entropy, sizeof now) != 0) {
+    KVZ_HIP_CHECK(hipMemcpyAsync(b->d_entropy, model->entropy_fbits, 128 * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    KVZ_HIP_CHECK(hipMemcpyAsync(b->d_entropy + 128, model->ctx_init, sizeof model->ctx_init, hipMemcpyHostToDevice, b->stream));
+    KVZ_HIP_CHECK(hipStreamSynchronize(b->stream));  // the sources are the caller's: staged before this call returns
+    memcpy(b->last_entropy, now, sizeof now);
+    b->entropy_valid = 1;
+  }
+}
 
 // The factor table of a launch on a batch that has lists: the batch's rows and every picture's two rows at the QP of its model (pm: the launch's table, or nullptr
 // and `qp` for all), copied when it differs from what the device holds; the two pointers go behind the ticket words (kvz_ctu_kernels.hpp KVZ_SCHED_LISTS_AT).
@@ -521,19 +542,7 @@ static int kvz_intra_frames_queue(kvz_hip_batch *b, const kvz_hip_intra_cost_mod
   cm.entropy_fbits = b->d_entropy;
   cm.ctx_init = (const uint8_t *)(b->d_entropy + 128);
   if (b->up_pending) { KVZ_HIP_CHECK(hipStreamWaitEvent(b->stream, b->ev_up, 0)); b->up_pending = 0; }  // pictures on their way (kvz_hip_batch_upload_all_async)
-  {  // the model's tables: copied when they differ from what the device holds (a small host-to-device copy waits behind whatever the copy engine is busy with)
-    static_assert(sizeof model->ctx_init <= 40 * sizeof(float), "last_entropy");
-    float now[128 + 40] = { 0 };
-    memcpy(now, model->entropy_fbits, 128 * sizeof(float));
-    memcpy(now + 128, model->ctx_init, sizeof model->ctx_init);
-    if (!b->entropy_valid || memcmp(now, b->last_entropy, sizeof now) != 0) {
-      KVZ_HIP_CHECK(hipMemcpyAsync(b->d_entropy, model->entropy_fbits, 128 * sizeof(float), hipMemcpyHostToDevice, b->stream));
-      KVZ_HIP_CHECK(hipMemcpyAsync(b->d_entropy + 128, model->ctx_init, sizeof model->ctx_init, hipMemcpyHostToDevice, b->stream));
-      KVZ_HIP_CHECK(hipStreamSynchronize(b->stream));  // the sources are the caller's: staged before this call returns
-      memcpy(b->last_entropy, now, sizeof now);
-      b->entropy_valid = 1;
-    }
-  }
+  kvz::entropy_table_stage(b, model);
   // argument errors are reported, not fatal (a HIP failure still aborts: there is no error channel for it and no CPU path to fall back to)
   if (!b->sched_ticket && (cm.search_32x32 || cm.rdoq || cm.search_nxn)) { fprintf(stderr, "kvz_hip_intra_frames: search_32x32 / rdoq / search_nxn need the ticket schedule\n"); return -1; }
   if (!b->sched_ticket && cm.no_wpp) { fprintf(stderr, "kvz_hip_intra_frames: the one-launch-per-diagonal schedule (KVZ_HIP_SCHED=wave) needs WPP\n"); return -1; }
@@ -643,6 +652,7 @@ int kvz_hip_batch_reset(kvz_hip_batch *b)
   KVZ_HIP_CHECK(hipMemset(b->d_error, 0, 3 * sizeof(unsigned)));
   *b->h_error = 0;
   b->failed = 0;
+  b->joint = nullptr;  // (the group clears its own word at its next launch, once every batch it marked has been reset)
   return 0;
 }
 
@@ -664,6 +674,175 @@ float kvz_hip_batch_last_kernel_ms(kvz_hip_batch *b)
   kvz::batch_enter(b);
   KVZ_HIP_CHECK(hipEventSynchronize(b->ev1));
   KVZ_HIP_CHECK(hipEventElapsedTime(&ms, b->ev0, b->ev1));
+  return ms;
+}
+}
+
+// ---- kvz_hip_batch_group: the CTU passes of several batches as ONE persistent launch (kvz_joint.hpp) ----
+struct kvz_hip_batch_group {
+  std::vector<kvz_hip_batch *> batches;
+  std::vector<uint32_t> batch_of_picture;
+  hipStream_t stream;              // the joint launch's own: it starts behind every batch's stream and every batch's stream continues behind it
+  hipEvent_t ev0, ev1, ev_done;    // around the kernel; behind the copy of the error words
+  hipEvent_t ev_staged[2];         // behind the copy out of records[k]
+  uint32_t *d_items, *d_items_raster, *d_pictures;
+  kvz::JointBatch *d_records;      // [batches], rewritten in front of every launch (the pass numbers, the model tables)
+  kvz::JointBatch *h_records[2];   // pinned; launch k is staged from [k & 1]
+  unsigned *d_ticket, *d_error, *h_error;  // as a batch's: ticket, sticky error word + two words of what the first CTU to give up saw; the JointTable at KVZ_SCHED_TABLE_AT
+  unsigned total_items, launches = 0;
+  int grid, reported = 0;
+  unsigned long long wait_ticks;
+};
+
+namespace kvz {
+inline std::vector<JointBatchInfo> joint_infos(kvz_hip_batch *const *batches, int n)
+{
+  std::vector<JointBatchInfo> info;
+  for (int i = 0; batches && i < n; i++) {
+    const kvz_hip_batch *b = batches[i];
+    info.push_back(b ? JointBatchInfo{ b, b->device, b->sched_ticket, b->n_frames, b->n_list_sets > 0, b->failed } : JointBatchInfo{ nullptr, 0, 0, 0, 0, 0 });
+  }
+  return info;
+}
+// the error words of the last joint pass, as copied behind it: set -> every batch still attached to the group is invalid until reset
+int joint_check(kvz_hip_batch *b)
+{
+  kvz_hip_batch_group *g = b->joint;
+  const unsigned err[3] = { ((volatile unsigned *)g->h_error)[0], ((volatile unsigned *)g->h_error)[1], ((volatile unsigned *)g->h_error)[2] };
+  std::vector<int> failed(g->batches.size(), 0);
+  char msg[640];
+  if (joint_error_fan_out(err, g->batch_of_picture.data(), (unsigned)g->batch_of_picture.size(), (int)g->batches.size(), failed.data(), msg, sizeof msg) == -2) return 0;
+  for (size_t i = 0; i < g->batches.size(); i++) if (g->batches[i]->joint == g && failed[i]) g->batches[i]->failed = 1;
+  if (!g->reported) { fprintf(stderr, "kvz_hip: %s\n", msg); g->reported = 1; }
+  return -1;
+}
+template <bool CABAC, bool S32, bool SH> void joint_launch(kvz_hip_batch_group *g, const CtuSched &sc)
+{
+  hipLaunchKernelGGL((intra_ctu_joint_kernel<CABAC, S32, SH>), dim3(g->grid), dim3(KVZ_CTU_THREADS), 0, g->stream, device_tables(), sc);
+}
+}  // namespace kvz
+
+extern "C" {
+
+kvz_hip_batch_group *kvz_hip_batch_group_create(kvz_hip_batch *const *batches, int n)
+{
+  const std::vector<kvz::JointBatchInfo> info = kvz::joint_infos(batches, n);
+  if (!kvz::joint_group_known(batches ? info.data() : nullptr, n, "kvz_hip_batch_group_create")) return nullptr;
+  kvz::batch_enter(batches[0]);
+  kvz_hip_batch_group *g = new kvz_hip_batch_group();
+  g->batches.assign(batches, batches + n);
+  std::vector<kvz::JointGeometry> geo;
+  for (int i = 0; i < n; i++) geo.push_back({ batches[i]->F.wc, batches[i]->F.hc, batches[i]->n_frames });
+  g->batch_of_picture = kvz::joint_pictures(geo.data(), n);
+  std::vector<uint32_t> wpp, raster;
+  kvz::joint_ticket_lists(geo.data(), n, &wpp, &raster);
+  g->total_items = (unsigned)wpp.size();
+  g->wait_ticks = batches[0]->wait_ticks;
+  g->grid = batches[0]->slots_per_cu * batches[0]->cus;  // the device's whole occupancy (KVZ_HIP_WG_PER_CU as the batch read it); a batch's set_device_share is not consulted
+  if ((unsigned)g->grid > g->total_items) g->grid = (int)g->total_items;
+  KVZ_HIP_CHECK(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
+  KVZ_HIP_CHECK(hipEventCreate(&g->ev0));
+  KVZ_HIP_CHECK(hipEventCreate(&g->ev1));
+  KVZ_HIP_CHECK(hipEventCreateWithFlags(&g->ev_done, hipEventDisableTiming));
+  for (int k = 0; k < 2; k++) {
+    KVZ_HIP_CHECK(hipEventCreateWithFlags(&g->ev_staged[k], hipEventDisableTiming));
+    KVZ_HIP_CHECK(hipHostMalloc((void **)&g->h_records[k], (size_t)n * sizeof(kvz::JointBatch), hipHostMallocDefault));
+  }
+  KVZ_HIP_CHECK(hipMalloc((void **)&g->d_items, wpp.size() * sizeof(uint32_t)));
+  KVZ_HIP_CHECK(hipMalloc((void **)&g->d_items_raster, raster.size() * sizeof(uint32_t)));
+  KVZ_HIP_CHECK(hipMalloc((void **)&g->d_pictures, g->batch_of_picture.size() * sizeof(uint32_t)));
+  KVZ_HIP_CHECK(hipMalloc((void **)&g->d_records, (size_t)n * sizeof(kvz::JointBatch)));
+  KVZ_HIP_CHECK(hipMalloc((void **)&g->d_ticket, kvz::KVZ_SCHED_TICKET_WORDS * sizeof(unsigned)));
+  KVZ_HIP_CHECK(hipMemcpy(g->d_items, wpp.data(), wpp.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  KVZ_HIP_CHECK(hipMemcpy(g->d_items_raster, raster.data(), raster.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  KVZ_HIP_CHECK(hipMemcpy(g->d_pictures, g->batch_of_picture.data(), g->batch_of_picture.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  KVZ_HIP_CHECK(hipMemset(g->d_ticket, 0, kvz::KVZ_SCHED_TICKET_WORDS * sizeof(unsigned)));
+  kvz::JointTable jt;
+  jt.batch_of_picture = g->d_pictures; jt.batches = g->d_records;
+  static_assert(sizeof(kvz::JointTable) <= (kvz::KVZ_SCHED_LISTS_AT - kvz::KVZ_SCHED_TABLE_AT) * sizeof(unsigned), "d_ticket");
+  KVZ_HIP_CHECK(hipMemcpy(g->d_ticket + kvz::KVZ_SCHED_TABLE_AT, &jt, sizeof jt, hipMemcpyHostToDevice));
+  g->d_error = g->d_ticket + 1;
+  KVZ_HIP_CHECK(hipHostMalloc((void **)&g->h_error, 64, hipHostMallocDefault));
+  g->h_error[0] = g->h_error[1] = g->h_error[2] = 0;
+  return g;
+}
+
+void kvz_hip_batch_group_destroy(kvz_hip_batch_group *g)
+{
+  if (!g) return;
+  kvz::batch_enter(g->batches[0]);
+  (void)hipStreamSynchronize(g->stream);
+  for (kvz_hip_batch *b : g->batches)
+    if (b->joint == g) { (void)hipStreamSynchronize(b->stream); if (!b->failed) kvz::joint_check(b); b->joint = nullptr; }  // what the last joint pass left stays with the batches
+  (void)hipFree(g->d_items); (void)hipFree(g->d_items_raster); (void)hipFree(g->d_pictures); (void)hipFree(g->d_records); (void)hipFree(g->d_ticket);
+  (void)hipHostFree(g->h_error);
+  for (int k = 0; k < 2; k++) { (void)hipHostFree(g->h_records[k]); (void)hipEventDestroy(g->ev_staged[k]); }
+  (void)hipEventDestroy(g->ev0); (void)hipEventDestroy(g->ev1); (void)hipEventDestroy(g->ev_done);
+  (void)hipStreamDestroy(g->stream);
+  delete g;
+}
+
+int kvz_hip_batch_group_intra_frames(kvz_hip_batch_group *g, const kvz_hip_picture_models *const *models)
+{
+  if (!g) return -1;
+  const int n = (int)g->batches.size();
+  for (kvz_hip_batch *b : g->batches) (void)kvz::batch_check(b);  // a joint pass that failed since marks its batches now
+  const std::vector<kvz::JointBatchInfo> info = kvz::joint_infos(g->batches.data(), n);
+  if (!kvz::joint_launch_known(info.data(), n, models, "kvz_hip_batch_group_intra_frames")) return -1;
+  kvz::batch_enter(g->batches[0]);
+  if (*(volatile unsigned *)g->h_error) {  // every batch the word marked has been reset since: the group starts over
+    KVZ_HIP_CHECK(hipStreamSynchronize(g->stream));
+    KVZ_HIP_CHECK(hipMemset(g->d_error, 0, 3 * sizeof(unsigned)));
+    g->h_error[0] = g->h_error[1] = g->h_error[2] = 0;
+    g->reported = 0;
+  }
+  const int slot = (int)(g->launches & 1u);
+  if (g->launches >= 2) KVZ_HIP_CHECK(hipEventSynchronize(g->ev_staged[slot]));  // the launch before the last has copied out of it
+  bool any_cabac = false, any_signhide = false;
+  for (int i = 0; i < n; i++) {
+    kvz_hip_batch *b = g->batches[i];
+    const kvz::ModelTableView view = kvz::picture_models_stage(b, models[i]);
+    kvz::entropy_table_stage(b, &models[i]->models[0]);
+    if (b->up_pending) { KVZ_HIP_CHECK(hipStreamWaitEvent(b->stream, b->ev_up, 0)); b->up_pending = 0; }  // pictures on their way (kvz_hip_batch_upload_all_async)
+    any_cabac |= kvz::picture_models_any_cabac(models[i]);
+    any_signhide |= kvz::picture_models_any_signhide(models[i]);
+    b->epoch++;  // the joint pass is this batch's next pass: its flags are compared with its own count
+    kvz::JointBatch &r = g->h_records[slot][i];
+    memset(&r, 0, sizeof r);
+    r.F = b->F; r.models = view.ctu; r.done = b->d_done; r.epoch = b->epoch; r.index = i;
+    KVZ_HIP_CHECK(hipEventRecord(b->ev0, b->stream));  // the joint launch starts after whatever the batch's stream held
+    KVZ_HIP_CHECK(hipStreamWaitEvent(g->stream, b->ev0, 0));
+  }
+  const kvz_hip_intra_cost_model &m0 = models[0]->models[0];
+  KVZ_HIP_CHECK(hipMemcpyAsync(g->d_records, g->h_records[slot], (size_t)n * sizeof(kvz::JointBatch), hipMemcpyHostToDevice, g->stream));
+  KVZ_HIP_CHECK(hipEventRecord(g->ev_staged[slot], g->stream));
+  KVZ_HIP_CHECK(hipMemsetAsync(g->d_ticket, 0, sizeof(unsigned), g->stream));  // the error word behind it stays: sticky across launches
+  KVZ_HIP_CHECK(hipEventRecord(g->ev0, g->stream));
+  const kvz::CtuSched sc{ m0.no_wpp ? g->d_items_raster : g->d_items, g->d_ticket, nullptr, g->d_error, g->total_items, 0u, (m0.no_wpp ? 1 : 0) | kvz::KVZ_SCHED_MODEL_TABLE, g->wait_ticks };
+  // the build is chosen as kvz_intra_frames_queue chooses it: sign hiding anywhere -> a sign-hiding build (CABAC inside), else the CABAC model anywhere -> a CABAC build
+  if (any_signhide) { if (m0.search_32x32) kvz::joint_launch<true, true, true>(g, sc); else kvz::joint_launch<true, false, true>(g, sc); }
+  else if (m0.search_32x32) { if (any_cabac) kvz::joint_launch<true, true, false>(g, sc); else kvz::joint_launch<false, true, false>(g, sc); }
+  else if (any_cabac) kvz::joint_launch<true, false, false>(g, sc);
+  else kvz::joint_launch<false, false, false>(g, sc);
+  KVZ_HIP_CHECK(hipGetLastError());
+  KVZ_HIP_CHECK(hipEventRecord(g->ev1, g->stream));
+  KVZ_HIP_CHECK(hipMemcpyAsync(g->h_error, g->d_error, 3 * sizeof(unsigned), hipMemcpyDeviceToHost, g->stream));  // what joint_check reads once a batch's stream has drained
+  KVZ_HIP_CHECK(hipEventRecord(g->ev_done, g->stream));
+  for (kvz_hip_batch *b : g->batches) {  // everything queued on a batch from now on starts after the joint pass; ev1 is what the batch's next upload waits for
+    KVZ_HIP_CHECK(hipStreamWaitEvent(b->stream, g->ev_done, 0));
+    KVZ_HIP_CHECK(hipEventRecord(b->ev1, b->stream));
+    b->joint = g;
+  }
+  g->launches++;
+  return 1;
+}
+
+float kvz_hip_batch_group_last_kernel_ms(kvz_hip_batch_group *g)
+{
+  float ms = 0;
+  kvz::batch_enter(g->batches[0]);
+  KVZ_HIP_CHECK(hipEventSynchronize(g->ev1));
+  KVZ_HIP_CHECK(hipEventElapsedTime(&ms, g->ev0, g->ev1));
   return ms;
 }
 }

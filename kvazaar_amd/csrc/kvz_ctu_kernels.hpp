@@ -1,12 +1,13 @@
 // kvz_ctu_kernels.hpp -- the __global__ entry points of the batched CTU pass (the program itself is kvz_ctu.hpp) and their scheduling protocol.
 //
-// Build layout: the twelve instantiations are the bulk of the library's compile time, so kvazaar_amd/build.py compiles each of them in a translation unit of
-// its own (kvz_ctu_tu.hip with -DKVZ_CTU_KERNEL_TU=<k>, k = 0..11), in parallel, next to kvz_hip.hip compiled with -DKVZ_CTU_SEPARATE_TUS -- which then only sees
+// Build layout: the eighteen instantiations are the bulk of the library's compile time, so kvazaar_amd/build.py compiles each of them in a translation unit of
+// its own (kvz_ctu_tu.hip with -DKVZ_CTU_KERNEL_TU=<k>, k = 0..17), in parallel, next to kvz_hip.hip compiled with -DKVZ_CTU_SEPARATE_TUS -- which then only sees
 // DECLARATIONS here and launches the kernels through their host stubs.  Without that define kvz_hip.hip is self-contained as before (tools/build_variants.sh).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "kvz_ctu.hpp"
+#include "kvz_joint.hpp"
 
 #if defined(KVZ_CTU_SEPARATE_TUS) && !defined(KVZ_CTU_KERNEL_TU)
 #define KVZ_CTU_KERNEL_BODIES 0
@@ -108,8 +109,26 @@ __device__ __forceinline__ bool wait_done(unsigned *flag, unsigned epoch, unsign
 // sched.no_wpp & KVZ_SCHED_MODEL_TABLE: the pictures of the launch have models of their own (kvz_hip_intra_frames_models) -- `m` is loaded per CTU from the drawn picture's
 // row of the table behind the ticket words.  (A bit of a word the loop keeps anyway and a pointer it keeps anyway: a kernel argument of its own stayed live across the
 // whole program and cost the instantiations that spill a register more.)
-template <bool CABAC, bool S32, bool RDOQ, bool SH = false, bool LISTS = false> __device__ __forceinline__ void ticket_loop(const CtuFrames &F, const CtuModel &model, const Tables *tb, const CtuSched &sched)
+//
+// JOINT (kvz_hip_batch_group, kvz_joint.hpp): the pictures of the launch belong to batches of different geometry.  The item's picture is numbered across the group; the
+// workgroup fetches the record of that picture's batch -- frames, model table, hand-off flags and the pass number they hold -- through uniform pointers into registers
+// (not LDS: the CABAC builds sit at exactly 20 480 B) and runs the program on it with the picture's index inside its batch.  The table's two pointers take the
+// model table's place behind the ticket words; F_arg, `model`, sched.done and sched.epoch are not read.
+template <class T> __device__ __forceinline__ T uniform_fetch(const T *p)  // *p, the same for every lane, as scalars
 {
+  static_assert(sizeof(T) % 4 == 0, "whole words");
+  int w[sizeof(T) / 4];
+  __builtin_memcpy(w, p, sizeof(T));
+  for (unsigned i = 0; i < sizeof(T) / 4; i++) w[i] = __builtin_amdgcn_readfirstlane(w[i]);
+  T v;
+  __builtin_memcpy(&v, w, sizeof(T));
+  return v;
+}
+template <bool CABAC, bool S32, bool RDOQ, bool SH = false, bool LISTS = false, bool JOINT = false> __device__ __forceinline__ void ticket_loop(const CtuFrames &F_arg, const CtuModel &model, const Tables *tb, const CtuSched &sched)
+{
+  static_assert(!(JOINT && (RDOQ || LISTS)), "joint launches: the ultrafast / fast builds");
+  CtuFrames F_joint;  // JOINT: the frames of the drawn picture's batch
+  const CtuFrames &F = JOINT ? F_joint : F_arg;
   __shared__ CtuSharedT<CABAC> shared;
   __shared__ CtuModel m;  // scalars in LDS; its price table stays in HBM (kvz_hip_batch::d_entropy)
   // The ticket is broadcast through a field of `shared` that is dead between two CTUs: with the CABAC contexts the block is exactly 20 480 B,
@@ -117,26 +136,44 @@ template <bool CABAC, bool S32, bool RDOQ, bool SH = false, bool LISTS = false> 
 #ifndef KVZ_CTU_PROFILE
   static_assert(sizeof(CtuSharedT<CABAC>) + sizeof(CtuModel) <= 20480, "eight workgroups per CU");
 #endif
-  if (threadIdx.x == 0 && !(sched.no_wpp & KVZ_SCHED_MODEL_TABLE)) m = model;
-  const int ctus = F.wc * F.hc;
+  if constexpr (!JOINT) { if (threadIdx.x == 0 && !(sched.no_wpp & KVZ_SCHED_MODEL_TABLE)) m = model; }
+  int ctus = 0;
+  if constexpr (!JOINT) ctus = F.wc * F.hc;
   for (;;) {
     __syncthreads();  // previous item fully retired (and m visible on the first trip)
     if (threadIdx.x == 0) shared.best_mode = (int)atomicAdd(sched.ticket, 1u);
     __syncthreads();
     const unsigned t = (unsigned)shared.best_mode;
     if (t >= sched.total) break;
-    const uint32_t item = sched.items[t];
-    const int frame = item >> 16, y = (item >> 8) & 0xff, x = item & 0xff;
+    uint32_t item = sched.items[t];
+    if constexpr (JOINT) item = (uint32_t)__builtin_amdgcn_readfirstlane((int)item);
+    const int picture = item >> 16, y = (item >> 8) & 0xff, x = item & 0xff;  // picture: what the item numbers, in the diagnostics below
+    int frame = picture;
+    unsigned *done_flags = sched.done;
+    unsigned epoch = sched.epoch;
+    CtuModelTable models;
+    if constexpr (JOINT) {
+      const JointTable jt = uniform_fetch(reinterpret_cast<const JointTable *>(sched.ticket + KVZ_SCHED_TABLE_AT));
+      const uint32_t word = (uint32_t)__builtin_amdgcn_readfirstlane((int)jt.batch_of_picture[picture]);
+      const JointBatch *jb = joint_record(jt, word);
+      F_joint = uniform_fetch(&jb->F);
+      models = uniform_fetch(&jb->models);
+      done_flags = uniform_fetch(&jb->done);
+      epoch = (unsigned)__builtin_amdgcn_readfirstlane((int)jb->epoch);
+      frame = joint_frame(word);
+      ctus = F.wc * F.hc;
+    }
     KVZ_TRACE(1);  // ticket drawn
     if (threadIdx.x == 0) {
-      if (sched.no_wpp & KVZ_SCHED_MODEL_TABLE) m = *picture_model(*reinterpret_cast<const CtuModelTable *>(sched.ticket + KVZ_SCHED_TABLE_AT), frame);  // no lane reads m between the barrier above and the one below; the table is constant during the launch
-      unsigned *done = sched.done + (long)frame * ctus;
+      if constexpr (JOINT) m = *picture_model(models, frame);
+      else if (sched.no_wpp & KVZ_SCHED_MODEL_TABLE) m = *picture_model(*reinterpret_cast<const CtuModelTable *>(sched.ticket + KVZ_SCHED_TABLE_AT), frame);  // no lane reads m between the barrier above and the one below; the table is constant during the launch
+      unsigned *done = done_flags + (long)frame * ctus;
       // a hand-off that timed out anywhere (this launch or an earlier one: the word is sticky until kvz_hip_batch_reset) poisons the pass: from then on
       // tickets are only drained -- no search on stale neighbour data, no further 30-second waits -- and every CTU still publishes its flag
       bool ok = __hip_atomic_load(sched.error, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0;
-      if (ok && x > 0) ok = wait_done(&done[y * F.wc + x - 1], sched.epoch, sched.error, sched.wait_ticks, ((unsigned)frame << 16 | (unsigned)y << 8 | (unsigned)(x - 1)) & 0x1fffffffu);
-      if (ok && y > 0) ok = wait_done(&done[(y - 1) * F.wc + (x + 1 < F.wc ? x + 1 : x)], sched.epoch, sched.error, sched.wait_ticks, 0x20000000u | (((unsigned)frame << 16 | (unsigned)(y - 1) << 8 | (unsigned)(x + 1 < F.wc ? x + 1 : x)) & 0x1fffffffu));  // above-right implies above and above-left
-      if (ok && (sched.no_wpp & 1) && x == 0 && y > 0) ok = wait_done(&done[(y - 1) * F.wc + F.wc - 1], sched.epoch, sched.error, sched.wait_ticks, 0x40000000u | (((unsigned)frame << 16 | (unsigned)(y - 1) << 8 | (unsigned)(F.wc - 1)) & 0x1fffffffu));  // its contexts come from there
+      if (ok && x > 0) ok = wait_done(&done[y * F.wc + x - 1], epoch, sched.error, sched.wait_ticks, ((unsigned)picture << 16 | (unsigned)y << 8 | (unsigned)(x - 1)) & 0x1fffffffu);
+      if (ok && y > 0) ok = wait_done(&done[(y - 1) * F.wc + (x + 1 < F.wc ? x + 1 : x)], epoch, sched.error, sched.wait_ticks, 0x20000000u | (((unsigned)picture << 16 | (unsigned)(y - 1) << 8 | (unsigned)(x + 1 < F.wc ? x + 1 : x)) & 0x1fffffffu));  // above-right implies above and above-left
+      if (ok && (sched.no_wpp & 1) && x == 0 && y > 0) ok = wait_done(&done[(y - 1) * F.wc + F.wc - 1], epoch, sched.error, sched.wait_ticks, 0x40000000u | (((unsigned)picture << 16 | (unsigned)(y - 1) << 8 | (unsigned)(F.wc - 1)) & 0x1fffffffu));  // its contexts come from there
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
       shared.best_mode = ok ? 1 : 0;
     }
@@ -165,7 +202,7 @@ template <bool CABAC, bool S32, bool RDOQ, bool SH = false, bool LISTS = false> 
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
       KVZ_TRACE(5);  // released
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __hip_atomic_store(&sched.done[(long)frame * ctus + y * F.wc + x], sched.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(&done_flags[(long)frame * ctus + y * F.wc + x], epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       KVZ_TRACE(6);  // flag stored
     }
   }
@@ -203,6 +240,19 @@ template <bool CABAC, bool S32> __global__ void __launch_bounds__(KVZ_CTU_THREAD
 #else
 {
   ticket_loop<CABAC, S32, false, false, true>(F, model, tb, sched);
+}
+#endif
+// Joint launches over the batches of a group (kvz_hip_batch_group_intra_frames): the builds above that a group may ask for -- fast estimate or CABAC coefficient model,
+// with and without the 32x32 search, and the two sign-hiding ones (SH: CABAC is implied) -- with the drawn picture's batch record fetched per ticket.  Instantiations of
+// their own: the kernels above are what they were.
+template <bool CABAC, bool S32, bool SH> __global__ void __launch_bounds__(KVZ_CTU_THREADS) __attribute__((amdgpu_waves_per_eu(KVZ_CTU_WAVES_PER_EU))) KVZ_CTU_VGPR_ATTR intra_ctu_joint_kernel(const Tables *tb, const CtuSched sched)
+#if !KVZ_CTU_KERNEL_BODIES
+;
+#else
+{
+  const CtuFrames no_frames = {};
+  const CtuModel no_model = {};
+  ticket_loop<CABAC || SH, S32, false, SH, false, true>(no_frames, no_model, tb, sched);
 }
 #endif
 // --rdoq / NxN partitions: its own register budget.  Round 3: kvz_rdoq runs as ONE out-of-line wavefront-cooperative routine (kvz_rdoq.hpp rdoq_block_wave), so the
