@@ -1,9 +1,10 @@
 """Builds libkvz_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
-The library is twenty-three translation units compiled in parallel: kvz_hip.hip (C ABI, per-call ops, streaming kernels, host side of the batch; with
--DKVZ_CTU_SEPARATE_TUS it only declares the CTU kernels) and kvz_ctu_tu.hip eighteen times, one CTU kernel instantiation each (-DKVZ_CTU_KERNEL_TU=0..17; 8..11 are the scaling-list ones, 12..17 the joint launches of a batch group,
-csrc/kvz_ctu_kernels.hpp) and kvz_inter_tu.hip four times (the inter CTU pass with and without the residual coder's contexts, with and without scaling lists).  Objects are rebuilt when one of the files they include (hipcc -MD) is newer."""
+The library's translation units are compiled in parallel: kvz_hip.hip (C ABI, per-call ops, streaming kernels, host side of the batch; with
+-DKVZ_CTU_SEPARATE_TUS it only declares the CTU kernels), kvz_ctu_tu.hip once per unit of the list in csrc/kvz_ctu_builds.hpp, one CTU kernel instantiation each
+(-DKVZ_CTU_KERNEL_TU=<unit>), and kvz_inter_tu.hip four times (the inter CTU pass with and without the residual coder's contexts, with and without scaling lists).  Objects are rebuilt when one of the files they include (hipcc -MD) is newer."""
 import os
+import re
 import subprocess
 from concurrent.futures import ThreadPoolExecutor
 
@@ -15,10 +16,12 @@ LIB_PATH = os.environ.get("KVZ_HIP_LIB") or os.path.join(LIB_DIR, "libkvz_hip.so
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -ffp-contract=off: pixel_var / cost arithmetic must not be contracted into FMAs (bit-exact double results)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off"]
+# the units of the CTU pass: every unit csrc/kvz_ctu_builds.hpp's two lists name.  The header is handed them as a bit mask and refuses to compile where this pattern and its own macros read the lists differently
+CTU_UNITS = sorted({int(k) for k in re.findall(r"\bX\((\d+),", open(os.path.join(CSRC, "kvz_ctu_builds.hpp")).read())})
 # (object name, source, extra defines)
 MFMA_VGPR_FORM = ["-mllvm", "-amdgpu-mfma-vgpr-form"]  # an internal LLVM option, only a tuning of the streaming transform kernels: dropped where hipcc does not know it (_probe_flags)
 UNITS = ([("kvz_hip", "kvz_hip.hip", ["-DKVZ_CTU_SEPARATE_TUS"] + MFMA_VGPR_FORM)]  # (the streaming transform kernels: accumulators in VGPRs, no v_accvgpr moves around the bias pass)
-         + [(f"kvz_ctu_tu{k}", "kvz_ctu_tu.hip", [f"-DKVZ_CTU_KERNEL_TU={k}"]) for k in range(18)]
+         + [(f"kvz_ctu_tu{k}", "kvz_ctu_tu.hip", [f"-DKVZ_CTU_KERNEL_TU={k}", f"-DKVZ_CTU_UNITS_BUILT={sum(1 << k for k in CTU_UNITS)}ull"]) for k in CTU_UNITS]
          + [("kvz_inter_tu0", "kvz_inter_tu.hip", ["-DKVZ_ICTU_CABAC=0"]), ("kvz_inter_tu1", "kvz_inter_tu.hip", ["-DKVZ_ICTU_CABAC=1"])]  # the inter CTU pass's two builds (csrc/kvz_inter_kernels.hpp)
          + [("kvz_inter_tu2", "kvz_inter_tu.hip", ["-DKVZ_ICTU_LISTS=1", "-DKVZ_ICTU_CABAC=0"]),  # ... and the two for launches with scaling lists
             ("kvz_inter_tu3", "kvz_inter_tu.hip", ["-DKVZ_ICTU_LISTS=1", "-DKVZ_ICTU_CABAC=1"])])

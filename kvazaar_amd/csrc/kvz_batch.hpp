@@ -16,7 +16,37 @@
 
 #include "kvz_ctu_kernels.hpp"
 
-namespace kvz { struct DevBuf { void *p = nullptr; size_t bytes = 0; }; }  // a grow-only device buffer (kvz_dev.hpp EntropyScratch::need)
+namespace kvz {
+struct DevBuf { void *p = nullptr; size_t bytes = 0; };  // a grow-only device buffer (kvz_dev.hpp EntropyScratch::need)
+
+// The words of a batch's or a group's ticket schedule.  Device: the ticket, the sticky error word, two words of what the first CTU to give up saw, the launch's tables
+// (KVZ_SCHED_TABLE_AT, KVZ_SCHED_LISTS_AT).  Pinned: the error words as the last pass left them (a synchronous copy would wait for all the copy engine holds: 84 ms).
+struct TicketWords {
+  unsigned *d_ticket = nullptr, *d_error = nullptr, *h_error = nullptr;
+  void create(hipStream_t stream)  // the stream of the passes (a non-blocking stream does not order against the null stream)
+  {
+    KVZ_HIP_CHECK(hipMalloc((void **)&d_ticket, KVZ_SCHED_TICKET_WORDS * sizeof(unsigned)));
+    KVZ_HIP_CHECK(hipMemsetAsync(d_ticket, 0, KVZ_SCHED_TICKET_WORDS * sizeof(unsigned), stream));
+    KVZ_HIP_CHECK(hipStreamSynchronize(stream));
+    d_error = d_ticket + 1;
+    KVZ_HIP_CHECK(hipHostMalloc((void **)&h_error, 64, hipHostMallocDefault));
+    h_error[0] = h_error[1] = h_error[2] = 0;
+  }
+  void destroy() { (void)hipFree(d_ticket); if (h_error) (void)hipHostFree(h_error); }
+  void clear_error() { KVZ_HIP_CHECK(hipMemset(d_error, 0, 3 * sizeof(unsigned))); h_error[0] = h_error[1] = h_error[2] = 0; }  // the sticky word (the stream of the passes has drained)
+  unsigned error(int i = 0) const { return ((volatile unsigned *)h_error)[i]; }
+  // one pass on `stream`: launch() between ev0 and ev1, in front of it the ticket zeroed (the error word behind it stays: sticky across passes), behind it the copy of the error words
+  template <class Launch> void pass(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, Launch &&launch)
+  {
+    KVZ_HIP_CHECK(hipMemsetAsync(d_ticket, 0, sizeof(unsigned), stream));
+    KVZ_HIP_CHECK(hipEventRecord(ev0, stream));
+    launch();
+    KVZ_HIP_CHECK(hipGetLastError());
+    KVZ_HIP_CHECK(hipEventRecord(ev1, stream));
+    KVZ_HIP_CHECK(hipMemcpyAsync(h_error, d_error, 3 * sizeof(unsigned), hipMemcpyDeviceToHost, stream));
+  }
+};
+}  // namespace kvz
 
 struct kvz_hip_batch {
   kvz::CtuFrames F;
@@ -36,8 +66,8 @@ struct kvz_hip_batch {
   unsigned long long *d_prof;
   float *d_entropy;  // the model's entropy_fbits [128 floats] followed by its ctx_init [160 bytes] of the run in flight
   uint32_t *d_items, *d_items_raster;  // ticket order with WPP (anti-diagonals) / without (raster order per picture)
-  unsigned *d_ticket, *d_done, *d_error;
-  unsigned *h_error = nullptr;  // pinned: the error word as the last pass left it, copied behind every pass on the batch's stream (batch_check reads it without a copy of its own)
+  unsigned *d_done;
+  kvz::TicketWords tw;
   float last_entropy[128 + 40];  // the price table and initial contexts d_entropy holds (a launch with the same model skips the copy)
   int entropy_valid = 0;
   int entropy_deferred = 0;     // kvz_hip_batch_entropy_defer_download: the coder's calls return with the slice data's download queued, not finished
@@ -78,12 +108,11 @@ inline int batch_check(kvz_hip_batch *b)
 {
   if (b->joint && !b->failed) joint_check(b);
   if (b->sched_ticket && !b->failed) {
-    // a synchronous hipMemcpy here waited for everything the copy engine held -- 84 ms of another batch's pictures on their way up in the double-buffered chain
-    const unsigned err = *(volatile unsigned *)b->h_error;
-    if (err) {
+    if (const unsigned err = b->tw.error()) {
+      const HandoffTag tag = handoff_tag_read(err);
       b->failed = 1;
       fprintf(stderr, "kvz_hip: a CTU hand-off wait timed out (KVZ_HIP_WAIT_MS to raise the bound) -- the results of this batch are invalid [first to give up waited for CTU x %u y %u of picture %u (%s), pass %u of the batch; that CTU's flag read at the memory side then: %u; tickets drawn then: %u of %u]\n",
-              err & 0xffu, (err >> 8) & 0xffu, (err >> 16) & 0x1fffu, (err & 0x20000000u) ? "its above-right neighbour" : ((err & 0x40000000u) ? "the end of the row above" : "its left neighbour"), b->epoch, ((volatile unsigned *)b->h_error)[1], ((volatile unsigned *)b->h_error)[2], b->total_items);
+              tag.x, tag.y, tag.picture, tag.neighbour, b->epoch, b->tw.error(1), b->tw.error(2), b->total_items);
     }
   }
   return b->failed ? -1 : 0;
@@ -227,7 +256,7 @@ inline ModelTableView picture_models_stage(kvz_hip_batch *b, const kvz_hip_pictu
   memcpy(image.data(), &v.ctu, sizeof v.ctu);
   if (fresh || image != b->h_models) {
     KVZ_HIP_CHECK(hipMemcpyAsync(d, image.data(), bytes, hipMemcpyHostToDevice, b->stream));
-    KVZ_HIP_CHECK(hipMemcpyAsync(b->d_ticket + KVZ_SCHED_TABLE_AT, image.data(), sizeof(CtuModelTable), hipMemcpyHostToDevice, b->stream));
+    KVZ_HIP_CHECK(hipMemcpyAsync(b->tw.d_ticket + KVZ_SCHED_TABLE_AT, image.data(), sizeof(CtuModelTable), hipMemcpyHostToDevice, b->stream));
     KVZ_HIP_CHECK(hipStreamSynchronize(b->stream));
     b->h_models.swap(image);
   }
@@ -276,7 +305,7 @@ inline void scaling_lists_stage(kvz_hip_batch *b, const kvz_hip_picture_models *
     lt.rows_of_picture = lt.rows + n_rows;
     static_assert(sizeof(CtuListTable) <= (KVZ_SCHED_TICKET_WORDS - KVZ_SCHED_LISTS_AT) * sizeof(unsigned), "d_ticket");
     KVZ_HIP_CHECK(hipMemcpyAsync(b->d_lists.p, image.data(), bytes, hipMemcpyHostToDevice, b->stream));
-    KVZ_HIP_CHECK(hipMemcpyAsync(b->d_ticket + KVZ_SCHED_LISTS_AT, &lt, sizeof lt, hipMemcpyHostToDevice, b->stream));
+    KVZ_HIP_CHECK(hipMemcpyAsync(b->tw.d_ticket + KVZ_SCHED_LISTS_AT, &lt, sizeof lt, hipMemcpyHostToDevice, b->stream));
     KVZ_HIP_CHECK(hipStreamSynchronize(b->stream));
     b->h_lists.swap(image);
   }
@@ -353,32 +382,19 @@ kvz_hip_batch *kvz_hip_batch_create_on(int device, int width, int height, int n_
   KVZ_HIP_CHECK(hipMalloc((void **)&b->d_border, nctu * KVZ_BORDER_BYTES));
   KVZ_HIP_CHECK(hipMemsetAsync(b->d_border, 0, nctu * KVZ_BORDER_BYTES, b->stream));
   F.border = b->d_border;
-  {  // ticket schedule: items in dependency order (anti-diagonal, frame, row)
-    std::vector<uint32_t> items;
-    items.reserve(nctu);
-    for (int wave = 0; wave <= (F.wc - 1) + 2 * (F.hc - 1); wave++)
-      for (int f = 0; f < n_frames; f++)
-        for (int y = 0; y < F.hc; y++) {
-          const int x = wave - 2 * y;
-          if (x >= 0 && x < F.wc) items.push_back((uint32_t)f << 16 | (uint32_t)y << 8 | (uint32_t)x);
-        }
-    b->total_items = (unsigned)items.size();
+  {  // ticket schedule: items in dependency order, with WPP (anti-diagonal, frame, row) and without (every CTU depends on its raster predecessor) -- the lists of a group of one
+    const kvz::JointGeometry geo{ F.wc, F.hc, n_frames };
+    std::vector<uint32_t> wpp, raster;
+    kvz::joint_ticket_lists(&geo, 1, &wpp, &raster);
+    b->total_items = (unsigned)wpp.size();
     b->epoch = 0;
-    KVZ_HIP_CHECK(hipMalloc((void **)&b->d_items, items.size() * sizeof(uint32_t)));
-    KVZ_HIP_CHECK(hipMemcpy(b->d_items, items.data(), items.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    items.clear();  // without WPP every CTU depends on its raster predecessor: CTU i of every picture, then CTU i + 1 of every picture
-    for (int y = 0; y < F.hc; y++)
-      for (int x = 0; x < F.wc; x++)
-        for (int f = 0; f < n_frames; f++) items.push_back((uint32_t)f << 16 | (uint32_t)y << 8 | (uint32_t)x);
-    KVZ_HIP_CHECK(hipMalloc((void **)&b->d_items_raster, items.size() * sizeof(uint32_t)));
-    KVZ_HIP_CHECK(hipMemcpy(b->d_items_raster, items.data(), items.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    KVZ_HIP_CHECK(hipMalloc((void **)&b->d_items, wpp.size() * sizeof(uint32_t)));
+    KVZ_HIP_CHECK(hipMemcpy(b->d_items, wpp.data(), wpp.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    KVZ_HIP_CHECK(hipMalloc((void **)&b->d_items_raster, raster.size() * sizeof(uint32_t)));
+    KVZ_HIP_CHECK(hipMemcpy(b->d_items_raster, raster.data(), raster.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     KVZ_HIP_CHECK(hipMalloc((void **)&b->d_done, nctu * sizeof(unsigned)));
     KVZ_HIP_CHECK(hipMemsetAsync(b->d_done, 0, nctu * sizeof(unsigned), b->stream));
-    KVZ_HIP_CHECK(hipMalloc((void **)&b->d_ticket, kvz::KVZ_SCHED_TICKET_WORDS * sizeof(unsigned)));  // the ticket, the error word, two words of what the first CTU to give up saw; the model table's pointers
-    KVZ_HIP_CHECK(hipMemsetAsync(b->d_ticket, 0, kvz::KVZ_SCHED_TICKET_WORDS * sizeof(unsigned), b->stream));
-    b->d_error = b->d_ticket + 1;
-    KVZ_HIP_CHECK(hipHostMalloc((void **)&b->h_error, 64, hipHostMallocDefault));
-    *b->h_error = 0;
+    b->tw.create(b->stream);
     const char *e = getenv("KVZ_HIP_SCHED");  // "wave": one launch per anti-diagonal (the simpler schedule, kept for A/B)
     b->sched_ticket = !(e && e[0] == 'w') && n_frames < 65536 && F.wc < 256 && F.hc < 256;
     int per_cu = 0, dev = 0, cus = 0;
@@ -403,10 +419,9 @@ void kvz_hip_batch_destroy(kvz_hip_batch *b)
   kvz::batch_enter(b);
   (void)hipStreamSynchronize(b->stream);
   (void)hipFree(b->d_ver); (void)hipFree(b->d_dbk); (void)hipFree(b->d_sao_merge); (void)hipFree(b->d_sao_stats); (void)hipFree(b->d_sao_cand); (void)hipFree(b->d_sao_recs); (void)hipFree(b->d_sao_fbits);
-  (void)hipFree(b->d_border); (void)hipFree(b->d_items); (void)hipFree(b->d_items_raster); (void)hipFree(b->d_done); (void)hipFree(b->d_ticket); (void)hipFree(b->d_prof); (void)hipFree(b->d_entropy);
+  (void)hipFree(b->d_border); (void)hipFree(b->d_items); (void)hipFree(b->d_items_raster); (void)hipFree(b->d_done); b->tw.destroy(); (void)hipFree(b->d_prof); (void)hipFree(b->d_entropy);
   (void)hipFree(b->d_src); (void)hipFree(b->d_rec); (void)hipFree(b->d_coeff); (void)hipFree(b->d_scratch); (void)hipFree(b->d_depth); (void)hipFree(b->d_mode); (void)hipFree(b->d_cost); (void)hipFree(b->d_part); (void)hipFree(b->d_mode4);
   (void)hipEventDestroy(b->ev0); (void)hipEventDestroy(b->ev1);
-  if (b->h_error) (void)hipHostFree(b->h_error);
   if (b->entropy_out.p) (void)hipFree(b->entropy_out.p);
   if (b->ev_up) { (void)hipEventSynchronize(b->ev_up); (void)hipEventDestroy(b->ev_up); }
   if (b->ev_src_read) (void)hipEventDestroy(b->ev_src_read);
@@ -533,6 +548,8 @@ void kvz_hip_batch_order_after(kvz_hip_batch *b, kvz_hip_batch *other)
 static int kvz_intra_frames_queue(kvz_hip_batch *b, const kvz_hip_intra_cost_model *model, const kvz_hip_picture_models *pm, bool any_cabac, bool any_signhide)
 {
   const bool table = pm != nullptr, lists = b->n_list_sets > 0;
+  const int build = kvz::ctu_build_choose({ model->search_32x32 != 0, model->rdoq != 0, model->search_nxn != 0, any_cabac, any_signhide, lists, false });  // (of the ticket schedule)
+  if (b->sched_ticket && build == kvz::KVZ_CTU_BUILD_NONE) { fprintf(stderr, "kvz_hip_intra_frames: no kernel build for this launch\n"); return -1; }  // (before anything is staged; the entry points refuse these with the reason)
   kvz::batch_enter(b);
   const kvz::CtuFrames &F = b->F;
   int launches = 0;
@@ -550,36 +567,20 @@ static int kvz_intra_frames_queue(kvz_hip_batch *b, const kvz_hip_intra_cost_mod
   if (lists) kvz::scaling_lists_stage(b, pm, model->qp);  // (a batch under the other schedule has none)
   if (b->sched_ticket) {
     b->epoch++;
-    KVZ_HIP_CHECK(hipMemsetAsync(b->d_ticket, 0, sizeof(unsigned), b->stream));  // the error word behind it stays: sticky across runs
-    KVZ_HIP_CHECK(hipEventRecord(b->ev0, b->stream));
-    kvz::CtuSched sc{ cm.no_wpp ? b->d_items_raster : b->d_items, b->d_ticket, b->d_done, b->d_error, b->total_items, b->epoch, cm.no_wpp | (table ? kvz::KVZ_SCHED_MODEL_TABLE : 0), b->wait_ticks };
-    // two instantiations: the one without the CABAC coefficient model carries none of its code, registers or context storage
-    // (the instantiations that search 32x32 CUs, --pu-depth-intra 1-3, are separate ones too: the others stay as they were)
-    if (lists) {
-      if (cm.search_32x32) {
-        if (cm.coeff_cabac) hipLaunchKernelGGL((kvz::intra_ctu_ticket_kernel_lists<true, true>), dim3(b->grid_ticket), dim3(KVZ_CTU_THREADS), 0, b->stream, F, cm, kvz::device_tables(), sc);
-        else hipLaunchKernelGGL((kvz::intra_ctu_ticket_kernel_lists<false, true>), dim3(b->grid_ticket), dim3(KVZ_CTU_THREADS), 0, b->stream, F, cm, kvz::device_tables(), sc);
-      } else if (cm.coeff_cabac) hipLaunchKernelGGL((kvz::intra_ctu_ticket_kernel_lists<true, false>), dim3(b->grid_ticket), dim3(KVZ_CTU_THREADS), 0, b->stream, F, cm, kvz::device_tables(), sc);
-      else hipLaunchKernelGGL((kvz::intra_ctu_ticket_kernel_lists<false, false>), dim3(b->grid_ticket), dim3(KVZ_CTU_THREADS), 0, b->stream, F, cm, kvz::device_tables(), sc);
-    } else if (cm.rdoq || cm.search_nxn) {  // --rdoq and / or NxN partitions (preset `medium`): their own instantiation (32x32 search and the coefficient cost model switched by the model)
-      if (cm.search_nxn && !b->d_part) {
-        KVZ_HIP_CHECK(hipMalloc((void **)&b->d_part, (size_t)(F.W / 8) * (F.H / 8) * b->n_frames));
-        KVZ_HIP_CHECK(hipMalloc((void **)&b->d_mode4, (size_t)(F.W / 4) * (F.H / 4) * b->n_frames));
-      }
-      kvz::CtuFrames Fr = F;
-      Fr.cu_part = b->d_part; Fr.cu_mode4 = b->d_mode4;
-      hipLaunchKernelGGL(kvz::intra_ctu_ticket_kernel_rdoq, dim3(b->grid_ticket), dim3(KVZ_CTU_THREADS), 0, b->stream, Fr, cm, kvz::device_tables(), sc);
-    } else if (any_signhide) {  // sign data hiding: its own instantiations, with the CABAC coefficient model inside (pictures priced by the fast estimate switch it off at run time, as in a mixed launch)
-      if (cm.search_32x32) hipLaunchKernelGGL(kvz::intra_ctu_ticket_kernel_signhide<true>, dim3(b->grid_ticket), dim3(KVZ_CTU_THREADS), 0, b->stream, F, cm, kvz::device_tables(), sc);
-      else hipLaunchKernelGGL(kvz::intra_ctu_ticket_kernel_signhide<false>, dim3(b->grid_ticket), dim3(KVZ_CTU_THREADS), 0, b->stream, F, cm, kvz::device_tables(), sc);
-    } else if (cm.search_32x32) {
-      if (cm.coeff_cabac) hipLaunchKernelGGL((kvz::intra_ctu_ticket_kernel<true, true>), dim3(b->grid_ticket), dim3(KVZ_CTU_THREADS), 0, b->stream, F, cm, kvz::device_tables(), sc);
-      else hipLaunchKernelGGL((kvz::intra_ctu_ticket_kernel<false, true>), dim3(b->grid_ticket), dim3(KVZ_CTU_THREADS), 0, b->stream, F, cm, kvz::device_tables(), sc);
-    } else if (cm.coeff_cabac) hipLaunchKernelGGL(kvz::intra_ctu_ticket_kernel<true>, dim3(b->grid_ticket), dim3(KVZ_CTU_THREADS), 0, b->stream, F, cm, kvz::device_tables(), sc);
-    else hipLaunchKernelGGL(kvz::intra_ctu_ticket_kernel<false>, dim3(b->grid_ticket), dim3(KVZ_CTU_THREADS), 0, b->stream, F, cm, kvz::device_tables(), sc);
-    KVZ_HIP_CHECK(hipGetLastError());
-    KVZ_HIP_CHECK(hipEventRecord(b->ev1, b->stream));
-    KVZ_HIP_CHECK(hipMemcpyAsync(b->h_error, b->d_error, 3 * sizeof(unsigned), hipMemcpyDeviceToHost, b->stream));  // what batch_check reads once the stream has drained
+    kvz::CtuSched sc{ cm.no_wpp ? b->d_items_raster : b->d_items, b->tw.d_ticket, b->d_done, b->tw.d_error, b->total_items, b->epoch, cm.no_wpp | (table ? kvz::KVZ_SCHED_MODEL_TABLE : 0), b->wait_ticks };
+    b->tw.pass(b->stream, b->ev0, b->ev1, [&] {
+      kvz::ctu_build_dispatch(build, [&](auto bt) {
+        kvz::CtuFrames Fr = F;
+        if constexpr (bt.rdoq) {  // the build that writes NxN flags and 4x4 modes
+          if (cm.search_nxn && !b->d_part) {
+            KVZ_HIP_CHECK(hipMalloc((void **)&b->d_part, (size_t)(F.W / 8) * (F.H / 8) * b->n_frames));
+            KVZ_HIP_CHECK(hipMalloc((void **)&b->d_mode4, (size_t)(F.W / 4) * (F.H / 4) * b->n_frames));
+          }
+          Fr.cu_part = b->d_part; Fr.cu_mode4 = b->d_mode4;
+        }
+        if constexpr (!bt.joint) hipLaunchKernelGGL(kvz::ctu_build_kernel(bt), dim3(b->grid_ticket), dim3(KVZ_CTU_THREADS), 0, b->stream, Fr, cm, kvz::device_tables(), sc);
+      });
+    });
     return 1;
   }
   KVZ_HIP_CHECK(hipEventRecord(b->ev0, b->stream));
@@ -649,8 +650,7 @@ int kvz_hip_batch_reset(kvz_hip_batch *b)
 {
   kvz::batch_enter(b);
   KVZ_HIP_CHECK(hipStreamSynchronize(b->stream));
-  KVZ_HIP_CHECK(hipMemset(b->d_error, 0, 3 * sizeof(unsigned)));
-  *b->h_error = 0;
+  b->tw.clear_error();
   b->failed = 0;
   b->joint = nullptr;  // (the group clears its own word at its next launch, once every batch it marked has been reset)
   return 0;
@@ -688,7 +688,7 @@ struct kvz_hip_batch_group {
   uint32_t *d_items, *d_items_raster, *d_pictures;
   kvz::JointBatch *d_records;      // [batches], rewritten in front of every launch (the pass numbers, the model tables)
   kvz::JointBatch *h_records[2];   // pinned; launch k is staged from [k & 1]
-  unsigned *d_ticket, *d_error, *h_error;  // as a batch's: ticket, sticky error word + two words of what the first CTU to give up saw; the JointTable at KVZ_SCHED_TABLE_AT
+  kvz::TicketWords tw;             // as a batch's; the JointTable at KVZ_SCHED_TABLE_AT
   unsigned total_items, launches = 0;
   int grid, reported = 0;
   unsigned long long wait_ticks;
@@ -708,17 +708,13 @@ inline std::vector<JointBatchInfo> joint_infos(kvz_hip_batch *const *batches, in
 int joint_check(kvz_hip_batch *b)
 {
   kvz_hip_batch_group *g = b->joint;
-  const unsigned err[3] = { ((volatile unsigned *)g->h_error)[0], ((volatile unsigned *)g->h_error)[1], ((volatile unsigned *)g->h_error)[2] };
+  const unsigned err[3] = { g->tw.error(0), g->tw.error(1), g->tw.error(2) };
   std::vector<int> failed(g->batches.size(), 0);
   char msg[640];
   if (joint_error_fan_out(err, g->batch_of_picture.data(), (unsigned)g->batch_of_picture.size(), (int)g->batches.size(), failed.data(), msg, sizeof msg) == -2) return 0;
   for (size_t i = 0; i < g->batches.size(); i++) if (g->batches[i]->joint == g && failed[i]) g->batches[i]->failed = 1;
   if (!g->reported) { fprintf(stderr, "kvz_hip: %s\n", msg); g->reported = 1; }
   return -1;
-}
-template <bool CABAC, bool S32, bool SH> void joint_launch(kvz_hip_batch_group *g, const CtuSched &sc)
-{
-  hipLaunchKernelGGL((intra_ctu_joint_kernel<CABAC, S32, SH>), dim3(g->grid), dim3(KVZ_CTU_THREADS), 0, g->stream, device_tables(), sc);
 }
 }  // namespace kvz
 
@@ -752,18 +748,14 @@ kvz_hip_batch_group *kvz_hip_batch_group_create(kvz_hip_batch *const *batches, i
   KVZ_HIP_CHECK(hipMalloc((void **)&g->d_items_raster, raster.size() * sizeof(uint32_t)));
   KVZ_HIP_CHECK(hipMalloc((void **)&g->d_pictures, g->batch_of_picture.size() * sizeof(uint32_t)));
   KVZ_HIP_CHECK(hipMalloc((void **)&g->d_records, (size_t)n * sizeof(kvz::JointBatch)));
-  KVZ_HIP_CHECK(hipMalloc((void **)&g->d_ticket, kvz::KVZ_SCHED_TICKET_WORDS * sizeof(unsigned)));
+  g->tw.create(g->stream);
   KVZ_HIP_CHECK(hipMemcpy(g->d_items, wpp.data(), wpp.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
   KVZ_HIP_CHECK(hipMemcpy(g->d_items_raster, raster.data(), raster.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
   KVZ_HIP_CHECK(hipMemcpy(g->d_pictures, g->batch_of_picture.data(), g->batch_of_picture.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-  KVZ_HIP_CHECK(hipMemset(g->d_ticket, 0, kvz::KVZ_SCHED_TICKET_WORDS * sizeof(unsigned)));
   kvz::JointTable jt;
   jt.batch_of_picture = g->d_pictures; jt.batches = g->d_records;
   static_assert(sizeof(kvz::JointTable) <= (kvz::KVZ_SCHED_LISTS_AT - kvz::KVZ_SCHED_TABLE_AT) * sizeof(unsigned), "d_ticket");
-  KVZ_HIP_CHECK(hipMemcpy(g->d_ticket + kvz::KVZ_SCHED_TABLE_AT, &jt, sizeof jt, hipMemcpyHostToDevice));
-  g->d_error = g->d_ticket + 1;
-  KVZ_HIP_CHECK(hipHostMalloc((void **)&g->h_error, 64, hipHostMallocDefault));
-  g->h_error[0] = g->h_error[1] = g->h_error[2] = 0;
+  KVZ_HIP_CHECK(hipMemcpy(g->tw.d_ticket + kvz::KVZ_SCHED_TABLE_AT, &jt, sizeof jt, hipMemcpyHostToDevice));
   return g;
 }
 
@@ -774,8 +766,7 @@ void kvz_hip_batch_group_destroy(kvz_hip_batch_group *g)
   (void)hipStreamSynchronize(g->stream);
   for (kvz_hip_batch *b : g->batches)
     if (b->joint == g) { (void)hipStreamSynchronize(b->stream); if (!b->failed) kvz::joint_check(b); b->joint = nullptr; }  // what the last joint pass left stays with the batches
-  (void)hipFree(g->d_items); (void)hipFree(g->d_items_raster); (void)hipFree(g->d_pictures); (void)hipFree(g->d_records); (void)hipFree(g->d_ticket);
-  (void)hipHostFree(g->h_error);
+  (void)hipFree(g->d_items); (void)hipFree(g->d_items_raster); (void)hipFree(g->d_pictures); (void)hipFree(g->d_records); g->tw.destroy();
   for (int k = 0; k < 2; k++) { (void)hipHostFree(g->h_records[k]); (void)hipEventDestroy(g->ev_staged[k]); }
   (void)hipEventDestroy(g->ev0); (void)hipEventDestroy(g->ev1); (void)hipEventDestroy(g->ev_done);
   (void)hipStreamDestroy(g->stream);
@@ -789,23 +780,22 @@ int kvz_hip_batch_group_intra_frames(kvz_hip_batch_group *g, const kvz_hip_pictu
   for (kvz_hip_batch *b : g->batches) (void)kvz::batch_check(b);  // a joint pass that failed since marks its batches now
   const std::vector<kvz::JointBatchInfo> info = kvz::joint_infos(g->batches.data(), n);
   if (!kvz::joint_launch_known(info.data(), n, models, "kvz_hip_batch_group_intra_frames")) return -1;
+  const kvz_hip_intra_cost_model &m0 = models[0]->models[0];
+  const int build = kvz::picture_models_build(models, n, false, true);  // (joint_launch_known: no batch has lists)
+  if (build == kvz::KVZ_CTU_BUILD_NONE) { fprintf(stderr, "kvz_hip_batch_group_intra_frames: no kernel build for this launch\n"); return -1; }  // (joint_launch_known has refused these, with the reason)
   kvz::batch_enter(g->batches[0]);
-  if (*(volatile unsigned *)g->h_error) {  // every batch the word marked has been reset since: the group starts over
+  if (g->tw.error()) {  // every batch the word marked has been reset since: the group starts over
     KVZ_HIP_CHECK(hipStreamSynchronize(g->stream));
-    KVZ_HIP_CHECK(hipMemset(g->d_error, 0, 3 * sizeof(unsigned)));
-    g->h_error[0] = g->h_error[1] = g->h_error[2] = 0;
+    g->tw.clear_error();
     g->reported = 0;
   }
   const int slot = (int)(g->launches & 1u);
   if (g->launches >= 2) KVZ_HIP_CHECK(hipEventSynchronize(g->ev_staged[slot]));  // the launch before the last has copied out of it
-  bool any_cabac = false, any_signhide = false;
   for (int i = 0; i < n; i++) {
     kvz_hip_batch *b = g->batches[i];
     const kvz::ModelTableView view = kvz::picture_models_stage(b, models[i]);
     kvz::entropy_table_stage(b, &models[i]->models[0]);
     if (b->up_pending) { KVZ_HIP_CHECK(hipStreamWaitEvent(b->stream, b->ev_up, 0)); b->up_pending = 0; }  // pictures on their way (kvz_hip_batch_upload_all_async)
-    any_cabac |= kvz::picture_models_any_cabac(models[i]);
-    any_signhide |= kvz::picture_models_any_signhide(models[i]);
     b->epoch++;  // the joint pass is this batch's next pass: its flags are compared with its own count
     kvz::JointBatch &r = g->h_records[slot][i];
     memset(&r, 0, sizeof r);
@@ -813,20 +803,14 @@ int kvz_hip_batch_group_intra_frames(kvz_hip_batch_group *g, const kvz_hip_pictu
     KVZ_HIP_CHECK(hipEventRecord(b->ev0, b->stream));  // the joint launch starts after whatever the batch's stream held
     KVZ_HIP_CHECK(hipStreamWaitEvent(g->stream, b->ev0, 0));
   }
-  const kvz_hip_intra_cost_model &m0 = models[0]->models[0];
   KVZ_HIP_CHECK(hipMemcpyAsync(g->d_records, g->h_records[slot], (size_t)n * sizeof(kvz::JointBatch), hipMemcpyHostToDevice, g->stream));
   KVZ_HIP_CHECK(hipEventRecord(g->ev_staged[slot], g->stream));
-  KVZ_HIP_CHECK(hipMemsetAsync(g->d_ticket, 0, sizeof(unsigned), g->stream));  // the error word behind it stays: sticky across launches
-  KVZ_HIP_CHECK(hipEventRecord(g->ev0, g->stream));
-  const kvz::CtuSched sc{ m0.no_wpp ? g->d_items_raster : g->d_items, g->d_ticket, nullptr, g->d_error, g->total_items, 0u, (m0.no_wpp ? 1 : 0) | kvz::KVZ_SCHED_MODEL_TABLE, g->wait_ticks };
-  // the build is chosen as kvz_intra_frames_queue chooses it: sign hiding anywhere -> a sign-hiding build (CABAC inside), else the CABAC model anywhere -> a CABAC build
-  if (any_signhide) { if (m0.search_32x32) kvz::joint_launch<true, true, true>(g, sc); else kvz::joint_launch<true, false, true>(g, sc); }
-  else if (m0.search_32x32) { if (any_cabac) kvz::joint_launch<true, true, false>(g, sc); else kvz::joint_launch<false, true, false>(g, sc); }
-  else if (any_cabac) kvz::joint_launch<true, false, false>(g, sc);
-  else kvz::joint_launch<false, false, false>(g, sc);
-  KVZ_HIP_CHECK(hipGetLastError());
-  KVZ_HIP_CHECK(hipEventRecord(g->ev1, g->stream));
-  KVZ_HIP_CHECK(hipMemcpyAsync(g->h_error, g->d_error, 3 * sizeof(unsigned), hipMemcpyDeviceToHost, g->stream));  // what joint_check reads once a batch's stream has drained
+  const kvz::CtuSched sc{ m0.no_wpp ? g->d_items_raster : g->d_items, g->tw.d_ticket, nullptr, g->tw.d_error, g->total_items, 0u, (m0.no_wpp ? 1 : 0) | kvz::KVZ_SCHED_MODEL_TABLE, g->wait_ticks };
+  g->tw.pass(g->stream, g->ev0, g->ev1, [&] {  // (what the copy behind it leaves, joint_check reads once a batch's stream has drained)
+    kvz::ctu_build_dispatch(build, [&](auto bt) {
+      if constexpr (bt.joint) hipLaunchKernelGGL(kvz::ctu_build_kernel(bt), dim3(g->grid), dim3(KVZ_CTU_THREADS), 0, g->stream, kvz::device_tables(), sc);
+    });
+  });
   KVZ_HIP_CHECK(hipEventRecord(g->ev_done, g->stream));
   for (kvz_hip_batch *b : g->batches) {  // everything queued on a batch from now on starts after the joint pass; ev1 is what the batch's next upload waits for
     KVZ_HIP_CHECK(hipStreamWaitEvent(b->stream, g->ev_done, 0));

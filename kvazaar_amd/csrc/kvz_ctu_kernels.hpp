@@ -1,12 +1,13 @@
 // kvz_ctu_kernels.hpp -- the __global__ entry points of the batched CTU pass (the program itself is kvz_ctu.hpp) and their scheduling protocol.
 //
-// Build layout: the eighteen instantiations are the bulk of the library's compile time, so kvazaar_amd/build.py compiles each of them in a translation unit of
-// its own (kvz_ctu_tu.hip with -DKVZ_CTU_KERNEL_TU=<k>, k = 0..17), in parallel, next to kvz_hip.hip compiled with -DKVZ_CTU_SEPARATE_TUS -- which then only sees
-// DECLARATIONS here and launches the kernels through their host stubs.  Without that define kvz_hip.hip is self-contained as before (tools/build_variants.sh).
+// Build layout: the instantiations (kvz_ctu_builds.hpp lists them) are the bulk of the library's compile time, so kvazaar_amd/build.py compiles each of them in a
+// translation unit of its own (kvz_ctu_tu.hip with -DKVZ_CTU_KERNEL_TU=<unit>), in parallel, next to kvz_hip.hip compiled with -DKVZ_CTU_SEPARATE_TUS -- which then
+// only sees DECLARATIONS here and launches the kernels through their host stubs.  Without that define kvz_hip.hip is self-contained as before.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "kvz_ctu.hpp"
+#include "kvz_ctu_builds.hpp"
 #include "kvz_joint.hpp"
 
 #if defined(KVZ_CTU_SEPARATE_TUS) && !defined(KVZ_CTU_KERNEL_TU)
@@ -95,7 +96,7 @@ __device__ __forceinline__ bool wait_done(unsigned *flag, unsigned epoch, unsign
           error[2] = __hip_atomic_load(error - 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         return false;
-      }  // the first CTU that gave up: which neighbour (bits 29-30), frame << 16 | y << 8 | x of the CTU waited FOR
+      }  // the first CTU that gave up: the CTU waited FOR and which neighbour it is (kvz_joint.hpp KVZ_HANDOFF_TAG)
     }
     // back off after the first half millisecond: a wait that long is on nobody's critical path (hand-offs arrive within microseconds), and where a pass has stalled --
     // tools/chain_stress.py, profiles/README.md round 6: an eighth of the workgroups standing still in their searches for seconds -- the other seven eighths
@@ -171,9 +172,9 @@ template <bool CABAC, bool S32, bool RDOQ, bool SH = false, bool LISTS = false, 
       // a hand-off that timed out anywhere (this launch or an earlier one: the word is sticky until kvz_hip_batch_reset) poisons the pass: from then on
       // tickets are only drained -- no search on stale neighbour data, no further 30-second waits -- and every CTU still publishes its flag
       bool ok = __hip_atomic_load(sched.error, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0;
-      if (ok && x > 0) ok = wait_done(&done[y * F.wc + x - 1], epoch, sched.error, sched.wait_ticks, ((unsigned)picture << 16 | (unsigned)y << 8 | (unsigned)(x - 1)) & 0x1fffffffu);
-      if (ok && y > 0) ok = wait_done(&done[(y - 1) * F.wc + (x + 1 < F.wc ? x + 1 : x)], epoch, sched.error, sched.wait_ticks, 0x20000000u | (((unsigned)picture << 16 | (unsigned)(y - 1) << 8 | (unsigned)(x + 1 < F.wc ? x + 1 : x)) & 0x1fffffffu));  // above-right implies above and above-left
-      if (ok && (sched.no_wpp & 1) && x == 0 && y > 0) ok = wait_done(&done[(y - 1) * F.wc + F.wc - 1], epoch, sched.error, sched.wait_ticks, 0x40000000u | (((unsigned)picture << 16 | (unsigned)(y - 1) << 8 | (unsigned)(F.wc - 1)) & 0x1fffffffu));  // its contexts come from there
+      if (ok && x > 0) ok = wait_done(&done[y * F.wc + x - 1], epoch, sched.error, sched.wait_ticks, KVZ_HANDOFF_TAG(KVZ_WAIT_LEFT, picture, y, x - 1));
+      if (ok && y > 0) ok = wait_done(&done[(y - 1) * F.wc + (x + 1 < F.wc ? x + 1 : x)], epoch, sched.error, sched.wait_ticks, KVZ_HANDOFF_TAG(KVZ_WAIT_ABOVE_RIGHT, picture, y - 1, x + 1 < F.wc ? x + 1 : x));  // above-right implies above and above-left
+      if (ok && (sched.no_wpp & 1) && x == 0 && y > 0) ok = wait_done(&done[(y - 1) * F.wc + F.wc - 1], epoch, sched.error, sched.wait_ticks, KVZ_HANDOFF_TAG(KVZ_WAIT_ROW_END, picture, y - 1, F.wc - 1));  // its contexts come from there
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
       shared.best_mode = ok ? 1 : 0;
     }
@@ -262,8 +263,9 @@ template <bool CABAC, bool S32, bool SH> __global__ void __launch_bounds__(KVZ_C
 #ifndef KVZ_RDOQ_WAVES_PER_EU
 #define KVZ_RDOQ_WAVES_PER_EU 4
 #endif
+#define KVZ_CTU_UNIT_HAS_RDOQ(unit, CABAC, S32, RDOQ, SH, LISTS, JOINT) || ((unit) == KVZ_CTU_KERNEL_TU && (RDOQ))
 __global__ void __launch_bounds__(KVZ_CTU_THREADS) __attribute__((amdgpu_waves_per_eu(KVZ_RDOQ_WAVES_PER_EU, KVZ_RDOQ_WAVES_PER_EU))) intra_ctu_ticket_kernel_rdoq(const CtuFrames F, const CtuModel model, const Tables *tb, const CtuSched sched)
-#if !KVZ_CTU_KERNEL_BODIES || (defined(KVZ_CTU_KERNEL_TU) && KVZ_CTU_KERNEL_TU != 5)
+#if !KVZ_CTU_KERNEL_BODIES || (defined(KVZ_CTU_KERNEL_TU) && !(0 KVZ_CTU_BUILDS(KVZ_CTU_UNIT_HAS_RDOQ)))  // (not a template: its body goes where its build is)
 ;
 #else
 {
@@ -271,5 +273,14 @@ __global__ void __launch_bounds__(KVZ_CTU_THREADS) __attribute__((amdgpu_waves_p
 }
 #endif
 
+// the kernel of a build (naming it instantiates it: kvz_ctu_tu.hip)
+template <class B> constexpr auto ctu_build_kernel(B)
+{
+  if constexpr (B::joint) return &intra_ctu_joint_kernel<B::cabac, B::s32, B::sh>;
+  else if constexpr (B::rdoq) return &intra_ctu_ticket_kernel_rdoq;
+  else if constexpr (B::lists) return &intra_ctu_ticket_kernel_lists<B::cabac, B::s32>;
+  else if constexpr (B::sh) return &intra_ctu_ticket_kernel_signhide<B::s32>;
+  else return &intra_ctu_ticket_kernel<B::cabac, B::s32, false>;
+}
 }  // namespace kvz
 

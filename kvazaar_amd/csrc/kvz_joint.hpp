@@ -1,5 +1,5 @@
 // kvz_joint.hpp -- batches of different picture sizes in ONE persistent launch of the all-intra CTU pass (kvz_hip_batch_group): the records a workgroup reads for the
-// picture it drew, the two joint ticket lists, what a group and a joint launch are refused for, and how a timed-out hand-off reaches every batch of the group.
+// picture it drew, the two ticket lists and the hand-off error tag (a batch on its own uses both as well), what a group and a joint launch are refused for, and how a timed-out hand-off reaches every batch of the group.
 // No HIP dependency: kvz_ctu_kernels.hpp reads the records on the device, kvz_batch.hpp lays them out, and the host simulation (tests/hostsim/hostsim_joint.cpp)
 // compiles the same text.
 //
@@ -50,7 +50,14 @@ inline std::vector<uint32_t> joint_pictures(const JointGeometry *g, int n)
   return words;
 }
 
-// The joint lists.  wpp: every picture's CTUs in ascending x + 2y, all pictures of all batches interleaved (one anti-diagonal of everybody, then the next: a small
+// The hand-off error tag: what the first CTU to give up a wait leaves in the error word (kvz_ctu_kernels.hpp wait_done, under bit 31) -- the CTU it waited FOR, as in
+// the item word but with the picture modulo 8192, and which neighbour of its own that is.
+enum : unsigned { KVZ_WAIT_LEFT = 0u, KVZ_WAIT_ABOVE_RIGHT = 0x20000000u, KVZ_WAIT_ROW_END = 0x40000000u };
+#define KVZ_HANDOFF_TAG(neighbour, picture, y, x) ((neighbour) | (((unsigned)(picture) << 16 | (unsigned)(y) << 8 | (unsigned)(x)) & 0x1fffffffu))  // (a macro: ticket_loop's code stays what it was, to the order of its instructions)
+struct HandoffTag { unsigned x, y, picture; const char *neighbour; };
+inline HandoffTag handoff_tag_read(unsigned err) { return { err & 0xffu, (err >> 8) & 0xffu, (err >> 16) & 0x1fffu, (err & KVZ_WAIT_ABOVE_RIGHT) ? "its above-right neighbour" : ((err & KVZ_WAIT_ROW_END) ? "the end of the row above" : "its left neighbour") }; }
+
+// The ticket lists of a group -- and of a batch on its own, a group of one.  wpp: every picture's CTUs in ascending x + 2y, all pictures of all batches interleaved (one anti-diagonal of everybody, then the next: a small
 // picture's CTUs sit among the first diagonals of the large ones).  raster: CTU i of every picture in raster order of its own grid, then CTU i + 1 of every picture.
 inline void joint_ticket_lists(const JointGeometry *g, int n, std::vector<uint32_t> *wpp, std::vector<uint32_t> *raster)
 {
@@ -124,14 +131,15 @@ inline int joint_error_fan_out(const unsigned err[3], const uint32_t *batch_of_p
   if (msg && msg_len) msg[0] = 0;
   if (!err[0]) return -2;
   for (int i = 0; i < n_batches; i++) failed[i] = 1;
-  const unsigned picture = (err[0] >> 16) & 0x1fffu;
+  const HandoffTag tag = handoff_tag_read(err[0]);
+  const unsigned picture = tag.picture;
   const bool named = n_pictures <= 0x2000u && picture < n_pictures;
   const int batch = named ? (int)(batch_of_picture[picture] >> 16) : -1;
   if (msg && msg_len)
     snprintf(msg, msg_len, "a CTU hand-off wait timed out inside a joint pass (KVZ_HIP_WAIT_MS to raise the bound) -- the results of ALL %d batches of the group are invalid "
              "[first to give up waited for CTU x %u y %u of picture %d of batch %d (group picture %u%s; %s); that CTU's flag read at the memory side then: %u; tickets drawn then: %u]",
-             n_batches, err[0] & 0xffu, (err[0] >> 8) & 0xffu, named ? joint_frame(batch_of_picture[picture]) : -1, batch, picture, named ? "" : " modulo 8192",
-             (err[0] & 0x20000000u) ? "its above-right neighbour" : ((err[0] & 0x40000000u) ? "the end of the row above" : "its left neighbour"), err[1], err[2]);
+             n_batches, tag.x, tag.y, named ? joint_frame(batch_of_picture[picture]) : -1, batch, picture, named ? "" : " modulo 8192",
+             tag.neighbour, err[1], err[2]);
   return batch;
 }
 

@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include "../../include/kvz_hip_types.h"
+#include "kvz_ctu_builds.hpp"
 
 namespace kvz {
 
@@ -78,5 +79,13 @@ inline bool picture_models_any_signhide(const kvz_hip_picture_models *pm)
 {
   for (int i = 0; i < pm->n_models; i++) if (pm->models[i].signhide) return true;
   return false;
+}
+// the build that serves a launch of these tables (checked; a group's: one per batch), as ctu_build_choose picks it
+inline int picture_models_build(const kvz_hip_picture_models *const *models, int n, bool lists, bool joint)
+{
+  const kvz_hip_intra_cost_model &m0 = models[0]->models[0];
+  bool any_cabac = false, any_signhide = false;
+  for (int i = 0; i < n; i++) { any_cabac |= picture_models_any_cabac(models[i]); any_signhide |= picture_models_any_signhide(models[i]); }
+  return ctu_build_choose({ m0.search_32x32 != 0, m0.rdoq != 0, m0.search_nxn != 0, any_cabac, any_signhide, lists, joint });
 }
 }  // namespace kvz

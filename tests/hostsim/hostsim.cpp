@@ -33,54 +33,51 @@ typedef kvz::Api<HostBackend> A;
 
 // ---- the batched CTU program (kvz_ctu.hpp) run on the host: CTUs in raster order, each one as 256 looped "threads" ----
 #include "../../kvazaar_amd/csrc/kvz_ctu.hpp"
+#include "../../kvazaar_amd/csrc/kvz_ctu_builds.hpp"
+#include <vector>
+namespace {
+// a batch's buffers as the device keeps them (kvz_hip_batch_create): the caller's, the border rows and the coefficient scratch; and one workgroup's shared block
+struct HostFrames {
+  kvz::CtuFrames F;
+  std::vector<uint8_t> border, shared;
+  std::vector<int16_t> scratch;
+  HostFrames(int width, int height, int n_frames, const uint8_t *src, uint8_t *rec, int16_t *coeff, uint8_t *cu_depth, uint8_t *cu_mode, double *ctu_cost, uint8_t *cu_part = nullptr,
+             uint8_t *cu_mode4 = nullptr)
+  {
+    F.W = width; F.H = height; F.wc = (width + 63) / 64; F.hc = (height + 63) / 64; F.frame_px = (long)width * height * 3 / 2;
+    F.src = src; F.rec = rec; F.coeff = coeff; F.cu_depth = cu_depth; F.cu_mode = cu_mode; F.ctu_cost = ctu_cost; F.prof = nullptr;
+    F.cu_part = cu_part; F.cu_mode4 = cu_mode4;
+    const size_t nctu = (size_t)F.wc * F.hc * n_frames;
+    border.assign(nctu * KVZ_BORDER_BYTES, 0); scratch.assign(nctu * 6144, 0);
+    shared.assign(sizeof(kvz::CtuSharedT<true>) > sizeof(kvz::CtuSharedT<false>) ? sizeof(kvz::CtuSharedT<true>) : sizeof(kvz::CtuSharedT<false>), 0);
+    F.border = border.data(); F.coeff_scratch = scratch.data();
+  }
+};
+// One CTU through the program of build B (kvz_ctu_builds.hpp), set up as ticket_loop sets it up: RDOQ's block, and under LISTS the picture's two factor rows
+template <class B> void run_ctu(B, const kvz::CtuModel *cm, const kvz::Tables *tb, const kvz::CtuFrames &F, void *sh, int frame, int cx, int cy, const uint32_t *lf_y = nullptr,
+                                const uint32_t *lf_c = nullptr)
+{
+  kvz::CtuProgramT<B::cabac, B::s32, B::rdoq, B::sh, B::lists> p;
+  if constexpr (B::rdoq) { static kvz::RdoqLds rdoq_lds; p.rl = &rdoq_lds; }
+  if constexpr (B::lists) { p.lf_y = lf_y; p.lf_c = lf_c; }
+  p.m = cm; p.tb = tb; p.F = F; p.s = (kvz::CtuSharedT<B::cabac> *)sh; p.frame = frame; p.cx = cx * 64; p.cy = cy * 64;
+  p.run();
+}
+const kvz::Tables *host_tables() { static kvz::Tables tb; kvz::build_tables(&tb); return &tb; }
+}  // namespace
+// kvz_hip_intra_frames on the host for one picture: like the device ONE instantiation of the program for the pass, the build kvz_batch.hpp launches for this model
 extern "C" void kvz_hostsim_intra_frame_nxn(const kvz_hip_intra_cost_model *m, int width, int height, const uint8_t *src /* Y|U|V */, uint8_t *rec,
                                             int16_t *coeff, uint8_t *cu_depth, uint8_t *cu_mode, double *ctu_cost, uint8_t *cu_part, uint8_t *cu_mode4)
 {
-  static kvz::Tables tb;
-  kvz::build_tables(&tb);
-  kvz::CtuFrames F;
-  F.W = width; F.H = height; F.wc = (width + 63) / 64; F.hc = (height + 63) / 64; F.frame_px = (long)width * height * 3 / 2;
-  F.src = src; F.rec = rec; F.coeff = coeff; F.cu_depth = cu_depth; F.cu_mode = cu_mode; F.ctu_cost = ctu_cost; F.prof = nullptr;
-  F.cu_part = cu_part; F.cu_mode4 = cu_mode4;
-  uint8_t *border = (uint8_t *)calloc((size_t)F.wc * F.hc, KVZ_BORDER_BYTES);
-  F.border = border;
-  int16_t *scratch = (int16_t *)calloc((size_t)F.wc * F.hc * 6144, sizeof(int16_t));
-  F.coeff_scratch = scratch;
-  // like the device, two instantiations of the program: with and without the CABAC coefficient model (kvz_batch.hpp picks by model)
-  void *sh = calloc(1, sizeof(kvz::CtuSharedT<true>) > sizeof(kvz::CtuSharedT<false>) ? sizeof(kvz::CtuSharedT<true>) : sizeof(kvz::CtuSharedT<false>));
+  HostFrames hf(width, height, 1, src, rec, coeff, cu_depth, cu_mode, ctu_cost, cu_part, cu_mode4);
   kvz::CtuModel cm;
   kvz::ctu_model_from(m, &cm);
-  for (int cy = 0; cy < F.hc; cy++)
-    for (int cx = 0; cx < F.wc; cx++) {
-      if (m->rdoq || m->search_nxn) {  // --rdoq / NxN partitions: the instantiation with kvz_rdoq in the quantisation stage and depth 4 of the search (coefficient cost model and 32x32 search switched by the model)
-        static kvz::RdoqLds rdoq_lds;
-        kvz::CtuProgramT<true, true, true> p;
-        p.rl = &rdoq_lds;
-        p.m = &cm; p.tb = &tb; p.F = F; p.s = (kvz::CtuSharedT<true> *)sh; p.frame = 0; p.cx = cx * 64; p.cy = cy * 64;
-        p.run();
-      } else if (m->search_32x32) {  // the instantiations that search 32x32 CUs
-        if (m->coeff_cabac) {
-          kvz::CtuProgramT<true, true> p;
-          p.m = &cm; p.tb = &tb; p.F = F; p.s = (kvz::CtuSharedT<true> *)sh; p.frame = 0; p.cx = cx * 64; p.cy = cy * 64;
-          p.run();
-        } else {
-          kvz::CtuProgramT<false, true> p;
-          p.m = &cm; p.tb = &tb; p.F = F; p.s = (kvz::CtuSharedT<false> *)sh; p.frame = 0; p.cx = cx * 64; p.cy = cy * 64;
-          p.run();
-        }
-      } else if (m->coeff_cabac) {
-        kvz::CtuProgramT<true> p;
-        p.m = &cm; p.tb = &tb; p.F = F; p.s = (kvz::CtuSharedT<true> *)sh; p.frame = 0; p.cx = cx * 64; p.cy = cy * 64;
-        p.run();
-      } else {
-        kvz::CtuProgramT<false> p;
-        p.m = &cm; p.tb = &tb; p.F = F; p.s = (kvz::CtuSharedT<false> *)sh; p.frame = 0; p.cx = cx * 64; p.cy = cy * 64;
-        p.run();
-      }
-    }
-  free(sh);
-  free(scratch);
-  free(border);
+  const bool ran = kvz::ctu_build_dispatch(kvz::ctu_build_choose({ m->search_32x32 != 0, m->rdoq != 0, m->search_nxn != 0, m->coeff_cabac != 0, m->signhide != 0, false, false }), [&](auto bt) {
+    if constexpr (!bt.joint && !bt.lists)  // (a picture on its own; lists are state of a batch: hostsim_scaling_lists.cpp)
+      for (int cy = 0; cy < hf.F.hc; cy++)
+        for (int cx = 0; cx < hf.F.wc; cx++) run_ctu(bt, &cm, host_tables(), hf.F, hf.shared.data(), 0, cx, cy);
+  });
+  if (!ran) { fprintf(stderr, "kvz_hostsim_intra_frame: no build of the CTU program serves this model (signhide with rdoq / search_nxn): the library refuses it\n"); abort(); }
 }
 extern "C" void kvz_hostsim_intra_frame(const kvz_hip_intra_cost_model *m, int width, int height, const uint8_t *src, uint8_t *rec, int16_t *coeff, uint8_t *cu_depth,
                                         uint8_t *cu_mode, double *ctu_cost)
@@ -92,7 +89,6 @@ extern "C" unsigned kvz_hostsim_ctu_shared_bytes(void) { return (unsigned)sizeof
 // ---- the SAO parameter decision (kvz_sao.hpp) on the host: statistics by plain loops over the view, then the device's own candidate and
 // chain code.  R / V / D: the reconstruction before deblocking, after the vertical edges, after all edges (Y|U|V tight). ----
 #include "../../kvazaar_amd/csrc/kvz_sao.hpp"
-#include <vector>
 extern "C" void kvz_hostsim_sao_decide(const kvz_hip_intra_cost_model *m, int width, int height, const uint8_t *src, const uint8_t *R, const uint8_t *V, const uint8_t *D,
                                        kvz_hip_sao_params *luma, kvz_hip_sao_params *chroma, uint8_t *merge)
 {

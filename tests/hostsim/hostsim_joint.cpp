@@ -47,6 +47,26 @@ extern "C" int kvz_hostsim_joint_fan_out(const unsigned *err, int n, const int *
   return kvz::joint_error_fan_out(err, p.data(), (unsigned)p.size(), n, failed, msg, msg_len);
 }
 
+// the hand-off error tag (kvz_joint.hpp): the word ticket_loop writes for a wait for CTU (x, y) of `picture`, `neighbour` of the waiting CTU (a KVZ_WAIT_* value), and
+// in *read what both diagnostics read out of the error word that holds it
+extern "C" unsigned kvz_hostsim_handoff_tag(unsigned neighbour, int picture, int y, int x, kvz::HandoffTag *read)
+{
+  const unsigned tag = KVZ_HANDOFF_TAG(neighbour, picture, y, x);
+  *read = kvz::handoff_tag_read(0x80000000u | tag);
+  return tag;
+}
+
+// what the entry points check of a launch before they ask for its build: signhide_known for every model of the table, scaling_lists_known for a batch with lists, and
+// for a joint launch joint_launch_known on a group of this one batch.  0 accepted, -1 refused
+extern "C" int kvz_hostsim_ctu_launch_check(const kvz_hip_picture_models *pm, int n_frames, int lists, int joint)
+{
+  const char *who = "kvz_hostsim_ctu_launch_check";
+  for (int i = 0; i < pm->n_models; i++) if (!kvz::signhide_known(&pm->models[i], true, who)) return -1;
+  if (!kvz::scaling_lists_known(pm, lists != 0, who)) return -1;
+  const kvz::JointBatchInfo info{ pm, 0, 1, n_frames, lists, 0 };
+  return !joint || kvz::joint_launch_known(&info, 1, &pm, who) ? 0 : -1;
+}
+
 // kvz_hip_batch_group_intra_frames on the host.  Per batch i: its table, geometry, and its buffers in the batch's layouts (pictures back to back).  has_lists / failed
 // (may be null): the state of the batches the launch refuses.  Returns 0; -1 refused (nothing computed); -3 the list drew a CTU before one of its dependencies.
 extern "C" int kvz_hostsim_joint_intra_frames(int n, const kvz_hip_picture_models *const *models, const int *widths, const int *heights, const int *n_frames,
@@ -57,8 +77,6 @@ extern "C" int kvz_hostsim_joint_intra_frames(int n, const kvz_hip_picture_model
   for (int i = 0; i < n; i++) info.push_back({ rec ? (const void *)rec[i] : nullptr, 0, 1, n_frames[i], has_lists ? has_lists[i] : 0, failed ? failed[i] : 0 });
   if (!kvz::joint_group_known(n > 0 ? info.data() : nullptr, n, "kvz_hostsim_joint_intra_frames")) return -1;
   if (!kvz::joint_launch_known(info.data(), n, models, "kvz_hostsim_joint_intra_frames")) return -1;
-  static kvz::Tables tb;
-  kvz::build_tables(&tb);
   const std::vector<kvz::JointGeometry> geo = joint_geometry(n, widths, heights, n_frames);
   std::vector<uint32_t> wpp, raster;
   kvz::joint_ticket_lists(geo.data(), n, &wpp, &raster);
@@ -67,32 +85,26 @@ extern "C" int kvz_hostsim_joint_intra_frames(int n, const kvz_hip_picture_model
   std::vector<kvz::JointBatch> records((size_t)n);
   std::vector<HostModelTable> tables;
   tables.reserve((size_t)n);
-  std::vector<std::vector<uint8_t>> borders((size_t)n);
-  std::vector<std::vector<int16_t>> scratch((size_t)n);
+  std::vector<HostFrames> frames;
+  frames.reserve((size_t)n);
   std::vector<std::vector<unsigned>> done((size_t)n);
-  bool any_cabac = false, any_signhide = false;
   for (int i = 0; i < n; i++) {
     tables.emplace_back(models[i]);
-    any_cabac |= kvz::picture_models_any_cabac(models[i]);
-    any_signhide |= kvz::picture_models_any_signhide(models[i]);
+    frames.emplace_back(widths[i], heights[i], n_frames[i], src[i], rec[i], coeff[i], cu_depth[i], cu_mode[i], ctu_cost[i]);
     kvz::JointBatch &r = records[(size_t)i];
     memset(&r, 0, sizeof r);
-    kvz::CtuFrames &F = r.F;
-    F.W = widths[i]; F.H = heights[i]; F.wc = geo[i].wc; F.hc = geo[i].hc; F.frame_px = (long)widths[i] * heights[i] * 3 / 2;
-    F.src = src[i]; F.rec = rec[i]; F.coeff = coeff[i]; F.cu_depth = cu_depth[i]; F.cu_mode = cu_mode[i]; F.ctu_cost = ctu_cost[i]; F.prof = nullptr;
-    const size_t nctu = (size_t)F.wc * F.hc * n_frames[i];
-    borders[(size_t)i].assign(nctu * KVZ_BORDER_BYTES, 0);
-    scratch[(size_t)i].assign(nctu * 6144, 0);
-    done[(size_t)i].assign(nctu, 0);
-    F.border = borders[(size_t)i].data(); F.coeff_scratch = scratch[(size_t)i].data();
+    r.F = frames[(size_t)i].F;
+    done[(size_t)i].assign((size_t)geo[i].wc * geo[i].hc * n_frames[i], 0);
     r.models = tables[(size_t)i].table; r.done = done[(size_t)i].data(); r.epoch = 7u + (unsigned)i; r.index = i;  // (every batch counts its own passes)
   }
   kvz::JointTable jt;
   jt.batch_of_picture = pictures.data(); jt.batches = records.data();
   const kvz_hip_intra_cost_model &m0 = models[0]->models[0];
   const std::vector<uint32_t> &items = m0.no_wpp ? raster : wpp;
-  void *sh = calloc(1, sizeof(kvz::CtuSharedT<true>) > sizeof(kvz::CtuSharedT<false>) ? sizeof(kvz::CtuSharedT<true>) : sizeof(kvz::CtuSharedT<false>));
+  void *sh = frames[0].shared.data();
   int rc = 0;
+  const int build = kvz::picture_models_build(models, n, false, true);  // ONE for the launch, as the library asks for it
+  if (build == kvz::KVZ_CTU_BUILD_NONE) return -1;
   for (size_t t = 0; t < items.size() && rc == 0; t++) {
     const uint32_t item = items[t];
     const int picture = (int)(item >> 16), y = (int)((item >> 8) & 0xff), x = (int)(item & 0xff);
@@ -109,14 +121,10 @@ extern "C" int kvz_hostsim_joint_intra_frames(int n, const kvz_hip_picture_model
     if (flags[y * F.wc + x] == jb->epoch) rc = -3;  // drawn twice
     if (rc) break;
     const kvz::CtuModel *cm = kvz::picture_model(jb->models, frame);
-    if (any_signhide) { if (m0.search_32x32) run_ctu_signhide<true>(cm, &tb, F, sh, frame, x, y); else run_ctu_signhide<false>(cm, &tb, F, sh, frame, x, y); }
-    else if (m0.search_32x32) { if (any_cabac) run_ctu<true, true, false>(cm, &tb, F, sh, frame, x, y); else run_ctu<false, true, false>(cm, &tb, F, sh, frame, x, y); }
-    else if (any_cabac) run_ctu<true, false, false>(cm, &tb, F, sh, frame, x, y);
-    else run_ctu<false, false, false>(cm, &tb, F, sh, frame, x, y);
+    kvz::ctu_build_dispatch(build, [&](auto bt) { if constexpr (bt.joint) run_ctu(bt, cm, host_tables(), F, sh, frame, x, y); });
     flags[y * F.wc + x] = jb->epoch;
   }
   for (int i = 0; i < n && rc == 0; i++)
     for (unsigned v : done[(size_t)i]) if (v != records[(size_t)i].epoch) rc = -3;  // a CTU the list left out
-  free(sh);
   return rc;
 }

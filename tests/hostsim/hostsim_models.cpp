@@ -1,10 +1,11 @@
 // hostsim_models.cpp -- TEST INFRASTRUCTURE (see hostsim.cpp, which this unit includes whole: one library with everything of libkvz_hostsim.so plus the twins of
 // the kvz_hip_*_models entry points).  A batch whose pictures run under models of their own (kvz_hip_picture_models), walked picture by picture on the host: every
 // picture's model is found through the function the device uses (kvz_ctu.hpp / kvz_syntax.hpp picture_model), the table is checked by the text the library checks it
-// with (kvz_picture_models.hpp), and the instantiation of the CTU program is chosen as kvz_batch.hpp chooses the kernel -- ONE for the whole batch, the one with the
-// CABAC coefficient model when any model asks for it.  tests/test_mixed_qp_sim.py builds and uses it.
+// with (kvz_picture_models.hpp), and the instantiation of the CTU program is the build kvz_batch.hpp launches -- ONE for the whole batch, chosen by the function
+// the library asks and reached through its dispatcher (kvz_ctu_builds.hpp).  tests/test_mixed_qp_sim.py builds and uses it.
 #include "hostsim.cpp"
 #include "../../kvazaar_amd/csrc/kvz_picture_models.hpp"
+#include "../../kvazaar_amd/csrc/kvz_scaling_lists.hpp"
 
 namespace {
 // the compact rows the device keeps (kvz_batch.hpp picture_models_stage), with host pointers
@@ -21,14 +22,40 @@ struct HostModelTable {
     table.model_of_picture = pm->model_of_picture;
   }
 };
-template <bool CABAC, bool S32, bool RDOQ> void run_ctu(const kvz::CtuModel *cm, const kvz::Tables *tb, const kvz::CtuFrames &F, void *sh, int frame, int cx, int cy)
+// kvz_intra_frames_queue on the host, the table checked: ONE build for the whole batch, every picture under its row of the table and, on a batch with scaling lists
+// (n_sets > 0; rows: as kvz_hip_batch_set_scaling_lists lays them out), on its two rows of the factor table.  -1: no build serves the launch
+int host_intra_frames_models(const kvz_hip_picture_models *pm, HostFrames &hf, int n_frames, const uint32_t *rows = nullptr, int n_sets = 0, const uint16_t *set_of_picture = nullptr)
 {
-  kvz::CtuProgramT<CABAC, S32, RDOQ> p;
-  if constexpr (RDOQ) { static kvz::RdoqLds rdoq_lds; p.rl = &rdoq_lds; }
-  p.m = cm; p.tb = tb; p.F = F; p.s = (kvz::CtuSharedT<CABAC> *)sh; p.frame = frame; p.cx = cx * 64; p.cy = cy * 64;
-  p.run();
+  const HostModelTable T(pm);
+  const bool ran = kvz::ctu_build_dispatch(kvz::picture_models_build(&pm, 1, n_sets > 0, false), [&](auto bt) {
+    if constexpr (!bt.joint)
+      for (int f = 0; f < n_frames; f++) {
+        const kvz::CtuModel *cm = kvz::picture_model(T.table, f);  // what thread 0 of a workgroup loads for the CTU it drew
+        const uint32_t at = n_sets ? kvz::scaling_list_rows_of_picture(set_of_picture ? set_of_picture[f] : 0, n_sets, cm->qp) : 0;
+        for (int cy = 0; cy < hf.F.hc; cy++)
+          for (int cx = 0; cx < hf.F.wc; cx++)
+            run_ctu(bt, cm, host_tables(), hf.F, hf.shared.data(), f, cx, cy, rows + (size_t)(at & 0xffffu) * kvz::KVZ_LIST_ROW, rows + (size_t)(at >> 16) * kvz::KVZ_LIST_ROW);
+      }
+  });
+  return ran ? 0 : -1;
 }
 }  // namespace
+
+// The build list and the choice (kvz_ctu_builds.hpp), for tests/test_ctu_builds_sim.py.  rows [n][7]: unit, CABAC, S32, RDOQ, SH, LISTS, JOINT of every build of the
+// list; returns n.  *unit_mask: the translation units, a bit each.
+extern "C" int kvz_hostsim_ctu_builds(int *rows, unsigned long long *unit_mask)
+{
+#define KVZ_CTU_X(...) __VA_ARGS__,
+  const int list[] = { KVZ_CTU_BUILDS(KVZ_CTU_X) };
+#undef KVZ_CTU_X
+  memcpy(rows, list, sizeof list);
+  *unit_mask = kvz::KVZ_CTU_UNIT_MASK;
+  return (int)(sizeof list / sizeof list[0] / 7);
+}
+extern "C" int kvz_hostsim_ctu_build_choose(int search_32x32, int rdoq, int search_nxn, int any_cabac, int any_signhide, int lists, int joint)
+{
+  return kvz::ctu_build_choose({ search_32x32 != 0, rdoq != 0, search_nxn != 0, any_cabac != 0, any_signhide != 0, lists != 0, joint != 0 });
+}
 
 // 0 when a batch of n_frames pictures accepts the table, -1 when the library refuses it (ticket_schedule == 0: as under KVZ_HIP_SCHED=wave)
 extern "C" int kvz_hostsim_picture_models_check(const kvz_hip_picture_models *pm, int n_frames, int ticket_schedule)
@@ -42,33 +69,8 @@ extern "C" int kvz_hostsim_intra_frames_models(const kvz_hip_picture_models *pm,
                                                uint8_t *cu_depth, uint8_t *cu_mode, double *ctu_cost, uint8_t *cu_part, uint8_t *cu_mode4)
 {
   if (!kvz::picture_models_known(pm, n_frames, true, "kvz_hostsim_intra_frames_models")) return -1;
-  static kvz::Tables tb;
-  kvz::build_tables(&tb);
-  kvz::CtuFrames F;
-  F.W = width; F.H = height; F.wc = (width + 63) / 64; F.hc = (height + 63) / 64; F.frame_px = (long)width * height * 3 / 2;
-  F.src = src; F.rec = rec; F.coeff = coeff; F.cu_depth = cu_depth; F.cu_mode = cu_mode; F.ctu_cost = ctu_cost; F.prof = nullptr;
-  F.cu_part = cu_part; F.cu_mode4 = cu_mode4;
-  const size_t nctu = (size_t)F.wc * F.hc * n_frames;
-  uint8_t *border = (uint8_t *)calloc(nctu, KVZ_BORDER_BYTES);
-  F.border = border;
-  int16_t *scratch = (int16_t *)calloc(nctu * 6144, sizeof(int16_t));
-  F.coeff_scratch = scratch;
-  void *sh = calloc(1, sizeof(kvz::CtuSharedT<true>) > sizeof(kvz::CtuSharedT<false>) ? sizeof(kvz::CtuSharedT<true>) : sizeof(kvz::CtuSharedT<false>));
-  const HostModelTable T(pm);
-  const kvz_hip_intra_cost_model &m0 = pm->models[0];
-  const bool any_cabac = kvz::picture_models_any_cabac(pm);
-  for (int f = 0; f < n_frames; f++) {
-    const kvz::CtuModel *cm = kvz::picture_model(T.table, f);  // what thread 0 of a workgroup loads for the CTU it drew
-    for (int cy = 0; cy < F.hc; cy++)
-      for (int cx = 0; cx < F.wc; cx++) {
-        if (m0.rdoq || m0.search_nxn) run_ctu<true, true, true>(cm, &tb, F, sh, f, cx, cy);
-        else if (m0.search_32x32) { if (any_cabac) run_ctu<true, true, false>(cm, &tb, F, sh, f, cx, cy); else run_ctu<false, true, false>(cm, &tb, F, sh, f, cx, cy); }
-        else if (any_cabac) run_ctu<true, false, false>(cm, &tb, F, sh, f, cx, cy);
-        else run_ctu<false, false, false>(cm, &tb, F, sh, f, cx, cy);
-      }
-  }
-  free(sh); free(scratch); free(border);
-  return 0;
+  HostFrames hf(width, height, n_frames, src, rec, coeff, cu_depth, cu_mode, ctu_cost, cu_part, cu_mode4);
+  return host_intra_frames_models(pm, hf, n_frames);
 }
 
 // kvz_hip_batch_entropy_code_models on the host: kvz_hostsim_entropy_code with every picture's initial context states from its row of the table

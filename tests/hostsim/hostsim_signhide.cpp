@@ -1,7 +1,7 @@
 // hostsim_signhide.cpp -- TEST INFRASTRUCTURE (see hostsim.cpp and hostsim_models.cpp, which this unit includes whole: one library with everything of
 // libkvz_hostsim_models.so plus what sign data hiding adds).  kvz_hip_intra_cost_model::signhide on the host: the shared hiding rule on one block (kvz_recon.hpp
-// sign_hide_block, what the lanes of the CTU pass apply a group each), the sign-hiding instantiations of the CTU program -- hostsim.cpp and hostsim_models.cpp
-// only instantiate the others -- chosen as kvz_batch.hpp chooses the kernel, and the entropy coder with every picture's switch read from its model's row, as
+// sign_hide_block, what the lanes of the CTU pass apply a group each), the pass on tables that have the switch (hostsim_models.cpp's, which takes the build the
+// library takes), and the entropy coder with every picture's switch read from its model's row, as
 // kvz_batch.hpp picture_models_stage lays the rows out.  tests/test_signhide_sim.py builds and uses it.
 #include "hostsim_models.cpp"
 
@@ -27,44 +27,12 @@ extern "C" int kvz_hostsim_signhide_model_check(const kvz_hip_intra_cost_model *
   return kvz::cost_model_known(m, "kvz_hostsim_signhide_model_check") && kvz::signhide_known(m, ticket_schedule != 0, "kvz_hostsim_signhide_model_check") ? 0 : -1;
 }
 
-namespace {
-template <bool S32> void run_ctu_signhide(const kvz::CtuModel *cm, const kvz::Tables *tb, const kvz::CtuFrames &F, void *sh, int frame, int cx, int cy)
-{
-  kvz::CtuProgramT<true, S32, false, true> p;
-  p.m = cm; p.tb = tb; p.F = F; p.s = (kvz::CtuSharedT<true> *)sh; p.frame = frame; p.cx = cx * 64; p.cy = cy * 64;
-  p.run();
-}
-}  // namespace
-
-// kvz_hip_intra_frames_models on the host, for tables with and without the switch: a table none of whose models hides signs runs as before
-// (kvz_hostsim_intra_frames_models); any other through ONE sign-hiding instantiation for the whole batch, which reads the switch of every picture's row.
+// kvz_hip_intra_frames_models on the host, for tables with and without the switch: the choice of the build sees it (a table with it runs through ONE sign-hiding
+// build for the whole batch, which reads the switch of every picture's row), so this is kvz_hostsim_intra_frames_models without the NxN outputs.
 extern "C" int kvz_hostsim_signhide_intra_frames_models(const kvz_hip_picture_models *pm, int width, int height, int n_frames, const uint8_t *src, uint8_t *rec,
                                                         int16_t *coeff, uint8_t *cu_depth, uint8_t *cu_mode, double *ctu_cost)
 {
-  if (!kvz::picture_models_known(pm, n_frames, true, "kvz_hostsim_signhide_intra_frames_models")) return -1;
-  if (!kvz::picture_models_any_signhide(pm)) return kvz_hostsim_intra_frames_models(pm, width, height, n_frames, src, rec, coeff, cu_depth, cu_mode, ctu_cost, nullptr, nullptr);
-  static kvz::Tables tb;
-  kvz::build_tables(&tb);
-  kvz::CtuFrames F;
-  F.W = width; F.H = height; F.wc = (width + 63) / 64; F.hc = (height + 63) / 64; F.frame_px = (long)width * height * 3 / 2;
-  F.src = src; F.rec = rec; F.coeff = coeff; F.cu_depth = cu_depth; F.cu_mode = cu_mode; F.ctu_cost = ctu_cost; F.prof = nullptr;
-  const size_t nctu = (size_t)F.wc * F.hc * n_frames;
-  uint8_t *border = (uint8_t *)calloc(nctu, KVZ_BORDER_BYTES);
-  F.border = border;
-  int16_t *scratch = (int16_t *)calloc(nctu * 6144, sizeof(int16_t));
-  F.coeff_scratch = scratch;
-  void *sh = calloc(1, sizeof(kvz::CtuSharedT<true>));
-  const HostModelTable T(pm);
-  for (int f = 0; f < n_frames; f++) {
-    const kvz::CtuModel *cm = kvz::picture_model(T.table, f);
-    for (int cy = 0; cy < F.hc; cy++)
-      for (int cx = 0; cx < F.wc; cx++) {
-        if (pm->models[0].search_32x32) run_ctu_signhide<true>(cm, &tb, F, sh, f, cx, cy);
-        else run_ctu_signhide<false>(cm, &tb, F, sh, f, cx, cy);
-      }
-  }
-  free(sh); free(scratch); free(border);
-  return 0;
+  return kvz_hostsim_intra_frames_models(pm, width, height, n_frames, src, rec, coeff, cu_depth, cu_mode, ctu_cost, nullptr, nullptr);
 }
 
 // kvz_hip_batch_entropy_code_models on the host with the rows as the library stages them: a model's initial states and, in the row's last byte, its signhide

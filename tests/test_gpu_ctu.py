@@ -54,6 +54,21 @@ def test_hip_ctu_equals_oracle(oracle, hiplib, size):
         assert not cc.compare(want, got[i]), (size, i, cc.compare(want, got[i]))
 
 
+def test_hip_ctu_older_schedule_with_the_cabac_model(oracle, hiplib, monkeypatch):
+    """KVZ_HIP_SCHED=wave, one launch per anti-diagonal, at QP 30 (the CABAC coefficient model from QP 28 on): intra_ctu_wave_kernel<true>, which nothing else
+    launches.  Three 136x136 pictures (3x3 CTUs, the right column and the bottom row partial), byte for byte against the host simulation and the oracle"""
+    w, h = 136, 136
+    model = _model(hiplib, oracle, 30)
+    assert model.coeff_cabac == 1
+    frames = cc.yuv_frames(w, h, 3, 1234, "small")
+    monkeypatch.setenv("KVZ_HIP_SCHED", "wave")  # read when a batch is created
+    got = _run_batch(hiplib, model, w, h, frames)
+    sim = C.CDLL(flatapi.hostsim_path())
+    for i, f in enumerate(frames):
+        assert not cc.compare(cc.run_hostsim(sim, model, w, h, f), got[i]), i
+        assert not cc.compare(cc.run_oracle(oracle, model, w, h, f), got[i]), i
+
+
 def test_hip_ctu_adversarial_and_qps(oracle, hiplib):
     w, h = 192, 136
     frames = list(cc.adversarial_frames(w, h).values())

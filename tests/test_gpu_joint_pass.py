@@ -120,6 +120,24 @@ def test_joint_builds(oracle, lib, name):
             _check(oracle, g, outs, "/fast", cu=False)
 
 
+@pytest.mark.parametrize("sw", [dict(search_32x32=1), dict(search_32x32=1, signhide=1)], ids=["search32", "signhide+search32"])
+def test_joint_builds_no_preset_reaches_equal_the_host_simulation(lib, sw):
+    """search_32x32 without the CABAC coefficient model -- intra_ctu_joint_kernel<false, true, false> -- and, hiding signs, <true, true, true>: three 136x136 pictures
+    (3x3 CTUs, the right column and the bottom row partial: every hand-off kind) in two batches, byte for byte against the host simulation, which takes its build as
+    the library does"""
+    p = cc.yuv_frames(136, 136, 3, 11, "small")
+    specs = [jc.Spec(136, 136, p[:2], [22, 27]), jc.Spec(136, 136, p[2:], [22])]
+    with Group(lib, specs, **sw) as g:
+        assert not any(t.model_of(i).coeff_cabac for t in g.tables for i in range(len(t.qps)))  # what selects those kernels
+        g.group.run(g.tables)
+        rc, want = jc.sim_joint(jc.load_sim(), specs, g.tables)
+        assert rc == 0
+        got = g.outputs()
+        bad = [(k, i, cc.compare(o, w)) for k, (a, b) in enumerate(zip(got, want)) for i, (o, w) in enumerate(zip(a, b)) if cc.compare(o, w)]
+        assert not bad, bad
+        assert 1 in {int(v) for a in got for o in a for v in np.unique(o["depth"])}  # 32x32 CUs do occur
+
+
 def test_sign_hiding_in_some_batches_of_a_group(lib):
     a, b = jc.clip_spec(64, 64, 2, 9, "small", [22, 22]), jc.clip_spec(200, 136, 2, 3, "small", [27, 27])
     specs, hide = [a, b, a, b], [1, 0, 0, 1]

@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
 """On the GPU box: bench.py under alternating builds of the library, one JSON line per run (the format of profiles/chains_ab.jsonl).
 
-usage: tools/bench_ab.py <tag> <reps> <out.jsonl> "<build name>=<library path>" ["<build name>=<library path>" ...] [-- bench args ...]
+usage: tools/bench_ab.py [--leg=<name>] <tag> <reps> <out.jsonl> "<build name>=<library path>" ["<build name>=<library path>" ...] [-- bench args ...]
 
 Every run is a fresh process (`KVZ_HIP_LIB=<library> python bench.py --steps 5 --warmup 2 <bench args>`) under a time limit; the builds alternate within a repetition,
 so that drift of the box lands on all of them alike.  The first run that fails, or whose result does not say `"verified": true` (bench.py checks its outputs under --full and in the --only legs: give `--full --no-extra`
 behind `--`), ends the script with its status.  KVZ_AB_NO_VERDICT_OK=1 lets `"verified": null` pass: what bench.py says where it has no digests of the reference
-encoder to compare with (a QP other than 22).  Afterwards:
+encoder to compare with (a QP other than 22).  --leg=<name> compares an auxiliary leg's value instead of the headline's (`chain_full`: give `--full` behind `--`); a leg that says `"verified": false` ends the script like the headline.  Afterwards:
 the median ratio of every build against the first one, each build's spread ((max - min) / median), and whether the slowest run of a build beats the fastest of the
 first -- the project's bar is a median ratio above 1 + 5 x the first build's spread together with that."""
 import json
@@ -24,6 +24,9 @@ def main():
     if "--" in argv:
         extra = argv[argv.index("--") + 1:]
         argv = argv[:argv.index("--")]
+    leg = None
+    if argv[0].startswith("--leg="):
+        leg, argv = argv[0][len("--leg="):], argv[1:]
     tag, reps, out = argv[0], int(argv[1]), argv[2]
     builds = [a.split("=", 1) for a in argv[3:]]
     limit = int(os.environ.get("KVZ_AB_TIMEOUT", "240"))
@@ -40,6 +43,12 @@ def main():
                 d = json.loads(r.stdout.strip().splitlines()[-1])
                 rec = {"tag": tag, "rep": rep, "bench_args": extra, "build": name, "value": d["value"], "ms_per_step": d.get("ms_per_step"), "steps": 5, "warmup": 2,
                        "unit": d.get("unit"), "verified": d.get("verified")}
+                if leg:
+                    if not d.get(leg, {}).get("value"):
+                        print(f"{tag} rep {rep} {name}: no leg {leg} in the result: {d.get(leg)}", flush=True)
+                        return 4
+                    rec.update(leg=leg, headline=d["value"], value=d[leg]["value"], leg_verified=d[leg].get("verified"))
+                    d = dict(d, value=rec["value"], verified=False if d[leg].get("verified") is False else d.get("verified"))
                 fh.write(json.dumps(rec) + "\n")
                 fh.flush()
                 print(f"{tag} rep {rep} {name}: {d['value']:.0f} {d.get('unit')} verified={d.get('verified')}", flush=True)
