@@ -1666,6 +1666,7 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false, bool
     KVZ_SYNC();
     KVZ_PROF(KVZ_P_SATD);
     KVZ_FOR_THREADS(tid) {
+      if (tid >= kHookThread && tid < kHookThread + kCostEntries) cu_cost_prepare(lv, x, y, depth, tid - kHookThread);  // beside the selection, which the other wavefront runs: read by thread 0 in eval_cu's cost phase
       const int final_mode = replay_selection(tid, log2w, nblk);
       if (final_mode >= 0) {
         if (tid == 0) s->best_mode = final_mode;
@@ -2611,59 +2612,87 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false, bool
 
   // cu_bits() * lambda + leaf_rd_cost() of the CU just evaluated at its own depth (eval_cu: search.c:895-940 + 425-541), bin for bin the same
   // prices and transitions on the search contexts -- but the six bins sit on five different contexts (only U's and V's coded-block flags share
-  // one), so thread 0's critical path is made of as few dependent LDS round trips as the data allow: (1) the ten syntax contexts as one 8-byte and one
-  // 2-byte read, together with the CU's coded-block flags, the sums of the reconstruction and lambda; (2) five prices and five successor-table entries;
-  // (3) the price and the successor of V's flag on U's successor state, the one true dependence; then everything is written back at once (KVZ_TOGETHER
-  // holds the loads of a round trip together).  The sums of prices are exact in any order
-  // (multiples of 2^-15 below 2^10), the cost expressions are the callees' own.
-  KVZ_DEV double cu_cost_batched(int lv, int x, int y, int depth, int mode, const int8_t *known_preds, const double *known_coeff_bits) const
+  // one), so the chain is as few dependent LDS round trips as the data allow: (1) a context's state; (2) its price and successor-table entry; (3) for V's
+  // flag the same once more on U's successor state, the one true dependence (KVZ_TOGETHER holds the loads of a round trip together).  The sums of prices are
+  // exact in any order (multiples of 2^-15 below 2^10), the cost expressions are the callees' own.
+  //
+  // Most of that does not wait for the CU's selection or reconstruction: which contexts are used, their states -- the syntax contexts 0..9 stand still from the
+  // end of the previous CU's cost to this one (the CABAC coefficient model moves the residual contexts only) --, and the price and successor of BOTH values of
+  // each bin that does.  cu_cost_prepare works that out inside the selection phase of rough_search on twelve lanes of the wavefront that has nothing to do there
+  // (threads kHookThread ..), a table entry each, and what remains on thread 0 is ONE round trip -- the table, the CU's flags, the sums -- the choice among
+  // prepared values, the callees' own double-precision expressions and the write-back.  The table lies in child_acc[1][1] .. [2][8], which only the 64x64
+  // attempt uses (try_merge, after every searched CU of the CTU; [0][0] and [3][1..4] have their other users).
+  enum { kSp = 0, kCh = 1, kIn = 2, kCl = 4, kCu = 6, kCv = 8, kCostEntries = 12 };  // split flag / part size, chroma mode; then per bin value: "the mode is an MPM", luma flag, U's flag; V's flag at [2 bu + bv]
+  struct CostPrep {
+    float f[kCostEntries];  // prices
+    u8 n[kCostEntries];     // the states that follow
+    int8_t preds[3];        // the most probable modes of the mock encode (its left-edge rule: intra_mode_syntax_bits)
+    u8 i_sp;                // the context entry kSp belongs to; kNoSplitFlag: the CU codes neither flag
+  };
+  static constexpr int kNoSplitFlag = 255;
+  static_assert(sizeof(CostPrep) == 64 && sizeof(CostPrep) <= 17 * sizeof(u32) && (__builtin_offsetof(CtuSharedT<CABAC>, child_acc) + 10 * sizeof(u32)) % 8 == 0, "the table fits child_acc[1][1] .. [2][8], 8-byte aligned");
+  KVZ_DEV CostPrep *cost_prep() const { return reinterpret_cast<CostPrep *>(&s->child_acc[1][1]); }
+  // entry j of the table (j < kCostEntries; every lane runs the same instructions on its own context and bin), entry 0's lane also the bytes about the CU
+  KVZ_DEV void cu_cost_prepare(int lv, int x, int y, int depth, int j) const
   {
-    const int xl = x - cx, yl = y - cy, w = 64 >> depth;
-    u8 *cs = s->cab.s;
-    const bool adaptive = m->adaptive != 0;
-    // (1) what does not depend on another read
-    u32 st03, st47, st89 = 0;  // contexts 0..3 (the split flag's three and the part size's), 4..7 (intra mode, chroma mode, luma flags), 8..9 (chroma flags)
-    __builtin_memcpy(&st03, cs, 4); __builtin_memcpy(&st47, cs + 4, 4); __builtin_memcpy(&st89, cs + 8, 2);
-    u32 cbf = s->cu[lv][(yl >> 3) * 8 + (xl >> 3)].cbf;
-    // the two neighbours, once: the split flag's context of a 16x16 CU looks at both, the most probable modes on the CTU's left edge at the one above
+    const int w = 64 >> depth;
+    const u8 *cs = s->cab.s;
+    CostPrep *t = cost_prep();
+    // the two neighbours: the split flag's context of a 16x16 CU looks at both, the most probable modes on the CTU's left edge at the one above
     const bool no_left = (x & 63) == 0;  // the mock encode's left neighbour (intra_mode_syntax_bits)
-    const bool own_preds = !known_preds || (no_left && x > 0);
+    const bool own_preds = no_left && x > 0;
     int left = 0, above = 0;
     if (depth != 3 || own_preds) neighbour_pair(lv, x, y, &left, &above);
+    const bool has_sp = depth == 3 || !(F.W < x + w || F.H < y + w);
+    const int i_sp = depth == 3 ? KVZ_CX_PART : KVZ_CX_SPLIT + (has_sp ? split_model_of(left, above, depth) : 0), b_sp = depth == 3 ? 1 : 0;
+    // which context, which bin; V's flag is priced on the state U's flag (value bu) leaves behind
+    const int ci = j == kSp ? i_sp : (j == kCh ? KVZ_CX_CHROMA : (j < kCl ? KVZ_CX_INTRA : (j < kCu ? KVZ_CX_CBF_LUMA + 1 : KVZ_CX_CBF_CHROMA)));
+    const int bin = j == kSp ? b_sp : (j == kCh ? 0 : (j & 1)), bu = (j >> 1) & 1;
+    int st = cs[ci];
+    if (j >= kCv && m->adaptive) st = ctx_next(st, bu);
+    float f = s->entropy_fbits[st ^ bin];
+    int l = s->ctx_lps[st >> 1];
+    KVZ_TOGETHER(f, l);
+    t->f[j] = f;
+    t->n[j] = (u8)ctx_next_with(st, bin, l);
+    if (j == 0) {
+      int8_t preds[3] = { s->preds[0], s->preds[1], s->preds[2] };  // rough_search's, from the true neighbours
+      if (own_preds) mpm_candidates(y, 0, above, preds);
+      t->preds[0] = preds[0]; t->preds[1] = preds[1]; t->preds[2] = preds[2];
+      t->i_sp = (u8)(has_sp ? i_sp : kNoSplitFlag);
+    }
+  }
+  KVZ_DEV double cu_cost_batched(int lv, int x, int y, int depth, int mode, const double *known_coeff_bits) const
+  {
+    const int xl = x - cx, yl = y - cy;
+    u8 *cs = s->cab.s;
+    const bool adaptive = m->adaptive != 0;
+    // the one round trip
+    unsigned long long tw[8];
+    __builtin_memcpy(tw, __builtin_assume_aligned(cost_prep(), 8), sizeof tw);
+    u32 cbf = s->cu[lv][(yl >> 3) * 8 + (xl >> 3)].cbf;
     u32 luma_ssd = s->acc[0], ssd_u = s->acc[1], ssd_v = s->acc[2], wy = 0, wu = 0, wv = 0;
     double coeff_bits = 0, lambda = m->lambda;
     if (known_coeff_bits) coeff_bits += *known_coeff_bits;
     else { wy = s->acc[3]; wu = s->acc[4]; wv = s->acc[5]; }
-    KVZ_TOGETHER(st03, st47, st89, cbf, luma_ssd, ssd_u, ssd_v, wy, wu, wv);
+    KVZ_TOGETHER(tw[0], tw[1], tw[2], tw[3], tw[4], tw[5], tw[6], tw[7], cbf, luma_ssd);
+    KVZ_TOGETHER(ssd_u, ssd_v, wy, wu, wv);
     KVZ_TOGETHER(coeff_bits, lambda);
-    // which contexts, which bins
-    const bool has_sp = depth == 3 || !(F.W < x + w || F.H < y + w);
-    const int i_sp = depth == 3 ? KVZ_CX_PART : KVZ_CX_SPLIT + (has_sp ? split_model_of(left, above, depth) : 0), b_sp = depth == 3 ? 1 : 0;
-    int8_t preds[3];
-    if (!own_preds) { preds[0] = known_preds[0]; preds[1] = known_preds[1]; preds[2] = known_preds[2]; }
-    else mpm_candidates(y, no_left ? 0 : left, above, preds);
+    CostPrep t;
+    __builtin_memcpy(&t, tw, sizeof t);
+    // which bins, and what was prepared for them
+    const int8_t preds[3] = { t.preds[0], t.preds[1], t.preds[2] };
+    const bool has_sp = t.i_sp != kNoSplitFlag;
     const int b_in = (mode == preds[0] || mode == preds[1] || mode == preds[2]) ? 1 : 0;
     const int cb_u = cbf_is_set((uint16_t)cbf, depth, 1), cb_v = cbf_is_set((uint16_t)cbf, depth, 2), cb_y = cbf_is_set((uint16_t)cbf, depth, 0);
-    static_assert(KVZ_CX_SPLIT == 0 && KVZ_CX_PART == 3 && KVZ_CX_INTRA == 4 && KVZ_CX_CHROMA == 5 && KVZ_CX_CBF_LUMA == 6 && KVZ_CX_CBF_CHROMA == 8, "the bytes picked out of st03 / st47 / st89 below");
-    const int s_sp = (int)((st03 >> (8 * i_sp)) & 255), s_in = (int)(st47 & 255), s_ch = (int)((st47 >> 8) & 255), s_cl = (int)(st47 >> 24), s_cu = (int)(st89 & 255);
-    // (2) prices and successor-table entries of the five states
-    float f_sp = s->entropy_fbits[s_sp ^ b_sp], f_in = s->entropy_fbits[s_in ^ b_in], f_ch = s->entropy_fbits[s_ch ^ 0];
-    float f_cu = s->entropy_fbits[s_cu ^ cb_u], f_cl = s->entropy_fbits[s_cl ^ cb_y];
-    int l_sp = s->ctx_lps[s_sp >> 1], l_in = s->ctx_lps[s_in >> 1], l_ch = s->ctx_lps[s_ch >> 1], l_cu = s->ctx_lps[s_cu >> 1], l_cl = s->ctx_lps[s_cl >> 1];
-    KVZ_TOGETHER(f_sp, f_in, f_ch, f_cu, f_cl, l_sp, l_in, l_ch, l_cu, l_cl);
-    const int n_sp = ctx_next_with(s_sp, b_sp, l_sp), n_in = ctx_next_with(s_in, b_in, l_in), n_ch = ctx_next_with(s_ch, 0, l_ch);
-    const int n_cu = ctx_next_with(s_cu, cb_u, l_cu), n_cl = ctx_next_with(s_cl, cb_y, l_cl);
-    // (3) the second bin on the chroma flag's context
-    const int s_cv = adaptive ? n_cu : s_cu;
-    float f_cv = s->entropy_fbits[s_cv ^ cb_v];
-    int l_cv = s->ctx_lps[s_cv >> 1];
-    KVZ_TOGETHER(f_cv, l_cv);
-    const int n_cv = ctx_next_with(s_cv, cb_v, l_cv);
-    if (adaptive) {
-      if (has_sp) st03 = (st03 & ~(255u << (8 * i_sp))) | ((u32)n_sp << (8 * i_sp));
-      st47 = (st47 & 0x00ff0000u) | (u32)n_in | ((u32)n_ch << 8) | ((u32)n_cl << 24);
-      st89 = (st89 & 0xff00u) | (u32)n_cv;
-      __builtin_memcpy(cs, &st03, 4); __builtin_memcpy(cs + 4, &st47, 4); __builtin_memcpy(cs + 8, &st89, 2);
+    const float f_sp = t.f[kSp], f_ch = t.f[kCh], f_in = b_in ? t.f[kIn + 1] : t.f[kIn], f_cl = cb_y ? t.f[kCl + 1] : t.f[kCl], f_cu = cb_u ? t.f[kCu + 1] : t.f[kCu];
+    const float f_cv = cb_u ? (cb_v ? t.f[kCv + 3] : t.f[kCv + 2]) : (cb_v ? t.f[kCv + 1] : t.f[kCv]);
+    if (adaptive) {  // every context once (U's flag and V's share one: its last state)
+      if (has_sp) cs[t.i_sp] = t.n[kSp];
+      cs[KVZ_CX_INTRA] = b_in ? t.n[kIn + 1] : t.n[kIn];
+      cs[KVZ_CX_CHROMA] = t.n[kCh];
+      cs[KVZ_CX_CBF_LUMA + 1] = cb_y ? t.n[kCl + 1] : t.n[kCl];
+      cs[KVZ_CX_CBF_CHROMA] = cb_u ? (cb_v ? t.n[kCv + 3] : t.n[kCv + 2]) : (cb_v ? t.n[kCv + 1] : t.n[kCv]);
     }
     // cu_bits
     double bits = 0;
@@ -2800,7 +2829,7 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false, bool
     KVZ_FOR_THREADS(tid) {
       if (tid == 0) {
         // search.c:895-940: cabac->update = 1 around the mock encode and the transform tree's flags (= cu_bits() * lambda + leaf_rd_cost())
-        *out_cost = cu_cost_batched(lv, x, y, depth, mode, s->preds, cabac_on() ? &s->child_bits[0] : nullptr);
+        *out_cost = cu_cost_batched(lv, x, y, depth, mode, cabac_on() ? &s->child_bits[0] : nullptr);  // on what rough_search's selection phase prepared
         const CtuCu *cu = &s->cu[lv][(yl >> 3) * 8 + (xl >> 3)];
         *out_cbf = cbf_is_set(cu->cbf, depth, 0) || cbf_is_set(cu->cbf, depth, 1) || cbf_is_set(cu->cbf, depth, 2);
       }
