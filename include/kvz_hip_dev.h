@@ -240,6 +240,20 @@ long kvz_hip_dev_entropy_code_inter_pictures(const kvz_hip_cu_info *cu, const kv
 int  kvz_hip_dev_inter_ctu_pass_lists(const uint8_t *src, const uint8_t *ref, const kvz_hip_cu_info *ref_cu, uint8_t *rec, kvz_hip_cu_info *cu, int16_t *coeff, int width,
                                       int height, int n_pictures, const kvz_hip_inter_params *params, const int32_t *tile_xy, int n_references,
                                       const kvz_hip_inter_pictures *pictures, const kvz_hip_scaling_lists *sets, int n_sets, const uint16_t *set_of_picture);
+/* B pictures of DIFFERENT SIZES in one launch of the inter CTU pass (kvz_hip_inter_group, kvz_hip_types.h): a host that encodes 1080p, 832x480 and 2160p streams side
+ * by side hands over one group per size, and the persistent workgroups of the one launch draw the CTUs of all of them -- instead of one partly empty launch per size,
+ * one after the other.  Pictures are numbered across the groups, group after group; the ticket list interleaves every picture's anti-diagonal x + 2y (its raster order
+ * with params->no_wpp), so a small picture's CTUs sit among the first diagonals of the large ones.
+ * params carries what the ONE kernel build and the ONE ticket list of the launch follow: mv_constraint, sao, deblock, fme_level, pu_depth_inter_max, no_wpp,
+ * fast_residual_cost, no_tmvp; qp / poc only for the groups whose `pictures` is NULL.  The launch takes the kernel build with the residual coder's contexts when any
+ * picture of any group prices with them.  With n_groups == 1 the outputs are byte for byte those of kvz_hip_dev_inter_ctu_pass_pictures on that group.
+ * The loop filters and the entropy coder stay per group: kvz_hip_dev_loop_filters_inter[_pictures] and kvz_hip_dev_entropy_code_inter[_pictures] take a group's
+ * outputs (rec, cu, coeff) as they are, with the group's width, height, n_pictures and table.
+ * Returns 0, -2 when a CTU hand-off timed out (no group has results then), and -1 with a message on stderr before anything is queued for: a struct_size (of a group or
+ * of params) that is not this library's, n_groups < 1, a group whose geometry the pass does not cover, a NULL buffer other than coeff, a `pictures` table
+ * kvz_hip_dev_inter_ctu_pass_pictures would refuse for the group, 65536 or more pictures in all, a tile member of params that is not zero (ref_width, ref_height,
+ * tile_x, tile_y: tiles are not part of joint launches), two groups with the same rec or the same cu buffer.  Scaling lists are not part of joint launches. */
+int  kvz_hip_dev_inter_ctu_pass_groups(const kvz_hip_inter_group *groups, int n_groups, const kvz_hip_inter_params *params);
 /* what the deblocking filter reads (kvz_hip_cu_dbk) of `count` CU records: type, depth, tr_depth, the luma coded block flag at tr_depth, motion */
 void kvz_hip_dev_cu_dbk_from_info(const kvz_hip_cu_info *cu, int count, kvz_hip_cu_dbk *out);
 

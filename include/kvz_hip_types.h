@@ -181,6 +181,22 @@ typedef struct kvz_hip_inter_pictures {
   const int32_t *poc;    /* [n_pictures]: >= 1; temporal AMVP candidates need poc > 1 */
 } kvz_hip_inter_pictures;
 
+/* One group of ONE joint launch of the inter CTU pass (kvz_hip_dev_inter_ctu_pass_groups, kvz_hip_dev.h): n_pictures pictures of one size with their buffers, in the
+ * layouts of kvz_hip_dev_inter_ctu_pass.  A launch takes several groups, so that pictures of different sizes share it.  width / height follow the pass's own rules:
+ * multiples of 8, at most 255 CTUs a side, fewer than 2^23 4x4 units.  All buffers are DEVICE pointers; coeff may be NULL, group by group.  pictures (HOST): a QP and
+ * a POC per picture of the group, or NULL: params->qp / params->poc for each.  struct_size: sizeof of the caller's headers (zero the struct, set it, then fill);
+ * an unknown size is refused with -1. */
+typedef struct kvz_hip_inter_group {
+  uint32_t struct_size;
+  int32_t  width, height, n_pictures;
+  const uint8_t *src, *ref;
+  const struct kvz_hip_cu_info *ref_cu;
+  uint8_t *rec;
+  struct kvz_hip_cu_info *cu;
+  int16_t *coeff;
+  const kvz_hip_inter_pictures *pictures;
+} kvz_hip_inter_group;
+
 /* Per-CTU result record of the batched pass: what kvazaar keeps in cu_array / lcu_t for the CTU. */
 #define KVZ_HIP_CTU_COEFFS 6144 /* 64*64 Y + 32*32 U + 32*32 V coefficients, each plane in lcu_t z-order (cu.h:385-421) */
 

@@ -1075,6 +1075,7 @@ __global__ void __launch_bounds__(64) dev_sao_chain_kernel(const SaoStats *stats
 #include "kvz_me.hpp"
 #include "kvz_inter_kernels.hpp"
 #include "kvz_inter_host.hpp"
+#include "kvz_inter_joint.hpp"
 
 namespace kvz {
 __global__ void dev_cu_dbk_kernel(const kvz_hip_cu_info *cu, int count, kvz_hip_cu_dbk *out)
@@ -1102,6 +1103,8 @@ struct InterScratch {
   void *lists = nullptr; size_t lists_bytes = 0;  // kvz_hip_dev_inter_ctu_pass_lists: the picture table with the factor rows behind it (kvz_inter_host.hpp
   std::vector<uint64_t> h_lists;                  // inter_picture_table_lists), grow-only, and what it holds: copied again only when a call's image differs
   uint8_t *entropy_table = nullptr; size_t entropy_table_bytes = 0;  // kvz_hip_dev_entropy_code_inter_pictures: context rows, POCs and rows of the pictures
+  void *joint = nullptr; size_t joint_bytes = 0;  // kvz_hip_dev_inter_ctu_pass_groups: the table of the launch (kvz_inter_joint.hpp inter_joint_table), grow-only,
+  std::vector<uint64_t> h_joint;                  // and what it holds: copied again only when a call's image differs
 };
 // One set per calling thread and device, like the stream the work is queued on (be() is thread_local): two threads, or two devices of one process, never share
 // ticket / done / slab buffers, and a buffer is only ever freed by the thread whose (synchronised) stream used it.
@@ -1118,7 +1121,7 @@ inline InterScratch &inter_scratch()
         InterScratch &x = all[d];
         if (!x.slabs && !x.ctx && !x.ticket) continue;
         (void)hipSetDevice(d);
-        (void)hipFree(x.slabs); (void)hipFree(x.ctx); (void)hipFree(x.done); (void)hipFree(x.items); (void)hipFree(x.ticket); (void)hipFree(x.model); (void)hipFree(x.lists); (void)hipFree(x.entropy_table);
+        (void)hipFree(x.slabs); (void)hipFree(x.ctx); (void)hipFree(x.done); (void)hipFree(x.items); (void)hipFree(x.ticket); (void)hipFree(x.model); (void)hipFree(x.lists); (void)hipFree(x.entropy_table); (void)hipFree(x.joint);
         x = InterScratch();
       }
     });
@@ -1677,6 +1680,92 @@ int kvz_hip_dev_inter_ctu_pass_lists(const uint8_t *src, const uint8_t *ref, con
     for (int i = 0; i < kvz::IP_COUNT; i++) fprintf(stderr, "ictu-profile %-18s %10.3f ms (sum over workgroups) %5.1f %%\n", names[i], hp[i] / 1e5, 100.0 * hp[i] / (double)hp[kvz::IP_TOTAL]);
   }
 #endif
+  return flags[1] ? -2 : 0;
+}
+
+// Pictures of different sizes in one launch (kvz_inter_joint.hpp): the checks, the ticket list and the table are that header's; the scratch, the choice of the build
+// and the resident workgroups are those of kvz_hip_dev_inter_ctu_pass_lists above
+int kvz_hip_dev_inter_ctu_pass_groups(const kvz_hip_inter_group *groups, int n_groups, const kvz_hip_inter_params *p)
+{
+  if (!kvz::inter_joint_known(groups, n_groups, p, "kvz_hip_dev_inter_ctu_pass_groups")) return -1;
+  hipStream_t st = be().stream;
+  kvz::InterScratch &sc = kvz::inter_scratch();
+  int dev_id = 0, n_cu = 256;
+  KVZ_HIP_CHECK(hipGetDevice(&dev_id));
+  KVZ_HIP_CHECK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev_id));
+  const char *env = getenv("KVZ_HIP_INTER_WG_PER_CU");
+  long total = 0;
+  for (int i = 0; i < n_groups; i++) total += (long)((groups[i].width + 63) / 64) * ((groups[i].height + 63) / 64) * groups[i].n_pictures;
+  if (total > sc.n_ctus) {  // (before the table: the table holds the context scratch's address)
+    if (sc.ctx) { KVZ_HIP_CHECK(hipFree(sc.ctx)); KVZ_HIP_CHECK(hipFree(sc.done)); KVZ_HIP_CHECK(hipFree(sc.items)); }
+    KVZ_HIP_CHECK(hipMalloc((void **)&sc.ctx, (size_t)total * sizeof(kvz::ICtx)));
+    KVZ_HIP_CHECK(hipMalloc((void **)&sc.done, (size_t)total * sizeof(unsigned)));
+    KVZ_HIP_CHECK(hipMalloc((void **)&sc.items, (size_t)total * sizeof(uint32_t)));
+    sc.n_ctus = total;
+  }
+  float fbits[128];
+  for (int i = 0; i < 128; i++) fbits[i] = (float)kvz::kEntropyBits[i] / 32768.0f;
+  const kvz::InterJointTable table = kvz::inter_joint_table(groups, n_groups, p, sc.ctx, [&](kvz::InterModel *row, int qp) {
+    // (no picture size: a row serves every group that has a picture at its QP, and the JOINT builds take ref_w / ref_h from the group record)
+    kvz::inter_model_init(row, qp, p->poc, kvz_hip_default_coeff_weights(qp), fbits, p->mv_constraint, p->sao, p->deblock, p->fme_level, p->pu_depth_inter_max, p->no_wpp, p->fast_residual_cost,
+                          0, 0, 0, 0, 0, 0, p->no_tmvp, 0);
+  });
+  const bool cabac_build = table.any_cabac;
+  const void *kernel = cabac_build ? (const void *)kvz::inter_ctu_ticket_kernel_joint_cabac : (const void *)kvz::inter_ctu_ticket_kernel_joint_fast;
+  int fit = 0;
+  KVZ_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&fit, kernel, KVZ_ICTU_THREADS, 0));
+  if (fit <= 0) fit = 8;
+  int per_cu = fit / kvz::inter_share();
+  if (env && atoi(env) > 0) per_cu = atoi(env) < fit ? atoi(env) : fit;
+  if (per_cu < 1) per_cu = 1;
+  int n_wg = n_cu * per_cu;
+  if (getenv("KVZ_HIP_INTER_VERBOSE")) fprintf(stderr, "kvz_hip inter pass: joint %s build, %d groups, %d workgroups per CU x %d CUs\n", cabac_build ? "cabac" : "fast", n_groups, per_cu, n_cu);
+  if ((long)n_wg > total) n_wg = (int)total;
+  if (n_wg > sc.n_slabs) {
+    if (sc.slabs) KVZ_HIP_CHECK(hipFree(sc.slabs));
+    KVZ_HIP_CHECK(hipMalloc((void **)&sc.slabs, (size_t)n_wg * sizeof(kvz::InterSlab)));
+    sc.n_slabs = n_wg;
+  }
+  if (!sc.ticket) KVZ_HIP_CHECK(hipMalloc((void **)&sc.ticket, 2 * sizeof(unsigned)));
+  bool fresh = false;
+  if (table.bytes() > sc.joint_bytes) {
+    if (sc.joint) KVZ_HIP_CHECK(hipFree(sc.joint));  // (the calling thread's stream is idle: every call ends synchronised)
+    sc.joint = nullptr; sc.joint_bytes = 0;
+    KVZ_HIP_CHECK(hipMalloc(&sc.joint, table.bytes() + table.bytes() / 8));
+    sc.joint_bytes = table.bytes() + table.bytes() / 8;
+    fresh = true;
+  }
+  if (fresh || table.image != sc.h_joint) {
+    KVZ_HIP_CHECK(hipMemcpyAsync(sc.joint, table.image.data(), table.bytes(), hipMemcpyHostToDevice, st));
+    KVZ_HIP_CHECK(hipStreamSynchronize(st));
+    sc.h_joint = table.image;
+  }
+  std::vector<uint32_t> items;
+  if (p->no_wpp) kvz::inter_joint_ticket_lists(table.geometry.data(), n_groups, nullptr, &items);
+  else kvz::inter_joint_ticket_lists(table.geometry.data(), n_groups, &items, nullptr);
+  KVZ_HIP_CHECK(hipMemcpyAsync(sc.items, items.data(), (size_t)total * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  KVZ_HIP_CHECK(hipMemsetAsync(sc.done, 0, (size_t)total * sizeof(unsigned), st));
+  KVZ_HIP_CHECK(hipMemsetAsync(sc.ticket, 0, 2 * sizeof(unsigned), st));
+  KVZ_HIP_CHECK(hipStreamSynchronize(st));  // `items` is a heap object of this call
+  kvz::InterFrames F;
+  memset(&F, 0, sizeof F);  // no geometry and no picture buffers: begin_ctu takes them from the drawn picture's group record
+  F.ctx_out = sc.ctx; F.slabs = sc.slabs;
+  F.pictures = (const kvz::InterPicture *)sc.joint;
+  const kvz::InterModel *d_model = table.model_of_picture(sc.joint, 0);
+  kvz::InterSched sched;
+  sched.items = sc.items; sched.ticket = sc.ticket; sched.done = sc.done; sched.error = sc.ticket + 1; sched.total = (unsigned)total; sched.no_wpp = p->no_wpp;
+  sched.wait_ticks = 3000000000ull;  // 30 s of the 100 MHz clock
+  kvz::DevTimer &tm = kvz::inter_timer();
+  if (!tm.e0) { KVZ_HIP_CHECK(hipEventCreate(&tm.e0)); KVZ_HIP_CHECK(hipEventCreate(&tm.e1)); }
+  KVZ_HIP_CHECK(hipEventRecord(tm.e0, st));
+  if (cabac_build) hipLaunchKernelGGL(kvz::inter_ctu_ticket_kernel_joint_cabac, dim3((unsigned)n_wg), dim3(KVZ_ICTU_THREADS), 0, st, F, d_model, kvz::device_tables(), sched);
+  else hipLaunchKernelGGL(kvz::inter_ctu_ticket_kernel_joint_fast, dim3((unsigned)n_wg), dim3(KVZ_ICTU_THREADS), 0, st, F, d_model, kvz::device_tables(), sched);
+  KVZ_HIP_CHECK(hipGetLastError());
+  KVZ_HIP_CHECK(hipEventRecord(tm.e1, st));
+  unsigned flags[2] = { 0, 0 };
+  KVZ_HIP_CHECK(hipMemcpyAsync(flags, sc.ticket, sizeof flags, hipMemcpyDeviceToHost, st));
+  KVZ_HIP_CHECK(hipStreamSynchronize(st));
+  KVZ_HIP_CHECK(hipEventElapsedTime(&kvz::inter_kernel_ms(), tm.e0, tm.e1));
   return flags[1] ? -2 : 0;
 }
 

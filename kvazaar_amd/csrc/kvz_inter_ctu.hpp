@@ -50,6 +50,19 @@ namespace kvz {
 #define KVZ_ICTU_LISTS_STATE KVZ_ICTU_LISTS
 #endif
 
+// The kernel's builds for joint launches (kvz_hip_dev_inter_ctu_pass_groups; kvz_inter_tu.hip -DKVZ_ICTU_JOINT=1): the pictures of a launch come in groups of different
+// sizes, and begin_ctu makes the geometry and the buffers the program works on those of the drawn picture's group.  A build constant on the device, so that the other
+// builds hold none of it; the host simulation of joint launches (tests/hostsim/hostsim_inter_joint.cpp) makes it a variable, as hostsim_inter_lists.cpp does with
+// KVZ_ICTU_LISTS.
+#ifndef KVZ_ICTU_JOINT
+#define KVZ_ICTU_JOINT 0
+#endif
+#ifdef KVZ_HOSTSIM
+#define KVZ_ICTU_JOINT_STATE 1
+#else
+#define KVZ_ICTU_JOINT_STATE KVZ_ICTU_JOINT
+#endif
+
 #ifndef KVZ_ICTU_THREADS
 #define KVZ_ICTU_THREADS 64  // lanes per CTU.  Measured on the MI355X with 256 sequences in flight (416x240): 64 lanes 20.9 k CTUs/s, 128: 18.8 k, 256: 11.9 k
                              // -- the program is a chain of short phases, and with one wavefront per CTU a barrier costs nothing and more CTUs share a CU
@@ -199,6 +212,28 @@ struct InterPictureLists {
   uint32_t lists_y_at, lists_c_at;  // bytes from the first record
 };
 
+// The records of a joint launch (the JOINT builds read these in InterPicture's place; kvz_inter_joint.hpp lays them out): pictures are numbered across the groups, and
+// InterFrames::pictures points at ONE buffer of [pictures] InterJointPicture records, then [groups] InterJointGroup records, then one InterModel row per distinct QP
+// of the launch.  Everything is addressed in bytes from the first record.  The InterFrames argument of a joint launch carries no geometry and no picture buffers
+// of its own: begin_ctu fills the workgroup's copy from the group record of the picture it drew.
+struct InterJointPicture {
+  uint32_t group_at;  // bytes from the first record to the picture's InterJointGroup
+  uint32_t index;     // the picture's index inside its group
+  uint32_t model_at;  // bytes from the first record to the picture's InterModel row
+  int32_t poc;
+};
+struct InterJointGroup {
+  int W, H, wc, hc;
+  long frame_px, cells;  // bytes of a picture, CU records of a picture
+  const u8 *src, *ref;
+  const kvz_hip_cu_info *ref_cu;
+  u8 *rec;
+  kvz_hip_cu_info *cu;
+  i16 *coeff;      // or NULL
+  ICtx *ctx_out;   // the launch's context scratch from the group's first CTU on: [pictures of the group][CTUs]
+  long ctu_base;   // the group's first index into the launch-wide `done` flags (InterSched): CTUs of all groups before it
+};
+
 struct InterSlab {  // HBM scratch of one resident workgroup: the quantised levels of the candidates of depth 1 and 2 (Y | U | V, raster inside each plane's block), written
                     // when the CU is quantised and copied to the output block if it wins; `out` stands in for the output block when the caller wants no coefficients
   i16 cand1[32 * 32 + 2 * 16 * 16];
@@ -220,7 +255,7 @@ struct InterFrames {
   const int *tile_xy;    // NULL, or [n][2]: every picture's own origin in its reference frame (tiles of one size from different places of the grid in one launch)
   int ref_count;         // 0, or the number of reference frames: picture p predicts from frame p % ref_count (several tiles of one frame in the launch)
   const InterPicture *pictures;  // NULL (the kernel's model argument for every picture), or [n]: every picture's own model row and POC (a launch with scaling
-                                 // lists always has them, as InterPictureLists records)
+                                 // lists always has them, as InterPictureLists records; a joint launch the table of InterJointPicture / InterJointGroup records)
   unsigned long long *prof;  // [IP_COUNT] or NULL (KVZ_ICTU_PROFILE)
 };
 
@@ -591,6 +626,13 @@ struct InterCtu {
   // the model of picture frame_ of a launch whose pictures have their own (F.pictures)
   IC_DEV const KVZ_GLB InterModel *picture_model_row(int frame_, int *poc)
   {
+#if KVZ_ICTU_JOINT_STATE
+    if (KVZ_ICTU_JOINT) {  // a joint launch: frame_ numbers the pictures across the groups
+      const KVZ_GLB InterJointPicture *rec = (const KVZ_GLB InterJointPicture *)F.pictures + frame_;
+      *poc = rec->poc;
+      return (const KVZ_GLB InterModel *)((const KVZ_GLB uint8_t *)F.pictures + rec->model_at);
+    }
+#endif
 #if KVZ_ICTU_LISTS_STATE
     if (KVZ_ICTU_LISTS) {  // a launch with lists: the wider record, and with it the picture's two factor rows (a picture without a set has the flat list's)
       const KVZ_GLB InterPictureLists *rec = (const KVZ_GLB InterPictureLists *)F.pictures + frame_;
@@ -607,11 +649,28 @@ struct InterCtu {
   IC_DEV void begin_ctu(int frame_, int cx_, int cy_)
   {
     IC_FOR(tid) { if (tid == 0) { frame = frame_; cx = cx_; cy = cy_;
+      const int picture_ = frame_;  // what the model row and the POC hang off: the launch's number of the picture
+#if KVZ_ICTU_JOINT_STATE
+      if (KVZ_ICTU_JOINT) {
+        // a persistent workgroup of a joint launch moves between pictures of different SIZES: the geometry and the buffers of the workgroup's InterFrames become the
+        // drawn picture's group's, and frame_ the picture's index inside that group, before any lane reads them -- everything below and everything the program reads
+        // through F is then what a launch of that group alone would hold.  The context scratch is the group's slice of the launch's (ctx_out of the record).
+        const KVZ_GLB InterJointPicture *jp = (const KVZ_GLB InterJointPicture *)F.pictures + picture_;
+        const KVZ_GLB InterJointGroup *jg = (const KVZ_GLB InterJointGroup *)((const KVZ_GLB uint8_t *)F.pictures + jp->group_at);
+        frame_ = (int)jp->index;
+        F.W = jg->W; F.H = jg->H; F.wc = jg->wc; F.hc = jg->hc; F.frame_px = jg->frame_px; F.cells = jg->cells;
+        F.src = jg->src; F.ref = jg->ref; F.ref_cu = jg->ref_cu; F.rec = jg->rec; F.cu = jg->cu; F.coeff = jg->coeff; F.ctx_out = jg->ctx_out;
+        // THE TRAP: load_constants took ref_w / ref_h from an InterModel row, and the rows of a joint launch are shared per QP ACROSS groups -- a row knows no
+        // picture size.  The reference frame of a picture of a joint launch is the picture's own size (no tiles): from the group record, never from the row
+        K->ref_w = jg->W; K->ref_h = jg->H; K->tile_x = 0; K->tile_y = 0;
+        frame = frame_;
+      }
+#endif
       if (F.pictures) {
         // a persistent workgroup moves between pictures: what load_constants took from the launch's one model and depends on the picture's QP or POC is the drawn
         // picture's from here on, and so is the model the coders' initial context states are read from (run: g_ic.model->ctx_init)
         int poc_;
-        const KVZ_GLB InterModel *pm = picture_model_row(frame_, &poc_);
+        const KVZ_GLB InterModel *pm = picture_model_row(picture_, &poc_);
         g_ic.model = (const InterModel *)pm;
         K->lambda = pm->lambda; K->lambda_sqrt = pm->lambda_sqrt; K->coeff_weights = pm->coeff_weights; K->qp = pm->qp; K->poc = poc_; K->coeff_cabac = pm->coeff_cabac;
         for (int i = 0; i < 8; i++) {

@@ -21,15 +21,27 @@ struct InterSched {
 
 // two builds of the kernel (kvz_inter_ctu.hpp KVZ_ICTU_CABAC): `_fast` for pictures whose coefficients are priced by kvz_fast_coeff_cost (small context sets: 20 KB of LDS,
 // eight workgroups per CU), `_cabac` for those priced with the residual coder's contexts; and the same two for launches with scaling lists
-// (-DKVZ_ICTU_LISTS=1, kvz_inter_ctu.hpp: kvz_hip_dev_inter_ctu_pass_lists), `_lists_fast` / `_lists_cabac`
+// (-DKVZ_ICTU_LISTS=1, kvz_inter_ctu.hpp: kvz_hip_dev_inter_ctu_pass_lists), `_lists_fast` / `_lists_cabac`; and the same two for joint launches of pictures of
+// different sizes (-DKVZ_ICTU_JOINT=1: kvz_hip_dev_inter_ctu_pass_groups), `_joint_fast` / `_joint_cabac`.  In a joint launch the item's picture numbers the pictures
+// across the groups; F holds no geometry, F.pictures the launch's table (kvz_inter_ctu.hpp InterJointPicture / InterJointGroup), and sched.done is indexed by the
+// group's first CTU + the picture's index in the group x the group's CTUs + the CTU
 #define KVZ_ICTU_KERNEL(name) __global__ void __launch_bounds__(KVZ_ICTU_THREADS) __attribute__((amdgpu_waves_per_eu(KVZ_ICTU_WAVES_PER_EU, KVZ_ICTU_WAVES_PER_EU))) name(const InterFrames F, const InterModel *model, const Tables *tb, const InterSched sched)
 #ifndef KVZ_INTER_KERNEL_BODY
 KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_fast);
 KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_cabac);
 KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_lists_fast);
 KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_lists_cabac);
+KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_joint_fast);
+KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_joint_cabac);
 #else
-#if KVZ_ICTU_LISTS && KVZ_ICTU_CABAC
+#if KVZ_ICTU_JOINT && KVZ_ICTU_LISTS
+#error "scaling lists are not part of joint launches"
+#endif
+#if KVZ_ICTU_JOINT && KVZ_ICTU_CABAC
+KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_joint_cabac)
+#elif KVZ_ICTU_JOINT
+KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_joint_fast)
+#elif KVZ_ICTU_LISTS && KVZ_ICTU_CABAC
 KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_lists_cabac)
 #elif KVZ_ICTU_LISTS
 KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_lists_fast)
@@ -40,7 +52,11 @@ KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_fast)
 #endif
 {
   __shared__ int s_ticket;
+#if KVZ_ICTU_JOINT
+  __shared__ unsigned s_done_at;  // the drawn CTU's own `done` flag: lane 0 finds it in the records once per CTU, before the wait
+#else
   const int ctus = F.wc * F.hc;
+#endif
   InterCtu::begin_launch(F, model, tb, F.slabs + blockIdx.x);  // the program's state and constants: workgroup-scope variables in LDS (kvz_inter_ctu.hpp)
   for (;;) {
     __syncthreads();
@@ -52,7 +68,16 @@ KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_fast)
     const int frame = item >> 16, y = (item >> 8) & 0xff, x = item & 0xff;
     __syncthreads();
     if (threadIdx.x == 0) {
+#if KVZ_ICTU_JOINT
+      // the picture's own flags under the picture's own width: the group record, before the wait (wavefront-uniform; the program's begin_ctu reads it again for the rest)
+      const InterJointPicture *jp = (const InterJointPicture *)F.pictures + frame;
+      const InterJointGroup *jg = (const InterJointGroup *)((const uint8_t *)F.pictures + jp->group_at);
+      const unsigned wc = (unsigned)jg->wc, first = (unsigned)jg->ctu_base + jp->index * (wc * (unsigned)jg->hc);
+      unsigned *done = sched.done + first;
+      s_done_at = first + y * wc + x;
+#else
       unsigned *done = sched.done + (long)frame * ctus;
+#endif
       auto wait = [&](unsigned *flag) -> bool {
         unsigned long long t0 = 0;
         for (unsigned spins = 0;; ++spins) {
@@ -68,9 +93,15 @@ KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_fast)
         }
       };
       bool ok = __hip_atomic_load(sched.error, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0;
+#if KVZ_ICTU_JOINT
+      if (ok && x > 0) ok = wait(&done[y * wc + x - 1]);
+      if (ok && y > 0) ok = wait(&done[(y - 1) * wc + ((unsigned)x + 1 < wc ? x + 1 : x)]);
+      if (ok && sched.no_wpp && x == 0 && y > 0) ok = wait(&done[(y - 1) * wc + wc - 1]);
+#else
       if (ok && x > 0) ok = wait(&done[y * F.wc + x - 1]);
       if (ok && y > 0) ok = wait(&done[(y - 1) * F.wc + (x + 1 < F.wc ? x + 1 : x)]);
       if (ok && sched.no_wpp && x == 0 && y > 0) ok = wait(&done[(y - 1) * F.wc + F.wc - 1]);
+#endif
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
       s_ticket = ok ? 1 : 0;
     }
@@ -84,7 +115,11 @@ KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_fast)
     if (threadIdx.x == 0) {
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#if KVZ_ICTU_JOINT
+      __hip_atomic_store(&sched.done[s_done_at], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
       __hip_atomic_store(&sched.done[(long)frame * ctus + y * F.wc + x], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#endif
     }
   }
 }

@@ -291,6 +291,48 @@ class InterPictures:
             self._entropy_ptr = self._entropy_out = None
 
 
+class InterGroupStruct(C.Structure):  # kvz_hip_inter_group
+    _fields_ = [("struct_size", C.c_uint32), ("width", C.c_int32), ("height", C.c_int32), ("n_pictures", C.c_int32)] + [(n, C.c_void_p) for n in ("src", "ref", "ref_cu", "rec", "cu", "coeff", "pictures")]
+
+
+class InterGroup:
+    """InterPictures objects of different sizes whose CTU passes run as ONE launch (kvz_hip_dev_inter_ctu_pass_groups): the persistent workgroups draw the CTUs of all
+    members, instead of one partly empty launch per size.  The members stay what they are: after run() each member's rec / cu / coeff hold what member.run(...)
+    would have made them, and its loop_filters, entropy_code, sse, advance and download work unchanged.  Scaling lists are not part of joint launches."""
+
+    def __init__(self, lib, members):
+        self.lib, self.members = lib, list(members)
+        if not self.members:
+            raise ValueError("an InterGroup needs at least one InterPictures member")
+        lib.kvz_hip_dev_inter_ctu_pass_groups.restype = C.c_int
+        lib.kvz_hip_dev_inter_ctu_pass_groups.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+
+    def structs(self, pictures=None):
+        """the kvz_hip_inter_group array of the members as they stand now (their buffers swap on advance() / use_source_set())"""
+        pictures = [None] * len(self.members) if pictures is None else list(pictures)
+        if len(pictures) != len(self.members):
+            raise ValueError(f"{len(pictures)} picture tables for {len(self.members)} members")
+        arr = (InterGroupStruct * len(self.members))()
+        for g, m, t in zip(arr, self.members, pictures):
+            g.struct_size, g.width, g.height, g.n_pictures = C.sizeof(InterGroupStruct), m.w, m.h, m.n
+            g.src, g.ref, g.ref_cu, g.rec, g.cu, g.coeff = m.d_src, m.d_ref, m.d_ref_cu, m.d_rec, m.d_cu, m.d_coeff
+            g.pictures = t.ptr if t is not None else None
+        return arr
+
+    def run(self, params, pictures=None):
+        """the CTU pass of every member's pictures in one launch.  pictures: one InterPictureParams, or None (params.qp / params.poc), per member.  Returns the
+        pass's code: 0, -1 for a refused launch (see stderr; nothing was queued), -2 for a hand-off time-out"""
+        for i, m in enumerate(self.members):
+            if m._n_list_sets:
+                raise ValueError(f"member {i} has scaling lists set: they are not part of joint launches (clear_scaling_lists(), or run the member on its own)")
+        arr = self.structs(pictures)  # (pictures' arrays live as long as the caller's objects; arr as long as this call)
+        return int(self.lib.kvz_hip_dev_inter_ctu_pass_groups(C.addressof(arr), len(self.members), C.addressof(params)))
+
+    def close(self):
+        """forgets the members; they stay open"""
+        self.members = []
+
+
 class TiledInterSequences:
     """BASELINE config 4 sharded by tile: picture k of `n` independent sequences of a width x height frame cut into kvazaar's uniform --tiles grid.  This rank's
     tiles are resident as pictures of their own (source, reconstruction, CU records: the tile is an independent sub-picture for prediction, neighbours, contexts and loop

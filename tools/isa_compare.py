@@ -59,20 +59,24 @@ def kernels(obj):
 def main():
     from kvazaar_amd.build import UNITS
     a_dir, b_dir = sys.argv[1:3]
-    bad = 0
+    bad = new = 0
     for unit, _, _ in UNITS:
-        a, b = kernels(os.path.join(a_dir, unit + ".o")), kernels(os.path.join(b_dir, unit + ".o"))
+        new_unit = not os.path.exists(os.path.join(a_dir, unit + ".o"))  # a translation unit the change adds: its kernels are listed, the parent has nothing to hold them against
+        a, b = ({} if new_unit else kernels(os.path.join(a_dir, unit + ".o"))), kernels(os.path.join(b_dir, unit + ".o"))
         for name in sorted(set(a) | set(b)):
-            if name not in a or name not in b:
+            if new_unit:
+                verdict = "NEW UNIT"
+            elif name not in a or name not in b:
                 verdict = "ONLY IN THE " + ("PARENT" if name in a else "CHANGE")
             else:
                 same = [a[name][1] == b[name][1] and a[name][0] == b[name][0], a[name][2] == b[name][2], a[name][3] == b[name][3]]
                 verdict = "identical" if all(same) else "DIFFERS in " + ", ".join(w for w, s in zip(("instructions", "descriptor", "resources"), same) if not s)
             n, digest, _, r = (b if name in b else a)[name]
-            bad += verdict != "identical"
+            bad += verdict not in ("identical", "NEW UNIT")
+            new += verdict == "NEW UNIT"
             print(f"{unit} {name}: {verdict} -- {n} instructions sha256 {digest}, VGPRs {r['.vgpr_count']} AGPRs {r.get('.agpr_count', 0)} SGPRs {r['.sgpr_count']} scratch {r['.private_segment_fixed_size']} B "
                   f"LDS {r['.group_segment_fixed_size']} B")
-    print(f"{'ALL KERNELS IDENTICAL' if not bad else str(bad) + ' KERNELS DIFFER'} ({len(UNITS)} objects)")
+    print(f"{('ALL KERNELS OF THE PARENT IDENTICAL' if new else 'ALL KERNELS IDENTICAL') if not bad else str(bad) + ' KERNELS DIFFER'} ({len(UNITS)} objects{', ' + str(new) + ' kernels in new units' if new else ''})")
     return 1 if bad else 0
 
 
