@@ -158,7 +158,7 @@ typedef struct kvz_hip_cu_info {
  * config 4's preset, whose QP 22 runs its pictures at 21-25), the residual coder in counting mode on the search contexts from there on.  Returns -1 on a bad argument, -2 when a CTU
  * hand-off timed out. */
 typedef struct kvz_hip_inter_params {
-  uint32_t struct_size;        /* sizeof(kvz_hip_inter_params) of the caller's headers: set it after zeroing the struct; an unknown size is refused with -1 */
+  uint32_t struct_size;        /* sizeof(kvz_hip_inter_params) of the caller's headers: set it after zeroing the struct; an unknown size is refused with -1 (known: this header's, and the struct before its me_* members) */
   int32_t qp;                  /* the picture's QP (state->frame->QP; kvz_oracle_lowdelay_qp states how kvazaar derives it from --qp and the GOP) */
   int32_t poc;                 /* picture order count inside the intra period (> 0); temporal AMVP candidates need poc > 1 (inter.c:1290) */
   int32_t mv_constraint;       /* cfg.owf && cfg.wpp */
@@ -177,13 +177,22 @@ typedef struct kvz_hip_inter_params {
    * picture and in the reference frame (16320x8192 is covered, 16320x8256 is not): the pass addresses CU records with 24-bit multiplies. */
   int32_t ref_width, ref_height, tile_x, tile_y;
   int32_t no_tmvp;             /* !cfg.tmvp_enable: no temporal merge / AMVP candidates (inter.c:1295-1302, 1471-1476) -- kvazaar switches TMVP off whenever tiles are used (cfg.c:920-975) */
+  /* The integer motion search (kvazaar --me, --me-steps, --me-early-termination; search_inter.c:1341-1383).  Zero in all three is the search every preset runs by
+   * default.  They hold for the whole launch, like fme_level, in kvz_hip_dev_inter_ctu_pass, _tiles and _pictures.  Refused with -1 and a message before anything is
+   * queued: an algorithm outside 0 .. 7, negative steps, a termination value outside 0 .. 2, and a non-zero member together with tiles (ref_width / ref_height /
+   * tile_xy), with scaling lists (n_sets > 0) or in kvz_hip_dev_inter_ctu_pass_groups.  kvz_hip_dev_pu_search stays hexbs.  A search loop that reaches its
+   * bound (a mistake: valid data cannot) ends the launch with -2. */
+  int32_t me_algorithm;          /* kvazaar's enum kvz_ime_algorithm: 0 hexbs (every preset), 1 tz, 2 full (= full32), 3 full8, 4 full16, 5 full32, 6 full64, 7 dia */
+  int32_t me_max_steps;          /* 0: no limit (kvazaar's default, -1); n >= 1: --me-steps n, as hexagon_search and diamond_search count them */
+  int32_t me_early_termination;  /* 0 sensitive (`ultrafast` .. `fast`), 1 on (`medium` and up), 2 off.  NOT the order of kvazaar's enum: zero must stay what every caller gets today */
 } kvz_hip_inter_params;
 int  kvz_hip_dev_inter_ctu_pass(const uint8_t *src, const uint8_t *ref, const kvz_hip_cu_info *ref_cu, uint8_t *rec, kvz_hip_cu_info *cu, int16_t *coeff, int width,
                                 int height, int n_pictures, const kvz_hip_inter_params *params);
 /* Threads and devices: the pass keeps its work memory (ticket list, done flags, contexts, the workgroups' level slabs) per CALLING THREAD and per DEVICE, like the
  * stream it is queued on -- two threads, or two devices of one process, never share it; calls of one thread are serialised on its stream.  `rec` is read back by the pass
  * itself (a finished CU is the intra reference of the next): it must not alias `ref`.  The struct grows at the end: zero it, set struct_size = sizeof(kvz_hip_inter_params), then fill it -- a caller
- * built against other headers than the library's is refused (-1) instead of handing the pass whatever lies behind a shorter struct. */
+ * built against other headers than the library's is refused (-1) instead of handing the pass whatever lies behind a shorter struct.  The one older version the library
+ * still takes is the struct that ends with no_tmvp (a binding compiled before the me_* members): its launch runs the default search. */
 /* ... with every picture's own tile origin: tile_xy (DEVICE pointer, n_pictures x {x, y}, multiples of 8 inside the reference frame; NULL: params->tile_x / tile_y for
  * all) -- the tiles of one size of MANY places of the grid in one launch (without WPP a tile offers one CTU at a time: the launch needs that many more chains).
  * n_references (0: one per picture): `ref` / `ref_cu` hold that many frames and picture p predicts from frame p % n_references -- several tiles of the same frame. */

@@ -1545,10 +1545,9 @@ int kvz_hip_dev_inter_ctu_pass_lists(const uint8_t *src, const uint8_t *ref, con
                                      const kvz_hip_inter_pictures *pictures, const kvz_hip_scaling_lists *sets, int n_sets, const uint16_t *set_of_picture)
 {
   if (n_pictures <= 0) return 0;
-  if (!p || p->struct_size != sizeof(kvz_hip_inter_params)) {
-    fprintf(stderr, "kvz_hip_dev_inter_ctu_pass: kvz_hip_inter_params.struct_size %u is not this library's %zu (zero the struct, set struct_size = sizeof, build against the library's headers)\n", p ? p->struct_size : 0u, sizeof(kvz_hip_inter_params));
-    return -1;
-  }
+  kvz_hip_inter_params full;
+  if (!kvz::inter_params_full(p, &full, "kvz_hip_dev_inter_ctu_pass")) return -1;
+  p = &full;  // (a caller from before the me_* members: they are zero)
   const int refused = kvz::inter_pass_geometry_refused(width, height, n_pictures, p->ref_width, p->ref_height, p->tile_x, p->tile_y);
   if (refused == 1) { fprintf(stderr, "kvz_hip_dev_inter_ctu_pass: bad geometry\n"); return -1; }
   if (pictures && !kvz::inter_pictures_known(pictures, n_pictures, "kvz_hip_dev_inter_ctu_pass_pictures")) return -1;
@@ -1559,7 +1558,8 @@ int kvz_hip_dev_inter_ctu_pass_lists(const uint8_t *src, const uint8_t *ref, con
     return -1;
   }
   if (!kvz::scaling_list_sets_known(sets, n_sets, set_of_picture, n_pictures, true /* the pass has no other schedule */, "kvz_hip_dev_inter_ctu_pass_lists")) return -1;
-  const bool lists = n_sets > 0;
+  if (!kvz::inter_me_known(p, (p->ref_width || p->ref_height || tile_xy) ? "tiles" : (n_sets > 0 ? "scaling lists" : nullptr), "kvz_hip_dev_inter_ctu_pass")) return -1;
+  const bool lists = n_sets > 0, me = kvz::inter_me_chosen(p);
   hipStream_t st = be().stream;
   const int wc = (width + 63) / 64, hc = (height + 63) / 64, ctus = wc * hc;
   const long total = (long)ctus * n_pictures;
@@ -1575,6 +1575,7 @@ int kvz_hip_dev_inter_ctu_pass_lists(const uint8_t *src, const uint8_t *ref, con
   auto model_at_qp = [&](kvz::InterModel *row, int qp) {
     kvz::inter_model_init(row, qp, p->poc, kvz_hip_default_coeff_weights(qp) /* 0 from QP 50 on, where kvz_fast_coeff_cost is never used (rdo.c:311-340) */, fbits, p->mv_constraint, p->sao, p->deblock, p->fme_level, p->pu_depth_inter_max, p->no_wpp, p->fast_residual_cost,
                           width, height, p->ref_width, p->ref_height, p->tile_x, p->tile_y, p->no_tmvp, lists ? 1 : 0);
+    kvz::inter_model_set_me(row, p);
   };
   kvz::InterPictureTable table;
   if (lists) {  // every picture has a record: its rows of the factor table travel with it
@@ -1583,7 +1584,8 @@ int kvz_hip_dev_inter_ctu_pass_lists(const uint8_t *src, const uint8_t *ref, con
     table = kvz::inter_picture_table_lists(pictures ? pictures->qp : qp_all.data(), pictures ? pictures->poc : poc_all.data(), n_pictures, model_at_qp, sets, n_sets, set_of_picture);
   } else if (pictures) table = kvz::inter_picture_table(pictures->qp, pictures->poc, n_pictures, model_at_qp);
   const bool cabac_build = (pictures || lists) ? table.any_cabac : kvz::inter_qp_prices_with_cabac(p->qp, p->fast_residual_cost);
-  const void *kernel = lists ? (cabac_build ? (const void *)kvz::inter_ctu_ticket_kernel_lists_cabac : (const void *)kvz::inter_ctu_ticket_kernel_lists_fast)
+  const void *kernel = me ? (cabac_build ? (const void *)kvz::inter_ctu_ticket_kernel_me_cabac : (const void *)kvz::inter_ctu_ticket_kernel_me_fast)
+                     : lists ? (cabac_build ? (const void *)kvz::inter_ctu_ticket_kernel_lists_cabac : (const void *)kvz::inter_ctu_ticket_kernel_lists_fast)
                              : (cabac_build ? (const void *)kvz::inter_ctu_ticket_kernel_cabac : (const void *)kvz::inter_ctu_ticket_kernel_fast);
   // resident workgroups (= wavefronts) per CU: what the kernel's registers and LDS allow -- a persistent grid, one workgroup per slot
   int fit = 0;
@@ -1594,7 +1596,7 @@ int kvz_hip_dev_inter_ctu_pass_lists(const uint8_t *src, const uint8_t *ref, con
   if (env && atoi(env) > 0) per_cu = atoi(env) < fit ? atoi(env) : fit;
   if (per_cu < 1) per_cu = 1;
   int n_wg = n_cu * per_cu;
-  if (getenv("KVZ_HIP_INTER_VERBOSE")) fprintf(stderr, "kvz_hip inter pass: %s%s build, %d workgroups per CU x %d CUs\n", lists ? "lists " : "", cabac_build ? "cabac" : "fast", per_cu, n_cu);
+  if (getenv("KVZ_HIP_INTER_VERBOSE")) fprintf(stderr, "kvz_hip inter pass: %s%s build, %d workgroups per CU x %d CUs\n", me ? "me " : lists ? "lists " : "", cabac_build ? "cabac" : "fast", per_cu, n_cu);
   if ((long)n_wg > total) n_wg = (int)total;
   if (n_wg > sc.n_slabs) {
     if (sc.slabs) KVZ_HIP_CHECK(hipFree(sc.slabs));
@@ -1662,7 +1664,9 @@ int kvz_hip_dev_inter_ctu_pass_lists(const uint8_t *src, const uint8_t *ref, con
   kvz::DevTimer &tm = kvz::inter_timer();
   if (!tm.e0) { KVZ_HIP_CHECK(hipEventCreate(&tm.e0)); KVZ_HIP_CHECK(hipEventCreate(&tm.e1)); }
   KVZ_HIP_CHECK(hipEventRecord(tm.e0, st));
-  if (lists && cabac_build) hipLaunchKernelGGL(kvz::inter_ctu_ticket_kernel_lists_cabac, dim3((unsigned)n_wg), dim3(KVZ_ICTU_THREADS), 0, st, F, d_model, kvz::device_tables(), sched);
+  if (me && cabac_build) hipLaunchKernelGGL(kvz::inter_ctu_ticket_kernel_me_cabac, dim3((unsigned)n_wg), dim3(KVZ_ICTU_THREADS), 0, st, F, d_model, kvz::device_tables(), sched);
+  else if (me) hipLaunchKernelGGL(kvz::inter_ctu_ticket_kernel_me_fast, dim3((unsigned)n_wg), dim3(KVZ_ICTU_THREADS), 0, st, F, d_model, kvz::device_tables(), sched);
+  else if (lists && cabac_build) hipLaunchKernelGGL(kvz::inter_ctu_ticket_kernel_lists_cabac, dim3((unsigned)n_wg), dim3(KVZ_ICTU_THREADS), 0, st, F, d_model, kvz::device_tables(), sched);
   else if (lists) hipLaunchKernelGGL(kvz::inter_ctu_ticket_kernel_lists_fast, dim3((unsigned)n_wg), dim3(KVZ_ICTU_THREADS), 0, st, F, d_model, kvz::device_tables(), sched);
   else if (cabac_build) hipLaunchKernelGGL(kvz::inter_ctu_ticket_kernel_cabac, dim3((unsigned)n_wg), dim3(KVZ_ICTU_THREADS), 0, st, F, d_model, kvz::device_tables(), sched);
   else hipLaunchKernelGGL(kvz::inter_ctu_ticket_kernel_fast, dim3((unsigned)n_wg), dim3(KVZ_ICTU_THREADS), 0, st, F, d_model, kvz::device_tables(), sched);
@@ -1688,6 +1692,9 @@ int kvz_hip_dev_inter_ctu_pass_lists(const uint8_t *src, const uint8_t *ref, con
 int kvz_hip_dev_inter_ctu_pass_groups(const kvz_hip_inter_group *groups, int n_groups, const kvz_hip_inter_params *p)
 {
   if (!kvz::inter_joint_known(groups, n_groups, p, "kvz_hip_dev_inter_ctu_pass_groups")) return -1;
+  kvz_hip_inter_params full;
+  kvz::inter_params_full(p, &full, "kvz_hip_dev_inter_ctu_pass_groups");  // (checked above)
+  p = &full;
   hipStream_t st = be().stream;
   kvz::InterScratch &sc = kvz::inter_scratch();
   int dev_id = 0, n_cu = 256;
@@ -2212,7 +2219,8 @@ long kvz_hip_dev_entropy_code_inter_pictures(const kvz_hip_cu_info *cu, const kv
                                              const kvz_hip_inter_pictures *pictures)
 {
   if (n_pictures <= 0) return 0;
-  if (params && params->struct_size != sizeof(kvz_hip_inter_params)) { fprintf(stderr, "kvz_hip_dev_entropy_code_inter: kvz_hip_inter_params.struct_size %u is not this library's %zu\n", params->struct_size, sizeof(kvz_hip_inter_params)); return -1; }
+  kvz_hip_inter_params full;  // (the coder reads members both known versions of the struct have)
+  if (params && !kvz::inter_params_full(params, &full, "kvz_hip_dev_entropy_code_inter")) return -1;
   if (!cu || !ref_cu || !coeff || !params || width <= 0 || height <= 0 || (width & 7) || (height & 7) || (!pictures && (params->qp < 0 || params->qp > 51 || params->poc < 1))) {
     fprintf(stderr, "kvz_hip_dev_entropy_code_inter: bad argument\n");
     return -1;

@@ -24,7 +24,8 @@
 // of many independent sequences.  tests/hostsim compiles this file for the host (a phase = a loop over tid).
 // Coefficients are priced as kvz_get_coeff_cost does (rdo.c:311-340): kvz_fast_coeff_cost while the picture QP lies below fast-residual-cost 28 (fused with the
 // quantisation), the residual coder in counting mode on the search contexts from there on (coeff_bits_cabac: kvz_residual.hpp's syntax walk into a price sink).
-// Restrictions of this version: square PUs, one reference picture.
+// Restrictions of this version: square PUs, one reference picture.  The integer motion search is hexbs with `sensitive` early termination unless the launch says
+// otherwise (KVZ_ICTU_ME below).
 #pragma once
 #include <stddef.h>
 
@@ -63,6 +64,22 @@ namespace kvz {
 #define KVZ_ICTU_JOINT_STATE KVZ_ICTU_JOINT
 #endif
 
+// The kernel's builds for launches that choose the integer motion search (kvz_hip_inter_params me_algorithm / me_max_steps / me_early_termination: kvazaar --me,
+// --me-steps, --me-early-termination; kvz_inter_tu.hip -DKVZ_ICTU_ME=1): me_integer (kvz_inter_ctu_pix.inc) runs early_terminate in any of its three settings and
+// then the hexagon search with a step limit, the diamond search, the TZ search or a full search, whose windows are swept a displacement per lane (sweep_window).  A
+// build constant on the device, so that the other builds hold none of it and search as they always did; the host simulation
+// (tests/hostsim/hostsim_inter_me.cpp) makes it a variable, as hostsim_inter_lists.cpp does with KVZ_ICTU_LISTS.
+// NOT COVERED: kvz_hip_dev_pu_search (kvz_me.hpp) stays hexbs, its params struct has no size member; the kvazaar-side binding (integration/) does not pass the
+// switches; tiles, scaling lists and joint launches are refused together with a non-zero field; bench.py measures the default search.
+#ifndef KVZ_ICTU_ME
+#define KVZ_ICTU_ME 0
+#endif
+#ifdef KVZ_HOSTSIM
+#define KVZ_ICTU_ME_STATE 1
+#else
+#define KVZ_ICTU_ME_STATE KVZ_ICTU_ME
+#endif
+
 #ifndef KVZ_ICTU_THREADS
 #define KVZ_ICTU_THREADS 64  // lanes per CTU.  Measured on the MI355X with 256 sequences in flight (416x240): 64 lanes 20.9 k CTUs/s, 128: 18.8 k, 256: 11.9 k
                              // -- the program is a chain of short phases, and with one wavefront per CTU a barrier costs nothing and more CTUs share a CU
@@ -86,6 +103,7 @@ static long g_ic_phases[32]; static int g_ic_cat = 31;
 // the 24-bit multiplies as the device executes them (v_mul_i32_i24 / v_mul_u32_u24): both operands cut to their low 24 bits (sign-extended / masked), the low 32 bits
 // of the product.  An operand that does not fit is counted: a call site whose "fits in 24 bits" comment is wrong shows here, not only on the device
 static unsigned long long g_mul24_violations;
+static unsigned long long g_me_events[16];  // what the chosen integer searches met (kvz_inter_ctu_pix.inc IC_ME_EVENT)
 static inline int sext24(int a) { return (int)(((unsigned)a & 0xffffffu) ^ 0x800000u) - 0x800000; }
 static inline int mul24(int a, int b)
 {
@@ -195,6 +213,7 @@ struct InterModel {  // per picture
   alignas(8) u8 ctx_init[IX_COUNT];  // an ICtx: the slice's initial states
   QuantScalars qf[2][4], qi[2][4];  // forward / inverse scalars, [luma, chroma][log2 size - 2]
   float fbits[128];                 // kvz_f_entropy_bits
+  int me_algorithm, me_max_steps, me_early_termination, me_pad_;  // kvz_hip_inter_params' members of the same names (the ME builds read them; at the end: nothing before them moves)
 };
 
 // Pictures with a QP and a POC of their own in one launch (kvz_hip_dev_inter_ctu_pass_pictures): the launch keeps one InterModel row per distinct QP and this record
@@ -295,6 +314,9 @@ struct InterConst {
 #if KVZ_ICTU_LISTS_STATE
   const KVZ_GLB u32 *lf_y, *lf_c;  // the picture's factor rows in HBM, luma and chroma QP (begin_ctu)
 #endif
+#if KVZ_ICTU_ME_STATE
+  int me_algorithm, me_max_steps, me_early_termination;  // the launch's integer motion search (include/kvz_hip_dev.h)
+#endif
 };
 
 // A 32x32 block is interpolated, compared and transformed in 16x16 TILES (its four quadrants; smaller blocks are one tile): the sample buffers below are sized for a tile.
@@ -384,6 +406,9 @@ struct InterState {
   const CuInfo *ref_cu_base;  // the reference frame's CU records
   int16_t *coef_out;  // the CTU's 6144 levels: F.coeff's slot of it, or the workgroup's scratch
   int acc_slot;
+#if KVZ_ICTU_ME_STATE
+  int me_overrun;  // a search loop that ends on data reached its bound (me_integer): the kernel raises the launch's error word
+#endif
 };
 
 IC_WGVAR InterLds g_il;
@@ -593,6 +618,10 @@ struct InterCtu {
         K->qp = model->qp; K->poc = model->poc; K->mv_constraint = model->mv_constraint; K->sao = model->sao; K->deblock = model->deblock; K->fme_level = model->fme_level;
         K->pu_depth_inter_max = model->pu_depth_inter_max; K->no_wpp = model->no_wpp; K->coeff_cabac = model->coeff_cabac;
         K->ref_w = model->ref_w; K->ref_h = model->ref_h; K->tile_x = model->tile_x; K->tile_y = model->tile_y; K->no_tmvp = model->no_tmvp;
+#if KVZ_ICTU_ME_STATE
+        K->me_algorithm = model->me_algorithm; K->me_max_steps = model->me_max_steps; K->me_early_termination = model->me_early_termination;
+        g_ic.me_overrun = 0;
+#endif
       }
       if (tid < 8) {
         const QuantScalars f = model->qf[tid >> 2][tid & 3], iv = model->qi[tid >> 2][tid & 3];

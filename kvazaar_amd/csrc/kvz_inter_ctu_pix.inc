@@ -445,6 +445,221 @@ IC_DEV int pat(unsigned long long packed, int i) { return (int)((packed >> (3 * 
 #define IC_PAT9(a, b, c, d, e, f, g, h, i) ((unsigned long long)((a) + 2) | (unsigned long long)((b) + 2) << 3 | (unsigned long long)((c) + 2) << 6 | (unsigned long long)((d) + 2) << 9 | \
                                             (unsigned long long)((e) + 2) << 12 | (unsigned long long)((f) + 2) << 15 | (unsigned long long)((g) + 2) << 18 | (unsigned long long)((h) + 2) << 21 | (unsigned long long)((i) + 2) << 24)
 
+#if KVZ_ICTU_ME_STATE
+// ---- the launch's choice of integer search (the ME builds, kvz_inter_ctu.hpp KVZ_ICTU_ME): what search_inter.c:1341-1383 runs behind select_starting_point ----
+#ifdef KVZ_HOSTSIM
+// what the searches met, for the script that chooses the fixture's clips (tests/golden/make_inter_me_golden.py): 0 TZ's second step 2 from zero, 1 a star refinement of
+// two or more rounds, 2 a TZ round at distance >= 16 that improved, 3 / 4 the full search's window around the best vector run / left out, 5 a merge-candidate window
+// with points an earlier window covered, 6 probes mv_allowed refused, 7 .. 10 a window that leaves the frame at its left / right / top / bottom, 11 / 12 a step limit
+// that ended a diamond / hexagon loop which would have gone on, 13 sweeps, 14 acceptances inside sweeps
+#define IC_ME_EVENT(slot) (++g_me_events[slot])
+#define IC_LANES(type, name) type name[KVZ_ICTU_THREADS]
+#define IC_LANE(name) name[tid]
+#else
+#define IC_ME_EVENT(slot)
+#define IC_LANES(type, name) type name
+#define IC_LANE(name) name
+#endif
+#define IC_ME_LOOP_BOUND (1 << 28)  /* a vector has at most 2^14 integer positions per axis and no centre comes twice (every move lowered the cost): no loop below takes more rounds */
+struct MeWin { int x0, y0, x1, y1; };  // a window of integer displacements, its corners included
+IC_DEV MeWin me_window(int mx, int my, int range) { return MeWin{ mx - range, my - range, mx + range, my + range }; }
+IC_DEV MeWin me_seen(int j) { const KVZ_LDS int *s = me_windows() + 4 * j; return MeWin{ s[0], s[1], s[2], s[3] }; }
+IC_DEV void me_see(int j, const MeWin &w) { KVZ_LDS int *s = me_windows() + 4 * j; IC_FOR(tid) { if (tid == 0) { s[0] = w.x0; s[1] = w.y0; s[2] = w.x1; s[3] = w.y1; } } }
+IC_DEV bool me_in_window(const MeWin &w, int x, int y) { return x >= w.x0 && x <= w.x1 && y >= w.y0 && y <= w.y1; }
+// probe k of L->px / L->py through check_mv_cost, counting refusals
+IC_DEV bool me_consider(MeBest &best, double lambda_sqrt, int k)
+{
+  if (L->pbits[k] < 0) IC_ME_EVENT(6);
+  return consider(best, lambda_sqrt, k);
+}
+// The full search's window `win` of integer displacements through check_mv_cost in raster order, A DISPLACEMENT PER LANE: the window's points are numbered row by
+// row, sixty-four consecutive ones go to the sixty-four lanes, and a lane sums its whole block -- the source row is one LDS address for all lanes, the reference is
+// read as unaligned dwords straight from the picture (v_sad_u8), byte by byte with clamped addresses where the lane's block leaves the reference frame; nothing is
+// reduced across lanes.  Points inside one of the first n_skip windows of me_windows() were probed before and are left out (search_inter.c:941-959; probing them again could not
+// be accepted).  The decision is check_mv_cost's, one probe after the other: a probe is accepted when its cost + 0.001 lies below the best so far, so the first lane
+// that qualifies is taken, the best moves there, and the lanes are asked again until none qualifies -- the raster-order result in as many steps as there were
+// improvements (the SAD-only test of check_mv_cost is implied: the bits only add to the cost).
+IC_DEV KVZ_LDS int *me_windows() { return (KVZ_LDS int *)L->g; }  // the windows probed so far, [6] x {x0, y0, x1, y1}: L->g is dead while the integer search runs (the SATD and the interpolation come after it)
+IC_FN void sweep_window(MeBest &best, double lambda_sqrt, const MeWin win, int n_skip)
+{
+  const PuSearch &pu = L->pu;
+  const gu8 *rp = refp(0);
+  const int w = pu.w, W = K->ref_w, H = K->ref_h, width = win.x1 - win.x0 + 1, points = width * (win.y1 - win.y0 + 1);
+  const int bx = K->tile_x + pu.x, by = K->tile_y + pu.y;
+  const PView o = orgv(0, pu.x - cx, pu.y - cy);
+  IC_ME_EVENT(13);
+  if (bx + win.x0 < 0) IC_ME_EVENT(7);
+  if (bx + win.x1 + w > W) IC_ME_EVENT(8);
+  if (by + win.y0 < 0) IC_ME_EVENT(9);
+  if (by + win.y1 + w > H) IC_ME_EVENT(10);
+  IC_LANES(int, lx); IC_LANES(int, ly);  // the lane's displacement: point chunk * 64 + lane of the window
+  IC_FOR(tid) {
+    int x = win.x0 + tid, y = win.y0;
+    for (int k = 0; k < 4; k++) if (x > win.x1) { x -= width; y++; }  // (a window is at least 17 wide: 63 is fewer than four rows)
+    IC_LANE(lx) = x; IC_LANE(ly) = y;
+  }
+  for (int p0 = 0; p0 < points; p0 += KVZ_ICTU_THREADS) {
+    IC_LANES(u32, lsad); IC_LANES(int, lbits);
+    IC_FOR(tid) {
+      const int x = IC_LANE(lx), y = IC_LANE(ly);
+      bool live = p0 + tid < points;
+      for (int j = 0; j < n_skip; j++) { const MeWin sw = me_seen(j); live = live && !me_in_window(sw, x, y); }
+      int bits = -1;
+      u32 sad = 0;
+      if (live) {
+        if (mv_allowed(x * 4, y * 4)) bits = mvd_bits(x * 4, y * 4); else IC_ME_EVENT(6);
+      }
+      if (bits >= 0) {
+        const int ox = bx + x, oy = by + y;
+        if (ox >= 0 && oy >= 0 && ox + w <= W && oy + w <= H) {  // the lane's block inside the reference frame
+          const int off = mul24(oy, W) + ox;
+          for (int yy = 0; yy < w; yy++) {
+            const int row = mul24(yy, W) + off;
+            for (int x4 = 0; x4 < w; x4 += 4) sad = sad4(lds_read32(o.p + yy * o.s + x4), glb_read32u(rp + (row + x4)), sad);
+          }
+        } else {
+          for (int yy = 0; yy < w; yy++) {
+            const int row = mul24(iclip(0, H - 1, oy + yy), W);
+            for (int xx = 0; xx < w; xx++) sad += (u32)iabs((int)o.p[yy * o.s + xx] - (int)rp[row + iclip(0, W - 1, ox + xx)]);
+          }
+        }
+      }
+      IC_LANE(lsad) = sad; IC_LANE(lbits) = bits;
+    }
+    for (int taken = 0; taken <= KVZ_ICTU_THREADS; taken++) {  // (every acceptance takes a later lane or ends the loop: never more rounds than lanes)
+      int first = -1;
+#ifdef KVZ_HOSTSIM
+      for (int l = KVZ_ICTU_THREADS - 1; l >= 0; l--) if (lbits[l] >= 0 && (double)lsad[l] + (double)lbits[l] * lambda_sqrt + 0.001 < best.cost) first = l;
+#else
+      const unsigned long long ask = __builtin_amdgcn_ballot_w64(lbits >= 0 && (double)lsad + (double)lbits * lambda_sqrt + 0.001 < best.cost);
+      if (ask) first = (int)__builtin_ctzll(ask);
+#endif
+      if (first < 0) break;
+      IC_ME_EVENT(14);
+#ifdef KVZ_HOSTSIM
+      const u32 s = lsad[first]; const int b = lbits[first], fx = lx[first], fy = ly[first];
+#else
+      const u32 s = (u32)__builtin_amdgcn_readlane((int)lsad, first); const int b = __builtin_amdgcn_readlane(lbits, first), fx = __builtin_amdgcn_readlane(lx, first), fy = __builtin_amdgcn_readlane(ly, first);
+#endif
+      best.mvx = fx * 4; best.mvy = fy * 4; best.bits = (double)b; best.cost = (double)s + (double)b * lambda_sqrt;
+    }
+    IC_FOR(tid) {  // on to the lane's point of the next chunk
+      int x = IC_LANE(lx) + KVZ_ICTU_THREADS, y = IC_LANE(ly);
+      for (int k = 0; k < 4; k++) if (x > win.x1) { x -= width; y++; }
+      IC_LANE(lx) = x; IC_LANE(ly) = y;
+    }
+  }
+}
+// search_mv_full (search_inter.c:892-965) on L->best: the window around zero, the one around the vector the search is entered with unless that is a merge candidate's, and one
+// around every merge candidate of a single list -- its vector cut with >> 2 here, not rounded as select_starting_point rounds it -- without the points of the zero
+// window and of the earlier candidates' windows.  One call (the windows of a search share one copy of the sweep).
+IC_FN_CALL void me_full(int range)
+{
+  const PuSearch &pu = L->pu;
+  const double lambda_sqrt = M->lambda_sqrt;
+  MeBest best{ L->best.mvx, L->best.mvy, L->best.cost, L->best.bits };
+  int n_seen = 0;
+  const int ex = best.mvx >> 2, ey = best.mvy >> 2;  // (extra_mv is the best vector the search was entered with)
+  for (int k = 0; k < 2 + pu.num_merge; k++) {  // 0: zero; 1: the best vector on entry; 2 ..: merge candidate k - 2
+    MeWin win = me_window(0, 0, range);
+    int skip = 0;
+    if (k == 1) {
+      bool in_merge = false;
+      for (int i = 0; i < pu.num_merge; i++) {
+        const MCand c = pu.merge[i];
+        const int cmx = c.dir == 1 ? c.mv[0][0] : c.mv[1][0], cmy = c.dir == 1 ? c.mv[0][1] : c.mv[1][1];
+        if (c.dir != 3 && ((cmx + 2) >> 2) == ex && ((cmy + 2) >> 2) == ey) in_merge = true;
+      }
+      if (in_merge) { IC_ME_EVENT(4); continue; }
+      IC_ME_EVENT(3);
+      win = me_window(ex, ey, range);
+    } else if (k >= 2) {
+      const MCand c = pu.merge[k - 2];
+      if (c.dir == 3) continue;
+      const int mx = (c.dir == 1 ? c.mv[0][0] : c.mv[1][0]) >> 2, my = (c.dir == 1 ? c.mv[0][1] : c.mv[1][1]) >> 2;
+      win = me_window(mx, my, range);
+      skip = n_seen;
+      me_see(n_seen, win);  // (its own window is not among the `skip` ones it is swept without)
+      n_seen++;
+      if (mx == 0 && my == 0) continue;
+#ifdef KVZ_HOSTSIM
+      for (int j = 0; j < skip; j++) { const MeWin sj = me_seen(j); if (win.x0 <= sj.x1 && win.x1 >= sj.x0 && win.y0 <= sj.y1 && win.y1 >= sj.y0) { IC_ME_EVENT(5); break; } }
+#endif
+    } else {
+      me_see(0, win);
+      n_seen = 1;
+    }
+    IC_SYNC();
+    sweep_window(best, lambda_sqrt, win, skip);
+  }
+  IC_FOR(tid) { if (tid == 0) { L->best.mvx = best.mvx; L->best.mvy = best.mvy; L->best.cost = best.cost; L->best.bits = best.bits; } }
+  IC_SYNC();
+}
+// one round of kvz_tz_pattern_search with the diamond pattern (search_inter.c:487-604, type 0) at distance d around (mx, my): true when a point was accepted
+IC_FN bool me_tz_round(MeBest &best, double lambda_sqrt, int mx, int my, int d)
+{
+  const int h = d >> 1, n = d == 1 ? 4 : 8;
+  i16 *px = L->px, *py = L->py;
+  px[0] = mx; py[0] = my + d; px[1] = mx + d; py[1] = my; px[2] = mx; py[2] = my - d; px[3] = mx - d; py[3] = my;
+  px[4] = mx + h; py[4] = my + h; px[5] = mx + h; py[5] = my - h; px[6] = mx - h; py[6] = my - h; px[7] = mx - h; py[7] = my + h;
+  probe(n);
+  bool any = false;
+  for (int j = 0; j < n; j++) if (me_consider(best, lambda_sqrt, j)) any = true;
+  if (any && d >= 16) IC_ME_EVENT(2);
+  return any;
+}
+// tz_search (search_inter.c:625-693) as the reference's compile-time switches leave it: step 2 from the best vector, step 2 from zero up to half the range when the
+// start was not zero, the star refinement; best_dist travels through all three
+IC_FN void me_tz(MeBest &best, double lambda_sqrt)
+{
+  const int range = 96;
+  int best_dist = 0;
+  const int sx0 = best.mvx >> 2, sy0 = best.mvy >> 2;
+  for (int part = 0; part < 2; part++) {
+    if (part == 1) { if (sx0 == 0 && sy0 == 0) break; IC_ME_EVENT(0); }
+    int idle = 0;
+    for (int d = 1; d <= (part ? range / 2 : range); d *= 2) {
+      if (me_tz_round(best, lambda_sqrt, part ? 0 : sx0, part ? 0 : sy0, d)) best_dist = d;
+      if (best_dist != d) idle++;
+      if (idle >= 3) break;
+    }
+  }
+  int rounds = 0;
+  while (best_dist > 0) {
+    if (++rounds > IC_ME_LOOP_BOUND) { g_ic.me_overrun = 1; break; }
+    if (rounds == 2) IC_ME_EVENT(1);
+    best_dist = 0;
+    const int mx = best.mvx >> 2, my = best.mvy >> 2;
+    for (int d = 1; d <= range; d *= 2) if (me_tz_round(best, lambda_sqrt, mx, my, d)) best_dist = d;
+  }
+}
+// diamond_search (search_inter.c:810-889): five points, the centre among them; then three per round, without the one at index best_index ^ 3 of the last move
+IC_FN void me_diamond(MeBest &best, double lambda_sqrt, int max_steps)
+{
+  const unsigned long long dx = IC_PAT9(0, 1, 0, -1, 0, 0, 0, 0, 0), dy = IC_PAT9(-1, 0, 1, 0, 0, 0, 0, 0, 0);
+  i16 *px = L->px, *py = L->py;
+  int mx = best.mvx >> 2, my = best.mvy >> 2, best_index = 4;
+  for (int j = 0; j < 5; j++) { px[j] = mx + pat(dx, j); py[j] = my + pat(dy, j); }
+  probe(5);
+  for (int j = 0; j < 5; j++) if (me_consider(best, lambda_sqrt, j)) best_index = j;
+  if (best_index == 4) return;
+  mx += pat(dx, best_index); my += pat(dy, best_index);
+  int from_dir = 4, steps = max_steps;
+  for (int rounds = 0;; rounds++) {
+    if (rounds >= IC_ME_LOOP_BOUND) { g_ic.me_overrun = 1; break; }
+    bool better = false;
+    if (steps > 0) steps--;
+    int n = 0, idx[4];
+    for (int i = 0; i < 4; i++) if (i != from_dir) { px[n] = mx + pat(dx, i); py[n] = my + pat(dy, i); idx[n] = i; n++; }
+    probe(n);
+    for (int j = 0; j < n; j++) if (me_consider(best, lambda_sqrt, j)) { best_index = idx[j]; better = true; }
+    if (better) { mx += pat(dx, best_index); my += pat(dy, best_index); from_dir = best_index ^ 3; }
+    if (!better) break;
+    if (max_steps > 0 && steps == 0) { IC_ME_EVENT(11); break; }
+  }
+}
+#endif
+
 // search_pu_inter_ref's search (oracle me_integer) for L->pu into L->best; (sx, sy): the co-located motion, if has_start
 IC_FN void me_integer(bool has_start, int sx, int sy)
 {
@@ -478,6 +693,59 @@ IC_FN void me_integer(bool has_start, int sx, int sy)
     for (int k = 0; k < n; k++) consider(best, lambda_sqrt, k);
   }
   bool skip_me = false;
+#if KVZ_ICTU_ME_STATE
+  if (KVZ_ICTU_ME) {  // the launch's own choice (search_inter.c:1341-1383)
+    const int algo = M->me_algorithm, term = M->me_early_termination, max_steps = M->me_max_steps;
+    {  // early_terminate (search_inter.c:436-484) runs whatever the setting -- it moves the best vector --, `off` (2) only ignores its verdict; `on` (1): the best cost itself is the threshold
+      const unsigned long long hx = IC_PAT9(0, -1, 0, 1, 0, -1, 0, 0, 0), hy = IC_PAT9(-1, 0, 1, 0, -1, 0, 0, 0, 0);
+      int mx = best.mvx >> 2, my = best.mvy >> 2, first = 0, last = 3;
+      for (int k = 0; k < 2; k++) {
+        const double threshold = term == 0 ? best.cost * 0.95 : best.cost;
+        int best_index = 6;
+        const int n = last - first + 1;
+        for (int j = 0; j < n; j++) { px[j] = mx + pat(hx, first + j); py[j] = my + pat(hy, first + j); }
+        probe(n);
+        for (int j = 0; j < n; j++) if (me_consider(best, lambda_sqrt, j)) best_index = first + j;
+        mx += pat(hx, best_index); my += pat(hy, best_index);
+        if (best.cost >= threshold) { skip_me = true; break; }
+        first = (best_index + 3) % 4;
+        last = first + 2;
+      }
+    }
+    if (term == 2) skip_me = false;
+    if (skip_me) {
+    } else if (algo == 1) me_tz(best, lambda_sqrt);
+    else if (algo >= 2 && algo <= 6) {
+      IC_FOR(tid) { if (tid == 0) { L->best.mvx = best.mvx; L->best.mvy = best.mvy; L->best.cost = best.cost; L->best.bits = best.bits; } }
+      IC_SYNC();
+      me_full(algo == 3 ? 8 : (algo == 4 ? 16 : (algo == 6 ? 64 : 32)));
+      best.mvx = L->best.mvx; best.mvy = L->best.mvy; best.cost = L->best.cost; best.bits = L->best.bits;
+    } else if (algo == 7) me_diamond(best, lambda_sqrt, max_steps);
+    else {  // hexagon_search with --me-steps (search_inter.c:712-792): the limit counts the moves of the large hexagon, the small one always runs
+      const unsigned long long lx = IC_PAT9(0, 1, 2, 1, -1, -2, -1, 1, 2), ly = IC_PAT9(0, -2, 0, 2, 2, 0, -2, -2, 0);
+      const unsigned long long sx9 = IC_PAT9(0, 0, -1, 1, 0, -1, 1, -1, 1), sy9 = IC_PAT9(0, -1, 0, 0, 1, -1, -1, 1, 1);
+      int mx = best.mvx >> 2, my = best.mvy >> 2, best_index = 0, steps = max_steps, rounds = 0;
+      for (int j = 0; j < 6; j++) { px[j] = mx + pat(lx, j + 1); py[j] = my + pat(ly, j + 1); }
+      probe(6);
+      for (int j = 0; j < 6; j++) if (me_consider(best, lambda_sqrt, j)) best_index = j + 1;
+      while (best_index != 0) {
+        if (max_steps > 0 && steps == 0) { IC_ME_EVENT(12); break; }
+        if (++rounds > IC_ME_LOOP_BOUND) { g_ic.me_overrun = 1; break; }
+        if (steps > 0) steps--;
+        const int start_i = best_index == 1 ? 6 : (best_index == 8 ? 1 : best_index - 1);
+        mx += pat(lx, best_index); my += pat(ly, best_index);
+        best_index = 0;
+        for (int j = 0; j < 3; j++) { px[j] = mx + pat(lx, start_i + j); py[j] = my + pat(ly, start_i + j); }
+        probe(3);
+        for (int j = 0; j < 3; j++) if (me_consider(best, lambda_sqrt, j)) best_index = start_i + j;
+      }
+      for (int j = 0; j < 8; j++) { px[j] = mx + pat(sx9, j + 1); py[j] = my + pat(sy9, j + 1); }
+      probe(8);
+      for (int j = 0; j < 8; j++) me_consider(best, lambda_sqrt, j);
+    }
+    skip_me = true;  // (nothing of the default search below)
+  } else
+#endif
   {  // early_terminate, sensitive (search_inter.c:425-486): the small cross, entries first .. last
     const unsigned long long hx = IC_PAT9(0, -1, 0, 1, 0, -1, 0, 0, 0), hy = IC_PAT9(-1, 0, 1, 0, -1, 0, 0, 0, 0);
     int mx = best.mvx >> 2, my = best.mvy >> 2, first = 0, last = 3;

@@ -2,6 +2,8 @@
 // initialisation, kvz_init_contexts context.c:202-305 with row 0 of the tables :36-193).
 #pragma once
 #include <math.h>
+#include <stddef.h>
+#include <stdio.h>
 #include <string.h>
 #include <vector>
 
@@ -61,6 +63,39 @@ inline int inter_pass_geometry_refused(int width, int height, int n_pictures, in
   }
   return 0;
 }
+
+// kvz_hip_inter_params grows at its end, and struct_size says which version the caller was built against.  Two are known: this library's, and the one before the
+// three me_* members (everything in front of me_algorithm) -- a binding that was compiled before them keeps working and gets the default search, which is what it
+// asked for.  *full: the caller's members in this library's struct, the rest zero.  Any other size is refused: false and a message.
+inline bool inter_params_full(const kvz_hip_inter_params *p, kvz_hip_inter_params *full, const char *who)
+{
+  const size_t before_me = offsetof(kvz_hip_inter_params, me_algorithm);
+  if (!p || (p->struct_size != sizeof(kvz_hip_inter_params) && p->struct_size != before_me)) {
+    fprintf(stderr, "%s: kvz_hip_inter_params.struct_size %u is not this library's %zu (zero the struct, set struct_size = sizeof, build against the library's headers)\n", who, p ? p->struct_size : 0u, sizeof(kvz_hip_inter_params));
+    return false;
+  }
+  memset(full, 0, sizeof *full);
+  memcpy(full, p, p->struct_size);
+  full->struct_size = (uint32_t)sizeof *full;
+  return true;
+}
+
+// The launch's choice of the integer motion search (kvz_hip_inter_params me_algorithm / me_max_steps / me_early_termination): what every entry point of the pass
+// refuses of it before anything is queued -- false and a message --, `excluded` naming what the call has that the ME builds do not cover ("tiles", "scaling lists",
+// "a joint launch") or nullptr
+inline bool inter_me_chosen(const kvz_hip_inter_params *p) { return p->me_algorithm != 0 || p->me_max_steps != 0 || p->me_early_termination != 0; }
+inline bool inter_me_known(const kvz_hip_inter_params *p, const char *excluded, const char *who)
+{
+  if (p->me_algorithm < 0 || p->me_algorithm > 7) { fprintf(stderr, "%s: me_algorithm %d outside 0..7\n", who, p->me_algorithm); return false; }
+  if (p->me_max_steps < 0) { fprintf(stderr, "%s: me_max_steps %d is negative (0: no limit)\n", who, p->me_max_steps); return false; }
+  if (p->me_early_termination < 0 || p->me_early_termination > 2) { fprintf(stderr, "%s: me_early_termination %d outside 0..2\n", who, p->me_early_termination); return false; }
+  if (excluded && inter_me_chosen(p)) {
+    fprintf(stderr, "%s: me_algorithm / me_max_steps / me_early_termination (%d, %d, %d) are not covered together with %s\n", who, p->me_algorithm, p->me_max_steps, p->me_early_termination, excluded);
+    return false;
+  }
+  return true;
+}
+inline void inter_model_set_me(InterModel *m, const kvz_hip_inter_params *p) { m->me_algorithm = p->me_algorithm; m->me_max_steps = p->me_max_steps; m->me_early_termination = p->me_early_termination; }
 
 inline void inter_model_init(InterModel *m, int qp, int poc, uint64_t coeff_weights, const float fbits[128], int mv_constraint, int sao, int deblock, int fme_level,
                              int pu_depth_inter_max, int no_wpp, int fast_residual_cost, int pic_w = 0, int pic_h = 0, int ref_w = 0, int ref_h = 0, int tile_x = 0, int tile_y = 0, int no_tmvp = 0,

@@ -62,10 +62,9 @@ inline void inter_joint_ticket_lists(const InterJointGeometry *g, int n, std::ve
 // Everything kvz_hip_dev_inter_ctu_pass_groups refuses, before anything is queued: true = the launch can run
 inline bool inter_joint_known(const kvz_hip_inter_group *groups, int n_groups, const kvz_hip_inter_params *p, const char *who)
 {
-  if (!p || p->struct_size != sizeof(kvz_hip_inter_params)) {
-    fprintf(stderr, "%s: kvz_hip_inter_params.struct_size %u is not this library's %zu (zero the struct, set struct_size = sizeof, build against the library's headers)\n", who, p ? p->struct_size : 0u, sizeof(kvz_hip_inter_params));
-    return false;
-  }
+  kvz_hip_inter_params full;
+  if (!inter_params_full(p, &full, who)) return false;
+  p = &full;
   if (n_groups < 1 || !groups) { fprintf(stderr, "%s: a joint launch needs at least one group (n_groups %d)\n", who, n_groups); return false; }
   if (p->ref_width || p->ref_height || p->tile_x || p->tile_y) {
     fprintf(stderr, "%s: ref_width / ref_height / tile_x / tile_y are %d / %d / %d / %d: tiles are not part of joint launches\n", who, p->ref_width, p->ref_height, p->tile_x, p->tile_y);
@@ -75,6 +74,7 @@ inline bool inter_joint_known(const kvz_hip_inter_group *groups, int n_groups, c
     fprintf(stderr, "%s: unsupported parameters (fme_level %d, pu_depth_inter_max %d, fast_residual_cost %d)\n", who, p->fme_level, p->pu_depth_inter_max, p->fast_residual_cost);
     return false;
   }
+  if (!inter_me_known(p, "a joint launch", who)) return false;
   long pictures = 0, ctus = 0;
   for (int i = 0; i < n_groups; i++) {
     const kvz_hip_inter_group &g = groups[i];

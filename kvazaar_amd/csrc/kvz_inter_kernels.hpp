@@ -24,7 +24,9 @@ struct InterSched {
 // (-DKVZ_ICTU_LISTS=1, kvz_inter_ctu.hpp: kvz_hip_dev_inter_ctu_pass_lists), `_lists_fast` / `_lists_cabac`; and the same two for joint launches of pictures of
 // different sizes (-DKVZ_ICTU_JOINT=1: kvz_hip_dev_inter_ctu_pass_groups), `_joint_fast` / `_joint_cabac`.  In a joint launch the item's picture numbers the pictures
 // across the groups; F holds no geometry, F.pictures the launch's table (kvz_inter_ctu.hpp InterJointPicture / InterJointGroup), and sched.done is indexed by the
-// group's first CTU + the picture's index in the group x the group's CTUs + the CTU
+// group's first CTU + the picture's index in the group x the group's CTUs + the CTU; and the same two for launches that choose the integer motion search
+// (-DKVZ_ICTU_ME=1: kvz_hip_inter_params me_algorithm / me_max_steps / me_early_termination), `_me_fast` / `_me_cabac`, which raise the launch's error word when a
+// search loop reached its bound (kvz_inter_ctu_pix.inc IC_ME_LOOP_BOUND)
 #define KVZ_ICTU_KERNEL(name) __global__ void __launch_bounds__(KVZ_ICTU_THREADS) __attribute__((amdgpu_waves_per_eu(KVZ_ICTU_WAVES_PER_EU, KVZ_ICTU_WAVES_PER_EU))) name(const InterFrames F, const InterModel *model, const Tables *tb, const InterSched sched)
 #ifndef KVZ_INTER_KERNEL_BODY
 KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_fast);
@@ -33,11 +35,20 @@ KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_lists_fast);
 KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_lists_cabac);
 KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_joint_fast);
 KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_joint_cabac);
+KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_me_fast);
+KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_me_cabac);
 #else
 #if KVZ_ICTU_JOINT && KVZ_ICTU_LISTS
 #error "scaling lists are not part of joint launches"
 #endif
-#if KVZ_ICTU_JOINT && KVZ_ICTU_CABAC
+#if KVZ_ICTU_ME && (KVZ_ICTU_JOINT || KVZ_ICTU_LISTS)
+#error "the choice of the integer motion search is not part of joint launches or of launches with scaling lists"
+#endif
+#if KVZ_ICTU_ME && KVZ_ICTU_CABAC
+KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_me_cabac)
+#elif KVZ_ICTU_ME
+KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_me_fast)
+#elif KVZ_ICTU_JOINT && KVZ_ICTU_CABAC
 KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_joint_cabac)
 #elif KVZ_ICTU_JOINT
 KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_joint_fast)
@@ -109,6 +120,9 @@ KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_fast)
     if (s_ticket != 0) {
       InterCtu::begin_ctu(frame, x * 64, y * 64);
       InterCtu::run();
+#if KVZ_ICTU_ME
+      if (threadIdx.x == 0 && g_ic.me_overrun) atomicExch(sched.error, 1u);
+#endif
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();

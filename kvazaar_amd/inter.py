@@ -13,13 +13,30 @@ assert CU_DTYPE.itemsize == 22
 
 class InterParams(C.Structure):  # kvz_hip_inter_params
     _fields_ = [("struct_size", C.c_uint32)] + [(n, C.c_int32) for n in ("qp", "poc", "mv_constraint", "sao", "deblock", "fme_level", "pu_depth_inter_max", "no_wpp", "fast_residual_cost",
-                                                "ref_width", "ref_height", "tile_x", "tile_y", "no_tmvp")]  # the last four: tiles (include/kvz_hip_dev.h), zero = the picture is the frame
+                                                "ref_width", "ref_height", "tile_x", "tile_y", "no_tmvp",  # ref_width .. tile_y: tiles (include/kvz_hip_dev.h), zero = the picture is the frame
+                                                "me_algorithm", "me_max_steps", "me_early_termination")]  # the integer motion search (me_search_fields), zero = hexbs, no step limit, sensitive
 
 
     def __init__(self, **kw):
         super().__init__(**kw)
         if "struct_size" not in kw:
             self.struct_size = C.sizeof(InterParams)  # the version of the struct this binding was written against (include/kvz_hip_dev.h)
+
+
+ME_ALGORITHMS = {"hexbs": 0, "tz": 1, "full": 2, "full8": 3, "full16": 4, "full32": 5, "full64": 6, "dia": 7}  # kvazaar's enum kvz_ime_algorithm
+ME_EARLY_TERMINATION = {"sensitive": 0, "on": 1, "off": 2}  # kvz_hip_inter_params' own order: zero is what every preset up to `fast` runs
+
+
+def me_search_fields(me="hexbs", me_steps=-1, me_early_termination="sensitive"):
+    """kvazaar's --me, --me-steps and --me-early-termination as the three members of kvz_hip_inter_params: InterParams(..., **me_search_fields(me="tz")).
+    me_steps: -1 (kvazaar's default, no limit) or a count >= 1"""
+    if me not in ME_ALGORITHMS:
+        raise ValueError(f"--me {me}: one of {', '.join(ME_ALGORITHMS)}")
+    if me_early_termination not in ME_EARLY_TERMINATION:
+        raise ValueError(f"--me-early-termination {me_early_termination}: one of {', '.join(ME_EARLY_TERMINATION)}")
+    if me_steps != -1 and me_steps < 1:
+        raise ValueError(f"--me-steps {me_steps}: -1 (no limit) or a count of at least 1")
+    return dict(me_algorithm=ME_ALGORITHMS[me], me_max_steps=0 if me_steps == -1 else int(me_steps), me_early_termination=ME_EARLY_TERMINATION[me_early_termination])
 
 
 class InterPicturesStruct(C.Structure):  # kvz_hip_inter_pictures
