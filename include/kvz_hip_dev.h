@@ -263,6 +263,32 @@ int  kvz_hip_dev_inter_ctu_pass_lists(const uint8_t *src, const uint8_t *ref, co
  * kvz_hip_dev_inter_ctu_pass_pictures would refuse for the group, 65536 or more pictures in all, a tile member of params that is not zero (ref_width, ref_height,
  * tile_x, tile_y: tiles are not part of joint launches), two groups with the same rec or the same cu buffer.  Scaling lists are not part of joint launches. */
 int  kvz_hip_dev_inter_ctu_pass_groups(const kvz_hip_inter_group *groups, int n_groups, const kvz_hip_inter_params *params);
+/* P pictures (kvazaar --no-bipred with --gop lp-g4d3t1 or --gop 0: the IPPP stream, HM's "low-delay P"): the three stages of an inter picture with the slice type
+ * of the launch's pictures as an argument, KVZ_HIP_SLICE_B / _P / _I (kvz_hip_types.h).  Each is a superset of its _pictures twin: with KVZ_HIP_SLICE_B it IS that
+ * call (its kernels, its bytes), and `pictures` may be NULL (params->qp / params->poc, or the scalar qp, for every picture).
+ * A P picture is not a B picture with a list ignored (encoderstate.c:1083-1099, 1618-1625 leave L1 empty and make the slice KVZ_SLICE_P):
+ *  - the pass (kernel builds of their own, -DKVZ_ICTU_P=1, with the L1 half compiled out) takes the temporal merge candidate for L0 only, builds no combined
+ *    candidates, fills with zero candidates of dir 1 (inter.c:1471-1569), searches and refines L0 alone and never prices inter_pred_idc
+ *    (encode_coding_tree.c:339); records come out with mv_dir 1, mv[1] = 0, mv_ref[1] = 255, mv_cand[1] = 0 where the search set them;
+ *  - every initial CABAC state, of the search and of the coder, comes from the P row of the standard's tables (H.265 9.3.2.2, initType 1);
+ *  - the coder writes no inter_pred_idc; the loop filters deblock without the B-slice rules (filter.c:428) and start the SAO decision from sao_type_idx 185.
+ * kvz_hip_dev_loop_filters_inter_slices: slice_type replaces slice_is_b -- KVZ_HIP_SLICE_I is what slice_is_b == 0 has always been (deblocking without the B rules,
+ * sao_type_idx 200); qp_of_picture (HOST) may be NULL, then `qp` holds for every picture.
+ * Refused with -1 and a message before anything is queued, besides what the _pictures twin refuses: a slice type that is none of the three; KVZ_HIP_SLICE_I for the
+ * pass or the coder; KVZ_HIP_SLICE_P together with tiles (ref_width, ref_height, tile_x or tile_y non-zero, tile_xy non-NULL) or with a non-zero me_algorithm /
+ * me_max_steps / me_early_termination.
+ * NOT COVERED: the entry points without a slice type -- everything above, _lists, _groups and _tiles included -- stay B, so P pictures have no scaling lists, no
+ * joint launches, no tiles and no choice of the integer search; B and P pictures do not share a launch; kvz_hip_dev_pu_search and the kvazaar-side binding
+ * (integration/, which keeps falling back to the host for a P slice) are untouched; one reference picture. */
+int  kvz_hip_dev_inter_ctu_pass_slices(const uint8_t *src, const uint8_t *ref, const kvz_hip_cu_info *ref_cu, uint8_t *rec, kvz_hip_cu_info *cu, int16_t *coeff, int width,
+                                       int height, int n_pictures, const kvz_hip_inter_params *params, const int32_t *tile_xy, int n_references,
+                                       const kvz_hip_inter_pictures *pictures, int slice_type);
+int  kvz_hip_dev_loop_filters_inter_slices(const uint8_t *src, uint8_t *rec, int width, int height, int n_pictures, const kvz_hip_cu_dbk *info, int qp,
+                                           const int32_t *qp_of_picture, int slice_type, int deblock, int beta_offset_div2, int tc_offset_div2, int sao, int no_wpp,
+                                           kvz_hip_sao_params *luma, kvz_hip_sao_params *chroma, uint8_t *merge);
+long kvz_hip_dev_entropy_code_inter_slices(const kvz_hip_cu_info *cu, const kvz_hip_cu_info *ref_cu, const int16_t *coeff, int width, int height, int n_pictures,
+                                           const kvz_hip_inter_params *params, uint8_t *out, size_t capacity, uint32_t *substream_bytes,
+                                           const kvz_hip_inter_pictures *pictures, int slice_type);
 /* what the deblocking filter reads (kvz_hip_cu_dbk) of `count` CU records: type, depth, tr_depth, the luma coded block flag at tr_depth, motion */
 void kvz_hip_dev_cu_dbk_from_info(const kvz_hip_cu_info *cu, int count, kvz_hip_cu_dbk *out);
 

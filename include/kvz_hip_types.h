@@ -197,6 +197,10 @@ typedef struct kvz_hip_inter_group {
   const kvz_hip_inter_pictures *pictures;
 } kvz_hip_inter_group;
 
+/* The slice type of the pictures of a launch, kvazaar's values (kvazaar.h enum kvz_slices): what the kvz_hip_dev_*_slices entry points (kvz_hip_dev.h) take.  A B
+ * picture here has the previous picture in both lists (--gop lp-g4d3t1 with --bipred 1), a P picture has it in L0 and an empty L1 (--no-bipred). */
+enum { KVZ_HIP_SLICE_B = 0, KVZ_HIP_SLICE_P = 1, KVZ_HIP_SLICE_I = 2 };
+
 /* Per-CTU result record of the batched pass: what kvazaar keeps in cu_array / lcu_t for the CTU. */
 #define KVZ_HIP_CTU_COEFFS 6144 /* 64*64 Y + 32*32 U + 32*32 V coefficients, each plane in lcu_t z-order (cu.h:385-421) */
 

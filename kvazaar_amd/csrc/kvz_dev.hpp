@@ -1076,6 +1076,7 @@ __global__ void __launch_bounds__(64) dev_sao_chain_kernel(const SaoStats *stats
 #include "kvz_inter_kernels.hpp"
 #include "kvz_inter_host.hpp"
 #include "kvz_inter_joint.hpp"
+#include "kvz_slice_contexts.hpp"
 
 namespace kvz {
 __global__ void dev_cu_dbk_kernel(const kvz_hip_cu_info *cu, int count, kvz_hip_cu_dbk *out)
@@ -1381,15 +1382,16 @@ inline LoopScratch &loop_scratch()
   return s[current_device() & 63];
 }
 }  // namespace kvz
-// kvz_hip_dev_loop_filters_inter (qp_host == nullptr: `qp` for every picture) and kvz_hip_dev_loop_filters_inter_pictures (qp_host: a checked HOST array, `qp` unused)
-static int kvz_loop_filters_inter_run(const uint8_t *src, uint8_t *rec, int width, int height, int n_pictures, const kvz_hip_cu_dbk *info, int qp, const int32_t *qp_host, int slice_is_b,
+// kvz_hip_dev_loop_filters_inter (qp_host == nullptr: `qp` for every picture) and kvz_hip_dev_loop_filters_inter_pictures (qp_host: a checked HOST array, `qp` unused);
+// slice_type: KVZ_HIP_SLICE_B, _P or _I -- slice_is_b != 0 is B, slice_is_b == 0 has always been I
+static int kvz_loop_filters_inter_run(const uint8_t *src, uint8_t *rec, int width, int height, int n_pictures, const kvz_hip_cu_dbk *info, int qp, const int32_t *qp_host, int slice_type,
                                       int deblock, int beta_offset_div2, int tc_offset_div2, int sao, int no_wpp, kvz_hip_sao_params *luma, kvz_hip_sao_params *chroma, uint8_t *merge);
 int kvz_hip_dev_loop_filters_inter(const uint8_t *src, uint8_t *rec, int width, int height, int n_pictures, const kvz_hip_cu_dbk *info, int qp, int slice_is_b, int deblock,
                                    int beta_offset_div2, int tc_offset_div2, int sao, int no_wpp, kvz_hip_sao_params *luma, kvz_hip_sao_params *chroma, uint8_t *merge)
 {
   if (n_pictures <= 0) return 0;
   if (!src || !rec || !info || width <= 0 || height <= 0 || (width & 7) || (height & 7) || qp < 0 || qp > 51) { fprintf(stderr, "kvz_hip_dev_loop_filters_inter: bad argument\n"); return -1; }
-  return kvz_loop_filters_inter_run(src, rec, width, height, n_pictures, info, qp, nullptr, slice_is_b, deblock, beta_offset_div2, tc_offset_div2, sao, no_wpp, luma, chroma, merge);
+  return kvz_loop_filters_inter_run(src, rec, width, height, n_pictures, info, qp, nullptr, slice_is_b ? KVZ_HIP_SLICE_B : KVZ_HIP_SLICE_I, deblock, beta_offset_div2, tc_offset_div2, sao, no_wpp, luma, chroma, merge);
 }
 int kvz_hip_dev_loop_filters_inter_pictures(const uint8_t *src, uint8_t *rec, int width, int height, int n_pictures, const kvz_hip_cu_dbk *info, const int32_t *qp_of_picture,
                                             int slice_is_b, int deblock, int beta_offset_div2, int tc_offset_div2, int sao, int no_wpp, kvz_hip_sao_params *luma,
@@ -1398,11 +1400,26 @@ int kvz_hip_dev_loop_filters_inter_pictures(const uint8_t *src, uint8_t *rec, in
   if (n_pictures <= 0) return 0;
   if (!src || !rec || !info || width <= 0 || height <= 0 || (width & 7) || (height & 7)) { fprintf(stderr, "kvz_hip_dev_loop_filters_inter_pictures: bad argument\n"); return -1; }
   if (!kvz::inter_picture_qps_known(qp_of_picture, n_pictures, "kvz_hip_dev_loop_filters_inter_pictures")) return -1;
-  return kvz_loop_filters_inter_run(src, rec, width, height, n_pictures, info, 0, qp_of_picture, slice_is_b, deblock, beta_offset_div2, tc_offset_div2, sao, no_wpp, luma, chroma, merge);
+  return kvz_loop_filters_inter_run(src, rec, width, height, n_pictures, info, 0, qp_of_picture, slice_is_b ? KVZ_HIP_SLICE_B : KVZ_HIP_SLICE_I, deblock, beta_offset_div2, tc_offset_div2, sao, no_wpp, luma, chroma, merge);
 }
-static int kvz_loop_filters_inter_run(const uint8_t *src, uint8_t *rec, int width, int height, int n_pictures, const kvz_hip_cu_dbk *info, int qp, const int32_t *qp_host, int slice_is_b,
+// ... with the slice type named (kvz_hip_dev.h): P is deblocked as every slice that is not B is (filter.c:428), its SAO decision starts from the P row's states
+int kvz_hip_dev_loop_filters_inter_slices(const uint8_t *src, uint8_t *rec, int width, int height, int n_pictures, const kvz_hip_cu_dbk *info, int qp, const int32_t *qp_of_picture,
+                                          int slice_type, int deblock, int beta_offset_div2, int tc_offset_div2, int sao, int no_wpp, kvz_hip_sao_params *luma,
+                                          kvz_hip_sao_params *chroma, uint8_t *merge)
+{
+  if (n_pictures <= 0) return 0;
+  if (slice_type != KVZ_HIP_SLICE_B && slice_type != KVZ_HIP_SLICE_P && slice_type != KVZ_HIP_SLICE_I) {
+    fprintf(stderr, "kvz_hip_dev_loop_filters_inter_slices: slice type %d is none of KVZ_HIP_SLICE_B (0), KVZ_HIP_SLICE_P (1), KVZ_HIP_SLICE_I (2)\n", slice_type);
+    return -1;
+  }
+  if (!src || !rec || !info || width <= 0 || height <= 0 || (width & 7) || (height & 7) || (!qp_of_picture && (qp < 0 || qp > 51))) { fprintf(stderr, "kvz_hip_dev_loop_filters_inter_slices: bad argument\n"); return -1; }
+  if (qp_of_picture && !kvz::inter_picture_qps_known(qp_of_picture, n_pictures, "kvz_hip_dev_loop_filters_inter_slices")) return -1;
+  return kvz_loop_filters_inter_run(src, rec, width, height, n_pictures, info, qp_of_picture ? 0 : qp, qp_of_picture, slice_type, deblock, beta_offset_div2, tc_offset_div2, sao, no_wpp, luma, chroma, merge);
+}
+static int kvz_loop_filters_inter_run(const uint8_t *src, uint8_t *rec, int width, int height, int n_pictures, const kvz_hip_cu_dbk *info, int qp, const int32_t *qp_host, int slice_type,
                                       int deblock, int beta_offset_div2, int tc_offset_div2, int sao, int no_wpp, kvz_hip_sao_params *luma, kvz_hip_sao_params *chroma, uint8_t *merge)
 {
+  const int slice_is_b = slice_type == KVZ_HIP_SLICE_B;  // what the deblocking kernels ask
   hipStream_t st = be().stream;
   const int32_t *qps = nullptr;  // device: the pictures' QPs
   if (qp_host) {
@@ -1450,8 +1467,8 @@ static int kvz_loop_filters_inter_run(const uint8_t *src, uint8_t *rec, int widt
   KVZ_HIP_CHECK(hipMemcpyAsync(sc.dbk, sc.ver, pic_bytes, hipMemcpyDeviceToDevice, st));
   if (deblock) kvz::deblock_frames_on(st, sc.dbk, width, height, n_pictures, nullptr, qp, beta_offset_div2, tc_offset_div2, 2, info, slice_is_b, qps);
   const kvz::SaoGeom g{ width, height, wc, hc, frame_px };
-  // rate_control.c:678-691 at the picture's QP; context.c:38-39 INIT_SAO_MERGE_FLAG / INIT_SAO_TYPE_IDX of the slice type (B: 153 / 160, I: 153 / 200)
-  auto sao_row = [&](int q) { return kvz::SaoQpRow{ 0.57 * pow(2.0, (q - 12) / 3.0), kvz::ctx_state(q, 153), kvz::ctx_state(q, slice_is_b ? 160 : 200) }; };
+  // rate_control.c:678-691 at the picture's QP; context.c:38-39 INIT_SAO_MERGE_FLAG / INIT_SAO_TYPE_IDX of the slice type (B: 153 / 160, P: 153 / 185, I: 153 / 200)
+  auto sao_row = [&](int q) { return kvz::SaoQpRow{ 0.57 * pow(2.0, (q - 12) / 3.0), kvz::ctx_state(q, 153), kvz::ctx_state(q, kvz::sao_type_init_value(slice_type)) }; };
   const kvz::SaoQpRow row = sao_row(qp);
   const double lambda = row.lambda;
   const int cx_merge = row.init_merge, cx_type = row.init_type;
@@ -1539,15 +1556,33 @@ int kvz_hip_dev_inter_ctu_pass_pictures(const uint8_t *src, const uint8_t *ref, 
 {
   return kvz_hip_dev_inter_ctu_pass_lists(src, ref, ref_cu, rec, cu, coeff, width, height, n_pictures, p, tile_xy, n_references, pictures, nullptr, 0, nullptr);
 }
+static int kvz_inter_ctu_pass_run(const uint8_t *src, const uint8_t *ref, const kvz_hip_cu_info *ref_cu, uint8_t *rec, kvz_hip_cu_info *cu, int16_t *coeff, int width,
+                                  int height, int n_pictures, const kvz_hip_inter_params *p, const int32_t *tile_xy, int n_references,
+                                  const kvz_hip_inter_pictures *pictures, const kvz_hip_scaling_lists *sets, int n_sets, const uint16_t *set_of_picture, int slice_type);
 // pictures == nullptr: p->qp / p->poc for every picture (kvz_hip_dev_inter_ctu_pass[_tiles]); n_sets == 0: no scaling lists (kvz_hip_dev_inter_ctu_pass_pictures)
 int kvz_hip_dev_inter_ctu_pass_lists(const uint8_t *src, const uint8_t *ref, const kvz_hip_cu_info *ref_cu, uint8_t *rec, kvz_hip_cu_info *cu, int16_t *coeff, int width,
                                      int height, int n_pictures, const kvz_hip_inter_params *p, const int32_t *tile_xy, int n_references,
                                      const kvz_hip_inter_pictures *pictures, const kvz_hip_scaling_lists *sets, int n_sets, const uint16_t *set_of_picture)
 {
+  return kvz_inter_ctu_pass_run(src, ref, ref_cu, rec, cu, coeff, width, height, n_pictures, p, tile_xy, n_references, pictures, sets, n_sets, set_of_picture, KVZ_HIP_SLICE_B);
+}
+// ... of B or of P pictures (kvz_hip_dev.h): KVZ_HIP_SLICE_B is kvz_hip_dev_inter_ctu_pass_pictures
+int kvz_hip_dev_inter_ctu_pass_slices(const uint8_t *src, const uint8_t *ref, const kvz_hip_cu_info *ref_cu, uint8_t *rec, kvz_hip_cu_info *cu, int16_t *coeff, int width,
+                                      int height, int n_pictures, const kvz_hip_inter_params *p, const int32_t *tile_xy, int n_references,
+                                      const kvz_hip_inter_pictures *pictures, int slice_type)
+{
+  return kvz_inter_ctu_pass_run(src, ref, ref_cu, rec, cu, coeff, width, height, n_pictures, p, tile_xy, n_references, pictures, nullptr, 0, nullptr, slice_type);
+}
+// slice_type: KVZ_HIP_SLICE_B, or -- kvz_hip_dev_inter_ctu_pass_slices only -- what that entry point was handed
+static int kvz_inter_ctu_pass_run(const uint8_t *src, const uint8_t *ref, const kvz_hip_cu_info *ref_cu, uint8_t *rec, kvz_hip_cu_info *cu, int16_t *coeff, int width,
+                                  int height, int n_pictures, const kvz_hip_inter_params *p, const int32_t *tile_xy, int n_references,
+                                  const kvz_hip_inter_pictures *pictures, const kvz_hip_scaling_lists *sets, int n_sets, const uint16_t *set_of_picture, int slice_type)
+{
   if (n_pictures <= 0) return 0;
   kvz_hip_inter_params full;
   if (!kvz::inter_params_full(p, &full, "kvz_hip_dev_inter_ctu_pass")) return -1;
   p = &full;  // (a caller from before the me_* members: they are zero)
+  if (!kvz::inter_slice_launch_known(p, tile_xy != nullptr, slice_type, "kvz_hip_dev_inter_ctu_pass_slices")) return -1;
   const int refused = kvz::inter_pass_geometry_refused(width, height, n_pictures, p->ref_width, p->ref_height, p->tile_x, p->tile_y);
   if (refused == 1) { fprintf(stderr, "kvz_hip_dev_inter_ctu_pass: bad geometry\n"); return -1; }
   if (pictures && !kvz::inter_pictures_known(pictures, n_pictures, "kvz_hip_dev_inter_ctu_pass_pictures")) return -1;
@@ -1559,7 +1594,7 @@ int kvz_hip_dev_inter_ctu_pass_lists(const uint8_t *src, const uint8_t *ref, con
   }
   if (!kvz::scaling_list_sets_known(sets, n_sets, set_of_picture, n_pictures, true /* the pass has no other schedule */, "kvz_hip_dev_inter_ctu_pass_lists")) return -1;
   if (!kvz::inter_me_known(p, (p->ref_width || p->ref_height || tile_xy) ? "tiles" : (n_sets > 0 ? "scaling lists" : nullptr), "kvz_hip_dev_inter_ctu_pass")) return -1;
-  const bool lists = n_sets > 0, me = kvz::inter_me_chosen(p);
+  const bool lists = n_sets > 0, me = kvz::inter_me_chosen(p), p_slice = slice_type == KVZ_HIP_SLICE_P;  // (P: neither lists -- no entry point hands both over -- nor me)
   hipStream_t st = be().stream;
   const int wc = (width + 63) / 64, hc = (height + 63) / 64, ctus = wc * hc;
   const long total = (long)ctus * n_pictures;
@@ -1574,7 +1609,7 @@ int kvz_hip_dev_inter_ctu_pass_lists(const uint8_t *src, const uint8_t *ref, con
   for (int i = 0; i < 128; i++) fbits[i] = (float)kvz::kEntropyBits[i] / 32768.0f;
   auto model_at_qp = [&](kvz::InterModel *row, int qp) {
     kvz::inter_model_init(row, qp, p->poc, kvz_hip_default_coeff_weights(qp) /* 0 from QP 50 on, where kvz_fast_coeff_cost is never used (rdo.c:311-340) */, fbits, p->mv_constraint, p->sao, p->deblock, p->fme_level, p->pu_depth_inter_max, p->no_wpp, p->fast_residual_cost,
-                          width, height, p->ref_width, p->ref_height, p->tile_x, p->tile_y, p->no_tmvp, lists ? 1 : 0);
+                          width, height, p->ref_width, p->ref_height, p->tile_x, p->tile_y, p->no_tmvp, lists ? 1 : 0, slice_type);
     kvz::inter_model_set_me(row, p);
   };
   kvz::InterPictureTable table;
@@ -1584,7 +1619,8 @@ int kvz_hip_dev_inter_ctu_pass_lists(const uint8_t *src, const uint8_t *ref, con
     table = kvz::inter_picture_table_lists(pictures ? pictures->qp : qp_all.data(), pictures ? pictures->poc : poc_all.data(), n_pictures, model_at_qp, sets, n_sets, set_of_picture);
   } else if (pictures) table = kvz::inter_picture_table(pictures->qp, pictures->poc, n_pictures, model_at_qp);
   const bool cabac_build = (pictures || lists) ? table.any_cabac : kvz::inter_qp_prices_with_cabac(p->qp, p->fast_residual_cost);
-  const void *kernel = me ? (cabac_build ? (const void *)kvz::inter_ctu_ticket_kernel_me_cabac : (const void *)kvz::inter_ctu_ticket_kernel_me_fast)
+  const void *kernel = p_slice ? (cabac_build ? (const void *)kvz::inter_ctu_ticket_kernel_p_cabac : (const void *)kvz::inter_ctu_ticket_kernel_p_fast)
+                     : me ? (cabac_build ? (const void *)kvz::inter_ctu_ticket_kernel_me_cabac : (const void *)kvz::inter_ctu_ticket_kernel_me_fast)
                      : lists ? (cabac_build ? (const void *)kvz::inter_ctu_ticket_kernel_lists_cabac : (const void *)kvz::inter_ctu_ticket_kernel_lists_fast)
                              : (cabac_build ? (const void *)kvz::inter_ctu_ticket_kernel_cabac : (const void *)kvz::inter_ctu_ticket_kernel_fast);
   // resident workgroups (= wavefronts) per CU: what the kernel's registers and LDS allow -- a persistent grid, one workgroup per slot
@@ -1596,7 +1632,7 @@ int kvz_hip_dev_inter_ctu_pass_lists(const uint8_t *src, const uint8_t *ref, con
   if (env && atoi(env) > 0) per_cu = atoi(env) < fit ? atoi(env) : fit;
   if (per_cu < 1) per_cu = 1;
   int n_wg = n_cu * per_cu;
-  if (getenv("KVZ_HIP_INTER_VERBOSE")) fprintf(stderr, "kvz_hip inter pass: %s%s build, %d workgroups per CU x %d CUs\n", me ? "me " : lists ? "lists " : "", cabac_build ? "cabac" : "fast", per_cu, n_cu);
+  if (getenv("KVZ_HIP_INTER_VERBOSE")) fprintf(stderr, "kvz_hip inter pass: %s%s build, %d workgroups per CU x %d CUs\n", p_slice ? "p " : me ? "me " : lists ? "lists " : "", cabac_build ? "cabac" : "fast", per_cu, n_cu);
   if ((long)n_wg > total) n_wg = (int)total;
   if (n_wg > sc.n_slabs) {
     if (sc.slabs) KVZ_HIP_CHECK(hipFree(sc.slabs));
@@ -1664,7 +1700,9 @@ int kvz_hip_dev_inter_ctu_pass_lists(const uint8_t *src, const uint8_t *ref, con
   kvz::DevTimer &tm = kvz::inter_timer();
   if (!tm.e0) { KVZ_HIP_CHECK(hipEventCreate(&tm.e0)); KVZ_HIP_CHECK(hipEventCreate(&tm.e1)); }
   KVZ_HIP_CHECK(hipEventRecord(tm.e0, st));
-  if (me && cabac_build) hipLaunchKernelGGL(kvz::inter_ctu_ticket_kernel_me_cabac, dim3((unsigned)n_wg), dim3(KVZ_ICTU_THREADS), 0, st, F, d_model, kvz::device_tables(), sched);
+  if (p_slice && cabac_build) hipLaunchKernelGGL(kvz::inter_ctu_ticket_kernel_p_cabac, dim3((unsigned)n_wg), dim3(KVZ_ICTU_THREADS), 0, st, F, d_model, kvz::device_tables(), sched);
+  else if (p_slice) hipLaunchKernelGGL(kvz::inter_ctu_ticket_kernel_p_fast, dim3((unsigned)n_wg), dim3(KVZ_ICTU_THREADS), 0, st, F, d_model, kvz::device_tables(), sched);
+  else if (me && cabac_build) hipLaunchKernelGGL(kvz::inter_ctu_ticket_kernel_me_cabac, dim3((unsigned)n_wg), dim3(KVZ_ICTU_THREADS), 0, st, F, d_model, kvz::device_tables(), sched);
   else if (me) hipLaunchKernelGGL(kvz::inter_ctu_ticket_kernel_me_fast, dim3((unsigned)n_wg), dim3(KVZ_ICTU_THREADS), 0, st, F, d_model, kvz::device_tables(), sched);
   else if (lists && cabac_build) hipLaunchKernelGGL(kvz::inter_ctu_ticket_kernel_lists_cabac, dim3((unsigned)n_wg), dim3(KVZ_ICTU_THREADS), 0, st, F, d_model, kvz::device_tables(), sched);
   else if (lists) hipLaunchKernelGGL(kvz::inter_ctu_ticket_kernel_lists_fast, dim3((unsigned)n_wg), dim3(KVZ_ICTU_THREADS), 0, st, F, d_model, kvz::device_tables(), sched);
@@ -1932,24 +1970,7 @@ int kvz_hip_batch_sao_params(kvz_hip_batch *b, int frame, kvz_hip_sao_params *lu
 // CTU pass (and of the loop filters' SAO decision).  Pictures are coded in chunks whose bin records fit a scratch budget (KVZ_HIP_ENTROPY_SCRATCH_MB, default 49152:
 // 25 MB per 1080p picture at the default capacity of 12 288 records per CTU); a CTU that produces more records than that makes its chunk run again with the room it needs.
 namespace kvz {
-// kvz_init_contexts for a B slice (context.c:36-193 row 0 of every table, :202-305) in the entropy coder's numbering: KVZ_HIP_CX_* then KVZ_EB_CX_* (kvz_entropy.hpp)
-inline void entropy_b_slice_contexts(int qp, uint8_t out[KVZ_ENTROPY_CTXS])
-{
-  static const uint8_t split[3] = { 107, 139, 126 }, skip[3] = { 197, 185, 201 }, mvd[2] = { 169, 198 }, inter_dir[5] = { 95, 79, 63, 31, 31 };
-  uint8_t init[KVZ_ENTROPY_CTXS];
-  memset(init, 154, sizeof init);
-  for (int i = 0; i < 3; i++) { init[KVZ_HIP_CX_SPLIT + i] = split[i]; init[KVZ_EB_CX_SKIP + i] = skip[i]; }
-  init[KVZ_HIP_CX_PART] = 154; init[KVZ_HIP_CX_INTRA] = 183; init[KVZ_HIP_CX_CHROMA] = 152;
-  init[KVZ_HIP_CX_CBF_LUMA] = 153; init[KVZ_HIP_CX_CBF_LUMA + 1] = 111;
-  init[KVZ_HIP_CX_CBF_CHROMA] = 149; init[KVZ_HIP_CX_CBF_CHROMA + 1] = 92; init[KVZ_HIP_CX_CBF_CHROMA_DEEP] = 167; init[KVZ_HIP_CX_CBF_CHROMA_DEEP + 1] = 154;
-  b_slice_residual_init_values(init + KVZ_HIP_CX_SIG_CG);  // kvz_inter_host.hpp: the tables' row 0
-  init[KVZ_HIP_CX_SAO_MERGE] = 153; init[KVZ_HIP_CX_SAO_TYPE] = 160;
-  init[KVZ_EB_CX_MERGE_FLAG] = 154; init[KVZ_EB_CX_MERGE_IDX] = 137; init[KVZ_EB_CX_PRED_MODE] = 134;
-  init[KVZ_EB_CX_MVD] = mvd[0]; init[KVZ_EB_CX_MVD + 1] = mvd[1]; init[KVZ_EB_CX_MVP_IDX] = 168;
-  for (int i = 0; i < 5; i++) init[KVZ_EB_CX_INTER_DIR + i] = inter_dir[i];
-  init[KVZ_EB_CX_ROOT_CBF] = 79;
-  for (int i = 0; i < KVZ_ENTROPY_CTXS; i++) out[i] = (uint8_t)ctx_state(qp, init[i]);
-}
+// (the initial context states of a B or a P slice in the coder's numbering: kvz_slice_contexts.hpp entropy_slice_contexts)
 // scratch of the entropy coder, kept between calls (grow-only; hipMalloc / hipFree per call cost more than a small batch's kernels): one caller at a time
 struct EntropyScratch {
   std::mutex lock;
@@ -2218,9 +2239,17 @@ long kvz_hip_dev_entropy_code_inter_pictures(const kvz_hip_cu_info *cu, const kv
                                              const kvz_hip_inter_params *params, uint8_t *out, size_t capacity, uint32_t *substream_bytes,
                                              const kvz_hip_inter_pictures *pictures)
 {
+  return kvz_hip_dev_entropy_code_inter_slices(cu, ref_cu, coeff, width, height, n_pictures, params, out, capacity, substream_bytes, pictures, KVZ_HIP_SLICE_B);
+}
+// ... of B or of P pictures (kvz_hip_dev.h): the slice's row of initial states, and no inter_pred_idc in a P slice (kvz_entropy.hpp EntropyJob::p_slice)
+long kvz_hip_dev_entropy_code_inter_slices(const kvz_hip_cu_info *cu, const kvz_hip_cu_info *ref_cu, const int16_t *coeff, int width, int height, int n_pictures,
+                                           const kvz_hip_inter_params *params, uint8_t *out, size_t capacity, uint32_t *substream_bytes,
+                                           const kvz_hip_inter_pictures *pictures, int slice_type)
+{
   if (n_pictures <= 0) return 0;
   kvz_hip_inter_params full;  // (the coder reads members both known versions of the struct have)
   if (params && !kvz::inter_params_full(params, &full, "kvz_hip_dev_entropy_code_inter")) return -1;
+  if (params && !kvz::inter_slice_launch_known(&full, false, slice_type, "kvz_hip_dev_entropy_code_inter_slices")) return -1;
   if (!cu || !ref_cu || !coeff || !params || width <= 0 || height <= 0 || (width & 7) || (height & 7) || (!pictures && (params->qp < 0 || params->qp > 51 || params->poc < 1))) {
     fprintf(stderr, "kvz_hip_dev_entropy_code_inter: bad argument\n");
     return -1;
@@ -2231,7 +2260,7 @@ long kvz_hip_dev_entropy_code_inter_pictures(const kvz_hip_cu_info *cu, const kv
   kvz::LoopScratch &ls = kvz::loop_scratch();
   if (params->sao && (!ls.recs || ls.lcus < (size_t)ctus * n_pictures)) { fprintf(stderr, "kvz_hip_dev_entropy_code_inter: kvz_hip_dev_loop_filters_inter(..., sao = 1) has not run on these pictures\n"); return -1; }
   uint8_t init[KVZ_ENTROPY_CTXS];
-  if (!pictures) kvz::entropy_b_slice_contexts(params->qp, init);
+  if (!pictures) kvz::entropy_slice_contexts(slice_type, params->qp, init);
   int device = 0;
   KVZ_HIP_CHECK(hipGetDevice(&device));
   // pictures with a QP and a POC of their own: a row of B-slice context states per distinct QP | every picture's POC (0: no temporal predictors) | every picture's row
@@ -2242,7 +2271,7 @@ long kvz_hip_dev_entropy_code_inter_pictures(const kvz_hip_cu_info *cu, const kv
     const size_t at_poc = (size_t)n_rows * KVZ_ENTROPY_CTX_ROW, at_row = at_poc + (size_t)n_pictures * sizeof(int32_t), bytes = at_row + (size_t)n_pictures * sizeof(uint16_t);
     static_assert(KVZ_ENTROPY_CTX_ROW % 4 == 0 && KVZ_ENTROPY_CTX_ROW >= KVZ_ENTROPY_CTXS, "the POCs behind the rows are 4-byte aligned");
     std::vector<uint8_t> image(bytes, 0);
-    for (int r = 0; r < n_rows; r++) kvz::entropy_b_slice_contexts(qp_of_row[r], &image[(size_t)r * KVZ_ENTROPY_CTX_ROW]);
+    for (int r = 0; r < n_rows; r++) kvz::entropy_slice_contexts(slice_type, qp_of_row[r], &image[(size_t)r * KVZ_ENTROPY_CTX_ROW]);
     for (int i = 0; i < n_pictures; i++) {
       ((int32_t *)&image[at_poc])[i] = params->no_tmvp ? 0 : pictures->poc[i];
       ((uint16_t *)&image[at_row])[i] = (uint16_t)row_of_qp[pictures->qp[i]];
@@ -2265,6 +2294,7 @@ long kvz_hip_dev_entropy_code_inter_pictures(const kvz_hip_cu_info *cu, const kv
     J.sao = params->sao ? ls.recs + (size_t)f0 * ctus * 3 : nullptr; J.sao_merge = params->sao ? ls.merge + (size_t)f0 * ctus : nullptr;
     if (pictures) { J.ctx_rows = d_rows; J.model_of_picture = d_row_of + f0; J.poc_of_picture = d_poc + f0; }
     else memcpy(J.ctx_init, init, sizeof init);
+    J.p_slice = slice_type == KVZ_HIP_SLICE_P;
     return J;
   };
   return kvz::entropy_code_pictures(be().stream, device, n_pictures, wc, hc, params->no_wpp, nullptr, job, out, capacity, substream_bytes);

@@ -59,6 +59,9 @@ struct EntropyJob {
   // I pictures coded with sign data hiding (kvz_hip_intra_cost_model::signhide): every picture of the job, or -- with ctx_rows -- those whose model's row says so in
   // its last byte (KVZ_ENTROPY_ROW_SIGNHIDE; the contexts end at KVZ_ENTROPY_CTXS)
   int signhide;
+  // P pictures (kvz_hip_dev_entropy_code_inter_slices with KVZ_HIP_SLICE_P): every picture of the job is a P slice -- inter_pred_idc is not part of its syntax
+  // (encode_coding_tree.c:339); ctx_init / ctx_rows hold the P row's states
+  int p_slice;
 };
 #define KVZ_ENTROPY_CTX_ROW 176
 #define KVZ_ENTROPY_ROW_SIGNHIDE (KVZ_ENTROPY_CTX_ROW - 1)
@@ -439,9 +442,11 @@ struct EntropyCtuB {
       s.ctx(KVZ_EB_CX_MERGE_FLAG, cur.merged);
       if (cur.merged) merge_idx(s, cur.merge_idx);
       else {
-        const int inter_dir = cur.mv_dir - 1;
-        s.ctx(KVZ_EB_CX_INTER_DIR + depth, inter_dir == 2);
-        if (inter_dir < 2) s.ctx(KVZ_EB_CX_INTER_DIR + 4, inter_dir);
+        if (!J.p_slice) {  // inter_pred_idc: B slices only
+          const int inter_dir = cur.mv_dir - 1;
+          s.ctx(KVZ_EB_CX_INTER_DIR + depth, inter_dir == 2);
+          if (inter_dir < 2) s.ctx(KVZ_EB_CX_INTER_DIR + 4, inter_dir);
+        }
         for (int l = 0; l < 2; l++) {
           if (!(cur.mv_dir & (1 << l))) continue;
           i16 cand[2][2];

@@ -80,6 +80,28 @@ namespace kvz {
 #define KVZ_ICTU_ME_STATE KVZ_ICTU_ME
 #endif
 
+// The kernel's builds for P pictures (kvz_hip_dev_inter_ctu_pass_slices with KVZ_HIP_SLICE_P: kvazaar --no-bipred, a slice whose L1 is empty; kvz_inter_tu.hip
+// -DKVZ_ICTU_P=1): the L1 half of the program is not there.  merge_candidates takes the temporal candidate for L0 only, builds no combined candidates and fills
+// with zero candidates of dir 1 (inter.c:1471-1569); search_pu_inter searches and refines list 0 alone, with no elimination between two lists' second bests;
+// inter_pu_bits prices no inter_pred_idc (encode_coding_tree.c:339); predict_into predicts from one list.  The initial context states are the P row's: the model
+// brings them (kvz_inter_host.hpp inter_model_init).  A build constant on the device, so that the B builds hold none of it; the host simulation
+// (tests/hostsim/hostsim_inter_p.cpp) makes it a variable, as hostsim_inter_me.cpp does with KVZ_ICTU_ME.
+// NOT COVERED together with P: tiles, scaling lists, joint launches, the me_* members (kvz_inter_kernels.hpp refuses to compile the combinations, the entry point
+// refuses the launches); B and P pictures in one launch.
+#ifndef KVZ_ICTU_P
+#define KVZ_ICTU_P 0
+#endif
+#define IC_LISTS (KVZ_ICTU_P ? 1 : 2)  /* the reference picture lists the search goes through */
+#ifdef KVZ_HOSTSIM
+#define IC_LISTS_STATE 2
+#else
+#define IC_LISTS_STATE IC_LISTS
+#endif
+
+#ifndef IC_MERGE_ORIGIN  // where the entries of a PU's merge list come from: only tests/hostsim/hostsim_inter_p.cpp, which counts what the chosen candidates were, defines it
+#define IC_MERGE_ORIGIN(x, y, w, n_spatial, n_temporal, n_zero_from) ((void)(n_spatial), (void)(n_temporal))
+#endif
+
 #ifndef KVZ_ICTU_THREADS
 #define KVZ_ICTU_THREADS 64  // lanes per CTU.  Measured on the MI355X with 256 sequences in flight (416x240): 64 lanes 20.9 k CTUs/s, 128: 18.8 k, 256: 11.9 k
                              // -- the program is a chain of short phases, and with one wavefront per CTU a barrier costs nothing and more CTUs share a CU
@@ -363,7 +385,7 @@ struct InterLds {
   // Scalar work memory.  Every lane runs the same control flow on the same values, and with one wavefront per CTU the lanes are in lockstep: small arrays that are
   // indexed at run time live here once instead of 64 times in private (scratch) memory
   union {
-    UMap amvp[2];      // search_pu_inter's candidates of the two lists (dead once search_cu_inter has returned)
+    UMap amvp[IC_LISTS_STATE];  // search_pu_inter's candidates of the two lists -- of list 0 in the P builds -- (dead once search_cu_inter has returned)
     double costs[36];  // search_cu_intra's sort
   };
   UMap merge;

@@ -101,7 +101,7 @@ IC_DEV void mot_put(Mot5 &e, int n, const Mot &v)  // e[n] = v
 IC_DEV Mot mot_at(const Mot5 &e, int i) { return i == 0 ? e.e0 : (i == 1 ? e.e1 : (i == 2 ? e.e2 : (i == 3 ? e.e3 : e.e4))); }  // (i a constant where it is used)
 static_assert(sizeof(MCand) == 12, "a merge candidate is written as three words: mv[0], mv[1], ref[0] | ref[1] << 8 | dir << 16");
 
-// inter.c:1440-1572 kvz_inter_get_merge_cand, B slice with one reference picture
+// inter.c:1440-1572 kvz_inter_get_merge_cand, B slice -- or, KVZ_ICTU_P, P slice -- with one reference picture
 // into L->pu.merge
 IC_FN int merge_candidates(int x, int y, int w, int h)
 {
@@ -115,12 +115,15 @@ IC_FN int merge_candidates(int x, int y, int w, int h)
   if (mot_valid(c.b0) && !same_motion(c.b0, c.b1)) { mot_put(e, n, Mot{ c.b0.m0, c.b0.m1, c.b0.d & 0xffffffu }); n++; }
   if (mot_valid(c.a0) && !same_motion(c.a0, c.a1)) { mot_put(e, n, Mot{ c.a0.m0, c.a0.m1, c.a0.d & 0xffffffu }); n++; }
   if (n < 4 && mot_valid(c.b2) && !same_motion(c.b2, c.a1) && !same_motion(c.b2, c.b1)) { mot_put(e, n, Mot{ c.b2.m0, c.b2.m1, c.b2.d & 0xffffffu }); n++; }
+  const int n_spatial = n;
   if (n < max && (mot_valid(c.th) || mot_valid(c.tc))) {
     const Mot col = mot_sel(mot_valid(c.th), c.th, c.tc);
-    mot_put(e, n, Mot{ temporal_mv(col, 0), temporal_mv(col, 1), 3u });
+    if (KVZ_ICTU_P) mot_put(e, n, Mot{ temporal_mv(col, 0), 0u, 1u });  // inter.c:1479 max_reflist 0 in a P slice: list 0 only
+    else mot_put(e, n, Mot{ temporal_mv(col, 0), temporal_mv(col, 1), 3u });
     n++;
   }
-  if (n < max) {
+  const int n_temporal = n;
+  if (!KVZ_ICTU_P && n < max) {  // (inter.c:1504: combined bi-predictive candidates are a B slice's)
     // the pairs (0,1) (1,0) (0,2) (2,0) (1,2) (2,1) (0,3) (3,0) (1,3) (3,1) (2,3) (3,2) of inter.c:1518-1519, unrolled: every entry named by a constant
     const int pairs = n * (n - 1);
     bool go = true;
@@ -136,10 +139,14 @@ IC_FN int merge_candidates(int x, int y, int w, int h)
       }
     }
   }
-  const Mot fill = { 0u, 0u, 3u };
+  IC_MERGE_ORIGIN(x, y, w, n_spatial, n_temporal, n);  // (the host simulation's census: entries below n_spatial are neighbours', then the temporal one, from n on zero)
+  const Mot fill = { 0u, 0u, KVZ_ICTU_P ? 1u : 3u };  // inter.c:1556-1569: the zero candidates, dir 1 in a P slice
   e.e0 = mot_sel(n <= 0, fill, e.e0); e.e1 = mot_sel(n <= 1, fill, e.e1); e.e2 = mot_sel(n <= 2, fill, e.e2); e.e3 = mot_sel(n <= 3, fill, e.e3); e.e4 = mot_sel(n <= 4, fill, e.e4);
   // which entries repeat an earlier one (the merge analysis skips them, search_inter.c:1710-1730: it compares with the entries it kept -- an earlier equal entry was
   // kept, or was skipped for what skips this one too)
+  // (In a P slice too the reference compares the fields of list 1, which move no sample: a neighbour's record carries mv_ref[1] 255 from the search and 0 from a
+  // temporal or zero candidate it merged with, and an entry that repeats an earlier one's list-0 motion under another mv_ref[1] is evaluated, and can be the
+  // cheaper one to signal.  What inter.c:1476-1569 does not write of such an entry in a P slice -- mv[1], and ref[1] of the temporal one -- is zero here)
   auto same = [](const Mot &a, const Mot &b) { return a.m0 == b.m0 && a.m1 == b.m1 && a.d == b.d; };
   int dup = 0;
   if (same(e.e1, e.e0)) dup |= 2;
@@ -171,7 +178,7 @@ IC_DEV bool add_mvp(const Mot &cand, int reflist, u32 &mv)  // the candidate's v
   if (!mot_valid(cand)) return false;
   const u32 first = reflist ? 2u : 1u, second = reflist ? 1u : 2u;
   if (cand.d & first) { mv = reflist ? cand.m1 : cand.m0; return true; }
-  if (cand.d & second) { mv = reflist ? cand.m0 : cand.m1; return true; }
+  if (!KVZ_ICTU_P && (cand.d & second)) { mv = reflist ? cand.m0 : cand.m1; return true; }  // (no record of a P picture or of its reference moves by list 1)
   return false;
 }
 IC_DEV void store_mv32(i16 *p, u32 v)

@@ -944,8 +944,9 @@ IC_DEV void predict_into(int c, int x, int y, int w, const CuInfo &pu, lu8 *dst,
       lu8 *d = dst + ty * tw * ds + tx * tw;
       // (both lists hold the one reference picture: two lists with one vector average a block with itself -- (2 v + 64) >> 7 = (v + 32) >> 6 -- predicted as one list
       // whose 14-bit samples are still the wrapped int16 operands of two: mode 3)
-      const bool twice = pu.mv_dir == 3 && pu.mv[0][0] == pu.mv[1][0] && pu.mv[0][1] == pu.mv[1][1];
-      const int first = pu.mv_dir == 2 ? 1 : 0, lists = pu.mv_dir == 3 && !twice ? 2 : 1;
+      // (a P slice predicts from list 0 and nothing else: no second list, nothing to recognise)
+      const bool twice = !KVZ_ICTU_P && pu.mv_dir == 3 && pu.mv[0][0] == pu.mv[1][0] && pu.mv[0][1] == pu.mv[1][1];
+      const int first = !KVZ_ICTU_P && pu.mv_dir == 2 ? 1 : 0, lists = !KVZ_ICTU_P && pu.mv_dir == 3 && !twice ? 2 : 1;
       if (twice) IC_COUNT(27);
       for (int k = 0; k < lists; k++) {
         const bool second = first + k != 0;

@@ -59,7 +59,7 @@ IC_FN void search_pu_inter_ref(int depth)
   const decltype(InterLds::best) best = L->best;
   const bool valid = mv_allowed(best.mvx, best.mvy) && best.cost < IC_MAX_COST;
   const int mvp = select_mv_cand(best.mvx, best.mvy);
-  for (int list = 0; list < 2; list++) {
+  for (int list = 0; list < IC_LISTS; list++) {  // (a P slice's L1 is empty: search_inter.c:1237-1259 finds the picture in list 0 alone)
     if (!valid) continue;
     UMap *m = &amvp[list];
     const int e = m->size;
@@ -172,12 +172,14 @@ IC_FN bool search_pu_inter(int lv, int x, int y, int depth)
       }
     }
   }
-  amvp[0].size = amvp[1].size = 0;  // (kvazaar's third list, the bi-prediction search of search_inter.c:1919-2034, needs two reference pictures)
-  for (int d = 0; d < 2; d++) { amvp[d].cost[0] = IC_MAX_COST; amvp[d].keys[0] = 0; }
+  if (KVZ_ICTU_P) amvp[0].size = 0;
+  else amvp[0].size = amvp[1].size = 0;  // (kvazaar's third list, the bi-prediction search of search_inter.c:1919-2034, needs two reference pictures)
+  for (int d = 0; d < IC_LISTS; d++) { amvp[d].cost[0] = IC_MAX_COST; amvp[d].keys[0] = 0; }
   search_pu_inter_ref(depth);
-  sort_keys(&amvp[0]); sort_keys(&amvp[1]);
-  int best_keys[2] = { amvp[0].size > 0 ? amvp[0].keys[0] : 0, amvp[1].size > 0 ? amvp[1].keys[0] : 0 };
-  if (amvp[0].size > 0 && amvp[1].size > 0) {
+  sort_keys(&amvp[0]);
+  if (!KVZ_ICTU_P) sort_keys(&amvp[1]);
+  int best_keys[2] = { amvp[0].size > 0 ? amvp[0].keys[0] : 0, !KVZ_ICTU_P && amvp[1].size > 0 ? amvp[1].keys[0] : 0 };
+  if (!KVZ_ICTU_P && amvp[0].size > 0 && amvp[1].size > 0) {  // (search_inter.c:1831 cfg->bipred: a P slice has one list, nothing to eliminate)
     const double l0_2nd = amvp[0].size > 1 ? amvp[0].cost[amvp[0].keys[1]] : IC_MAX_COST, l1_2nd = amvp[1].size > 1 ? amvp[1].cost[amvp[1].keys[1]] : IC_MAX_COST;
     const int list = l0_2nd <= l1_2nd ? 1 : 0;
     amvp[list].cost[best_keys[list]] = IC_MAX_COST;
@@ -185,7 +187,7 @@ IC_FN bool search_pu_inter(int lv, int x, int y, int depth)
     amvp[list].size--;
     best_keys[list] = amvp[list].keys[0];
   }
-  for (int list = 0; list < 2; list++) {
+  for (int list = 0; list < IC_LISTS; list++) {
     const int n_best = amvp[list].size < 1 ? amvp[list].size : 1;
     if (M->fme_level > 0) {
       for (int i = 0; i < n_best; i++) {
@@ -218,7 +220,7 @@ IC_FN bool search_pu_inter(int lv, int x, int y, int depth)
     const int sk = skip_context(x, y);
     const double no_skip_flag = M->fbits[cab.s[IX_SKIP + sk] ^ 0], pred_mode_bits = M->fbits[cab.s[IX_PRED_MODE] ^ 0];
     const double total_bits = no_skip_flag + 0 + pred_mode_bits;
-    for (int i = 0; i < 2; i++) if (amvp[i].size > 0) {
+    for (int i = 0; i < IC_LISTS; i++) if (amvp[i].size > 0) {
       const int k = amvp[i].keys[0];
       amvp[i].bits[k] += total_bits;
       amvp[i].cost[k] += total_bits * M->lambda_sqrt;
@@ -238,7 +240,7 @@ IC_FN_INTER void search_cu_inter(int lv, int x, int y, int depth)
   *inter_bitcost = IC_MAX_INT;
   if (search_pu_inter(lv, x, y, depth)) { *inter_cost = merge.cost[0]; *inter_bitcost = merge.bits[0]; return; }
   int which = -1, wk = 0;
-  for (int d = 0; d < 2; d++) {
+  for (int d = 0; d < IC_LISTS; d++) {
     const int k = amvp[d].keys[0];
     if (amvp[d].size > 0 && amvp[d].cost[k] < *inter_cost) { which = d; wk = k; *inter_cost = amvp[d].cost[k]; *inter_bitcost = amvp[d].bits[k]; }
   }
@@ -284,10 +286,12 @@ IC_FN double inter_pu_bits(int x, int y, int depth, const CuInfo cu, bool update
   const int w = 64 >> depth;
   double bits = price(IX_MERGE_FLAG, cu.merged, update);
   if (cu.merged) return bits + merge_idx_bits(cu.merge_idx, update);
-  const int inter_dir = cu.mv_dir - 1;
-  bits += price(IX_INTER_DIR + depth, inter_dir == 2, update);
-  if (inter_dir < 2) bits += price(IX_INTER_DIR + 4, inter_dir, update);
-  for (int l = 0; l < 2; l++) {
+  if (!KVZ_ICTU_P) {  // inter_pred_idc is B-slice syntax (encode_coding_tree.c:339)
+    const int inter_dir = cu.mv_dir - 1;
+    bits += price(IX_INTER_DIR + depth, inter_dir == 2, update);
+    if (inter_dir < 2) bits += price(IX_INTER_DIR + 4, inter_dir, update);
+  }
+  for (int l = 0; l < IC_LISTS; l++) {
     if (!(cu.mv_dir & (1 << l))) continue;
     mv_candidates(x, y, w, w, l);
     const int k = cu.mv_cand[l];

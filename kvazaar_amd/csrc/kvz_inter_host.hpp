@@ -1,5 +1,5 @@
-// kvz_inter_host.hpp -- host side of the inter CTU pass (kvz_inter_ctu.hpp): the per-picture model (lambda, quantisation scalars, the B slice's context
-// initialisation, kvz_init_contexts context.c:202-305 with row 0 of the tables :36-193).
+// kvz_inter_host.hpp -- host side of the inter CTU pass (kvz_inter_ctu.hpp): the per-picture model (lambda, quantisation scalars, the B or P slice's context
+// initialisation, kvz_init_contexts context.c:202-305 with row 0 of the tables :36-193 or -- P -- their row 1, typed here from H.265 9.3.2.2).
 #pragma once
 #include <math.h>
 #include <stddef.h>
@@ -44,6 +44,55 @@ inline void b_slice_residual_init_values(uint8_t v[KVZ_HIP_CX_ABS_CHROMA + 2 - K
   for (int i = 0; i < 8; i++) v[KVZ_HIP_CX_ONE_CHROMA - b + i] = one[16 + i];
   for (int i = 0; i < 4; i++) v[KVZ_HIP_CX_ABS_LUMA - b + i] = absf[i];
   for (int i = 0; i < 2; i++) v[KVZ_HIP_CX_ABS_CHROMA - b + i] = absf[4 + i];
+}
+
+// ... and the P row of the same tables (H.265 9.3.2.2 Tables 9-26 to 9-31, initType 1: coded_sub_block_flag, sig_coeff_flag, last_sig_coeff_{x,y}_prefix,
+// coeff_abs_level_greater1_flag, coeff_abs_level_greater2_flag), in the same layout
+inline void p_slice_residual_init_values(uint8_t v[KVZ_HIP_CX_ABS_CHROMA + 2 - KVZ_HIP_CX_SIG_CG])
+{
+  static const uint8_t sig_cg[4] = { 121, 140, 61, 154 };
+  static const uint8_t sig[42] = { 155, 154, 139, 153, 139, 123, 123, 63, 153, 166, 183, 140, 136, 153, 154, 166, 183, 140, 136, 153, 154, 166, 183, 140, 136, 153, 154,
+                                   170, 153, 123, 123, 107, 121, 107, 121, 167, 151, 183, 140, 151, 183, 140 };
+  static const uint8_t last[30] = { 125, 110, 94, 110, 95, 79, 125, 111, 110, 78, 110, 111, 111, 95, 94, 108, 123, 108, 154, 154, 154, 154, 154, 154, 154, 154, 154, 154, 154, 154 };
+  static const uint8_t one[24] = { 154, 196, 196, 167, 154, 152, 167, 182, 182, 134, 149, 136, 153, 121, 136, 137, 169, 194, 166, 167, 154, 167, 137, 182 };
+  static const uint8_t absf[6] = { 107, 167, 91, 122, 107, 167 };
+  const int b = KVZ_HIP_CX_SIG_CG;
+  for (int i = 0; i < 4; i++) v[KVZ_HIP_CX_SIG_CG - b + i] = sig_cg[i];
+  for (int i = 0; i < 27; i++) v[KVZ_HIP_CX_SIG_LUMA - b + i] = sig[i];
+  for (int i = 0; i < 15; i++) {
+    v[KVZ_HIP_CX_SIG_CHROMA - b + i] = sig[27 + i];
+    v[KVZ_HIP_CX_LAST_Y_LUMA - b + i] = v[KVZ_HIP_CX_LAST_X_LUMA - b + i] = last[i];
+    v[KVZ_HIP_CX_LAST_Y_CHROMA - b + i] = v[KVZ_HIP_CX_LAST_X_CHROMA - b + i] = last[15 + i];
+  }
+  for (int i = 0; i < 16; i++) v[KVZ_HIP_CX_ONE_LUMA - b + i] = one[i];
+  for (int i = 0; i < 8; i++) v[KVZ_HIP_CX_ONE_CHROMA - b + i] = one[16 + i];
+  for (int i = 0; i < 4; i++) v[KVZ_HIP_CX_ABS_LUMA - b + i] = absf[i];
+  for (int i = 0; i < 2; i++) v[KVZ_HIP_CX_ABS_CHROMA - b + i] = absf[4 + i];
+}
+
+// The initial values of the syntax contexts an inter slice codes with, by name: the B row (initType 2) and the P row (initType 1) of H.265 Tables 9-5 to 9-25.
+// What both the search contexts (inter_model_init, IX_*) and the entropy coder's set (kvz_slice_contexts.hpp, KVZ_HIP_CX_* / KVZ_EB_CX_*) are filled from.
+// P differs from B in merge_flag, merge_idx, pred_mode_flag, abs_mvd_greater0_flag, prev_intra_luma_pred_flag, cbf_cb / cbf_cr at depth 1 and sao_type_idx.
+struct SliceSyntaxInit {
+  uint8_t split[3], skip[3], merge_flag, merge_idx, pred_mode, part, intra, chroma, cbf_luma[2], cbf_chroma[4], mvd[2], mvp_idx, inter_dir[5], root_cbf, sao_merge, sao_type;
+};
+inline const SliceSyntaxInit &slice_syntax_init(int slice_type)
+{
+  static const SliceSyntaxInit b = { { 107, 139, 126 }, { 197, 185, 201 }, 154, 137, 134, 154, 183, 152, { 153, 111 }, { 149, 92, 167, 154 }, { 169, 198 }, 168, { 95, 79, 63, 31, 31 }, 79, 153, 160 };
+  static const SliceSyntaxInit p = { { 107, 139, 126 }, { 197, 185, 201 }, 110, 122, 149, 154, 154, 152, { 153, 111 }, { 149, 107, 167, 154 }, { 140, 198 }, 168, { 95, 79, 63, 31, 31 }, 79, 153, 185 };
+  return slice_type == KVZ_HIP_SLICE_P ? p : b;
+}
+inline void slice_residual_init_values(int slice_type, uint8_t v[KVZ_HIP_CX_ABS_CHROMA + 2 - KVZ_HIP_CX_SIG_CG])
+{
+  if (slice_type == KVZ_HIP_SLICE_P) p_slice_residual_init_values(v); else b_slice_residual_init_values(v);
+}
+// a slice type the inter pass and the inter coder cover: B or P.  false and a message otherwise
+inline bool inter_slice_type_known(int slice_type, const char *who)
+{
+  if (slice_type == KVZ_HIP_SLICE_B || slice_type == KVZ_HIP_SLICE_P) return true;
+  if (slice_type == KVZ_HIP_SLICE_I) fprintf(stderr, "%s: slice type I (%d): an I picture has no inter pass and no inter coder (kvz_hip_batch.h)\n", who, slice_type);
+  else fprintf(stderr, "%s: slice type %d is none of KVZ_HIP_SLICE_B (0), KVZ_HIP_SLICE_P (1), KVZ_HIP_SLICE_I (2)\n", who, slice_type);
+  return false;
 }
 
 // The geometry kvz_hip_dev_inter_ctu_pass[_tiles] covers: pictures of whole 8x8 blocks up to 255 CTUs a side (the ticket packs the CTU column and row into a byte each),
@@ -95,11 +144,28 @@ inline bool inter_me_known(const kvz_hip_inter_params *p, const char *excluded, 
   }
   return true;
 }
+// The slice type of a launch (kvz_hip_dev_inter_ctu_pass_slices, kvz_hip_dev_entropy_code_inter_slices): what those entry points refuse of it before anything is
+// queued -- false and a message: a type that is neither B nor P, and P together with what the P builds do not cover (tiles; a chosen integer search)
+inline bool inter_slice_launch_known(const kvz_hip_inter_params *p, bool has_tile_xy, int slice_type, const char *who)
+{
+  if (!inter_slice_type_known(slice_type, who)) return false;
+  if (slice_type != KVZ_HIP_SLICE_P) return true;
+  if (p->ref_width || p->ref_height || p->tile_x || p->tile_y || has_tile_xy) {
+    fprintf(stderr, "%s: P pictures are not covered together with tiles (ref_width %d, ref_height %d, tile_x %d, tile_y %d%s)\n", who, p->ref_width, p->ref_height, p->tile_x, p->tile_y, has_tile_xy ? ", tile_xy" : "");
+    return false;
+  }
+  if (inter_me_chosen(p)) {
+    fprintf(stderr, "%s: P pictures are not covered together with me_algorithm / me_max_steps / me_early_termination (%d, %d, %d)\n", who, p->me_algorithm, p->me_max_steps, p->me_early_termination);
+    return false;
+  }
+  return true;
+}
 inline void inter_model_set_me(InterModel *m, const kvz_hip_inter_params *p) { m->me_algorithm = p->me_algorithm; m->me_max_steps = p->me_max_steps; m->me_early_termination = p->me_early_termination; }
 
 inline void inter_model_init(InterModel *m, int qp, int poc, uint64_t coeff_weights, const float fbits[128], int mv_constraint, int sao, int deblock, int fme_level,
                              int pu_depth_inter_max, int no_wpp, int fast_residual_cost, int pic_w = 0, int pic_h = 0, int ref_w = 0, int ref_h = 0, int tile_x = 0, int tile_y = 0, int no_tmvp = 0,
-                             int scaling_list = 0 /* a launch with scaling lists: the inverse scalars of the rule that takes a factor per position (quant-generic.c:309-333) */)
+                             int scaling_list = 0 /* a launch with scaling lists: the inverse scalars of the rule that takes a factor per position (quant-generic.c:309-333) */,
+                             int slice_type = KVZ_HIP_SLICE_B /* or KVZ_HIP_SLICE_P: the row of the tables the initial context states come from */)
 {
   memset(m, 0, sizeof *m);
   m->qp = qp; m->poc = poc;
@@ -112,18 +178,18 @@ inline void inter_model_init(InterModel *m, int qp, int poc, uint64_t coeff_weig
   m->mv_constraint = mv_constraint; m->sao = sao; m->deblock = deblock; m->fme_level = fme_level; m->pu_depth_inter_max = pu_depth_inter_max; m->no_wpp = no_wpp;
   uint8_t init[IX_COUNT];
   memset(init, 154, sizeof init);
-  const uint8_t split[3] = { 107, 139, 126 }, skip[3] = { 197, 185, 201 }, inter_dir[5] = { 95, 79, 63, 31, 31 };
-  for (int i = 0; i < 3; i++) { init[IX_SPLIT + i] = split[i]; init[IX_SKIP + i] = skip[i]; }
-  init[IX_MERGE_FLAG] = 154; init[IX_MERGE_IDX] = 137; init[IX_PRED_MODE] = 134; init[IX_PART] = 154; init[IX_INTRA] = 183; init[IX_CHROMA] = 152;
-  init[IX_CBF_LUMA] = 153; init[IX_CBF_LUMA + 1] = 111; init[IX_CBF_CHROMA] = 149; init[IX_CBF_CHROMA + 1] = 92;
-  init[IX_MVD] = 169; init[IX_MVD + 1] = 198; init[IX_MVP_IDX] = 168;
-  for (int i = 0; i < 5; i++) init[IX_INTER_DIR + i] = inter_dir[i];
-  init[IX_ROOT_CBF] = 79;
-  b_slice_residual_init_values(init + IX_RES);
+  const SliceSyntaxInit &v = slice_syntax_init(slice_type);
+  for (int i = 0; i < 3; i++) { init[IX_SPLIT + i] = v.split[i]; init[IX_SKIP + i] = v.skip[i]; }
+  init[IX_MERGE_FLAG] = v.merge_flag; init[IX_MERGE_IDX] = v.merge_idx; init[IX_PRED_MODE] = v.pred_mode; init[IX_PART] = v.part; init[IX_INTRA] = v.intra; init[IX_CHROMA] = v.chroma;
+  init[IX_CBF_LUMA] = v.cbf_luma[0]; init[IX_CBF_LUMA + 1] = v.cbf_luma[1]; init[IX_CBF_CHROMA] = v.cbf_chroma[0]; init[IX_CBF_CHROMA + 1] = v.cbf_chroma[1];
+  init[IX_MVD] = v.mvd[0]; init[IX_MVD + 1] = v.mvd[1]; init[IX_MVP_IDX] = v.mvp_idx;
+  for (int i = 0; i < 5; i++) init[IX_INTER_DIR + i] = v.inter_dir[i];
+  init[IX_ROOT_CBF] = v.root_cbf;
+  slice_residual_init_values(slice_type, init + IX_RES);
   for (int i = 0; i < IX_COUNT; i++) m->ctx_init[i] = (uint8_t)inter_ctx_state(qp, init[i]);
   for (int l2 = 2; l2 <= 5; l2++)
     for (int c = 0; c < 2; c++) {
-      m->qf[c][l2 - 2] = quant_scalars(qp, 8, 0 /* B slice: rounding 85 */, 0, 1 << l2, c ? 2 : 0);
+      m->qf[c][l2 - 2] = quant_scalars(qp, 8, 0 /* B and P slices: rounding 85, the non-intra one */, 0, 1 << l2, c ? 2 : 0);
       m->qi[c][l2 - 2] = quant_scalars(qp, 8, 0, scaling_list, 1 << l2, c ? 2 : 0);
     }
   memcpy(m->fbits, fbits, sizeof m->fbits);

@@ -39,6 +39,18 @@ def me_search_fields(me="hexbs", me_steps=-1, me_early_termination="sensitive"):
     return dict(me_algorithm=ME_ALGORITHMS[me], me_max_steps=0 if me_steps == -1 else int(me_steps), me_early_termination=ME_EARLY_TERMINATION[me_early_termination])
 
 
+SLICE_TYPES = {"B": 0, "P": 1, "I": 2}  # KVZ_HIP_SLICE_* (include/kvz_hip_types.h), kvazaar's enum kvz_slices
+
+
+def slice_type_value(slice_type):
+    """"B" / "P" / "I" (or the KVZ_HIP_SLICE_* number itself, which the library checks) -> the argument of the kvz_hip_dev_*_slices entry points"""
+    if isinstance(slice_type, str):
+        if slice_type not in SLICE_TYPES:
+            raise ValueError(f"slice type {slice_type!r}: one of {', '.join(SLICE_TYPES)}")
+        return SLICE_TYPES[slice_type]
+    return int(slice_type)
+
+
 class InterPicturesStruct(C.Structure):  # kvz_hip_inter_pictures
     _fields_ = [("struct_size", C.c_uint32), ("n_pictures", C.c_int32), ("qp", C.c_void_p), ("poc", C.c_void_p)]
 
@@ -146,6 +158,13 @@ class InterPictures:
         if hasattr(lib, "kvz_hip_dev_inter_ctu_pass_lists"):  # (a library from before the entry point still loads: tools/bench_inter_scaling_lists.py times one)
             lib.kvz_hip_dev_inter_ctu_pass_lists.restype = C.c_int
             lib.kvz_hip_dev_inter_ctu_pass_lists.argtypes = [C.c_void_p] * 6 + [C.c_int] * 3 + [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        if hasattr(lib, "kvz_hip_dev_inter_ctu_pass_slices"):  # (likewise: tools/bench_inter_p.py times the library of the parent commit)
+            lib.kvz_hip_dev_inter_ctu_pass_slices.restype = C.c_int
+            lib.kvz_hip_dev_inter_ctu_pass_slices.argtypes = [C.c_void_p] * 6 + [C.c_int] * 3 + [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+            lib.kvz_hip_dev_loop_filters_inter_slices.restype = C.c_int
+            lib.kvz_hip_dev_loop_filters_inter_slices.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 3
+            lib.kvz_hip_dev_entropy_code_inter_slices.restype = C.c_long
+            lib.kvz_hip_dev_entropy_code_inter_slices.argtypes = [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int]
         self.d_dbk = None
         lib.kvz_hip_dev_entropy_code_inter.restype = C.c_long
         lib.kvz_hip_dev_entropy_code_inter.argtypes = [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
@@ -186,9 +205,19 @@ class InterPictures:
         """the object is again what it was before the first set_scaling_lists"""
         self.set_scaling_lists([])
 
-    def run(self, params, pictures=None):
+    def run(self, params, pictures=None, slice_type="B"):
         """the CTU pass of the n pictures; pictures (InterPictureParams): every picture at its own QP and POC instead of params.qp / params.poc.  While the object
-        holds scaling lists (set_scaling_lists) the launch is kvz_hip_dev_inter_ctu_pass_lists"""
+        holds scaling lists (set_scaling_lists) the launch is kvz_hip_dev_inter_ctu_pass_lists.
+        slice_type: "B" (the default: the calls this method has always made) or "P" -- kvazaar's --no-bipred -- through kvz_hip_dev_inter_ctu_pass_slices, as is
+        every slice type given as a KVZ_HIP_SLICE_* number.  P pictures take no scaling lists"""
+        if slice_type != "B":
+            if self._n_list_sets:
+                raise ValueError("scaling lists are set: kvz_hip_dev_inter_ctu_pass_lists has no slice type, its pictures are B (clear_scaling_lists())")
+            rc = self.lib.kvz_hip_dev_inter_ctu_pass_slices(self.d_src, self.d_ref, self.d_ref_cu, self.d_rec, self.d_cu, self.d_coeff, self.w, self.h, self.n, C.addressof(params), None, 0,
+                                                            pictures.ptr if pictures is not None else None, slice_type_value(slice_type))
+            if rc != 0:
+                raise RuntimeError(f"kvz_hip_dev_inter_ctu_pass_slices returned {rc}")
+            return
         if self._n_list_sets:
             rc = self.lib.kvz_hip_dev_inter_ctu_pass_lists(self.d_src, self.d_ref, self.d_ref_cu, self.d_rec, self.d_cu, self.d_coeff, self.w, self.h, self.n, C.addressof(params), None, 0,
                                                            pictures.ptr if pictures is not None else None, C.addressof(self._list_sets), self._n_list_sets,
@@ -221,12 +250,21 @@ class InterPictures:
         self._source_sets = getattr(self, "_source_sets", [self.d_src])
         self.d_src = self._source_sets[k]
 
-    def loop_filters(self, params, slice_is_b=True, pictures=None):
+    def loop_filters(self, params, slice_is_b=True, pictures=None, slice_type=None):
         """deblocking and SAO of the pictures the pass just produced, in place (kvz_hip_dev_loop_filters_inter): d_rec becomes what the next picture predicts from.
-        pictures (InterPictureParams): every picture at its own QP (kvz_hip_dev_loop_filters_inter_pictures)"""
+        pictures (InterPictureParams): every picture at its own QP (kvz_hip_dev_loop_filters_inter_pictures).
+        slice_type: None (slice_is_b says it, as it always has: B, or the I slice's rules) or "B" / "P" / "I" through kvz_hip_dev_loop_filters_inter_slices"""
         if self.d_dbk is None:
             self.d_dbk = self.dev.empty(self.n * self.cells * 20)  # kvz_hip_cu_dbk
         self.lib.kvz_hip_dev_cu_dbk_from_info(self.d_cu, self.n * self.cells, self.d_dbk)
+        if slice_type is not None:
+            if pictures is not None and len(pictures) != self.n:
+                raise ValueError(f"{len(pictures)} picture QPs for {self.n} pictures")
+            rc = self.lib.kvz_hip_dev_loop_filters_inter_slices(self.d_src, self.d_rec, self.w, self.h, self.n, self.d_dbk, params.qp, pictures.qps.ctypes.data if pictures is not None else None,
+                                                                slice_type_value(slice_type), params.deblock, 0, 0, params.sao, params.no_wpp, None, None, None)
+            if rc != 0:
+                raise RuntimeError(f"kvz_hip_dev_loop_filters_inter_slices returned {rc}")
+            return
         if pictures is not None:
             if len(pictures) != self.n:
                 raise ValueError(f"{len(pictures)} picture QPs for {self.n} pictures")
@@ -240,9 +278,10 @@ class InterPictures:
         if rc != 0:
             raise RuntimeError(f"kvz_hip_dev_loop_filters_inter returned {rc}")
 
-    def entropy_code(self, params, pictures=None):
+    def entropy_code(self, params, pictures=None, slice_type="B"):
         """kvz_hip_dev_entropy_code_inter: the slice data of the pictures the pass just produced (after loop_filters when params.sao: their SAO decisions are coded).
         pictures (InterPictureParams): every picture at its own QP and POC (kvz_hip_dev_entropy_code_inter_pictures).
+        slice_type: "B" (the default: the calls this method has always made) or "P" through kvz_hip_dev_entropy_code_inter_slices.
         -> (bytes of all substreams back to back, sizes [sequence][substream])"""
         if self.d_coeff is None:
             raise RuntimeError("InterPictures(..., with_levels=True) keeps the levels the entropy coder needs")
@@ -253,7 +292,10 @@ class InterPictures:
             from .batch import pinned_bytes
             self._entropy_ptr, self._entropy_out = pinned_bytes(self.lib, capacity)  # pinned: the call downloads the slice data straight into it
         sizes = np.zeros((self.n, rows), np.uint32)
-        if pictures is not None:
+        if slice_type != "B":
+            total = self.lib.kvz_hip_dev_entropy_code_inter_slices(self.d_cu, self.d_ref_cu, self.d_coeff, self.w, self.h, self.n, C.addressof(params), self._entropy_out.ctypes.data,
+                                                                   capacity, sizes.ctypes.data, pictures.ptr if pictures is not None else None, slice_type_value(slice_type))
+        elif pictures is not None:
             total = self.lib.kvz_hip_dev_entropy_code_inter_pictures(self.d_cu, self.d_ref_cu, self.d_coeff, self.w, self.h, self.n, C.addressof(params), self._entropy_out.ctypes.data,
                                                                      capacity, sizes.ctypes.data, pictures.ptr)
         else:
