@@ -289,6 +289,34 @@ int  kvz_hip_dev_loop_filters_inter_slices(const uint8_t *src, uint8_t *rec, int
 long kvz_hip_dev_entropy_code_inter_slices(const kvz_hip_cu_info *cu, const kvz_hip_cu_info *ref_cu, const int16_t *coeff, int width, int height, int n_pictures,
                                            const kvz_hip_inter_params *params, uint8_t *out, size_t capacity, uint32_t *substream_bytes,
                                            const kvz_hip_inter_pictures *pictures, int slice_type);
+/* P pictures with reference lists of 1 .. 4 pictures (kvazaar --no-bipred --ref N, HM's low-delay P; kvz_hip_inter_refs, kvz_hip_types.h): the three stages with the
+ * arguments of their _slices twins and `refs`.  refs == NULL: each IS its _slices twin.  With refs, `ref` and `ref_cu` hold the refs->n_frames frames of a POOL
+ * (not one frame per picture), picture i predicts from the frames refs->ref_frame[i][0 .. n_refs[i] - 1], and pictures->poc[i] is its POC.  Pictures with lists of
+ * different lengths, QPs and POCs share a launch; each comes out as from a launch of its own.
+ *  - the pass (kernel builds of their own, -DKVZ_ICTU_P=1 -DKVZ_ICTU_REFS=1) searches every picture of the list (search_inter.c:1237-1435, 1807-1830) from that
+ *    picture's own scaled co-located start vector against AMVP predictors derived for that reference index (unscaled neighbour of the same picture first, then the
+ *    scaled one: inter.c:1183-1310), refines the cheapest, prices ref_idx_l0 in its mock encode; merge candidates carry their reference index, the temporal one is
+ *    scaled to L0[0] from the co-located picture L0[0], zero candidates step through the list (inter.c:1471-1569).  MV scaling is inter.c:1078-1103 exactly, as
+ *    factors the host lays into the picture's record (kvz_inter_refs.hpp): the kernel divides no integers.  Records leave with mv_ref[0] = the index into the list.
+ *  - the coder writes ref_idx_l0 (truncated unary: two context-coded bins, then bypass; contexts from the P row of H.265 Table 9-17) for a picture whose list has
+ *    more than one entry, and derives the MVD's predictors with the same scaling.  `ref_cu` is the pool; the co-located picture is the frame of L0[0].
+ *  - kvz_hip_dev_loop_filters_inter_refs is a thin form: a P slice has one list, so two reference indices are the same picture exactly when they are equal, which
+ *    is what the deblocking kernels compare for a slice that is not B.  It checks refs and runs kvz_hip_dev_loop_filters_inter_slices.
+ * Refused with -1 and a message before anything is queued, besides what the _slices twins refuse: a struct_size that is not this library's, refs->n_pictures !=
+ * n_pictures, a NULL array, n_frames < 1, n_refs outside 1 .. 4, a frame index outside the pool, two entries of a list naming frames of the same POC, a reference
+ * POC not below the picture's; refs without `pictures`; refs with a slice type other than KVZ_HIP_SLICE_P; refs with tiles (already refused for P), with a non-zero
+ * me_* member (likewise), or -- they have no entry point with refs -- scaling lists and joint launches.
+ * NOT COVERED: B pictures with several references, kvazaar's --gop 8 and its fixed lowdelay4 table (encoder.c:172, what --gop lp-g4d3t1 --ref 4 selects),
+ * kvz_hip_dev_pu_search, the kvazaar-side binding (integration/), bench.py. */
+int  kvz_hip_dev_inter_ctu_pass_refs(const uint8_t *src, const uint8_t *ref, const kvz_hip_cu_info *ref_cu, uint8_t *rec, kvz_hip_cu_info *cu, int16_t *coeff, int width,
+                                     int height, int n_pictures, const kvz_hip_inter_params *params, const int32_t *tile_xy, int n_references,
+                                     const kvz_hip_inter_pictures *pictures, int slice_type, const kvz_hip_inter_refs *refs);
+int  kvz_hip_dev_loop_filters_inter_refs(const uint8_t *src, uint8_t *rec, int width, int height, int n_pictures, const kvz_hip_cu_dbk *info, int qp,
+                                         const int32_t *qp_of_picture, int slice_type, int deblock, int beta_offset_div2, int tc_offset_div2, int sao, int no_wpp,
+                                         kvz_hip_sao_params *luma, kvz_hip_sao_params *chroma, uint8_t *merge, const kvz_hip_inter_refs *refs);
+long kvz_hip_dev_entropy_code_inter_refs(const kvz_hip_cu_info *cu, const kvz_hip_cu_info *ref_cu, const int16_t *coeff, int width, int height, int n_pictures,
+                                         const kvz_hip_inter_params *params, uint8_t *out, size_t capacity, uint32_t *substream_bytes,
+                                         const kvz_hip_inter_pictures *pictures, int slice_type, const kvz_hip_inter_refs *refs);
 /* what the deblocking filter reads (kvz_hip_cu_dbk) of `count` CU records: type, depth, tr_depth, the luma coded block flag at tr_depth, motion */
 void kvz_hip_dev_cu_dbk_from_info(const kvz_hip_cu_info *cu, int count, kvz_hip_cu_dbk *out);
 

@@ -201,6 +201,23 @@ typedef struct kvz_hip_inter_group {
  * picture here has the previous picture in both lists (--gop lp-g4d3t1 with --bipred 1), a P picture has it in L0 and an empty L1 (--no-bipred). */
 enum { KVZ_HIP_SLICE_B = 0, KVZ_HIP_SLICE_P = 1, KVZ_HIP_SLICE_I = 2 };
 
+/* The reference picture lists of the P pictures of ONE launch (kvazaar --ref N with --no-bipred; the kvz_hip_dev_*_refs entry points, kvz_hip_dev.h): a pool of
+ * reference frames and, per picture, its list L0 as 1 .. 4 indices into the pool.  The call's `ref` and `ref_cu` then hold the n_frames frames of the pool in the
+ * layouts of kvz_hip_dev_inter_ctu_pass (a frame after its loop filters, its CU records), not one frame per picture.  A P slice has one list, so a reference index
+ * of a CU record (mv_ref[0]) is an index into the picture's row of ref_frame.  HOST arrays.  struct_size: sizeof of the caller's headers; an unknown size is
+ * refused with -1. */
+#define KVZ_HIP_MAX_REFS 4
+typedef struct kvz_hip_inter_refs {
+  uint32_t struct_size;
+  int32_t  n_pictures;           /* the n_pictures of the call */
+  int32_t  n_frames;             /* frames in `ref` / `ref_cu` */
+  const int32_t *frame_poc;      /* [n_frames]: POC of each frame of the pool */
+  const int32_t *frame_ref_poc;  /* [n_frames][4]: POC of the picture that index i of that frame's OWN L0 pointed to when it was coded (what a co-located vector is
+                                  * scaled by, inter.c:1173-1179); the row of an I frame is not read */
+  const int32_t *n_refs;         /* [n_pictures]: 1 .. 4, the length of the picture's L0 */
+  const int32_t *ref_frame;      /* [n_pictures][4]: pool index of entry i of the picture's L0, in list order; entries from n_refs on are not read */
+} kvz_hip_inter_refs;
+
 /* Per-CTU result record of the batched pass: what kvazaar keeps in cu_array / lcu_t for the CTU. */
 #define KVZ_HIP_CTU_COEFFS 6144 /* 64*64 Y + 32*32 U + 32*32 V coefficients, each plane in lcu_t z-order (cu.h:385-421) */
 

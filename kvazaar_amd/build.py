@@ -2,7 +2,7 @@
 
 The library's translation units are compiled in parallel: kvz_hip.hip (C ABI, per-call ops, streaming kernels, host side of the batch; with
 -DKVZ_CTU_SEPARATE_TUS it only declares the CTU kernels), kvz_ctu_tu.hip once per unit of the list in csrc/kvz_ctu_builds.hpp, one CTU kernel instantiation each
-(-DKVZ_CTU_KERNEL_TU=<unit>), and kvz_inter_tu.hip ten times (the inter CTU pass with and without the residual coder's contexts: plain, with scaling lists, for joint launches, with a chosen integer motion search, for P pictures).  Objects are rebuilt when one of the files they include (hipcc -MD) is newer."""
+(-DKVZ_CTU_KERNEL_TU=<unit>), and kvz_inter_tu.hip twelve times (the inter CTU pass with and without the residual coder's contexts: plain, with scaling lists, for joint launches, with a chosen integer motion search, for P pictures, for P pictures with reference lists).  Objects are rebuilt when one of the files they include (hipcc -MD) is newer."""
 import os
 import re
 import subprocess
@@ -30,7 +30,9 @@ UNITS = ([("kvz_hip", "kvz_hip.hip", ["-DKVZ_CTU_SEPARATE_TUS"] + MFMA_VGPR_FORM
          + [("kvz_inter_tu6", "kvz_inter_tu.hip", ["-DKVZ_ICTU_ME=1", "-DKVZ_ICTU_CABAC=0"]),  # ... and the two for launches that choose the integer motion search (--me, --me-steps, --me-early-termination)
             ("kvz_inter_tu7", "kvz_inter_tu.hip", ["-DKVZ_ICTU_ME=1", "-DKVZ_ICTU_CABAC=1"])]
          + [("kvz_inter_tu8", "kvz_inter_tu.hip", ["-DKVZ_ICTU_P=1", "-DKVZ_ICTU_CABAC=0"]),  # ... and the two for launches of P pictures (--no-bipred: the program without its L1 half)
-            ("kvz_inter_tu9", "kvz_inter_tu.hip", ["-DKVZ_ICTU_P=1", "-DKVZ_ICTU_CABAC=1"])])
+            ("kvz_inter_tu9", "kvz_inter_tu.hip", ["-DKVZ_ICTU_P=1", "-DKVZ_ICTU_CABAC=1"])]
+         + [("kvz_inter_tu10", "kvz_inter_tu.hip", ["-DKVZ_ICTU_P=1", "-DKVZ_ICTU_REFS=1", "-DKVZ_ICTU_CABAC=0"]),  # ... and the two for launches of P pictures with reference lists of 1 .. 4 pictures (--ref N)
+            ("kvz_inter_tu11", "kvz_inter_tu.hip", ["-DKVZ_ICTU_P=1", "-DKVZ_ICTU_REFS=1", "-DKVZ_ICTU_CABAC=1"])])
 
 
 def _deps(dfile):

@@ -1416,6 +1416,21 @@ int kvz_hip_dev_loop_filters_inter_slices(const uint8_t *src, uint8_t *rec, int 
   if (qp_of_picture && !kvz::inter_picture_qps_known(qp_of_picture, n_pictures, "kvz_hip_dev_loop_filters_inter_slices")) return -1;
   return kvz_loop_filters_inter_run(src, rec, width, height, n_pictures, info, qp_of_picture ? 0 : qp, qp_of_picture, slice_type, deblock, beta_offset_div2, tc_offset_div2, sao, no_wpp, luma, chroma, merge);
 }
+// ... of P pictures with reference lists (kvz_hip_dev.h): a thin form.  A P slice has one list, so two reference indices name the same picture exactly when they are
+// equal, and that is what dbk_strength compares for a slice that is not B: the kernels need nothing new.  refs == NULL is kvz_hip_dev_loop_filters_inter_slices; with
+// refs the table is checked (the filters read no POC, so the order of the POCs is not) and the slice type must be P
+int kvz_hip_dev_loop_filters_inter_refs(const uint8_t *src, uint8_t *rec, int width, int height, int n_pictures, const kvz_hip_cu_dbk *info, int qp, const int32_t *qp_of_picture,
+                                        int slice_type, int deblock, int beta_offset_div2, int tc_offset_div2, int sao, int no_wpp, kvz_hip_sao_params *luma,
+                                        kvz_hip_sao_params *chroma, uint8_t *merge, const kvz_hip_inter_refs *refs)
+{
+  if (n_pictures <= 0) return 0;
+  if (refs && slice_type != KVZ_HIP_SLICE_B && slice_type != KVZ_HIP_SLICE_P && slice_type != KVZ_HIP_SLICE_I) {
+    fprintf(stderr, "kvz_hip_dev_loop_filters_inter_refs: slice type %d is none of KVZ_HIP_SLICE_B (0), KVZ_HIP_SLICE_P (1), KVZ_HIP_SLICE_I (2)\n", slice_type);
+    return -1;
+  }
+  if (!kvz::inter_refs_launch_known(refs, n_pictures, true, nullptr, slice_type, "kvz_hip_dev_loop_filters_inter_refs")) return -1;
+  return kvz_hip_dev_loop_filters_inter_slices(src, rec, width, height, n_pictures, info, qp, qp_of_picture, slice_type, deblock, beta_offset_div2, tc_offset_div2, sao, no_wpp, luma, chroma, merge);
+}
 static int kvz_loop_filters_inter_run(const uint8_t *src, uint8_t *rec, int width, int height, int n_pictures, const kvz_hip_cu_dbk *info, int qp, const int32_t *qp_host, int slice_type,
                                       int deblock, int beta_offset_div2, int tc_offset_div2, int sao, int no_wpp, kvz_hip_sao_params *luma, kvz_hip_sao_params *chroma, uint8_t *merge)
 {
@@ -1558,7 +1573,7 @@ int kvz_hip_dev_inter_ctu_pass_pictures(const uint8_t *src, const uint8_t *ref, 
 }
 static int kvz_inter_ctu_pass_run(const uint8_t *src, const uint8_t *ref, const kvz_hip_cu_info *ref_cu, uint8_t *rec, kvz_hip_cu_info *cu, int16_t *coeff, int width,
                                   int height, int n_pictures, const kvz_hip_inter_params *p, const int32_t *tile_xy, int n_references,
-                                  const kvz_hip_inter_pictures *pictures, const kvz_hip_scaling_lists *sets, int n_sets, const uint16_t *set_of_picture, int slice_type);
+                                  const kvz_hip_inter_pictures *pictures, const kvz_hip_scaling_lists *sets, int n_sets, const uint16_t *set_of_picture, int slice_type, const kvz_hip_inter_refs *refs = nullptr);
 // pictures == nullptr: p->qp / p->poc for every picture (kvz_hip_dev_inter_ctu_pass[_tiles]); n_sets == 0: no scaling lists (kvz_hip_dev_inter_ctu_pass_pictures)
 int kvz_hip_dev_inter_ctu_pass_lists(const uint8_t *src, const uint8_t *ref, const kvz_hip_cu_info *ref_cu, uint8_t *rec, kvz_hip_cu_info *cu, int16_t *coeff, int width,
                                      int height, int n_pictures, const kvz_hip_inter_params *p, const int32_t *tile_xy, int n_references,
@@ -1573,10 +1588,17 @@ int kvz_hip_dev_inter_ctu_pass_slices(const uint8_t *src, const uint8_t *ref, co
 {
   return kvz_inter_ctu_pass_run(src, ref, ref_cu, rec, cu, coeff, width, height, n_pictures, p, tile_xy, n_references, pictures, nullptr, 0, nullptr, slice_type);
 }
-// slice_type: KVZ_HIP_SLICE_B, or -- kvz_hip_dev_inter_ctu_pass_slices only -- what that entry point was handed
+// ... of P pictures with reference lists (kvz_hip_dev.h): refs == NULL is kvz_hip_dev_inter_ctu_pass_slices; with refs, ref / ref_cu are the pool of refs->n_frames frames
+int kvz_hip_dev_inter_ctu_pass_refs(const uint8_t *src, const uint8_t *ref, const kvz_hip_cu_info *ref_cu, uint8_t *rec, kvz_hip_cu_info *cu, int16_t *coeff, int width,
+                                    int height, int n_pictures, const kvz_hip_inter_params *p, const int32_t *tile_xy, int n_references,
+                                    const kvz_hip_inter_pictures *pictures, int slice_type, const kvz_hip_inter_refs *refs)
+{
+  return kvz_inter_ctu_pass_run(src, ref, ref_cu, rec, cu, coeff, width, height, n_pictures, p, tile_xy, n_references, pictures, nullptr, 0, nullptr, slice_type, refs);
+}
+// slice_type: KVZ_HIP_SLICE_B, or -- kvz_hip_dev_inter_ctu_pass_slices / _refs only -- what that entry point was handed; refs: kvz_hip_dev_inter_ctu_pass_refs only
 static int kvz_inter_ctu_pass_run(const uint8_t *src, const uint8_t *ref, const kvz_hip_cu_info *ref_cu, uint8_t *rec, kvz_hip_cu_info *cu, int16_t *coeff, int width,
                                   int height, int n_pictures, const kvz_hip_inter_params *p, const int32_t *tile_xy, int n_references,
-                                  const kvz_hip_inter_pictures *pictures, const kvz_hip_scaling_lists *sets, int n_sets, const uint16_t *set_of_picture, int slice_type)
+                                  const kvz_hip_inter_pictures *pictures, const kvz_hip_scaling_lists *sets, int n_sets, const uint16_t *set_of_picture, int slice_type, const kvz_hip_inter_refs *refs)
 {
   if (n_pictures <= 0) return 0;
   kvz_hip_inter_params full;
@@ -1586,6 +1608,8 @@ static int kvz_inter_ctu_pass_run(const uint8_t *src, const uint8_t *ref, const 
   const int refused = kvz::inter_pass_geometry_refused(width, height, n_pictures, p->ref_width, p->ref_height, p->tile_x, p->tile_y);
   if (refused == 1) { fprintf(stderr, "kvz_hip_dev_inter_ctu_pass: bad geometry\n"); return -1; }
   if (pictures && !kvz::inter_pictures_known(pictures, n_pictures, "kvz_hip_dev_inter_ctu_pass_pictures")) return -1;
+  if (!kvz::inter_refs_launch_known(refs, n_pictures, pictures != nullptr, pictures ? pictures->poc : nullptr, slice_type, "kvz_hip_dev_inter_ctu_pass_refs")) return -1;
+  if (refs && n_references > 0) { fprintf(stderr, "kvz_hip_dev_inter_ctu_pass_refs: n_references %d belongs to tiles of shared frames, which reference lists are not covered with\n", n_references); return -1; }
   if (!pictures && (p->qp < 0 || p->qp > 51)) { fprintf(stderr, "kvz_hip_dev_inter_ctu_pass: picture QP %d outside 0..51\n", p->qp); return -1; }
   if (p->fme_level < 0 || p->fme_level > 4 || p->pu_depth_inter_max < 1 || p->pu_depth_inter_max > 3 || (!pictures && p->poc < 1) || p->fast_residual_cost < 0 || p->fast_residual_cost > 51) { fprintf(stderr, "kvz_hip_dev_inter_ctu_pass: unsupported parameters\n"); return -1; }
   if (refused) {  // the pictures are tiles of a ref_width x ref_height frame
@@ -1609,7 +1633,7 @@ static int kvz_inter_ctu_pass_run(const uint8_t *src, const uint8_t *ref, const 
   for (int i = 0; i < 128; i++) fbits[i] = (float)kvz::kEntropyBits[i] / 32768.0f;
   auto model_at_qp = [&](kvz::InterModel *row, int qp) {
     kvz::inter_model_init(row, qp, p->poc, kvz_hip_default_coeff_weights(qp) /* 0 from QP 50 on, where kvz_fast_coeff_cost is never used (rdo.c:311-340) */, fbits, p->mv_constraint, p->sao, p->deblock, p->fme_level, p->pu_depth_inter_max, p->no_wpp, p->fast_residual_cost,
-                          width, height, p->ref_width, p->ref_height, p->tile_x, p->tile_y, p->no_tmvp, lists ? 1 : 0, slice_type);
+                          width, height, p->ref_width, p->ref_height, p->tile_x, p->tile_y, p->no_tmvp, lists ? 1 : 0, slice_type, refs ? 1 : 0);
     kvz::inter_model_set_me(row, p);
   };
   kvz::InterPictureTable table;
@@ -1617,9 +1641,11 @@ static int kvz_inter_ctu_pass_run(const uint8_t *src, const uint8_t *ref, const 
     std::vector<int32_t> qp_all, poc_all;
     if (!pictures) { qp_all.assign((size_t)n_pictures, p->qp); poc_all.assign((size_t)n_pictures, p->poc); }
     table = kvz::inter_picture_table_lists(pictures ? pictures->qp : qp_all.data(), pictures ? pictures->poc : poc_all.data(), n_pictures, model_at_qp, sets, n_sets, set_of_picture);
-  } else if (pictures) table = kvz::inter_picture_table(pictures->qp, pictures->poc, n_pictures, model_at_qp);
+  } else if (refs) table = kvz::inter_picture_table_refs(pictures->qp, pictures->poc, n_pictures, model_at_qp, refs);  // (P, and `pictures` is there: inter_refs_launch_known)
+  else if (pictures) table = kvz::inter_picture_table(pictures->qp, pictures->poc, n_pictures, model_at_qp);
   const bool cabac_build = (pictures || lists) ? table.any_cabac : kvz::inter_qp_prices_with_cabac(p->qp, p->fast_residual_cost);
-  const void *kernel = p_slice ? (cabac_build ? (const void *)kvz::inter_ctu_ticket_kernel_p_cabac : (const void *)kvz::inter_ctu_ticket_kernel_p_fast)
+  const void *kernel = refs ? (cabac_build ? (const void *)kvz::inter_ctu_ticket_kernel_refs_cabac : (const void *)kvz::inter_ctu_ticket_kernel_refs_fast)
+                     : p_slice ? (cabac_build ? (const void *)kvz::inter_ctu_ticket_kernel_p_cabac : (const void *)kvz::inter_ctu_ticket_kernel_p_fast)
                      : me ? (cabac_build ? (const void *)kvz::inter_ctu_ticket_kernel_me_cabac : (const void *)kvz::inter_ctu_ticket_kernel_me_fast)
                      : lists ? (cabac_build ? (const void *)kvz::inter_ctu_ticket_kernel_lists_cabac : (const void *)kvz::inter_ctu_ticket_kernel_lists_fast)
                              : (cabac_build ? (const void *)kvz::inter_ctu_ticket_kernel_cabac : (const void *)kvz::inter_ctu_ticket_kernel_fast);
@@ -1632,7 +1658,7 @@ static int kvz_inter_ctu_pass_run(const uint8_t *src, const uint8_t *ref, const 
   if (env && atoi(env) > 0) per_cu = atoi(env) < fit ? atoi(env) : fit;
   if (per_cu < 1) per_cu = 1;
   int n_wg = n_cu * per_cu;
-  if (getenv("KVZ_HIP_INTER_VERBOSE")) fprintf(stderr, "kvz_hip inter pass: %s%s build, %d workgroups per CU x %d CUs\n", p_slice ? "p " : me ? "me " : lists ? "lists " : "", cabac_build ? "cabac" : "fast", per_cu, n_cu);
+  if (getenv("KVZ_HIP_INTER_VERBOSE")) fprintf(stderr, "kvz_hip inter pass: %s%s build, %d workgroups per CU x %d CUs\n", refs ? "refs " : p_slice ? "p " : me ? "me " : lists ? "lists " : "", cabac_build ? "cabac" : "fast", per_cu, n_cu);
   if ((long)n_wg > total) n_wg = (int)total;
   if (n_wg > sc.n_slabs) {
     if (sc.slabs) KVZ_HIP_CHECK(hipFree(sc.slabs));
@@ -1700,7 +1726,9 @@ static int kvz_inter_ctu_pass_run(const uint8_t *src, const uint8_t *ref, const 
   kvz::DevTimer &tm = kvz::inter_timer();
   if (!tm.e0) { KVZ_HIP_CHECK(hipEventCreate(&tm.e0)); KVZ_HIP_CHECK(hipEventCreate(&tm.e1)); }
   KVZ_HIP_CHECK(hipEventRecord(tm.e0, st));
-  if (p_slice && cabac_build) hipLaunchKernelGGL(kvz::inter_ctu_ticket_kernel_p_cabac, dim3((unsigned)n_wg), dim3(KVZ_ICTU_THREADS), 0, st, F, d_model, kvz::device_tables(), sched);
+  if (refs && cabac_build) hipLaunchKernelGGL(kvz::inter_ctu_ticket_kernel_refs_cabac, dim3((unsigned)n_wg), dim3(KVZ_ICTU_THREADS), 0, st, F, d_model, kvz::device_tables(), sched);
+  else if (refs) hipLaunchKernelGGL(kvz::inter_ctu_ticket_kernel_refs_fast, dim3((unsigned)n_wg), dim3(KVZ_ICTU_THREADS), 0, st, F, d_model, kvz::device_tables(), sched);
+  else if (p_slice && cabac_build) hipLaunchKernelGGL(kvz::inter_ctu_ticket_kernel_p_cabac, dim3((unsigned)n_wg), dim3(KVZ_ICTU_THREADS), 0, st, F, d_model, kvz::device_tables(), sched);
   else if (p_slice) hipLaunchKernelGGL(kvz::inter_ctu_ticket_kernel_p_fast, dim3((unsigned)n_wg), dim3(KVZ_ICTU_THREADS), 0, st, F, d_model, kvz::device_tables(), sched);
   else if (me && cabac_build) hipLaunchKernelGGL(kvz::inter_ctu_ticket_kernel_me_cabac, dim3((unsigned)n_wg), dim3(KVZ_ICTU_THREADS), 0, st, F, d_model, kvz::device_tables(), sched);
   else if (me) hipLaunchKernelGGL(kvz::inter_ctu_ticket_kernel_me_fast, dim3((unsigned)n_wg), dim3(KVZ_ICTU_THREADS), 0, st, F, d_model, kvz::device_tables(), sched);
@@ -2241,10 +2269,28 @@ long kvz_hip_dev_entropy_code_inter_pictures(const kvz_hip_cu_info *cu, const kv
 {
   return kvz_hip_dev_entropy_code_inter_slices(cu, ref_cu, coeff, width, height, n_pictures, params, out, capacity, substream_bytes, pictures, KVZ_HIP_SLICE_B);
 }
+static long kvz_entropy_code_inter_run(const kvz_hip_cu_info *cu, const kvz_hip_cu_info *ref_cu, const int16_t *coeff, int width, int height, int n_pictures,
+                                       const kvz_hip_inter_params *params, uint8_t *out, size_t capacity, uint32_t *substream_bytes,
+                                       const kvz_hip_inter_pictures *pictures, int slice_type, const kvz_hip_inter_refs *refs);
 // ... of B or of P pictures (kvz_hip_dev.h): the slice's row of initial states, and no inter_pred_idc in a P slice (kvz_entropy.hpp EntropyJob::p_slice)
 long kvz_hip_dev_entropy_code_inter_slices(const kvz_hip_cu_info *cu, const kvz_hip_cu_info *ref_cu, const int16_t *coeff, int width, int height, int n_pictures,
                                            const kvz_hip_inter_params *params, uint8_t *out, size_t capacity, uint32_t *substream_bytes,
                                            const kvz_hip_inter_pictures *pictures, int slice_type)
+{
+  return kvz_entropy_code_inter_run(cu, ref_cu, coeff, width, height, n_pictures, params, out, capacity, substream_bytes, pictures, slice_type, nullptr);
+}
+// ... of P pictures with reference lists (kvz_hip_dev.h): refs == NULL is kvz_hip_dev_entropy_code_inter_slices; with refs, ref_cu is the pool's records, ref_idx_l0 is
+// coded where a list has more than one entry, and the MVD's predictors are scaled as the pass scaled them (kvz_entropy.hpp EntropyJob::refs)
+long kvz_hip_dev_entropy_code_inter_refs(const kvz_hip_cu_info *cu, const kvz_hip_cu_info *ref_cu, const int16_t *coeff, int width, int height, int n_pictures,
+                                         const kvz_hip_inter_params *params, uint8_t *out, size_t capacity, uint32_t *substream_bytes,
+                                         const kvz_hip_inter_pictures *pictures, int slice_type, const kvz_hip_inter_refs *refs)
+{
+  return kvz_entropy_code_inter_run(cu, ref_cu, coeff, width, height, n_pictures, params, out, capacity, substream_bytes, pictures, slice_type, refs);
+}
+// refs: kvz_hip_dev_entropy_code_inter_refs only
+static long kvz_entropy_code_inter_run(const kvz_hip_cu_info *cu, const kvz_hip_cu_info *ref_cu, const int16_t *coeff, int width, int height, int n_pictures,
+                                       const kvz_hip_inter_params *params, uint8_t *out, size_t capacity, uint32_t *substream_bytes,
+                                       const kvz_hip_inter_pictures *pictures, int slice_type, const kvz_hip_inter_refs *refs)
 {
   if (n_pictures <= 0) return 0;
   kvz_hip_inter_params full;  // (the coder reads members both known versions of the struct have)
@@ -2255,6 +2301,7 @@ long kvz_hip_dev_entropy_code_inter_slices(const kvz_hip_cu_info *cu, const kvz_
     return -1;
   }
   if (pictures && !kvz::inter_pictures_known(pictures, n_pictures, "kvz_hip_dev_entropy_code_inter_pictures")) return -1;
+  if (!kvz::inter_refs_launch_known(refs, n_pictures, pictures != nullptr, pictures ? pictures->poc : nullptr, slice_type, "kvz_hip_dev_entropy_code_inter_refs")) return -1;
   const int wc = (width + 63) >> 6, hc = (height + 63) >> 6, ctus = wc * hc;
   const long cells4 = (long)(height >> 2) * (width >> 2);
   kvz::LoopScratch &ls = kvz::loop_scratch();
@@ -2264,15 +2311,18 @@ long kvz_hip_dev_entropy_code_inter_slices(const kvz_hip_cu_info *cu, const kvz_
   int device = 0;
   KVZ_HIP_CHECK(hipGetDevice(&device));
   // pictures with a QP and a POC of their own: a row of B-slice context states per distinct QP | every picture's POC (0: no temporal predictors) | every picture's row
-  const uint8_t *d_rows = nullptr; const int32_t *d_poc = nullptr; const uint16_t *d_row_of = nullptr;
+  // ... and, with reference lists, every picture's list behind them (kvz_inter_refs.hpp InterRefsRecord)
+  const uint8_t *d_rows = nullptr; const int32_t *d_poc = nullptr; const uint16_t *d_row_of = nullptr; const kvz::InterRefsRecord *d_refs = nullptr;
   if (pictures) {
     int row_of_qp[52], qp_of_row[52];
     const int n_rows = kvz::inter_qp_rows(pictures->qp, n_pictures, row_of_qp, qp_of_row);
-    const size_t at_poc = (size_t)n_rows * KVZ_ENTROPY_CTX_ROW, at_row = at_poc + (size_t)n_pictures * sizeof(int32_t), bytes = at_row + (size_t)n_pictures * sizeof(uint16_t);
+    const size_t at_poc = (size_t)n_rows * KVZ_ENTROPY_CTX_ROW, at_row = at_poc + (size_t)n_pictures * sizeof(int32_t);
+    const size_t at_refs = (at_row + (size_t)n_pictures * sizeof(uint16_t) + 3) & ~(size_t)3, bytes = refs ? at_refs + (size_t)n_pictures * sizeof(kvz::InterRefsRecord) : at_row + (size_t)n_pictures * sizeof(uint16_t);
     static_assert(KVZ_ENTROPY_CTX_ROW % 4 == 0 && KVZ_ENTROPY_CTX_ROW >= KVZ_ENTROPY_CTXS, "the POCs behind the rows are 4-byte aligned");
     std::vector<uint8_t> image(bytes, 0);
-    for (int r = 0; r < n_rows; r++) kvz::entropy_slice_contexts(slice_type, qp_of_row[r], &image[(size_t)r * KVZ_ENTROPY_CTX_ROW]);
+    for (int r = 0; r < n_rows; r++) kvz::entropy_slice_contexts(slice_type, qp_of_row[r], &image[(size_t)r * KVZ_ENTROPY_CTX_ROW], refs != nullptr);
     for (int i = 0; i < n_pictures; i++) {
+      if (refs) ((kvz::InterRefsRecord *)&image[at_refs])[i] = kvz::inter_refs_record(refs, i, pictures->poc[i]);
       ((int32_t *)&image[at_poc])[i] = params->no_tmvp ? 0 : pictures->poc[i];
       ((uint16_t *)&image[at_row])[i] = (uint16_t)row_of_qp[pictures->qp[i]];
     }
@@ -2284,17 +2334,19 @@ long kvz_hip_dev_entropy_code_inter_slices(const kvz_hip_cu_info *cu, const kvz_
     }
     KVZ_HIP_CHECK(hipMemcpy(isc.entropy_table, image.data(), bytes, hipMemcpyHostToDevice));
     d_rows = isc.entropy_table; d_poc = (const int32_t *)(isc.entropy_table + at_poc); d_row_of = (const uint16_t *)(isc.entropy_table + at_row);
+    if (refs) d_refs = (const kvz::InterRefsRecord *)(isc.entropy_table + at_refs);
   }
   auto job = [&](int f0, int nf) {
     kvz::EntropyJob J;
     memset(&J, 0, sizeof J);
     J.W = width; J.H = height; J.wc = wc; J.hc = hc; J.n_frames = nf; J.no_wpp = params->no_wpp;
-    J.cu = cu + f0 * cells4; J.ref_cu = ref_cu + f0 * cells4; J.poc = params->no_tmvp ? 0 : params->poc;  // (the coder only asks the POC whether temporal predictors exist)
+    J.cu = cu + f0 * cells4; J.ref_cu = refs ? ref_cu /* the pool: a picture's co-located frame is named by its list */ : ref_cu + f0 * cells4; J.poc = params->no_tmvp ? 0 : params->poc;  // (the coder only asks the POC whether temporal predictors exist)
     J.coeff = coeff + (size_t)f0 * ctus * KVZ_HIP_CTU_COEFFS;
     J.sao = params->sao ? ls.recs + (size_t)f0 * ctus * 3 : nullptr; J.sao_merge = params->sao ? ls.merge + (size_t)f0 * ctus : nullptr;
     if (pictures) { J.ctx_rows = d_rows; J.model_of_picture = d_row_of + f0; J.poc_of_picture = d_poc + f0; }
     else memcpy(J.ctx_init, init, sizeof init);
     J.p_slice = slice_type == KVZ_HIP_SLICE_P;
+    if (refs) J.refs = d_refs + f0;
     return J;
   };
   return kvz::entropy_code_pictures(be().stream, device, n_pictures, wc, hc, params->no_wpp, nullptr, job, out, capacity, substream_bytes);

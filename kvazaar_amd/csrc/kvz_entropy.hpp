@@ -25,6 +25,7 @@
 #include "kvz_residual.hpp"
 #include "../../include/kvz_hip_types.h"
 #include "../../include/kvz_hip_dev.h"
+#include "kvz_inter_refs.hpp"
 
 namespace kvz {
 
@@ -32,7 +33,7 @@ namespace kvz {
 // contexts of the inter syntax, behind the KVZ_HIP_CX_* ones (cabac.h:63-100: cu_skip_flag_model[3], cu_merge_flag_ext_model, cu_merge_idx_ext_model, cu_pred_mode_model,
 // cu_mvd_model[2], mvp_idx_model[2], inter_dir[5], cu_qt_root_cbf_model)
 enum { KVZ_EB_CX_SKIP = 150, KVZ_EB_CX_MERGE_FLAG = 153, KVZ_EB_CX_MERGE_IDX = 154, KVZ_EB_CX_PRED_MODE = 155, KVZ_EB_CX_MVD = 156, KVZ_EB_CX_MVP_IDX = 158,
-       KVZ_EB_CX_INTER_DIR = 160, KVZ_EB_CX_ROOT_CBF = 165 };
+       KVZ_EB_CX_INTER_DIR = 160, KVZ_EB_CX_ROOT_CBF = 165, KVZ_EB_CX_REF_IDX = 166 /* 2: ref_idx_l0 of P pictures with reference lists */ };
 
 struct EntropyJob {
   int W, H, wc, hc, n_frames, no_wpp;
@@ -62,7 +63,11 @@ struct EntropyJob {
   // P pictures (kvz_hip_dev_entropy_code_inter_slices with KVZ_HIP_SLICE_P): every picture of the job is a P slice -- inter_pred_idc is not part of its syntax
   // (encode_coding_tree.c:339); ctx_init / ctx_rows hold the P row's states
   int p_slice;
+  // P pictures with reference lists (kvz_hip_dev_entropy_code_inter_refs): [frames] every picture's list (kvz_inter_refs.hpp), or null.  ref_cu is then the POOL of
+  // reference frames' records, the co-located picture of picture f the frame of its entry 0; ref_idx_l0 is coded for a picture whose list has more than one entry
+  const InterRefsRecord *refs;
 };
+KVZ_HD const kvz_hip_cu_info *entropy_ref_cu(const EntropyJob &J, int f, long cells4) { return J.refs ? J.ref_cu + J.refs[f].pool_frame[0] * cells4 : J.ref_cu + f * cells4; }
 #define KVZ_ENTROPY_CTX_ROW 176
 #define KVZ_ENTROPY_ROW_SIGNHIDE (KVZ_ENTROPY_CTX_ROW - 1)
 // the initial context states of picture f of the job
@@ -322,6 +327,7 @@ struct EntropyCtuB {
   const i16 *ctu;
   int w4, cx, cy;
   int poc;  // the picture's (entropy_picture_poc)
+  const InterRefsRecord *rf;  // the picture's list, or null: one reference picture
   KVZ_DEV const kvz_hip_cu_info &at(int x, int y) const { return cu[(y >> 2) * w4 + (x >> 2)]; }
   KVZ_DEV static bool a0_coded(int x, int y, int width, int height)  // inter.c:686-741 is_a0_cand_coded
   {
@@ -358,7 +364,17 @@ struct EntropyCtuB {
     }
     return false;
   }
-  KVZ_DEV void mv_candidates(int x, int y, int w, int h, int reflist, i16 mv_cand[2][2]) const  // inter.c:1147-1352
+  // add_mvp_candidate (inter.c:1186-1220) for reference index r of a P picture's list: without scaling the neighbour must refer to the same picture -- the same index
+  // of the one list --, with scaling its vector is brought to the distance of entry r (kvz_inter_refs.hpp: the scale the host laid beside the list)
+  KVZ_DEV bool add_mvp_ref(const kvz_hip_cu_info &c, bool valid, int r, bool scaling, i16 out[2]) const
+  {
+    if (!valid || !(c.mv_dir & 1)) return false;
+    if (!scaling && c.mv_ref[0] != r) return false;
+    const int scale = scaling ? rf->spatial[r & 3][c.mv_ref[0] & 3] : KVZ_MV_SCALE_NONE;
+    out[0] = (i16)mv_scale(c.mv[0][0], scale); out[1] = (i16)mv_scale(c.mv[0][1], scale);
+    return true;
+  }
+  KVZ_DEV void mv_candidates(int x, int y, int w, int h, int reflist, i16 mv_cand[2][2], int r = 0) const  // inter.c:1147-1352; r: the reference index (rf)
   {
     const int xl = x - cx, yl = y - cy;
     kvz_hip_cu_info a[2], b[3], col;
@@ -382,6 +398,22 @@ struct EntropyCtuB {
       if (!vh && xc < J.W && yc < J.H) { const kvz_hip_cu_info &c = ref_cu[(((yc >> 4) << 4) >> 2) * w4 + (((xc >> 4) << 4) >> 2)]; if (c.type == 2) { col = c; vcol = true; } }
     }
     int n = 0, nb_b = 0;
+    if (rf) {  // get_mv_cand_from_candidates (inter.c:1225-1317) with a list of references: the passes without and with scaling differ
+      for (int i = 0; i < 2; i++) if (add_mvp_ref(a[i], va[i], r, false, mv_cand[n])) { n++; break; }
+      if (n == 0) for (int i = 0; i < 2; i++) if (add_mvp_ref(a[i], va[i], r, true, mv_cand[n])) { n++; break; }
+      for (int i = 0; i < 3; i++) if (add_mvp_ref(b[i], vb[i], r, false, mv_cand[n < 2 ? n : 1])) { nb_b++; break; }
+      n += nb_b;
+      if (va[0] || va[1]) nb_b = 1; else if (n != 2) nb_b = 0;
+      if (!nb_b) for (int i = 0; i < 3; i++) if (add_mvp_ref(b[i], vb[i], r, true, mv_cand[n < 2 ? n : 1])) { n++; break; }
+      if (n == 2 && mv_cand[0][0] == mv_cand[1][0] && mv_cand[0][1] == mv_cand[1][1]) n = 1;
+      if (poc > 1 && n < 2 && vcol) {  // add_temporal_candidate (inter.c:1134-1184): from the co-located picture and ITS reference to the picture and entry r
+        const int col_list = (col.mv_dir & 1) ? 0 : 1, scale = rf->temporal[r & 3][(col_list ? col.mv_ref[1] : col.mv_ref[0]) & 3];
+        mv_cand[n][0] = (i16)mv_scale(col_list ? col.mv[1][0] : col.mv[0][0], scale); mv_cand[n][1] = (i16)mv_scale(col_list ? col.mv[1][1] : col.mv[0][1], scale);
+        n++;
+      }
+      while (n < 2) { mv_cand[n][0] = 0; mv_cand[n][1] = 0; n++; }
+      return;
+    }
     for (int i = 0; i < 2; i++) if (add_mvp(a[i], va[i], reflist, mv_cand[n])) { n++; break; }
     if (n == 0) for (int i = 0; i < 2; i++) if (add_mvp(a[i], va[i], reflist, mv_cand[n])) { n++; break; }
     for (int i = 0; i < 3; i++) if (add_mvp(b[i], vb[i], reflist, mv_cand[n < 2 ? n : 1])) { nb_b++; break; }
@@ -450,7 +482,17 @@ struct EntropyCtuB {
         for (int l = 0; l < 2; l++) {
           if (!(cur.mv_dir & (1 << l))) continue;
           i16 cand[2][2];
-          mv_candidates(x, y, w, w, l, cand);
+          if (rf && rf->n_refs > 1) {  // ref_idx_lX (encode_coding_tree.c:359-383): truncated unary, two context-coded bins, bypass from the third on
+            const int ref = cur.mv_ref[l];
+            s.ctx(KVZ_EB_CX_REF_IDX, ref != 0);
+            if (ref > 0)
+              for (int i = 0; i < rf->n_refs - 2; i++) {
+                const int symbol = i == ref - 1 ? 0 : 1;
+                if (i == 0) s.ctx(KVZ_EB_CX_REF_IDX + 1, symbol); else s.ep((u32)symbol, 1);
+                if (!symbol) break;
+              }
+          }
+          mv_candidates(x, y, w, w, l, cand, rf ? cur.mv_ref[l] : 0);
           const int k = cur.mv_cand[l];
           mvd(s, cur.mv[l][0] - cand[k][0], cur.mv[l][1] - cand[k][1]);
           s.ctx(KVZ_EB_CX_MVP_IDX, k);
@@ -545,7 +587,7 @@ KVZ_DEV void entropy_ctu_bins(const EntropyJob &J, const Tables *tb, long item)
     }
   }
   if (J.cu) {  // a B picture: the inter syntax from the CU records
-    const EntropyCtuB cb{ J, tb, J.cu + f * cells4, J.ref_cu + f * cells4, J.coeff + item * KVZ_HIP_CTU_COEFFS, J.W >> 2, lx * 64, ly * 64, entropy_picture_poc(J, f) };
+    const EntropyCtuB cb{ J, tb, J.cu + f * cells4, entropy_ref_cu(J, f, cells4), J.coeff + item * KVZ_HIP_CTU_COEFFS, J.W >> 2, lx * 64, ly * 64, entropy_picture_poc(J, f), J.refs ? J.refs + f : nullptr };
     cb.coding_tree(s);
   } else {
     const EntropyCtu c{ J, tb, J.depth + f * cells8, J.mode + f * cells8, J.part ? J.part + f * cells8 : nullptr, J.mode4 ? J.mode4 + f * cells4 : nullptr,
@@ -596,7 +638,7 @@ KVZ_DEV void entropy_ctu_bins_phased(const EntropyJob &J, const Tables *tb, long
     }
   }
   const i16 *ctu = J.coeff + item * KVZ_HIP_CTU_COEFFS;
-  const EntropyCtuB cb{ J, tb, J.cu ? J.cu + f * cells4 : nullptr, J.cu ? J.ref_cu + f * cells4 : nullptr, ctu, J.W >> 2, lx * 64, ly * 64, J.cu ? entropy_picture_poc(J, f) : 0 };
+  const EntropyCtuB cb{ J, tb, J.cu ? J.cu + f * cells4 : nullptr, J.cu ? entropy_ref_cu(J, f, cells4) : nullptr, ctu, J.W >> 2, lx * 64, ly * 64, J.cu ? entropy_picture_poc(J, f) : 0, J.cu && J.refs ? J.refs + f : nullptr };
   const EntropyCtu ci{ J, tb, J.cu ? nullptr : J.depth + f * cells8, J.cu ? nullptr : J.mode + f * cells8, J.part ? J.part + f * cells8 : nullptr,
                        J.mode4 ? J.mode4 + f * cells4 : nullptr, ctu, J.W >> 3, J.W >> 2 };
   LaneStack stack{ stack_mem, stride };

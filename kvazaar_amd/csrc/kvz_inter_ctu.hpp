@@ -35,6 +35,7 @@
 #include "kvz_tables.hpp"
 #include "kvz_residual.hpp"
 #include "kvz_recon.hpp"
+#include "kvz_inter_refs.hpp"
 
 namespace kvz {
 
@@ -96,6 +97,27 @@ namespace kvz {
 #define IC_LISTS_STATE 2
 #else
 #define IC_LISTS_STATE IC_LISTS
+#endif
+
+// The kernel's builds for P pictures with reference lists of 1 .. 4 pictures (kvz_hip_dev_inter_ctu_pass_refs: kvazaar --no-bipred --ref N; kvz_inter_tu.hip
+// -DKVZ_ICTU_P=1 -DKVZ_ICTU_REFS=1): F.ref / F.ref_cu are a POOL of frames, the picture's record (InterPictureRefs) names the frames of its list and carries the
+// scales of every vector it can meet (kvz_inter_refs.hpp).  merge_candidates keeps the neighbours' reference indices, scales the temporal candidate to entry 0
+// and steps the zero candidates through the list (inter.c:1471-1569); mv_candidates derives the predictors of ONE reference index -- unscaled neighbours of the
+// same picture first, then scaled ones, the temporal one scaled to it (inter.c:1183-1310); search_pu_inter_ref runs once per entry from that entry's own scaled
+// co-located vector (search_inter.c:1286-1339, 1807-1812) and every sample read goes to the entry a vector names (use_ref); inter_pu_bits prices ref_idx_l0
+// (encode_coding_tree.c:359-383).  A build constant on the device, so that the other builds hold none of it; the host simulation
+// (tests/hostsim/hostsim_inter_refs.cpp) makes it a variable, as hostsim_inter_p.cpp does with KVZ_ICTU_P.
+// NOT COVERED: B pictures with several references; tiles, scaling lists, joint launches and the me_* members together with reference lists.
+#ifndef KVZ_ICTU_REFS
+#define KVZ_ICTU_REFS 0
+#endif
+#ifdef KVZ_HOSTSIM
+#define KVZ_ICTU_REFS_STATE 1
+#else
+#define KVZ_ICTU_REFS_STATE KVZ_ICTU_REFS
+#endif
+#ifndef IC_REFS_EVENT  // what the program met of the reference lists: only tests/hostsim/hostsim_inter_refs.cpp, which counts it, defines it
+#define IC_REFS_EVENT(slot) ((void)0)
 #endif
 
 #ifndef IC_MERGE_ORIGIN  // where the entries of a PU's merge list come from: only tests/hostsim/hostsim_inter_p.cpp, which counts what the chosen candidates were, defines it
@@ -214,7 +236,7 @@ typedef KVZ_GLB i16 gi16;
 // compact context numbering of a B slice (cabac.h:63-100): the CU / transform-tree syntax in the first 32 bytes -- all that moves while coefficients are priced with the
 // fast estimate --, then the residual coder's contexts, KVZ_HIP_CX_SIG_CG .. KVZ_HIP_CX_ABS_CHROMA + 1 of include/kvz_hip_types.h in that order (picture QP >= 28)
 enum { IX_SPLIT = 0 /* 3 */, IX_SKIP = 3 /* 3 */, IX_MERGE_FLAG = 6, IX_MERGE_IDX = 7, IX_PRED_MODE = 8, IX_PART = 9, IX_INTRA = 10, IX_CHROMA = 11, IX_CBF_LUMA = 12 /* 2 */,
-       IX_CBF_CHROMA = 14 /* 2 */, IX_MVD = 16 /* 2 */, IX_MVP_IDX = 18, IX_INTER_DIR = 19 /* 5 */, IX_ROOT_CBF = 24, IX_SYNTAX = 32,
+       IX_CBF_CHROMA = 14 /* 2 */, IX_MVD = 16 /* 2 */, IX_MVP_IDX = 18, IX_INTER_DIR = 19 /* 5 */, IX_ROOT_CBF = 24, IX_REF_IDX = 25 /* 2: the REFS builds */, IX_SYNTAX = 32,
        IX_RES = 32 /* 136 */, IX_COUNT = IX_RES + (KVZ_HIP_CX_ABS_CHROMA + 2 - KVZ_HIP_CX_SIG_CG) };
 struct alignas(8) ICtx { u8 s[IX_COUNT]; };
 static_assert(IX_COUNT == 168 && sizeof(ICtx) == 168, "context sets are copied as 32-bit words");
@@ -251,6 +273,14 @@ struct InterPictureLists {
   uint32_t model_at;
   int32_t poc;
   uint32_t lists_y_at, lists_c_at;  // bytes from the first record
+};
+
+// ... and the record of a launch of P pictures with reference lists (the REFS builds read these in InterPicture's place): the picture's list
+struct InterPictureRefs {
+  uint32_t model_at;
+  int32_t poc;
+  InterRefsRecord refs;  // pool frames and scales (kvz_inter_refs.hpp)
+  uint32_t pad_;
 };
 
 // The records of a joint launch (the JOINT builds read these in InterPicture's place; kvz_inter_joint.hpp lays them out): pictures are numbered across the groups, and
@@ -305,7 +335,12 @@ struct InterFrames {
 #define IC_MREF_STRIDE 36  /* q in [-16, 17] for a 16x16 CU (an odd number of dwords: the modes fall into different banks) */
 #define IC_MREF_ORG 16
 struct MCand { i16 mv[2][2]; u8 ref[2], dir; };                         // inter_merge_cand_t
-struct PuSearch { int x, y, w; i16 mv_cand[2][2]; MCand merge[5]; int num_merge, merge_dup; };  // merge_dup: bit k = merge[k] repeats an earlier entry
+struct PuSearch {
+  int x, y, w; i16 mv_cand[2][2]; MCand merge[5]; int num_merge, merge_dup;  // merge_dup: bit k = merge[k] repeats an earlier entry
+#ifdef KVZ_HOSTSIM
+  int zero_from;  // the first zero candidate of the list (the census of tests/hostsim/hostsim_inter_refs.cpp)
+#endif
+};
 struct UMap { CuInfo unit[5]; double cost[5], bits[5]; int8_t keys[5]; int size; };
 
 struct PView { lu8 *p; int s; };  // a plane of a block in LDS: sample (x, y) at p[y * s + x]
@@ -407,6 +442,11 @@ struct InterLds {
   struct { int mvx, mvy; double cost, bits; } best;  // check_mv_cost's best so far
   struct { int mv[2]; double cost, bits; } frac;     // me_fractional's result
   double inter_cost, inter_bitcost, intra_cost;      // results of search_cu_inter / search_cu_intra
+#if KVZ_ICTU_REFS_STATE
+  InterRefsRecord rf;                    // the drawn picture's list (begin_ctu)
+  const uint8_t *rf_base[KVZ_HIP_MAX_REFS];  // ... and the luma planes / CU records of its entries' frames
+  const CuInfo *rf_cu[KVZ_HIP_MAX_REFS];
+#endif
   double ccost[3];  // kvz_fast_coeff_cost of the transform units the CU under evaluation was last quantised into (one per plane: its transform tree is one unit); unused when coeff_cabac
   InterConst k;
 };
@@ -491,6 +531,15 @@ struct InterCtu {
   IC_DEV int ref_index() { return g_ic.ref_idx; }
   IC_DEV const gu8 *refp(int c) { const int n = K->ref_w * K->ref_h; return (const gu8 *)g_ic.ref_base + (c == 0 ? 0 : (c == 1 ? n : n + (n >> 2))); }
   IC_DEV const CuInfo *ref_cu_frame() { return g_ic.ref_cu_base; }
+#if KVZ_ICTU_REFS_STATE
+  // every sample the program reads of "the reference picture" (refp) from here on is entry r's of the picture's list; the co-located picture stays entry 0
+  IC_DEV void use_ref(int r)
+  {
+    IC_FOR(tid) { if (tid == 0) g_ic.ref_base = g_il.rf_base[r & (KVZ_HIP_MAX_REFS - 1)]; }
+    IC_SYNC();
+  }
+  IC_DEV int list_length() { return g_il.rf.n_refs; }
+#endif
   IC_DEV const gu8 *srcp(int c) { return (const gu8 *)g_ic.src_base + plane_off(c); }
   IC_DEV gu8 *recp(int c) { return (gu8 *)g_ic.rec_base + plane_off(c); }
   IC_DEV CuInfo *dcell(int xl, int yl) { return &L->Dcu[((yl >> 3) & 7) * 8 + ((xl >> 3) & 7)].c; }  // (& 7: nothing for a position inside the CTU; the index's range lets the record size multiply at full rate)
@@ -684,6 +733,14 @@ struct InterCtu {
       return (const KVZ_GLB InterModel *)((const KVZ_GLB uint8_t *)F.pictures + rec->model_at);
     }
 #endif
+#if KVZ_ICTU_REFS_STATE
+    if (KVZ_ICTU_REFS) {  // a launch with reference lists: the wider record, and with it the picture's list
+      const KVZ_GLB InterPictureRefs *rec = (const KVZ_GLB InterPictureRefs *)F.pictures + frame_;
+      *poc = rec->poc;
+      for (int i = 0; i < (int)(sizeof(InterRefsRecord) / 4); i++) ((KVZ_LDS u32 *)&g_il.rf)[i] = ((const KVZ_GLB u32 *)&rec->refs)[i];
+      return (const KVZ_GLB InterModel *)((const KVZ_GLB uint8_t *)F.pictures + rec->model_at);
+    }
+#endif
 #if KVZ_ICTU_LISTS_STATE
     if (KVZ_ICTU_LISTS) {  // a launch with lists: the wider record, and with it the picture's two factor rows (a picture without a set has the flat list's)
       const KVZ_GLB InterPictureLists *rec = (const KVZ_GLB InterPictureLists *)F.pictures + frame_;
@@ -734,6 +791,19 @@ struct InterCtu {
       }
       g_ic.ref_idx = F.ref_count ? frame_ % F.ref_count : frame_; g_ic.cu_frame = (const CuInfo *)F.cu + (long)frame_ * F.cells;
       g_ic.ref_base = (const uint8_t *)F.ref + g_ic.ref_idx * ((long)K->ref_w * K->ref_h * 3 / 2); g_ic.ref_cu_base = F.ref_cu + g_ic.ref_idx * ((long)(K->ref_w >> 2) * (K->ref_h >> 2)); g_ic.src_base = (const uint8_t *)F.src + frame_ * F.frame_px; g_ic.rec_base = (uint8_t *)F.rec + frame_ * F.frame_px;
+#if KVZ_ICTU_REFS_STATE
+      if (KVZ_ICTU_REFS) {
+        // F.ref / F.ref_cu are the pool: the frames of the picture's entries, entry 0 (the co-located picture) as the program's reference until use_ref says otherwise.
+        // The frame indices are the host's, validated before the launch (inter_refs_known), entries past the list's end frame 0: whatever reference index a
+        // record holds, use_ref stays inside the pool
+        const long ref_px = (long)K->ref_w * K->ref_h * 3 / 2, ref_cells = (long)(K->ref_w >> 2) * (K->ref_h >> 2);
+        for (int r = 0; r < KVZ_HIP_MAX_REFS; r++) {
+          g_il.rf_base[r] = (const uint8_t *)F.ref + g_il.rf.pool_frame[r] * ref_px;
+          g_il.rf_cu[r] = F.ref_cu + g_il.rf.pool_frame[r] * ref_cells;
+        }
+        g_ic.ref_base = g_il.rf_base[0]; g_ic.ref_cu_base = g_il.rf_cu[0];
+      }
+#endif
       g_ic.coef_out = F.coeff ? (int16_t *)F.coeff + ((long)frame_ * F.wc * F.hc + (cy_ >> 6) * F.wc + (cx_ >> 6)) * 6144 : (int16_t *)S->out;
       if (F.tile_xy) {
       // the origin is a DEVICE-side input nobody validated: brought inside the reference frame here (multiples of 8, the tile inside the frame), so that no read of

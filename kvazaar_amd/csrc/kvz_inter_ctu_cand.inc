@@ -84,6 +84,19 @@ IC_DEV Cands cand_gather(int x, int y, int w, int h)
 }
 // the motion one list of a temporal candidate predicts (inter.c:1093-1135 with one reference picture: the co-located vector of that list, else of the other)
 IC_DEV u32 temporal_mv(const Mot &col, int reflist) { return reflist ? ((col.d & 2u) ? col.m1 : col.m0) : ((col.d & 1u) ? col.m0 : col.m1); }
+// ... and, in a launch with reference lists, scaled to entry r of the picture's list from the co-located picture -- entry 0 -- and the picture ITS vector
+// referred to (add_temporal_candidate, inter.c:1134-1184; a P record moves by list 0)
+IC_DEV u32 temporal_mv_to(const Mot &col, int r)
+{
+#if KVZ_ICTU_REFS_STATE
+  if (KVZ_ICTU_REFS) {
+    const int scale = L->rf.temporal[r & 3][(col.d >> ((col.d & 1u) ? 8 : 16)) & 3u];
+    if (scale != KVZ_MV_SCALE_NONE) IC_REFS_EVENT(1);
+    return mv_scale_packed(temporal_mv(col, 0), scale);
+  }
+#endif
+  return temporal_mv(col, 0);
+}
 IC_DEV bool same_motion(const Mot &a, const Mot &b)  // b is there and moves as a does
 {
   if (!mot_valid(b)) return false;
@@ -118,7 +131,7 @@ IC_FN int merge_candidates(int x, int y, int w, int h)
   const int n_spatial = n;
   if (n < max && (mot_valid(c.th) || mot_valid(c.tc))) {
     const Mot col = mot_sel(mot_valid(c.th), c.th, c.tc);
-    if (KVZ_ICTU_P) mot_put(e, n, Mot{ temporal_mv(col, 0), 0u, 1u });  // inter.c:1479 max_reflist 0 in a P slice: list 0 only
+    if (KVZ_ICTU_P) mot_put(e, n, Mot{ temporal_mv_to(col, 0), 0u, 1u });  // inter.c:1479 max_reflist 0 in a P slice: list 0 only, reference index 0 (:1490-1496)
     else mot_put(e, n, Mot{ temporal_mv(col, 0), temporal_mv(col, 1), 3u });
     n++;
   }
@@ -141,7 +154,17 @@ IC_FN int merge_candidates(int x, int y, int w, int h)
   }
   IC_MERGE_ORIGIN(x, y, w, n_spatial, n_temporal, n);  // (the host simulation's census: entries below n_spatial are neighbours', then the temporal one, from n on zero)
   const Mot fill = { 0u, 0u, KVZ_ICTU_P ? 1u : 3u };  // inter.c:1556-1569: the zero candidates, dir 1 in a P slice
-  e.e0 = mot_sel(n <= 0, fill, e.e0); e.e1 = mot_sel(n <= 1, fill, e.e1); e.e2 = mot_sel(n <= 2, fill, e.e2); e.e3 = mot_sel(n <= 3, fill, e.e3); e.e4 = mot_sel(n <= 4, fill, e.e4);
+#if KVZ_ICTU_REFS_STATE
+  if (KVZ_ICTU_REFS) {  // inter.c:1539-1569 with num_ref the length of the list: zero candidate z refers to entry z while z < num_ref - 1, to entry 0 from there on (ref[1] = ref[0])
+    const int nr = list_length();
+    auto zero_of = [&](int k) { const u32 r = (k - n >= nr - 1 || k < n) ? 0u : (u32)(k - n); return Mot{ 0u, 0u, 1u | r << 8 | r << 16 }; };
+    e.e0 = mot_sel(n <= 0, zero_of(0), e.e0); e.e1 = mot_sel(n <= 1, zero_of(1), e.e1); e.e2 = mot_sel(n <= 2, zero_of(2), e.e2); e.e3 = mot_sel(n <= 3, zero_of(3), e.e3); e.e4 = mot_sel(n <= 4, zero_of(4), e.e4);
+#ifdef KVZ_HOSTSIM
+    L->pu.zero_from = n;
+#endif
+  } else
+#endif
+  { e.e0 = mot_sel(n <= 0, fill, e.e0); e.e1 = mot_sel(n <= 1, fill, e.e1); e.e2 = mot_sel(n <= 2, fill, e.e2); e.e3 = mot_sel(n <= 3, fill, e.e3); e.e4 = mot_sel(n <= 4, fill, e.e4); }
   // which entries repeat an earlier one (the merge analysis skips them, search_inter.c:1710-1730: it compares with the entries it kept -- an earlier equal entry was
   // kept, or was skipped for what skips this one too)
   // (In a P slice too the reference compares the fields of list 1, which move no sample: a neighbour's record carries mv_ref[1] 255 from the search and 0 from a
@@ -216,9 +239,45 @@ IC_DEV void mv_candidates_derive(int x, int y, int w, int h, int reflist, u32 mv
   if (n < 1) mv[0] = 0;
   if (n < 2) mv[1] = 0;
 }
-// into L->pu.mv_cand
-IC_FN void mv_candidates(int x, int y, int w, int h, int reflist)
+#if KVZ_ICTU_REFS_STATE
+// ... for reference index r of a P picture's list (add_mvp_candidate, inter.c:1186-1220): without scaling the neighbour must refer to the same picture -- in a P slice,
+// whose one list names every picture once, the same index --, with scaling any neighbour's vector is taken and brought to the distance of entry r
+IC_DEV bool add_mvp_ref(const Mot &cand, int r, bool scaling, u32 &mv)
 {
+  if (!mot_valid(cand) || !(cand.d & 1u)) return false;
+  const int c = (int)((cand.d >> 8) & 0xffu);
+  if (scaling) {
+    const int scale = L->rf.spatial[r & 3][c & 3];
+    if (scale != KVZ_MV_SCALE_NONE) IC_REFS_EVENT(0);
+    mv = mv_scale_packed(cand.m0, scale);
+    return true;
+  }
+  if (c != r) return false;
+  mv = cand.m0;
+  return true;
+}
+IC_DEV void mv_candidates_derive_refs(int x, int y, int w, int h, int r, u32 mv[2])  // get_mv_cand_from_candidates (inter.c:1225-1317), list 0 of a P slice
+{
+  const Cands c = cand_gather(x, y, w, h);
+  int n = 0, nb_b = 0;
+  u32 t = 0;
+  mv[0] = mv[1] = 0;
+  if (add_mvp_ref(c.a0, r, false, t) || add_mvp_ref(c.a1, r, false, t)) { mv[0] = t; n = 1; }
+  if (n == 0 && (add_mvp_ref(c.a0, r, true, t) || add_mvp_ref(c.a1, r, true, t))) { mv[0] = t; n = 1; }
+  if (add_mvp_ref(c.b0, r, false, t) || add_mvp_ref(c.b1, r, false, t) || add_mvp_ref(c.b2, r, false, t)) { if (n == 0) mv[0] = t; else mv[1] = t; nb_b = 1; }
+  n += nb_b;
+  if (mot_valid(c.a0) || mot_valid(c.a1)) nb_b = 1; else if (n != 2) nb_b = 0;
+  if (!nb_b && (add_mvp_ref(c.b0, r, true, t) || add_mvp_ref(c.b1, r, true, t) || add_mvp_ref(c.b2, r, true, t))) { if (n == 0) mv[0] = t; else mv[1] = t; n++; }  // (no left neighbour: n <= 1 here)
+  if (n == 2 && mv[0] == mv[1]) n = 1;
+  if (M->poc > 1 && n < 2 && (mot_valid(c.th) || mot_valid(c.tc))) { t = temporal_mv_to(mot_sel(mot_valid(c.th), c.th, c.tc), r); if (n == 0) mv[0] = t; else mv[1] = t; n++; }
+  if (n < 1) mv[0] = 0;
+  if (n < 2) mv[1] = 0;
+}
+#endif
+// into L->pu.mv_cand; ref: the reference index the predictors are for (a launch with reference lists; 0 otherwise)
+IC_FN void mv_candidates(int x, int y, int w, int h, int reflist_, int ref = 0)
+{
+  const int reflist = reflist_ | ref << 1;  // (what the cache of the last derivation is keyed by)
   IC_COUNT(19);
   i16 (*mv_cand)[2] = L->pu.mv_cand;
   // the neighbours a PU's predictors come from are all coded before it and do not change while it is searched, priced and, later, coded
@@ -227,7 +286,10 @@ IC_FN void mv_candidates(int x, int y, int w, int h, int reflist)
     return;
   }
   u32 mv[2];
-  mv_candidates_derive(x, y, w, h, reflist, mv);
+#if KVZ_ICTU_REFS_STATE
+  if (KVZ_ICTU_REFS) mv_candidates_derive_refs(x, y, w, h, ref, mv); else
+#endif
+  mv_candidates_derive(x, y, w, h, reflist_, mv);
   L->mvc_key[0] = x; L->mvc_key[1] = y; L->mvc_key[2] = w; L->mvc_key[3] = reflist;
   store_mv32(mv_cand[0], mv[0]); store_mv32(mv_cand[1], mv[1]);
   store_mv32(L->mvc[0], mv[0]); store_mv32(L->mvc[1], mv[1]);

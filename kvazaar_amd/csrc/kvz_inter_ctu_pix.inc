@@ -959,6 +959,9 @@ IC_DEV void predict_into(int c, int x, int y, int w, const CuInfo &pu, lu8 *dst,
 IC_FN void inter_predict(int lv, int x, int y, int w, const CuInfo pu, bool luma, bool chroma)
 {
   const int xl = x - cx, yl = y - cy;
+#if KVZ_ICTU_REFS_STATE
+  if (KVZ_ICTU_REFS) use_ref(pu.mv_ref[0]);  // the picture the reference index names (inter.c:574-586); a P record moves by list 0
+#endif
   for (int c = 0; c < 3; c++) {
     if ((c == 0 && !luma) || (c > 0 && !chroma)) continue;
     const PView dv = lvl(lv, c, xl, yl);

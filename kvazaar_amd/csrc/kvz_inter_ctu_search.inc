@@ -46,15 +46,26 @@ IC_DEV void set_record(int lv, int xl, int yl)
   IC_SYNC();
 }
 
-IC_FN void search_pu_inter_ref(int depth)
+// ref: the entry of the picture's list that is searched (a launch with reference lists; 0 otherwise, the one reference picture)
+IC_FN void search_pu_inter_ref(int depth, int ref = 0)
 {
   PuSearch &pu = L->pu;
   UMap *amvp = L->amvp;
-  IC_PROF(IP_CAND, mv_candidates(pu.x, pu.y, pu.w, pu.w, 0));
+  IC_PROF(IP_CAND, mv_candidates(pu.x, pu.y, pu.w, pu.w, 0, ref));
   int sx = 0, sy = 0;
-  const CuInfo ref_cu = load_cu(ref_cu_frame() + (((K->tile_y + pu.y + (pu.w >> 1)) >> 2) * (K->ref_w >> 2) + ((K->tile_x + pu.x + (pu.w >> 1)) >> 2)));  // search_inter.c:1286-1287: the frame position
+  const CuInfo *col_frame = ref_cu_frame();
+#if KVZ_ICTU_REFS_STATE
+  if (KVZ_ICTU_REFS) { use_ref(ref); col_frame = L->rf_cu[ref & (KVZ_HIP_MAX_REFS - 1)]; }  // search_inter.c:1288: the searched picture's own CU records
+#endif
+  const CuInfo ref_cu = load_cu(col_frame + (((K->tile_y + pu.y + (pu.w >> 1)) >> 2) * (K->ref_w >> 2) + ((K->tile_x + pu.x + (pu.w >> 1)) >> 2)));  // search_inter.c:1286-1287: the frame position
   const bool has_start = ref_cu.type == 2;
   if (has_start) { const bool l0 = (ref_cu.mv_dir & 1) != 0; sx = l0 ? ref_cu.mv[0][0] : ref_cu.mv[1][0]; sy = l0 ? ref_cu.mv[0][1] : ref_cu.mv[1][1]; }
+#if KVZ_ICTU_REFS_STATE
+  if (KVZ_ICTU_REFS && has_start) {  // search_inter.c:1300-1333: from the distance of the co-located CU's own reference to the distance of the searched picture
+    const int scale = L->rf.start[ref & 3][((ref_cu.mv_dir & 1) ? ref_cu.mv_ref[0] : ref_cu.mv_ref[1]) & 3];
+    sx = mv_scale(sx, scale); sy = mv_scale(sy, scale);
+  }
+#endif
   IC_PROF(IP_ME, me_integer(has_start, sx, sy));
   const decltype(InterLds::best) best = L->best;
   const bool valid = mv_allowed(best.mvx, best.mvy) && best.cost < IC_MAX_COST;
@@ -68,7 +79,7 @@ IC_FN void search_pu_inter_ref(int depth)
     u->type = 2; u->merged = 0; u->skipped = 0;
     u->mv_dir = (u8)(list + 1);
     u->mv[0][0] = u->mv[0][1] = u->mv[1][0] = u->mv[1][1] = 0; u->mv_ref[0] = u->mv_ref[1] = 255;
-    u->mv_ref[list] = 0;
+    u->mv_ref[list] = (u8)ref;
     u->mv[list][0] = (i16)best.mvx; u->mv[list][1] = (i16)best.mvy;
     u->mv_cand[0] = u->mv_cand[1] = 0;
     u->mv_cand[list] = (u8)mvp;
@@ -133,6 +144,9 @@ IC_FN bool search_pu_inter(int lv, int x, int y, int depth)
     // the candidate's luma prediction goes into the level's samples (nothing else is there yet) and, if it is the best so far, a copy into best_luma
     const PView cand = lvl(lv, 0, xl, yl);
     IC_PROF(IP_MERGE, { inter_predict(lv, x, y, w, cur, true, false); merge_satd = satd_block(cand.p, cand.s, org0.p, org0.s, w); });
+#if defined(KVZ_HOSTSIM)
+    if (KVZ_ICTU_REFS && mi >= pu.zero_from && c.ref[0] > 0) IC_REFS_EVENT(2);  // a zero candidate of a reference index above 0 is evaluated
+#endif
     const int e = merge.size;
     merge.unit[e] = cur;
     merge.unit[e].type = 2; merge.unit[e].merge_idx = (u8)mi; merge.unit[e].merged = 1; merge.unit[e].skipped = 0;
@@ -175,6 +189,9 @@ IC_FN bool search_pu_inter(int lv, int x, int y, int depth)
   if (KVZ_ICTU_P) amvp[0].size = 0;
   else amvp[0].size = amvp[1].size = 0;  // (kvazaar's third list, the bi-prediction search of search_inter.c:1919-2034, needs two reference pictures)
   for (int d = 0; d < IC_LISTS; d++) { amvp[d].cost[0] = IC_MAX_COST; amvp[d].keys[0] = 0; }
+#if KVZ_ICTU_REFS_STATE
+  if (KVZ_ICTU_REFS) { for (int r = 0; r < list_length(); r++) search_pu_inter_ref(depth, r); } else  // search_inter.c:1807-1812: every picture of the list
+#endif
   search_pu_inter_ref(depth);
   sort_keys(&amvp[0]);
   if (!KVZ_ICTU_P) sort_keys(&amvp[1]);
@@ -193,6 +210,9 @@ IC_FN bool search_pu_inter(int lv, int x, int y, int depth)
       for (int i = 0; i < n_best; i++) {
         const int key = amvp[list].keys[i];
         CuInfo *u = &amvp[list].unit[key];
+#if KVZ_ICTU_REFS_STATE
+        if (KVZ_ICTU_REFS) { use_ref(u->mv_ref[list]); mv_candidates(x, y, w, w, list, u->mv_ref[list]); } else  // search_inter.c:1871-1883: the picture and the predictors of the entry's reference index
+#endif
         mv_candidates(x, y, w, w, list);
         L->frac.mv[0] = u->mv[list][0]; L->frac.mv[1] = u->mv[list][1];
         bool frac_ok = false;
@@ -201,7 +221,10 @@ IC_FN bool search_pu_inter(int lv, int x, int y, int depth)
         const int frac_mv[2] = { L->frac.mv[0], L->frac.mv[1] };
         double frac_cost = L->frac.cost, frac_bits = L->frac.bits;
         const int mvp = select_mv_cand(frac_mv[0], frac_mv[1]);
-        const int extra_bits = list;
+        int extra_bits = list;
+#if KVZ_ICTU_REFS_STATE
+        if (KVZ_ICTU_REFS) extra_bits += u->mv_ref[list];  // search_inter.c:1897-1899 mv_ref_coded
+#endif
         frac_cost += extra_bits * M->lambda_sqrt;
         frac_bits += extra_bits;
         if (mv_allowed(frac_mv[0], frac_mv[1])) {
@@ -281,6 +304,20 @@ IC_DEV double merge_idx_bits(int merge_idx, bool update)
   }
   return bits;
 }
+#if KVZ_ICTU_REFS_STATE
+// ref_idx_lX of a list of n > 1 entries (encode_coding_tree.c:359-383): truncated unary, two context-coded bins, bypass from the third on
+IC_DEV double ref_idx_bits(int ref, int n, bool update)
+{
+  double bits = price(IX_REF_IDX, ref != 0, update);
+  if (ref > 0)
+    for (int i = 0; i < n - 2; i++) {
+      const int symbol = i == ref - 1 ? 0 : 1;
+      if (i == 0) bits += price(IX_REF_IDX + 1, symbol, update); else bits += 1;
+      if (!symbol) break;
+    }
+  return bits;
+}
+#endif
 IC_FN double inter_pu_bits(int x, int y, int depth, const CuInfo cu, bool update)
 {
   const int w = 64 >> depth;
@@ -293,6 +330,12 @@ IC_FN double inter_pu_bits(int x, int y, int depth, const CuInfo cu, bool update
   }
   for (int l = 0; l < IC_LISTS; l++) {
     if (!(cu.mv_dir & (1 << l))) continue;
+#if KVZ_ICTU_REFS_STATE
+    if (KVZ_ICTU_REFS) {
+      if (list_length() > 1) bits += ref_idx_bits(cu.mv_ref[l], list_length(), update);
+      mv_candidates(x, y, w, w, l, cu.mv_ref[l]);
+    } else
+#endif
     mv_candidates(x, y, w, w, l);
     const int k = cu.mv_cand[l];
     bits += mvd_syntax_bits(cu.mv[l][0] - L->pu.mv_cand[k][0], cu.mv[l][1] - L->pu.mv_cand[k][1], update);

@@ -9,6 +9,7 @@
 
 #include "kvz_inter_ctu.hpp"
 #include "kvz_inter_pictures.hpp"
+#include "kvz_inter_refs.hpp"
 #include "kvz_scaling_lists.hpp"
 #include "kvz_tables.hpp"
 
@@ -75,11 +76,12 @@ inline void p_slice_residual_init_values(uint8_t v[KVZ_HIP_CX_ABS_CHROMA + 2 - K
 // P differs from B in merge_flag, merge_idx, pred_mode_flag, abs_mvd_greater0_flag, prev_intra_luma_pred_flag, cbf_cb / cbf_cr at depth 1 and sao_type_idx.
 struct SliceSyntaxInit {
   uint8_t split[3], skip[3], merge_flag, merge_idx, pred_mode, part, intra, chroma, cbf_luma[2], cbf_chroma[4], mvd[2], mvp_idx, inter_dir[5], root_cbf, sao_merge, sao_type;
+  uint8_t ref_idx[2];  // ref_idx_l0 / ref_idx_l1 (Table 9-17): only a launch with reference lists (kvz_hip_inter_refs) has contexts for it
 };
 inline const SliceSyntaxInit &slice_syntax_init(int slice_type)
 {
-  static const SliceSyntaxInit b = { { 107, 139, 126 }, { 197, 185, 201 }, 154, 137, 134, 154, 183, 152, { 153, 111 }, { 149, 92, 167, 154 }, { 169, 198 }, 168, { 95, 79, 63, 31, 31 }, 79, 153, 160 };
-  static const SliceSyntaxInit p = { { 107, 139, 126 }, { 197, 185, 201 }, 110, 122, 149, 154, 154, 152, { 153, 111 }, { 149, 107, 167, 154 }, { 140, 198 }, 168, { 95, 79, 63, 31, 31 }, 79, 153, 185 };
+  static const SliceSyntaxInit b = { { 107, 139, 126 }, { 197, 185, 201 }, 154, 137, 134, 154, 183, 152, { 153, 111 }, { 149, 92, 167, 154 }, { 169, 198 }, 168, { 95, 79, 63, 31, 31 }, 79, 153, 160, { 153, 153 } };
+  static const SliceSyntaxInit p = { { 107, 139, 126 }, { 197, 185, 201 }, 110, 122, 149, 154, 154, 152, { 153, 111 }, { 149, 107, 167, 154 }, { 140, 198 }, 168, { 95, 79, 63, 31, 31 }, 79, 153, 185, { 153, 153 } };
   return slice_type == KVZ_HIP_SLICE_P ? p : b;
 }
 inline void slice_residual_init_values(int slice_type, uint8_t v[KVZ_HIP_CX_ABS_CHROMA + 2 - KVZ_HIP_CX_SIG_CG])
@@ -160,12 +162,24 @@ inline bool inter_slice_launch_known(const kvz_hip_inter_params *p, bool has_til
   }
   return true;
 }
+// The reference lists of a launch (the kvz_hip_dev_*_refs entry points): what those entry points refuse of them before anything is queued, besides what
+// inter_slice_launch_known refuses of the slice type -- false and a message: lists without a POC per picture, with a slice type other than P (which brings the
+// refusal of tiles and of the me_* members with it), and whatever inter_refs_known refuses of the struct.  has_pictures / poc: the call's kvz_hip_inter_pictures
+// (the loop filters have none and pass poc == nullptr with has_pictures true: their twin takes a QP array)
+inline bool inter_refs_launch_known(const kvz_hip_inter_refs *refs, int n_pictures, bool has_pictures, const int32_t *poc, int slice_type, const char *who)
+{
+  if (!refs) return true;
+  if (slice_type != KVZ_HIP_SLICE_P) { fprintf(stderr, "%s: reference lists (kvz_hip_inter_refs) are covered for KVZ_HIP_SLICE_P only, not slice type %d\n", who, slice_type); return false; }
+  if (!has_pictures) { fprintf(stderr, "%s: reference lists (kvz_hip_inter_refs) need `pictures`: the POC of every picture comes from there\n", who); return false; }
+  return inter_refs_known(refs, n_pictures, poc, who);
+}
 inline void inter_model_set_me(InterModel *m, const kvz_hip_inter_params *p) { m->me_algorithm = p->me_algorithm; m->me_max_steps = p->me_max_steps; m->me_early_termination = p->me_early_termination; }
 
 inline void inter_model_init(InterModel *m, int qp, int poc, uint64_t coeff_weights, const float fbits[128], int mv_constraint, int sao, int deblock, int fme_level,
                              int pu_depth_inter_max, int no_wpp, int fast_residual_cost, int pic_w = 0, int pic_h = 0, int ref_w = 0, int ref_h = 0, int tile_x = 0, int tile_y = 0, int no_tmvp = 0,
                              int scaling_list = 0 /* a launch with scaling lists: the inverse scalars of the rule that takes a factor per position (quant-generic.c:309-333) */,
-                             int slice_type = KVZ_HIP_SLICE_B /* or KVZ_HIP_SLICE_P: the row of the tables the initial context states come from */)
+                             int slice_type = KVZ_HIP_SLICE_B /* or KVZ_HIP_SLICE_P: the row of the tables the initial context states come from */,
+                             int refs = 0 /* a launch with reference lists: the search contexts hold ref_idx_l0's two (IX_REF_IDX) */)
 {
   memset(m, 0, sizeof *m);
   m->qp = qp; m->poc = poc;
@@ -185,6 +199,7 @@ inline void inter_model_init(InterModel *m, int qp, int poc, uint64_t coeff_weig
   init[IX_MVD] = v.mvd[0]; init[IX_MVD + 1] = v.mvd[1]; init[IX_MVP_IDX] = v.mvp_idx;
   for (int i = 0; i < 5; i++) init[IX_INTER_DIR + i] = v.inter_dir[i];
   init[IX_ROOT_CBF] = v.root_cbf;
+  if (refs) { init[IX_REF_IDX] = v.ref_idx[0]; init[IX_REF_IDX + 1] = v.ref_idx[1]; }
   slice_residual_init_values(slice_type, init + IX_RES);
   for (int i = 0; i < IX_COUNT; i++) m->ctx_init[i] = (uint8_t)inter_ctx_state(qp, init[i]);
   for (int l2 = 2; l2 <= 5; l2++)
@@ -236,6 +251,28 @@ template <class InitRow> inline InterPictureTable inter_picture_table(const int3
     t.any_cabac = t.any_cabac || m->coeff_cabac;
   }
   for (int i = 0; i < n_pictures; i++) ((InterPicture *)base)[i] = InterPicture{ (uint32_t)(rows_at + (size_t)row_of_qp[qp[i]] * sizeof(InterModel)), poc[i] };
+  return t;
+}
+
+// ... and of a launch of P pictures with reference lists (kvz_hip_dev_inter_ctu_pass_refs; checked by inter_refs_launch_known): n InterPictureRefs records -- the
+// picture's list as pool frames and the scales of every vector it can meet (kvz_inter_refs.hpp inter_refs_record) --, then the InterModel rows.  init_row must make
+// its rows for a launch with lists of references (inter_model_init's refs).
+template <class InitRow> inline InterPictureTable inter_picture_table_refs(const int32_t *qp, const int32_t *poc, int n_pictures, const InitRow &init_row, const kvz_hip_inter_refs *refs)
+{
+  static_assert(sizeof(InterPictureRefs) == 128, "records and rows share a buffer of 8-byte words");
+  InterPictureTable t;
+  t.record_bytes = sizeof(InterPictureRefs);
+  int row_of_qp[52], qp_of_row[52];
+  t.n_rows = inter_qp_rows(qp, n_pictures, row_of_qp, qp_of_row);
+  const size_t rows_at = (size_t)n_pictures * sizeof(InterPictureRefs);
+  t.image.assign((rows_at + (size_t)t.n_rows * sizeof(InterModel)) / sizeof(uint64_t), 0);
+  uint8_t *base = (uint8_t *)t.image.data();
+  for (int r = 0; r < t.n_rows; r++) {
+    InterModel *m = (InterModel *)(base + rows_at) + r;
+    init_row(m, qp_of_row[r]);
+    t.any_cabac = t.any_cabac || m->coeff_cabac;
+  }
+  for (int i = 0; i < n_pictures; i++) ((InterPictureRefs *)base)[i] = InterPictureRefs{ (uint32_t)(rows_at + (size_t)row_of_qp[qp[i]] * sizeof(InterModel)), poc[i], inter_refs_record(refs, i, poc[i]), 0u };
   return t;
 }
 

@@ -27,7 +27,9 @@ struct InterSched {
 // group's first CTU + the picture's index in the group x the group's CTUs + the CTU; and the same two for launches that choose the integer motion search
 // (-DKVZ_ICTU_ME=1: kvz_hip_inter_params me_algorithm / me_max_steps / me_early_termination), `_me_fast` / `_me_cabac`, which raise the launch's error word when a
 // search loop reached its bound (kvz_inter_ctu_pix.inc IC_ME_LOOP_BOUND); and the same two for launches of P pictures (-DKVZ_ICTU_P=1:
-// kvz_hip_dev_inter_ctu_pass_slices with KVZ_HIP_SLICE_P), `_p_fast` / `_p_cabac`, the program without its L1 half (kvz_inter_ctu.hpp KVZ_ICTU_P)
+// kvz_hip_dev_inter_ctu_pass_slices with KVZ_HIP_SLICE_P), `_p_fast` / `_p_cabac`, the program without its L1 half (kvz_inter_ctu.hpp KVZ_ICTU_P); and the same two for launches of P pictures with
+// reference lists (-DKVZ_ICTU_P=1 -DKVZ_ICTU_REFS=1: kvz_hip_dev_inter_ctu_pass_refs), `_refs_fast` / `_refs_cabac`: F.ref / F.ref_cu are a pool of frames and
+// F.pictures holds InterPictureRefs records (kvz_inter_ctu.hpp KVZ_ICTU_REFS)
 #define KVZ_ICTU_KERNEL(name) __global__ void __launch_bounds__(KVZ_ICTU_THREADS) __attribute__((amdgpu_waves_per_eu(KVZ_ICTU_WAVES_PER_EU, KVZ_ICTU_WAVES_PER_EU))) name(const InterFrames F, const InterModel *model, const Tables *tb, const InterSched sched)
 #ifndef KVZ_INTER_KERNEL_BODY
 KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_fast);
@@ -40,6 +42,8 @@ KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_me_fast);
 KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_me_cabac);
 KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_p_fast);
 KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_p_cabac);
+KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_refs_fast);
+KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_refs_cabac);
 #else
 #if KVZ_ICTU_JOINT && KVZ_ICTU_LISTS
 #error "scaling lists are not part of joint launches"
@@ -50,7 +54,14 @@ KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_p_cabac);
 #if KVZ_ICTU_P && (KVZ_ICTU_LISTS || KVZ_ICTU_JOINT || KVZ_ICTU_ME)
 #error "P pictures are not part of launches with scaling lists, of joint launches or of launches that choose the integer motion search"
 #endif
-#if KVZ_ICTU_P && KVZ_ICTU_CABAC
+#if KVZ_ICTU_REFS && !KVZ_ICTU_P
+#error "reference lists are built for P pictures only"
+#endif
+#if KVZ_ICTU_REFS && KVZ_ICTU_CABAC
+KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_refs_cabac)
+#elif KVZ_ICTU_REFS
+KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_refs_fast)
+#elif KVZ_ICTU_P && KVZ_ICTU_CABAC
 KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_p_cabac)
 #elif KVZ_ICTU_P
 KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_p_fast)

@@ -8,7 +8,8 @@
 
 namespace kvz {
 
-inline void entropy_slice_contexts(int slice_type, int qp, uint8_t out[KVZ_ENTROPY_CTXS])
+// refs: pictures with reference lists (kvz_hip_dev_entropy_code_inter_refs) -- the set then holds ref_idx_l0's two contexts (KVZ_EB_CX_REF_IDX)
+inline void entropy_slice_contexts(int slice_type, int qp, uint8_t out[KVZ_ENTROPY_CTXS], bool refs = false)
 {
   const SliceSyntaxInit &v = slice_syntax_init(slice_type);
   uint8_t init[KVZ_ENTROPY_CTXS];
@@ -23,6 +24,7 @@ inline void entropy_slice_contexts(int slice_type, int qp, uint8_t out[KVZ_ENTRO
   init[KVZ_EB_CX_MVD] = v.mvd[0]; init[KVZ_EB_CX_MVD + 1] = v.mvd[1]; init[KVZ_EB_CX_MVP_IDX] = v.mvp_idx;
   for (int i = 0; i < 5; i++) init[KVZ_EB_CX_INTER_DIR + i] = v.inter_dir[i];
   init[KVZ_EB_CX_ROOT_CBF] = v.root_cbf;
+  if (refs) { init[KVZ_EB_CX_REF_IDX] = v.ref_idx[0]; init[KVZ_EB_CX_REF_IDX + 1] = v.ref_idx[1]; }
   for (int i = 0; i < KVZ_ENTROPY_CTXS; i++) out[i] = (uint8_t)inter_ctx_state(qp, init[i]);
 }
 

@@ -59,10 +59,15 @@ class InterPictureParams:
     """a QP and a POC per picture of one launch (kvz_hip_inter_pictures): the `pictures=` of InterPictures.run / .loop_filters / .entropy_code.  Everything else --
     preset, switches, geometry -- stays the launch's InterParams, whose qp and poc are then ignored"""
 
-    def __init__(self, qps, pocs):
+    def __init__(self, qps, pocs, references=None):
+        """references (InterReferences): the pictures are P pictures with reference lists over the object's pool -- InterPictures.run / .loop_filters /
+        .entropy_code then go through the kvz_hip_dev_*_refs entry points (slice_type="P"); the lists travel with the POCs they are checked against"""
         self.qps, self.pocs = np.ascontiguousarray(qps, np.int32).reshape(-1), np.ascontiguousarray(pocs, np.int32).reshape(-1)
         if self.qps.size != self.pocs.size:
             raise ValueError(f"{self.qps.size} QPs for {self.pocs.size} POCs")
+        if references is not None and len(references) != self.qps.size:
+            raise ValueError(f"{len(references)} reference lists for {self.qps.size} pictures")
+        self.references = references
         self.struct = InterPicturesStruct(struct_size=C.sizeof(InterPicturesStruct), n_pictures=self.qps.size, qp=self.qps.ctypes.data, poc=self.pocs.ctypes.data)  # (the arrays live as long as self)
 
     def __len__(self):
@@ -71,6 +76,74 @@ class InterPictureParams:
     @property
     def ptr(self):
         return C.addressof(self.struct)
+
+
+MAX_REFS = 4  # KVZ_HIP_MAX_REFS
+
+
+class InterRefsStruct(C.Structure):  # kvz_hip_inter_refs
+    _fields_ = [("struct_size", C.c_uint32), ("n_pictures", C.c_int32), ("n_frames", C.c_int32)] + [(n, C.c_void_p) for n in ("frame_poc", "frame_ref_poc", "n_refs", "ref_frame")]
+
+
+class InterReferences:
+    """the reference picture lists of the P pictures of one launch over a pool of reference frames (kvz_hip_inter_refs): the `references=` of InterPictureParams,
+    which InterPictures.run / .loop_filters / .entropy_code take as `pictures`.  frame_pocs [n_frames]: the POC of every frame of the pool; frame_ref_pocs [n_frames][<= 4]: the POCs that frame's own list
+    named when it was coded (an I frame: anything); n_refs [n_pictures]: the length of every picture's list; ref_frames [n_pictures][<= 4]: the pool indices of
+    its entries in list order.  The library checks the table when a launch is made"""
+
+    def __init__(self, frame_pocs, frame_ref_pocs, n_refs, ref_frames):
+        def rows(a, n):
+            out = np.zeros((n, MAX_REFS), np.int32)
+            for i, row in enumerate(a):
+                row = [int(v) for v in row][:MAX_REFS]
+                out[i, :len(row)] = row
+            return out
+        self.frame_pocs = np.ascontiguousarray(frame_pocs, np.int32).reshape(-1)
+        self.n_refs = np.ascontiguousarray(n_refs, np.int32).reshape(-1)
+        if len(frame_ref_pocs) != self.frame_pocs.size or len(ref_frames) != self.n_refs.size:
+            raise ValueError(f"{len(frame_ref_pocs)} rows of reference POCs for {self.frame_pocs.size} frames, {len(ref_frames)} lists for {self.n_refs.size} pictures")
+        self.frame_ref_pocs, self.ref_frames = rows(frame_ref_pocs, self.frame_pocs.size), rows(ref_frames, self.n_refs.size)
+        self.struct = InterRefsStruct(struct_size=C.sizeof(InterRefsStruct), n_pictures=self.n_refs.size, n_frames=self.frame_pocs.size, frame_poc=self.frame_pocs.ctypes.data,
+                                      frame_ref_poc=self.frame_ref_pocs.ctypes.data, n_refs=self.n_refs.ctypes.data, ref_frame=self.ref_frames.ctypes.data)  # (the arrays live as long as self)
+
+    def __len__(self):
+        return int(self.n_refs.size)
+
+    @property
+    def ptr(self):
+        return C.addressof(self.struct)
+
+
+def lowdelay_ref_distances(g, ref, gop_len):
+    """the POC distances picture g (1 .. gop_len) of `--gop lp-g<gop_len>d<..>t1 --ref <ref>` asks for (cfg.c:1468-1507 with t = 1): the previous picture, then the
+    previous key pictures -- g, g + gop_len, ... back, skipping a distance the entry before already has"""
+    neg = [1]
+    keyframe = g
+    for i in range(1, ref):
+        while keyframe == neg[i - 1]:
+            keyframe += gop_len
+        neg.append(keyframe)
+    return neg
+
+
+def reference_pocs(poc, ref, gop="lp-g4d3t1"):
+    """the POCs of picture `poc`'s list L0, in list order, under kvazaar's `--gop <gop> --ref <ref>` with one I picture at POC 0: `gop` "0" -- the previous `ref`
+    pictures, as far as they exist --, or "lp-g<len>d<depth>t1" -- the pictures at lowdelay_ref_distances that are still in the decoded picture buffer, which drops
+    every picture the current one does not ask for (encoderstate.c:1139-1182).  L0 is ordered by descending POC (encoderstate.c:1040-1115)"""
+    if poc < 1:
+        return []
+    if gop == "0":
+        return [poc - d for d in range(1, ref + 1) if poc - d >= 0]
+    if not (gop.startswith("lp-g") and gop.endswith("t1") and "d" in gop):
+        raise ValueError(f"--gop {gop}: \"0\" or lp-g<len>d<depth>t1")
+    gop_len = int(gop[4:gop.index("d")])
+    dpb = [0]
+    for p in range(1, poc + 1):
+        wanted = [p - d for d in lowdelay_ref_distances((p - 1) % gop_len + 1, ref, gop_len)]
+        dpb = [q for q in dpb if q in wanted]
+        if p == poc:
+            return sorted(dpb, reverse=True)
+        dpb.append(p)
 
 
 def veryfast_params(qp, poc, mv_constraint=True):
@@ -139,9 +212,13 @@ def cu_digest(cu):
 class InterPictures:
     """picture k of `n` independent sequences, resident on the device: sources, references (+ their CU info), and the pass's outputs"""
 
-    def __init__(self, lib, width, height, n, with_levels=False):
+    def __init__(self, lib, width, height, n, with_levels=False, pool=1):
+        """pool: reference frames kept per picture slot (P pictures with reference lists: kvz_hip_dev_*_refs).  The reference buffers then hold pool * n frames,
+        frame s * n + i = slot s of sequence i; with pool == 1 they are what they have always been"""
         from .dev import Dev
-        self.lib, self.dev, self.w, self.h, self.n = lib, Dev(lib), width, height, n
+        self.lib, self.dev, self.w, self.h, self.n, self.pool = lib, Dev(lib), width, height, n, int(pool)
+        if self.pool < 1:
+            raise ValueError(f"pool {pool}: at least one reference frame per picture")
         self.fs, self.cells = width * height * 3 // 2, (width // 4) * (height // 4)
         lib.kvz_hip_dev_inter_ctu_pass.restype = C.c_int
         lib.kvz_hip_dev_inter_ctu_pass.argtypes = [C.c_void_p] * 6 + [C.c_int] * 3 + [C.c_void_p]
@@ -169,8 +246,17 @@ class InterPictures:
         lib.kvz_hip_dev_entropy_code_inter.restype = C.c_long
         lib.kvz_hip_dev_entropy_code_inter.argtypes = [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         e = self.dev.empty
-        self.d_src, self.d_ref, self.d_rec = e(n * self.fs), e(n * self.fs), e(n * self.fs)
-        self.d_ref_cu, self.d_cu = e(n * self.cells * CU_DTYPE.itemsize), e(n * self.cells * CU_DTYPE.itemsize)
+        self.d_src, self.d_ref, self.d_rec = e(n * self.fs), e(self.pool * n * self.fs), e(n * self.fs)
+        self.d_ref_cu, self.d_cu = e(self.pool * n * self.cells * CU_DTYPE.itemsize), e(n * self.cells * CU_DTYPE.itemsize)
+        if hasattr(lib, "kvz_hip_dev_inter_ctu_pass_refs"):  # (a library from before the entry points still loads: tools/bench_inter_refs.py times the parent commit's)
+            lib.kvz_hip_dev_inter_ctu_pass_refs.restype = C.c_int
+            lib.kvz_hip_dev_inter_ctu_pass_refs.argtypes = [C.c_void_p] * 6 + [C.c_int] * 3 + [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+            lib.kvz_hip_dev_loop_filters_inter_refs.restype = C.c_int
+            lib.kvz_hip_dev_loop_filters_inter_refs.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 4
+            lib.kvz_hip_dev_entropy_code_inter_refs.restype = C.c_long
+            lib.kvz_hip_dev_entropy_code_inter_refs.argtypes = [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+            lib.kvz_hip_dev_copy.restype = None
+            lib.kvz_hip_dev_copy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         self.ctus = ((width + 63) // 64) * ((height + 63) // 64)
         self.d_coeff = e(n * self.ctus * 6144 * 2) if with_levels else None  # KVZ_HIP_CTU_COEFFS int16 per CTU: what the entropy coder reads
         self._entropy_out = None
@@ -205,11 +291,41 @@ class InterPictures:
         """the object is again what it was before the first set_scaling_lists"""
         self.set_scaling_lists([])
 
+    def upload_pool(self, slot, i, ref, ref_cu):
+        """slot `slot` of sequence i's reference pool: a reference frame (after its loop filters) and its CU records"""
+        if not 0 <= slot < self.pool:
+            raise ValueError(f"slot {slot} of a pool of {self.pool}")
+        for base, a, size in ((self.d_ref, ref, self.fs), (self.d_ref_cu, ref_cu, self.cells * CU_DTYPE.itemsize)):
+            a = np.ascontiguousarray(a)
+            assert a.nbytes == size
+            self.lib.kvz_hip_dev_upload(base + (slot * self.n + i) * size, a.ctypes.data, size)
+
+    def pool_frame(self, slot, i):
+        """the index into the pool (InterReferences ref_frames) of slot `slot` of sequence i"""
+        return slot * self.n + i
+
+    def advance_pool(self, keep):
+        """the pictures just encoded (after their loop filters) and their CU records move into slot `keep` of every sequence's pool, on the device: the next
+        pictures' lists can name them"""
+        if not 0 <= keep < self.pool:
+            raise ValueError(f"slot {keep} of a pool of {self.pool}")
+        self.lib.kvz_hip_dev_copy(self.d_ref + keep * self.n * self.fs, self.d_rec, self.n * self.fs)
+        self.lib.kvz_hip_dev_copy(self.d_ref_cu + keep * self.n * self.cells * CU_DTYPE.itemsize, self.d_cu, self.n * self.cells * CU_DTYPE.itemsize)
+
     def run(self, params, pictures=None, slice_type="B"):
         """the CTU pass of the n pictures; pictures (InterPictureParams): every picture at its own QP and POC instead of params.qp / params.poc.  While the object
         holds scaling lists (set_scaling_lists) the launch is kvz_hip_dev_inter_ctu_pass_lists.
         slice_type: "B" (the default: the calls this method has always made) or "P" -- kvazaar's --no-bipred -- through kvz_hip_dev_inter_ctu_pass_slices, as is
         every slice type given as a KVZ_HIP_SLICE_* number.  P pictures take no scaling lists"""
+        references = getattr(pictures, "references", None)
+        if references is not None:  # P pictures with reference lists over the pool (InterPictureParams(..., references=InterReferences)): kvz_hip_dev_inter_ctu_pass_refs
+            if self._n_list_sets:
+                raise ValueError("scaling lists are set: kvz_hip_dev_inter_ctu_pass_lists has no reference lists (clear_scaling_lists())")
+            rc = self.lib.kvz_hip_dev_inter_ctu_pass_refs(self.d_src, self.d_ref, self.d_ref_cu, self.d_rec, self.d_cu, self.d_coeff, self.w, self.h, self.n, C.addressof(params), None, 0,
+                                                          pictures.ptr if pictures is not None else None, slice_type_value(slice_type), references.ptr)
+            if rc != 0:
+                raise RuntimeError(f"kvz_hip_dev_inter_ctu_pass_refs returned {rc}")
+            return
         if slice_type != "B":
             if self._n_list_sets:
                 raise ValueError("scaling lists are set: kvz_hip_dev_inter_ctu_pass_lists has no slice type, its pictures are B (clear_scaling_lists())")
@@ -257,6 +373,15 @@ class InterPictures:
         if self.d_dbk is None:
             self.d_dbk = self.dev.empty(self.n * self.cells * 20)  # kvz_hip_cu_dbk
         self.lib.kvz_hip_dev_cu_dbk_from_info(self.d_cu, self.n * self.cells, self.d_dbk)
+        references = getattr(pictures, "references", None)
+        if references is not None:  # kvz_hip_dev_loop_filters_inter_refs: the table is checked, the filters are the slice type's
+            if pictures is not None and len(pictures) != self.n:
+                raise ValueError(f"{len(pictures)} picture QPs for {self.n} pictures")
+            rc = self.lib.kvz_hip_dev_loop_filters_inter_refs(self.d_src, self.d_rec, self.w, self.h, self.n, self.d_dbk, params.qp, pictures.qps.ctypes.data if pictures is not None else None,
+                                                              slice_type_value("P" if slice_type is None else slice_type), params.deblock, 0, 0, params.sao, params.no_wpp, None, None, None, references.ptr)
+            if rc != 0:
+                raise RuntimeError(f"kvz_hip_dev_loop_filters_inter_refs returned {rc}")
+            return
         if slice_type is not None:
             if pictures is not None and len(pictures) != self.n:
                 raise ValueError(f"{len(pictures)} picture QPs for {self.n} pictures")
@@ -292,7 +417,11 @@ class InterPictures:
             from .batch import pinned_bytes
             self._entropy_ptr, self._entropy_out = pinned_bytes(self.lib, capacity)  # pinned: the call downloads the slice data straight into it
         sizes = np.zeros((self.n, rows), np.uint32)
-        if slice_type != "B":
+        references = getattr(pictures, "references", None)
+        if references is not None:  # the pool's records are the reference records: the co-located picture of a picture is the frame of its list's first entry
+            total = self.lib.kvz_hip_dev_entropy_code_inter_refs(self.d_cu, self.d_ref_cu, self.d_coeff, self.w, self.h, self.n, C.addressof(params), self._entropy_out.ctypes.data,
+                                                                 capacity, sizes.ctypes.data, pictures.ptr if pictures is not None else None, slice_type_value(slice_type), references.ptr)
+        elif slice_type != "B":
             total = self.lib.kvz_hip_dev_entropy_code_inter_slices(self.d_cu, self.d_ref_cu, self.d_coeff, self.w, self.h, self.n, C.addressof(params), self._entropy_out.ctypes.data,
                                                                    capacity, sizes.ctypes.data, pictures.ptr if pictures is not None else None, slice_type_value(slice_type))
         elif pictures is not None:
