@@ -62,6 +62,11 @@ int  kvz_hip_dev_intra_select(int log2w, int nblk, const uint32_t *raw, const in
  * A developer entry point: the pass itself works in LDS.  -1: arguments it does not take. */
 int  kvz_hip_dev_cu8_units(int count, int from_coeffs, const int16_t *in, const int32_t *qp, int16_t *levels, int16_t *dequant, int16_t *resid);
 
+/* The Hadamard half of the CTU pass's rough search (kvz_mfma.hpp satd8_group_mfma, 32 block pairs per wavefront on v_mfma_i32_32x32x32_i8) on `count` pairs of 8x8
+ * byte blocks in device memory, 64 bytes each, row-major: out[i] = sum |H8 (a[i] - b[i]) H8|, the unrounded 8x8 SATD (kvz_satd_8x8 is (out[i] + 2) >> 2).  A
+ * developer entry point: the pass itself predicts the blocks in registers.  -1: a negative count. */
+int  kvz_hip_dev_satd8_blocks(const uint8_t *a, const uint8_t *b, int count, uint32_t *out);
+
 /* Deblocking of all-intra, constant-QP pictures in place: kvz_filter_deblock_lcu (filter.c:783) over every LCU of every
  * frame.  frames = n_frames x [Y | U | V] tight planar 4:2:0 (the batch layout), cu_depth = n_frames x [H/8][W/8] CU depths
  * as the CTU pass returns them; beta / tc offsets are cfg.deblock_beta / cfg.deblock_tc (cfg.c: 0, 0).  Not a strategy in

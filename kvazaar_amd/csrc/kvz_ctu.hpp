@@ -1242,70 +1242,6 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false, bool
     constexpr int NR = PAIR ? 4 : 8;
     const int r0 = PAIR ? 4 * half : 0;
     Pk16 d[NR][4];
-#ifndef KVZ_HOSTSIM
-    if (!big) {
-      // Packed rows (8x8 and 16x16 CUs): the eight predicted samples of a row as four u16 pairs, minus the source row widened the same way.  Every intermediate
-      // fits 16 bits ((32 - f) a + f b + 16 <= 8176; the planar sum <= 2 w 255 + w), so the arithmetic is that of intra-generic.c sample for sample.
-      if (flat) {
-        if (mode == 0) {  // planar (intra-generic.c:165-201) on the filtered references: (w-1-x) L + (x+1) TR + (w-1-y) T[x] + (y+1) BL + w
-          const u8 *top = s->fref[0], *left = s->fref[1];
-          const int tr = top[w + 1], bl = left[w + 1];
-          U16x2 tp[4], xs[4];
-          widen8(top + bx + 1, tp);
-#pragma unroll
-          for (int j = 0; j < 4; j++) { xs[j].x = (unsigned short)(bx + 2 * j); xs[j].y = (unsigned short)(bx + 2 * j + 1); }
-#pragma unroll
-          for (int i = 0; i < NR; i++) {
-            const int y = by + r0 + i, l = left[y + 1];
-            const U16x2 dl = splat16(tr - l), wy = splat16(w - 1 - y), hb = splat16((w - 1) * l + tr + (y + 1) * bl + w);
-            U16x2 o[4];
-            widen8(org + (r0 + i) * ostride, o);
-#pragma unroll
-            for (int j = 0; j < 4; j++) d[i][j] = as_pk16(((xs[j] * dl + (tp[j] * wy + hb)) >> (unsigned short)(log2w + 1)) - o[j]);
-          }
-        } else {  // DC with its edge smoothing (intra-generic.c:210-241) on the unfiltered references
-          const u8 *top = s->ref[0][0], *left = s->ref[0][1];
-          const int dc = s->dcval[0];
-          U16x2 tp[4];
-          widen8(top + bx + 1, tp);
-#pragma unroll
-          for (int i = 0; i < NR; i++) {
-            const int y = by + r0 + i;
-            U16x2 o[4], v[4];
-            widen8(org + (r0 + i) * ostride, o);
-#pragma unroll
-            for (int j = 0; j < 4; j++) v[j] = y == 0 ? (U16x2)((tp[j] + splat16(3 * dc + 2)) >> (unsigned short)2) : splat16(dc);
-            if (bx == 0) v[0].x = (unsigned short)(y == 0 ? (left[1] + 2 * dc + top[1] + 2) >> 2 : (left[y + 1] + 3 * dc + 2) >> 2);
-#pragma unroll
-            for (int j = 0; j < 4; j++) d[i][j] = as_pk16(v[j] - o[j]);
-          }
-        }
-      } else {
-        unsigned rnd_bits = 0x00100010u;
-        asm("" : "+v"(rnd_bits));  // opaque, or the compiler pulls the constant out of the multiply-add chain: mul + mad + add where two mads do
-#pragma unroll
-        for (int i = 0; i < NR; i++) {
-          const int qa = q0 + r0 + i + 1, delta = qa * disp, di = delta >> 5, df = delta & 31;
-          const u8 *m = mr + di;
-          unsigned mw[2];
-          __builtin_memcpy(mw, m, 8);
-          const unsigned m8 = m[8];
-          const U16x2 c1 = splat16(df), c0 = splat16(32 - df), rnd = u16x2_of(rnd_bits);
-          U16x2 pa[4], pb[4], o[4];
-          pa[0] = widen(0, mw[0], 0x0c010c00u); pa[1] = widen(0, mw[0], 0x0c030c02u); pa[2] = widen(0, mw[1], 0x0c010c00u); pa[3] = widen(0, mw[1], 0x0c030c02u);
-          pb[0] = widen(0, mw[0], 0x0c020c01u); pb[1] = widen(mw[1], mw[0], 0x0c040c03u); pb[2] = widen(0, mw[1], 0x0c020c01u); pb[3] = widen(m8, mw[1], 0x0c040c03u);
-          widen8(org + (r0 + i) * ostride, o);
-          U16x2 v[4];
-#pragma unroll
-          for (int j = 0; j < 4; j++) v[j] = (pa[j] * c0 + (pb[j] * c1 + rnd)) >> (unsigned short)5;
-          if (edge) v[0].x = (unsigned short)iclip(0, 255, (int)v[0].x + (((int)side[qa] - (int)side[0]) >> 1));
-#pragma unroll
-          for (int j = 0; j < 4; j++) d[i][j] = as_pk16(v[j] - o[j]);
-        }
-      }
-    } else
-#endif
-    {
 #pragma unroll
     for (int i = 0; i < NR; i++) {
       const int r = r0 + i;
@@ -1336,7 +1272,6 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false, bool
       }
       if (edge) v[0] = iclip(0, 255, v[0] + (((int)side[qa] - (int)side[0]) >> 1));
       for (int j = 0; j < 4; j++) d[i][j] = pk_make(v[2 * j] - (int)((ow >> (16 * j)) & 0xff), v[2 * j + 1] - (int)((ow >> (16 * j + 8)) & 0xff));
-    }
     }
 #ifndef KVZ_HOSTSIM
     if (PAIR ? half == 0 : true) d[0][0] = pk_add(d[0][0], KVZ_PK_BIAS);  // sample (0, 0), in the lane that holds row 0: see pk_abs2_biased
@@ -1392,6 +1327,60 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false, bool
   }
 
 #ifndef KVZ_HOSTSIM
+  // The same total for one angular mode (2..33) on one 8x8 block of an 8x8 / 16x16 CU, as this lane's column of a GROUP of 32 (mode, block) pairs that the whole
+  // wavefront scores together on the matrix cores (satd8_group_mfma, kvz_mfma.hpp): lanes l and l + 32 share the pair, `half` 0 / 1 predicting rows 0..3 / 4..7
+  // (across the main reference).  The row generator is angular_block_satd's arithmetic two samples per register (v_pk_mad_u16 / v_pk_lshrrev_b16; every intermediate
+  // fits 16 bits: (32 - f) a + f b + 16 <= 8176), with 128 << 5 riding on the rounding constant: the low byte of a result is the sample xor 0x80, the signed byte the
+  // product takes, and the source rows go in as they lie in memory, xor 0x80 -- no subtraction, no widening, no butterflies on the vector pipe.  Must be called by all
+  // 64 lanes.  Both lanes of a pair return the block's total.
+  KVZ_DEV u32 angular_group_satd(const SatdWalsh &wm, int log2w, int mode, int bx, int by, int xl, int yl, int half) const
+  {
+    const int w = 1 << log2w;
+    const bool vertical = mode >= 18;
+    const int disp = s->mode_disp[mode];
+    const int p0 = vertical ? bx : by, q0 = vertical ? by : bx;  // block origin along / across the main reference
+    const u8 *mr;
+    if (disp < 0) mr = s->mref[mode - 11] + KVZ_MREF_ORG;
+    else {
+      const bool filt = imin(iabs(mode - 26), iabs(mode - 10)) > (log2w == 3 ? 7 : 1);
+      mr = filt ? s->fref[vertical ? 0 : 1] : s->ref[0][vertical ? 0 : 1];
+    }
+    mr += p0 + 1;
+    const u8 *org = vertical ? org_at(0, xl + bx, yl + by) : s->org_t + bx * w + by;
+    const int ostride = vertical ? 32 : w;
+    const u8 *side = vertical ? s->ref[0][1] : s->ref[0][0];  // intra.c:207-219: modes 10 / 26 use the unfiltered references
+    const bool edge = disp == 0 && p0 == 0;
+    const int r0 = 4 * half;
+    unsigned rnd_bits = 0x10101010u;  // 16 + (128 << 5) in both halves
+    asm("" : "+v"(rnd_bits));  // opaque, or the compiler pulls the constant out of the multiply-add chain: mul + mad + add where two mads do
+    dev_int4 p[2], o[2];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const int qa = q0 + r0 + i + 1, delta = qa * disp, di = delta >> 5, df = delta & 31;
+      const u8 *m = mr + di;
+      unsigned mw[2], ow[2];
+      __builtin_memcpy(mw, m, 8);
+      const unsigned m8 = m[8];
+      __builtin_memcpy(ow, org + (r0 + i) * ostride, 8);
+      const U16x2 c1 = splat16(df), c0 = splat16(32 - df), rnd = u16x2_of(rnd_bits);
+      // samples k and k + 2 share a register (k = 0, 1, 4, 5): the bytes k, k + 2 and their right neighbours k + 1, k + 3 are six widenings for the eight
+      // samples (the odd bytes serve twice, as right neighbours of the even ones and as the samples 1, 3 / 5, 7) where adjacent pairs take eight
+      const U16x2 e0 = widen(0, mw[0], 0x0c020c00u), o0 = widen(0, mw[0], 0x0c030c01u), f0 = widen(mw[1], mw[0], 0x0c040c02u);
+      const U16x2 e1 = widen(0, mw[1], 0x0c020c00u), o1 = widen(0, mw[1], 0x0c030c01u), f1 = widen(m8, mw[1], 0x0c040c02u);
+      U16x2 v[4];  // the predicted samples + 128: (0, 2), (1, 3), (4, 6), (5, 7)
+      v[0] = (e0 * c0 + (o0 * c1 + rnd)) >> (unsigned short)5; v[1] = (o0 * c0 + (f0 * c1 + rnd)) >> (unsigned short)5;
+      v[2] = (e1 * c0 + (o1 * c1 + rnd)) >> (unsigned short)5; v[3] = (o1 * c0 + (f1 * c1 + rnd)) >> (unsigned short)5;
+      if (edge) v[0].x = (unsigned short)iclip(128, 128 + 255, (int)v[0].x + (((int)side[qa] - (int)side[0]) >> 1));
+      unsigned vw[4];
+      __builtin_memcpy(vw, v, 16);
+      p[i >> 1][2 * (i & 1)] = (int)__builtin_amdgcn_perm(vw[1], vw[0], 0x06020400u);  // the low bytes of the four u16, in sample order
+      p[i >> 1][2 * (i & 1) + 1] = (int)__builtin_amdgcn_perm(vw[3], vw[2], 0x06020400u);
+      o[i >> 1][2 * (i & 1)] = (int)(ow[0] ^ 0x80808080u);
+      o[i >> 1][2 * (i & 1) + 1] = (int)(ow[1] ^ 0x80808080u);
+    }
+    return satd8_group_mfma(wm, p, o);
+  }
+
   // Planar, DC or mode 34 on one 8x8 block of an 8x8 / 16x16 CU by EIGHT neighbouring lanes, one row each (lane & 7 = the row): the three modes that do not fit
   // the wavefront of the 32 other ones (two lanes a block, angular_block_satd) would otherwise cost a second round of that routine's four-rows-a-lane code for a
   // handful of lanes.  Row generator (the same integers as angular_block_satd's), the row's butterflies in the lane, the column's through three DPP exchanges
@@ -1639,16 +1628,17 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false, bool
         s->satd_raw[mode][b] = angular_block_satd<false>(log2w, mode, bx, by, xl, yl, 0);
       }
 #else
-      // modes 2..33
-      if (log2w == 4) {
-        // a 16x16 CU has 128 (mode, block) pairs: ONE lane each, all eight rows in the lane (angular_block_satd<false>) -- one round of the two wavefronts, no exchange stage
-        const int mode = 2 + (tid >> 2), b = tid & 3;
-        s->satd_raw[mode][b] = angular_block_satd<false>(4, mode, (b & 1) * 8, (b >> 1) * 8, xl, yl, 0);
-      } else  // an 8x8 CU (nblk 1): TWO lanes per mode, rows 0..3 and 4..7 of the block (angular_block_satd<true>) -- 64 lane tasks, one wavefront
-      for (int t = tid; t < 64 * nblk; t += KVZ_CTU_THREADS) {
-        const int p = t >> 1, mode = 2 + (p >> lb), b = p & (nblk - 1), bx = (b & ((w >> 3) - 1)) * 8, by = (b >> (log2w - 3)) * 8;
-        const u32 v = angular_block_satd<true>(log2w, mode, bx, by, xl, yl, t & 1);
-        if (!(t & 1)) s->satd_raw[mode][b] = v;
+      // modes 2..33: a wavefront scores a GROUP of 32 (mode, block) pairs at a time, the lanes l and l + 32 predicting rows 0..3 / 4..7 of pair l's block and the
+      // matrix cores taking the Hadamard transforms (angular_group_satd).  An 8x8 CU's 32 modes are one group, on the first wavefront; a 16x16 CU's 128 pairs
+      // (mode, block) are four, two per wavefront
+      if (log2w == 4 || tid < 64) {  // (whole wavefronts)
+        const int lane = tid & 63;
+        const SatdWalsh wm = satd8_walsh(tb, lane);
+        for (int g = log2w == 4 ? 2 * (tid >> 6) : 0, ge = g + (log2w == 4 ? 2 : 1); g < ge; g++) {
+          const int p = 32 * g + (lane & 31), mode = 2 + (p >> lb), b = p & (nblk - 1), bx = (b & ((w >> 3) - 1)) * 8, by = (b >> (log2w - 3)) * 8;
+          const u32 v = angular_group_satd(wm, log2w, mode, bx, by, xl, yl, lane >> 5);
+          if (lane < 32) s->satd_raw[mode][b] = v;
+        }
       }
       // mode 34, planar, DC: EIGHT lanes per (mode, block), one row each (flat_block_satd8), taken from the far end of the thread ids -- the other wavefront of an
       // 8x8 CU (24 lane tasks; 96 for a 16x16 one)

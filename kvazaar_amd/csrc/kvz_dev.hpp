@@ -360,6 +360,13 @@ __global__ void __launch_bounds__(256) dev_cu8_units_kernel(const i16 *in, const
   }
 }
 
+// kvz_hip_dev_satd8_blocks: the rough search's group routine (kvz_mfma.hpp satd8_group_mfma: what kvz_ctu.hpp angular_group_satd calls) on pairs of 8x8 byte blocks
+// in memory, a wavefront per 32 pairs
+__global__ void __launch_bounds__(256) dev_satd8_blocks_kernel(const Tables *tb, const u8 *a, const u8 *b, const int count, u32 *out)
+{
+  dev_satd8_blocks_wave(tb, a, b, count, out, (int)(blockIdx.x * 4 + (threadIdx.x >> 6)), (int)(threadIdx.x & 63));
+}
+
 template <int L2> __global__ void __launch_bounds__(256) dev_angular_kernel(const u8 *above, const u8 *left, const int count, const int mode, u8 *out)
 {
   constexpr int W = 1 << L2, NG = kAngularGroupsPerLane, GPB = W * W / 4, BLOCKS = 256 * NG / GPB, RS = 2 * W + 1, ES = (2 * W + 1 + 8 + 3) & ~3;
@@ -1335,6 +1342,13 @@ int kvz_hip_dev_cu8_units(int count, int from_coeffs, const int16_t *in, const i
   if (count < 0 || (from_coeffs != 0 && from_coeffs != 1)) { fprintf(stderr, "kvz_hip_dev_cu8_units: count=%d from_coeffs=%d\n", count, from_coeffs); return -1; }
   if (count == 0) return 0;
   KVZ_DEV_LAUNCH(kvz::dev_cu8_units_kernel, ((long)count + 1) / 2 * 256, in, qp, count, from_coeffs, kvz::device_tables(), levels, dequant, resid);
+  return 0;
+}
+
+int kvz_hip_dev_satd8_blocks(const uint8_t *a, const uint8_t *b, int count, uint32_t *out)
+{
+  if (count < 0) { fprintf(stderr, "kvz_hip_dev_satd8_blocks: count=%d\n", count); return -1; }
+  KVZ_DEV_LAUNCH(kvz::dev_satd8_blocks_kernel, ((long)count + 31) / 32 * 64, kvz::device_tables(), a, b, count, out);
   return 0;
 }
 

@@ -178,4 +178,60 @@ template <int NB> __device__ __forceinline__ void mfma_transform_blocks16(const 
   for (int b = 0; b < NB; b++) for (int r = 0; r < 4; r++) o[b * 256 + M::row(lane, r) * 16 + col] = (i16)(inverse ? iclip(-32768, 32767, w[b][r] >> 12) : w[b][r] >> 10);
 }
 
+// ---- sum |H8 (P - O) H8| of 32 pairs of 8x8 byte blocks, one wavefront, v_mfma_i32_32x32x32_i8 (the rough search's SATD, kvz_ctu.hpp; kvz_hip_dev_satd8_blocks) ----
+// The sum of magnitudes asks for the 64 two-dimensional Walsh functions in any order and with any sign, so the product is W x [P - 128 ; O - 128] with a 64 x 128 matrix
+// W = [W64 | -W64] of +-1 bytes (A operand: two tiles of 32 rows, four steps of 32 k) and the samples as they lie in memory, xor 0x80, as B: column = lane & 31 = the
+// block, and the lane halves bring rows 0..3 / 4..7 of both blocks, two rows (16 bytes) per step -- P in steps 0 and 1, O in steps 2 and 3.  Which k a (lane half, byte)
+// slot is called does not matter: A and B meet slot by slot.  Row m = 32 tile + i of W64 (i = lane & 31) pairs its bits with the sample's
+//   bit 5 (tile) <-> step within P / O,   bit 4 <-> lane half,   bit 3 <-> the row within the step,   bits 2..0 <-> the column,
+// W64[m][sample] = (-1)^(sum of the paired bits' products): an invertible pairing, so the 64 rows are the 64 Walsh functions, once each.  With the tile bit paired with
+// the step, an A fragment is +-(one set of four registers): pos, or neg = -pos, for every (tile, step, P / O).  The accumulators start at kSatdBias > 64 x 255, so
+// every output is positive and |coefficient| = |output - bias| is one v_sad_u16 that also adds up.  Exact integers throughout.
+struct SatdWalsh { dev_int4 pos, neg; };
+constexpr int kSatdBias = 1 << 15;
+__device__ __forceinline__ SatdWalsh satd8_walsh(const Tables *tb, int lane)  // this lane's fragment and its negative (Tables::satd_walsh, kvz_ops.hpp satd_walsh_word)
+{
+  const dev_int4 *row = reinterpret_cast<const dev_int4 *>(tb->satd_walsh[lane]);
+  SatdWalsh w;
+  w.pos = row[0];
+  w.neg = row[1];
+  return w;
+}
+// p, o: the lane's four rows of its column's block (rows 4 (lane >> 5) ..), every byte xor 0x80 (= sample - 128): [0] rows 0 and 1, [1] rows 2 and 3.  Returns the
+// block's total on both lanes of the column.
+__device__ __forceinline__ u32 satd8_group_mfma(const SatdWalsh &w, const dev_int4 p[2], const dev_int4 o[2])
+{
+  u32 sums[2] = { 0, 0 };  // two running sums: a v_sad does not wait for the one in front of it
+#pragma unroll
+  for (int tile = 0; tile < 2; tile++) {  // one tile's sixteen accumulators at a time: the second tile's products start when the first's magnitudes are summed
+    dev_int16 t;
+#pragma unroll
+    for (int r = 0; r < 16; r++) t[r] = kSatdBias;
+    t = __builtin_amdgcn_mfma_i32_32x32x32_i8(tile ? w.neg : w.pos, p[1], t, 0, 0, 0);  // (the product that differs first: the tiles share none, and no accumulator outlives its tile)
+    t = __builtin_amdgcn_mfma_i32_32x32x32_i8(w.pos, p[0], t, 0, 0, 0);
+    t = __builtin_amdgcn_mfma_i32_32x32x32_i8(tile ? w.pos : w.neg, o[1], t, 0, 0, 0);
+    t = __builtin_amdgcn_mfma_i32_32x32x32_i8(w.neg, o[0], t, 0, 0, 0);
+#pragma unroll
+    for (int r = 0; r < 16; r++) sums[r & 1] = __builtin_amdgcn_sad_u16((u32)t[r], (u32)kSatdBias, sums[r & 1]);  // the high halves are zero: v_sad_u16 adds |x - bias| alone
+  }
+  const u32 sum = sums[0] + sums[1];
+  const auto both = __builtin_amdgcn_permlane32_swap(sum, sum, false, false);  // the other half's sum beside this one's, in both halves
+  return both[0] + both[1];
+}
+// out[b] of the blocks 32 group .. 32 group + 31 below count: block b's P at a + 64 b, its O at bsrc + 64 b, row-major
+__device__ __forceinline__ void dev_satd8_blocks_wave(const Tables *tb, const u8 *a, const u8 *bsrc, int count, u32 *out, int group, int lane)
+{
+  const long blk = 32l * group + (lane & 31);
+  const bool live = blk < count;
+  dev_int4 p[2] = {}, o[2] = {};
+  if (live) {
+    const dev_int4 *pa = reinterpret_cast<const dev_int4 *>(a + 64 * blk + 32 * (lane >> 5)), *po = reinterpret_cast<const dev_int4 *>(bsrc + 64 * blk + 32 * (lane >> 5));
+    p[0] = pa[0]; p[1] = pa[1]; o[0] = po[0]; o[1] = po[1];
+  }
+#pragma unroll
+  for (int q = 0; q < 2; q++) { p[q] ^= (int)0x80808080u; o[q] ^= (int)0x80808080u; }
+  const u32 v = satd8_group_mfma(satd8_walsh(tb, lane), p, o);
+  if (live && lane < 32) out[blk] = v;
+}
+
 }  // namespace kvz

@@ -105,7 +105,21 @@ struct Tables {
   u32 entropy_bits[128];       // kvz_entropy_bits (rdo.c:69-80): Q15 price of a bin, index = context state ^ bin
   int8_t luma_filter[4][8];    // filter.c:66-72
   int8_t chroma_filter[8][4];  // filter.c:74-84
+  // CTU pass, rough search on the matrix cores (kvz_mfma.hpp satd8_group_mfma): lane l's A operand, sixteen +-1 bytes of its row of the 64 x 64 Walsh matrix
+  // ([l][0..3], satd_walsh_word) and their negatives ([l][4..7])
+  alignas(16) u32 satd_walsh[64][8];
 };
+
+// Register q (0..3) of lane `lane`'s fragment of the Walsh matrix of satd8_group_mfma: byte b is the entry of row i = lane & 31 (of either tile) for the sample in
+// row q >> 1 of a step, column 4 (q & 1) + b, as the lane half h = lane >> 5 brings it.  The bits pair up: i bit 4 <-> h, bit 3 <-> the row, bits 2..0 <-> the column
+// (the tile bit pairs with the step: a sign for the whole fragment).  +1 = 0x01, -1 = 0xff = 0x01 ^ 0xfe.
+KVZ_HD u32 satd_walsh_word(int lane, int q)
+{
+  const int i = lane & 31, h = lane >> 5;
+  const u32 base = 0x01010101u ^ ((i & 1) ? 0xfe00fe00u : 0u) ^ ((i & 2) ? 0xfefe0000u : 0u);
+  const int minus = (((i >> 4) & h) ^ ((i >> 3) & (q >> 1)) ^ ((i >> 2) & q)) & 1;
+  return base ^ (minus ? 0xfefefefeu : 0u);
+}
 
 // ------------------------------------------------------------------------------------------------
 // Picture costs

@@ -134,6 +134,8 @@ inline void build_tables(Tables *t)
     }
     for (int i = 15 * nq; i < 512; i++) t->mref_tab[l2 - 3][i] = t->mref_tab[l2 - 3][15 * nq - 1];  // the lanes past the end repeat the last entry: no bounds test in the kernel
   }
+  for (int lane = 0; lane < 64; lane++)
+    for (int q = 0; q < 4; q++) { t->satd_walsh[lane][q] = satd_walsh_word(lane, q); t->satd_walsh[lane][4 + q] = satd_walsh_word(lane, q) ^ 0xfefefefeu; }
   static const i16 dst4[16] = { 29, 55, 74, 84, 74, 74, 0, -74, 84, -29, -74, 55, 55, -84, 74, -29 };
   memcpy(t->dst4, dst4, sizeof dst4);
   for (int kind = 0; kind < 3; kind++) {

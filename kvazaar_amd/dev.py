@@ -24,6 +24,7 @@ class Dev:
         l.kvz_hip_dev_angular_pred.restype = None; l.kvz_hip_dev_angular_pred.argtypes = [ci, ci, vp, vp, ci, vp]
         l.kvz_hip_dev_intra_select.restype = ci; l.kvz_hip_dev_intra_select.argtypes = [ci, ci, vp, vp, vp, ci, vp]
         l.kvz_hip_dev_cu8_units.restype = ci; l.kvz_hip_dev_cu8_units.argtypes = [ci, ci, vp, vp, vp, vp, vp]
+        l.kvz_hip_dev_satd8_blocks.restype = ci; l.kvz_hip_dev_satd8_blocks.argtypes = [vp, vp, ci, vp]
 
     def put(self, a):
         a = np.ascontiguousarray(a)

@@ -8,7 +8,7 @@ files, ranges = {}, {}
 def fn_of(fname, line):
     if fname not in ranges:
         st = []
-        p = os.path.join(csrc, fname)
+        p = os.path.join(csrc, os.path.basename(fname))  # the .file entries may carry a directory prefix
         if os.path.exists(p):
             for i, l in enumerate(open(p), 1):
                 m = re.match(r'\s*(?:template\s*<[^>]*>\s*)?(?:KVZ_DEV|KVZ_HD|__device__|__global__)[^;(]*?(\w+)\s*\(', l)
