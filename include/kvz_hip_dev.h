@@ -67,6 +67,13 @@ int  kvz_hip_dev_cu8_units(int count, int from_coeffs, const int16_t *in, const 
  * developer entry point: the pass itself predicts the blocks in registers.  -1: a negative count. */
 int  kvz_hip_dev_satd8_blocks(const uint8_t *a, const uint8_t *b, int count, uint32_t *out);
 
+/* The prediction half of the CTU pass's rough search of modes 2..33 for 8x8 (log2w 3) / 16x16 (log2w 4) CUs, on `count` reference sets in device memory: top / left =
+ * count x (2 w + 1) unfiltered reference samples, [0] the corner (intra.c:303-462 order).  Runs the pass's own reference filter, extended references, edge samples of
+ * modes 10 / 26 and table-driven row generator (Tables::satd_rows) in its lane roles.  out = count x 32 modes (2..33) x (w / 8)^2 blocks (raster order) x 64 bytes:
+ * the predicted 8x8 blocks, row-major -- what kvz_intra_predict gives for the block's part of the CU.  A developer entry point: the pass itself hands the rows to the
+ * matrix cores in registers.  -1: a size it does not take, or a negative count. */
+int  kvz_hip_dev_rough_rows(int log2w, const uint8_t *top, const uint8_t *left, int count, uint8_t *out);
+
 /* Deblocking of all-intra, constant-QP pictures in place: kvz_filter_deblock_lcu (filter.c:783) over every LCU of every
  * frame.  frames = n_frames x [Y | U | V] tight planar 4:2:0 (the batch layout), cu_depth = n_frames x [H/8][W/8] CU depths
  * as the CTU pass returns them; beta / tc offsets are cfg.deblock_beta / cfg.deblock_tc (cfg.c: 0, 0).  Not a strategy in

@@ -306,6 +306,7 @@ template <bool CABAC> struct CtuSharedT {
   unsigned long long prof_rq[16];   // rdoq_block_wave's sections and sizes (luma blocks, so one wavefront adds), flushed with prof_acc
   unsigned long long prof_acc[96];  // [category] cycles, [KVZ_P_COUNT + category] marks; [32 prof_pu + ...] the same inside the 4x4 PUs of the NxN attempt (eval_pu) or a 16x16 CU's reconstruction (1), a 32x32 unit's (2)
   int prof_pu;
+  int prof_pad_[3];  // the counters are a multiple of 16 bytes: what follows lies as in the other builds relative to `ref` (Tables::mref_tab, Tables::satd_rows)
 #endif
   CtuCu cu[4][64];
   u8 ref[3][2][68];          // [plane][0 top / 1 left][2w+1], w <= 32
@@ -336,6 +337,10 @@ template <bool CABAC> struct CtuSharedT {
       // ref / fref directly.
       u8 mref[15][KVZ_MREF_STRIDE];
       u32 satd_raw[35][4];     // sum |Hadamard| per (mode, 8x8 block) before the per-block rounding
+      // Rough search of an 8x8 / 16x16 CU: [0] a zero, [1 + q] / [1 + w + q] what intra_post_process_angular (intra.c:207-219) changes in row q of mode 26 / column
+      // q of mode 10, as the xor of the patched and the unpatched sample (satd_edge_byte).  Written once per CU beside build_mref; the row generator xors the byte
+      // its table row names into the row's first sample (kvz_mfma.hpp satd_rows_predict).  In room the 32x32 regime left over: the block keeps its size.
+      u8 edge_x[36];
     };
   };
   alignas(16) i16 lv2_coeff[384];       // quantised levels of the 16x16 CU being tried (Y 256 | U 64 | V 64): they only go to HBM if it wins
@@ -377,6 +382,15 @@ static_assert(__builtin_offsetof(CtuSharedT<true>, fref) == __builtin_offsetof(C
               "Tables::mref_tab addresses the filtered references 408 bytes behind the unfiltered ones");
 static_assert(KVZ_MREF_STRIDE == kMrefStride && KVZ_MREF_ORG == kMrefOrg && sizeof(((CtuSharedT<true> *)0)->ref[0][0]) == kMrefRefRow && kMrefFiltered == 408,
               "Tables::mref_tab (kvz_tables.hpp) is built for this layout of the reference arrays");
+#define KVZ_FROM_REF(T, member) (__builtin_offsetof(T, member) - __builtin_offsetof(T, ref))
+static_assert(KVZ_FROM_REF(CtuSharedT<true>, mref) == kMrefExtended && KVZ_FROM_REF(CtuSharedT<false>, mref) == kMrefExtended && KVZ_FROM_REF(CtuSharedT<true>, org_t) == kSatdSrcT &&
+              KVZ_FROM_REF(CtuSharedT<false>, org_t) == kSatdSrcT && KVZ_FROM_REF(CtuSharedT<true>, edge_x) == kSatdEdge && KVZ_FROM_REF(CtuSharedT<false>, edge_x) == kSatdEdge,
+              "Tables::satd_rows (kvz_tables.hpp) addresses the extended references, the transposed source block and the edge bytes from CtuShared::ref");
+static_assert(sizeof(((CtuSharedT<true> *)0)->edge_x) >= 1 + 2 * 16 && __builtin_offsetof(CtuSharedT<true>, edge_x) + sizeof(((CtuSharedT<true> *)0)->edge_x) <= __builtin_offsetof(CtuSharedT<true>, lv2_coeff) &&
+              __builtin_offsetof(CtuSharedT<true>, org) == 0 && __builtin_offsetof(CtuSharedT<true>, ref) % 8 == 0 && __builtin_offsetof(CtuSharedT<true>, org_t) % 8 == 0,
+              "the edge bytes of a 16x16 CU fit, behind satd_raw and inside the union; source rows (offsets that are multiples of 8 from org / org_t) are 8-byte aligned");
+static_assert(__builtin_offsetof(CtuSharedT<true>, lv2_coeff) - __builtin_offsetof(CtuSharedT<true>, tb_big) == 3072 + 1536, "the union is as large as its 32x32 regime: edge_x added nothing");
+#undef KVZ_FROM_REF
 static_assert(KVZ_CTU_THREADS == 128, "two wavefronts per CTU: thread 64 is 'the other wavefront' (recon_cu8, eval_pu, wide_task, rdoq_unit, prices_coeffs, kHookThread), a 16x16 CU's "
                                       "128 (mode, block) pairs are one round of rough_search, plane_sums routes DPP rows per wavefront, and mref_pre[4] covers Tables::mref_tab's 510 entries");
 
@@ -1106,12 +1120,7 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false, bool
         const int n = 2 * (1 << log2w_y) + 1;
         for (int i = tid; i < 2 * n; i += KVZ_CTU_THREADS) {
           const int side = i >= n, k = side ? i - n : i;
-          const u8 *r = s->ref[0][side];
-          u8 v;
-          if (k == 0) v = (u8)((s->ref[0][1][1] + 2 * s->ref[0][1][0] + s->ref[0][0][1] + 2) / 4);
-          else if (k == n - 1) v = r[k];
-          else v = (u8)((r[k - 1] + 2 * r[k] + r[k + 1] + 2) / 4);
-          s->fref[side][k] = v;
+          s->fref[side][k] = luma_filtered_ref(&s->ref[0][0][0], n, i);
         }
       }
       const int c = mover_lane(tid) - (KVZ_CTU_THREADS - 3);  // the last three lanes: one DC value each (opaque: what follows from c is the same in every call, and the
@@ -1205,11 +1214,7 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false, bool
   // row r + 4 -- the even lane keeps the sums, the odd one the differences --, finish their halves alone and add up.  Both lanes
   // return the block's total.  Device only (the host simulation has no cross-lane operations and runs the one-lane form).
 #ifndef KVZ_HOSTSIM
-  // Two u16 per register for the row generators below (v_pk_mad_u16 / v_pk_lshrrev_b16; bytes widened by v_perm_b32, whose selector value 0x0c reads as a zero byte)
-  typedef unsigned short U16x2 __attribute__((ext_vector_type(2)));
-  KVZ_DEV static U16x2 u16x2_of(unsigned v) { U16x2 r; __builtin_memcpy(&r, &v, 4); return r; }
-  KVZ_DEV static U16x2 splat16(int v) { U16x2 r; r.x = (unsigned short)v; r.y = (unsigned short)v; return r; }
-  KVZ_DEV static U16x2 widen(unsigned hi, unsigned lo, unsigned sel) { return u16x2_of(__builtin_amdgcn_perm(hi, lo, sel)); }
+  // (two u16 per register for the row generators below: U16x2, widen, splat16 of kvz_mfma.hpp)
   KVZ_DEV static Pk16 as_pk16(U16x2 v) { Pk16 r; __builtin_memcpy(&r, &v, 4); return r; }
   // The eight bytes at p (any alignment) as four u16 pairs
   KVZ_DEV static void widen8(const u8 *p, U16x2 out[4])
@@ -1329,55 +1334,15 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false, bool
 #ifndef KVZ_HOSTSIM
   // The same total for one angular mode (2..33) on one 8x8 block of an 8x8 / 16x16 CU, as this lane's column of a GROUP of 32 (mode, block) pairs that the whole
   // wavefront scores together on the matrix cores (satd8_group_mfma, kvz_mfma.hpp): lanes l and l + 32 share the pair, `half` 0 / 1 predicting rows 0..3 / 4..7
-  // (across the main reference).  The row generator is angular_block_satd's arithmetic two samples per register (v_pk_mad_u16 / v_pk_lshrrev_b16; every intermediate
-  // fits 16 bits: (32 - f) a + f b + 16 <= 8176), with 128 << 5 riding on the rounding constant: the low byte of a result is the sample xor 0x80, the signed byte the
-  // product takes, and the source rows go in as they lie in memory, xor 0x80 -- no subtraction, no widening, no butterflies on the vector pipe.  Must be called by all
-  // 64 lanes.  Both lanes of a pair return the block's total.
-  KVZ_DEV u32 angular_group_satd(const SatdWalsh &wm, int log2w, int mode, int bx, int by, int xl, int yl, int half) const
+  // (across the main reference).  Which mode and block the lane has, and with them the array, window, fraction, edge byte and source rows of its four rows, are
+  // constants of (CU size, group, lane, row): `rows` is the lane's entry of Tables::satd_rows, and the row generator (satd_rows_predict) is angular_block_satd's
+  // arithmetic on it, two samples per register, straight into the signed bytes the product takes.  `o`: the lane's source rows (satd_rows_source) -- the two groups
+  // a wavefront scores for a 16x16 CU have the same blocks in the same orientation, so they are fetched once.  Must be called by all 64 lanes.  Both lanes of a
+  // pair return the block's total.
+  KVZ_DEV u32 angular_group_satd(const SatdWalsh &wm, const dev_int4 rows[2], const dev_int4 o[2]) const
   {
-    const int w = 1 << log2w;
-    const bool vertical = mode >= 18;
-    const int disp = s->mode_disp[mode];
-    const int p0 = vertical ? bx : by, q0 = vertical ? by : bx;  // block origin along / across the main reference
-    const u8 *mr;
-    if (disp < 0) mr = s->mref[mode - 11] + KVZ_MREF_ORG;
-    else {
-      const bool filt = imin(iabs(mode - 26), iabs(mode - 10)) > (log2w == 3 ? 7 : 1);
-      mr = filt ? s->fref[vertical ? 0 : 1] : s->ref[0][vertical ? 0 : 1];
-    }
-    mr += p0 + 1;
-    const u8 *org = vertical ? org_at(0, xl + bx, yl + by) : s->org_t + bx * w + by;
-    const int ostride = vertical ? 32 : w;
-    const u8 *side = vertical ? s->ref[0][1] : s->ref[0][0];  // intra.c:207-219: modes 10 / 26 use the unfiltered references
-    const bool edge = disp == 0 && p0 == 0;
-    const int r0 = 4 * half;
-    unsigned rnd_bits = 0x10101010u;  // 16 + (128 << 5) in both halves
-    asm("" : "+v"(rnd_bits));  // opaque, or the compiler pulls the constant out of the multiply-add chain: mul + mad + add where two mads do
-    dev_int4 p[2], o[2];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      const int qa = q0 + r0 + i + 1, delta = qa * disp, di = delta >> 5, df = delta & 31;
-      const u8 *m = mr + di;
-      unsigned mw[2], ow[2];
-      __builtin_memcpy(mw, m, 8);
-      const unsigned m8 = m[8];
-      __builtin_memcpy(ow, org + (r0 + i) * ostride, 8);
-      const U16x2 c1 = splat16(df), c0 = splat16(32 - df), rnd = u16x2_of(rnd_bits);
-      // samples k and k + 2 share a register (k = 0, 1, 4, 5): the bytes k, k + 2 and their right neighbours k + 1, k + 3 are six widenings for the eight
-      // samples (the odd bytes serve twice, as right neighbours of the even ones and as the samples 1, 3 / 5, 7) where adjacent pairs take eight
-      const U16x2 e0 = widen(0, mw[0], 0x0c020c00u), o0 = widen(0, mw[0], 0x0c030c01u), f0 = widen(mw[1], mw[0], 0x0c040c02u);
-      const U16x2 e1 = widen(0, mw[1], 0x0c020c00u), o1 = widen(0, mw[1], 0x0c030c01u), f1 = widen(m8, mw[1], 0x0c040c02u);
-      U16x2 v[4];  // the predicted samples + 128: (0, 2), (1, 3), (4, 6), (5, 7)
-      v[0] = (e0 * c0 + (o0 * c1 + rnd)) >> (unsigned short)5; v[1] = (o0 * c0 + (f0 * c1 + rnd)) >> (unsigned short)5;
-      v[2] = (e1 * c0 + (o1 * c1 + rnd)) >> (unsigned short)5; v[3] = (o1 * c0 + (f1 * c1 + rnd)) >> (unsigned short)5;
-      if (edge) v[0].x = (unsigned short)iclip(128, 128 + 255, (int)v[0].x + (((int)side[qa] - (int)side[0]) >> 1));
-      unsigned vw[4];
-      __builtin_memcpy(vw, v, 16);
-      p[i >> 1][2 * (i & 1)] = (int)__builtin_amdgcn_perm(vw[1], vw[0], 0x06020400u);  // the low bytes of the four u16, in sample order
-      p[i >> 1][2 * (i & 1) + 1] = (int)__builtin_amdgcn_perm(vw[3], vw[2], 0x06020400u);
-      o[i >> 1][2 * (i & 1)] = (int)(ow[0] ^ 0x80808080u);
-      o[i >> 1][2 * (i & 1) + 1] = (int)(ow[1] ^ 0x80808080u);
-    }
+    dev_int4 p[2];
+    satd_rows_predict(&s->ref[0][0][0], rows, p);
     return satd8_group_mfma(wm, p, o);
   }
 
@@ -1459,12 +1424,9 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false, bool
     u8 vals[N];
     if constexpr (L2 != 5) {
       static_assert(N * KVZ_CTU_THREADS <= 512, "Tables::mref_tab rows");
-      const u8 *src = &s->ref[0][0][0];
-      u8 *dst = &s->mref[0][0];
       u32 e[N];
       for (int k = 0; k < N; k++) e[k] = pre ? pre[k] : tb->mref_tab[L2 - 3][tid + k * KVZ_CTU_THREADS];
-      for (int k = 0; k < N; k++) vals[k] = src[e[k] & 0xffff];
-      for (int k = 0; k < N; k++) dst[e[k] >> 16] = vals[k];
+      mref_copy<N>(&s->ref[0][0][0], e);
       return;
     }
     for (int k = 0; k < N; k++) {
@@ -1565,6 +1527,16 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false, bool
       const u32 *row = tb->mref_tab[log2w - 3] + ((threadIdx.x + lane_rot) & (KVZ_CTU_THREADS - 1));
       for (int k = 0; k < 4; k++) mref_pre[k] = row[k * KVZ_CTU_THREADS];
     }
+    // ... and its rows of Tables::satd_rows: the group of an 8x8 CU (the wavefront that plays threads 0..63), groups 2 t and 2 t + 1 of a 16x16 one (wavefront t)
+    dev_int4 rows_pre[2][2] = {};
+    {
+      const int t = (threadIdx.x + lane_rot) & (KVZ_CTU_THREADS - 1);
+      if (log2w == 4 || (log2w == 3 && t < 64)) {
+        const dev_int4 *row = reinterpret_cast<const dev_int4 *>(tb->satd_rows[log2w == 4 ? 1 + 2 * (t >> 6) : 0][t & 63]);
+        rows_pre[0][0] = row[0]; rows_pre[0][1] = row[1];
+        if (log2w == 4) { rows_pre[1][0] = row[2 * 64]; rows_pre[1][1] = row[2 * 64 + 1]; }
+      }
+    }
 #endif
     build_refs(lv, x, y, log2w, depth == 3 ? 2 : log2w - 1, true, true, first);
     if (S32 && log2w == 5) {
@@ -1610,6 +1582,13 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false, bool
         const int ex = e >> log2w, ey = e & (w - 1);
         s->org_t[e] = *org_at(0, xl + ex, yl + ey);
       }
+#ifndef KVZ_HOSTSIM
+      // the edge samples of modes 10 / 26 (CtuShared::edge_x), a lane each, and the zero that every other row reads
+      if (tid <= 2 * w) {
+        const u8 xv = satd_edge_byte(&s->ref[0][0][0], log2w, tid & (2 * w - 1));
+        s->edge_x[tid == 2 * w ? 0 : 1 + tid] = tid == 2 * w ? (u8)0 : xv;
+      }
+#endif
       if (tid == KVZ_CTU_THREADS - 1) {
         int left, above;
         neighbour_pair(lv, x, y, &left, &above);
@@ -1634,10 +1613,14 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false, bool
       if (log2w == 4 || tid < 64) {  // (whole wavefronts)
         const int lane = tid & 63;
         const SatdWalsh wm = satd8_walsh(tb, lane);
-        for (int g = log2w == 4 ? 2 * (tid >> 6) : 0, ge = g + (log2w == 4 ? 2 : 1); g < ge; g++) {
-          const int p = 32 * g + (lane & 31), mode = 2 + (p >> lb), b = p & (nblk - 1), bx = (b & ((w >> 3) - 1)) * 8, by = (b >> (log2w - 3)) * 8;
-          const u32 v = angular_group_satd(wm, log2w, mode, bx, by, xl, yl, lane >> 5);
-          if (lane < 32) s->satd_raw[mode][b] = v;
+        dev_int4 o[2];
+        satd_rows_source(&s->ref[0][0][0], org_at(0, xl, yl), rows_pre[0], o);
+        const int p = (log2w == 4 ? 64 * (tid >> 6) : 0) + (lane & 31), mode = 2 + (p >> lb), b = p & (nblk - 1);  // the pair of the first group; the second's: 32 on
+        const u32 v0 = angular_group_satd(wm, rows_pre[0], o);
+        if (lane < 32) s->satd_raw[mode][b] = v0;
+        if (log2w == 4) {
+          const u32 v1 = angular_group_satd(wm, rows_pre[1], o);
+          if (lane < 32) s->satd_raw[mode + 8][b] = v1;
         }
       }
       // mode 34, planar, DC: EIGHT lanes per (mode, block), one row each (flat_block_satd8), taken from the far end of the thread ids -- the other wavefront of an

@@ -367,6 +367,54 @@ __global__ void __launch_bounds__(256) dev_satd8_blocks_kernel(const Tables *tb,
   dev_satd8_blocks_wave(tb, a, b, count, out, (int)(blockIdx.x * 4 + (threadIdx.x >> 6)), (int)(threadIdx.x & 63));
 }
 
+// kvz_hip_dev_rough_rows: what the rough search of an 8x8 / 16x16 CU predicts for modes 2..33, from unfiltered references in memory: the pass's own reference filter
+// (luma_filtered_ref), extended references (Tables::mref_tab, mref_copy), edge bytes (satd_edge_byte) and row generator (Tables::satd_rows, satd_rows_predict) on an
+// LDS image laid out like CtuShared from its `ref` on, two wavefronts per CU in the pass's roles (an 8x8 CU's group on the first; groups 2 t, 2 t + 1 of a 16x16 CU
+// on wavefront t).  The generator's rows run across the main reference: a horizontal mode's block comes out transposed and is written back upright.
+template <int L2> __global__ void __launch_bounds__(256) dev_rough_rows_kernel(const Tables *tb, const u8 *top, const u8 *left, const int count, u8 *out)
+{
+  constexpr int W = 1 << L2, N = 2 * W + 1, NM = (15 * (2 * W + 2) + 127) / 128, LB = 2 * (L2 - 3), NBLK = 1 << LB;
+  static_assert(2 * N <= 128 && NM * 128 <= 512, "a lane per reference sample; Tables::mref_tab rows");
+  __shared__ alignas(16) u8 lds[2][(kSatdEdge + 1 + 2 * 16 + 15) & ~15u];  // two CUs per workgroup, each on its own pair of wavefronts
+  const int half = threadIdx.x >> 7, tid = threadIdx.x & 127, lane = tid & 63;
+  const long cu = 2l * blockIdx.x + half;
+  const bool live = cu < count;  // (every thread stays for the barriers)
+  u8 *ref0 = lds[half];
+  const int side = tid >= N, k = side ? tid - N : tid;
+  if (live && tid < 2 * N) ref0[kMrefRefRow * side + k] = (side ? left : top)[cu * N + k];
+  __syncthreads();
+  if (live && tid < 2 * N) ref0[kMrefFiltered + kMrefRefRow * side + k] = luma_filtered_ref(ref0, N, tid);
+  __syncthreads();
+  if (live) {
+    u32 e[NM];
+    for (int j = 0; j < NM; j++) e[j] = tb->mref_tab[L2 - 3][tid + j * 128];
+    mref_copy<NM>(ref0, e);
+    if (tid <= 2 * W) {
+      const u8 xv = satd_edge_byte(ref0, L2, tid & (2 * W - 1));
+      ref0[kSatdEdge + (tid == 2 * W ? 0 : 1 + tid)] = tid == 2 * W ? (u8)0 : xv;
+    }
+  }
+  __syncthreads();
+  if (!live || (L2 == 3 && tid >= 64)) return;
+#pragma unroll
+  for (int j = 0; j < (L2 == 4 ? 2 : 1); j++) {
+    const int g = L2 == 4 ? 2 * (tid >> 6) + j : 0, pr = 32 * g + (lane & 31), mode = 2 + (pr >> LB), b = pr & (NBLK - 1);
+    const dev_int4 *row = reinterpret_cast<const dev_int4 *>(tb->satd_rows[L2 == 4 ? 1 + g : 0][lane]);
+    const dev_int4 e[2] = { row[0], row[1] };
+    dev_int4 p[2];
+    satd_rows_predict(ref0, e, p);
+    u8 *o = out + ((cu * 32 + (mode - 2)) * NBLK + b) * 64;
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+#pragma unroll
+      for (int x = 0; x < 8; x++) {
+        const int r = 4 * (lane >> 5) + i;
+        const u8 v = (u8)(((u32)p[i >> 1][2 * (i & 1) + (x >> 2)] >> (8 * (x & 3))) ^ 0x80);
+        o[mode >= 18 ? 8 * r + x : 8 * x + r] = v;
+      }
+  }
+}
+
 template <int L2> __global__ void __launch_bounds__(256) dev_angular_kernel(const u8 *above, const u8 *left, const int count, const int mode, u8 *out)
 {
   constexpr int W = 1 << L2, NG = kAngularGroupsPerLane, GPB = W * W / 4, BLOCKS = 256 * NG / GPB, RS = 2 * W + 1, ES = (2 * W + 1 + 8 + 3) & ~3;
@@ -1342,6 +1390,14 @@ int kvz_hip_dev_cu8_units(int count, int from_coeffs, const int16_t *in, const i
   if (count < 0 || (from_coeffs != 0 && from_coeffs != 1)) { fprintf(stderr, "kvz_hip_dev_cu8_units: count=%d from_coeffs=%d\n", count, from_coeffs); return -1; }
   if (count == 0) return 0;
   KVZ_DEV_LAUNCH(kvz::dev_cu8_units_kernel, ((long)count + 1) / 2 * 256, in, qp, count, from_coeffs, kvz::device_tables(), levels, dequant, resid);
+  return 0;
+}
+
+int kvz_hip_dev_rough_rows(int log2w, const uint8_t *top, const uint8_t *left, int count, uint8_t *out)
+{
+  if (count < 0 || (log2w != 3 && log2w != 4)) { fprintf(stderr, "kvz_hip_dev_rough_rows: log2w=%d count=%d\n", log2w, count); return -1; }
+  if (log2w == 3) KVZ_DEV_LAUNCH(kvz::dev_rough_rows_kernel<3>, ((long)count + 1) / 2 * 256, kvz::device_tables(), top, left, count, out);
+  else KVZ_DEV_LAUNCH(kvz::dev_rough_rows_kernel<4>, ((long)count + 1) / 2 * 256, kvz::device_tables(), top, left, count, out);
   return 0;
 }
 

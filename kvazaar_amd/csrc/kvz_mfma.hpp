@@ -218,6 +218,58 @@ __device__ __forceinline__ u32 satd8_group_mfma(const SatdWalsh &w, const dev_in
   const auto both = __builtin_amdgcn_permlane32_swap(sum, sum, false, false);  // the other half's sum beside this one's, in both halves
   return both[0] + both[1];
 }
+// Two u16 per register for the row generators (v_pk_mad_u16; bytes widened by v_perm_b32, whose selector value 0x0c reads as a zero byte)
+typedef unsigned short U16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ U16x2 u16x2_of(unsigned v) { U16x2 r; __builtin_memcpy(&r, &v, 4); return r; }
+__device__ __forceinline__ U16x2 splat16(int v) { U16x2 r; r.x = (unsigned short)v; r.y = (unsigned short)v; return r; }
+__device__ __forceinline__ U16x2 widen(unsigned hi, unsigned lo, unsigned sel) { return u16x2_of(__builtin_amdgcn_perm(hi, lo, sel)); }
+
+// ---- the P operand of satd8_group_mfma for a group of 32 (angular mode, block) pairs of an 8x8 / 16x16 CU, from the lane's rows of Tables::satd_rows ----
+// e: the lane's four rows ([i >> 1][2 (i & 1)], [.. + 1]: see Tables::satd_rows), ref0: CtuShared::ref with the filtered and extended references and the edge
+// bytes behind it.  The row generator is intra-generic.c:125-148 two samples per register with the weights times 8: (32 - f) 8 a + 8 f b + 8 (16 + (128 << 5)) wraps
+// mod 2^16, and bits 8..15 of it are the sample xor 0x80, the signed byte the product takes -- no shift, and the packing v_perm_b32 picks the high bytes.  A row of
+// modes 10 / 26 that carries intra_post_process_angular's samples gets its first byte xor-ed with the edge byte (satd_edge_byte); every other row's is the zero.
+// Nine bytes of the window are used, kSatdWindow are read (Tables::satd_rows keeps the read inside the array's row).
+__device__ __forceinline__ void satd_rows_predict(const u8 *ref0, const dev_int4 e[2], dev_int4 p[2])
+{
+  unsigned rnd_bits = 0x80808080u;  // 8 (16 + (128 << 5)) in both halves
+  asm("" : "+v"(rnd_bits));  // opaque, or the compiler pulls the constant out of the multiply-add chain: mul + mad + add where two mads do
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const unsigned w0 = (unsigned)e[i >> 1][2 * (i & 1)], w1 = (unsigned)e[i >> 1][2 * (i & 1) + 1];
+    unsigned mw[3];
+    static_assert(kSatdWindow == sizeof mw, "the window read");
+    __builtin_memcpy(mw, ref0 + (w0 & 0xffff), sizeof mw);
+    const unsigned ex = ref0[w0 >> 16];
+    const U16x2 wt = u16x2_of(w1), c1 = wt.xx, c0 = splat16(256) - c1, rnd = u16x2_of(rnd_bits);
+    // samples k and k + 2 share a register (k = 0, 1, 4, 5): the bytes k, k + 2 and their right neighbours k + 1, k + 3 are six widenings for the eight
+    // samples (the odd bytes serve twice, as right neighbours of the even ones and as the samples 1, 3 / 5, 7) where adjacent pairs take eight
+    const U16x2 e0 = widen(0, mw[0], 0x0c020c00u), o0 = widen(0, mw[0], 0x0c030c01u), f0 = widen(mw[1], mw[0], 0x0c040c02u);
+    const U16x2 e1 = widen(0, mw[1], 0x0c020c00u), o1 = widen(0, mw[1], 0x0c030c01u), f1 = widen(mw[2], mw[1], 0x0c040c02u);
+    U16x2 v[4];  // 256 x (the predicted samples xor 0x80) + a remainder below 256: (0, 2), (1, 3), (4, 6), (5, 7)
+    v[0] = e0 * c0 + (o0 * c1 + rnd); v[1] = o0 * c0 + (f0 * c1 + rnd);
+    v[2] = e1 * c0 + (o1 * c1 + rnd); v[3] = o1 * c0 + (f1 * c1 + rnd);
+    unsigned vw[4];
+    __builtin_memcpy(vw, v, 16);
+    p[i >> 1][2 * (i & 1)] = (int)(__builtin_amdgcn_perm(vw[1], vw[0], 0x07030501u) ^ ex);  // the high bytes of the four u16, in sample order
+    p[i >> 1][2 * (i & 1) + 1] = (int)__builtin_amdgcn_perm(vw[3], vw[2], 0x07030501u);
+  }
+}
+// ... and the O operand: the lane's four source rows as they lie in memory, xor 0x80.  cu_org: the CU's origin in the quadrant buffer (vertical modes read their
+// rows there; horizontal ones read the transposed block behind ref0).  A lane's rows share the orientation.  Rows are 8-byte aligned.
+__device__ __forceinline__ void satd_rows_source(const u8 *ref0, const u8 *cu_org, const dev_int4 e[2], dev_int4 o[2])
+{
+  const u8 *base = ((unsigned)e[0][1] >> 16 & kSatdSrcVertical) ? cu_org : ref0;
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const unsigned src = (unsigned)e[i >> 1][2 * (i & 1) + 1] >> 16 & (kSatdSrcVertical - 1);
+    unsigned ow[2];
+    __builtin_memcpy(ow, __builtin_assume_aligned(base + src, 8), 8);
+    o[i >> 1][2 * (i & 1)] = (int)(ow[0] ^ 0x80808080u);
+    o[i >> 1][2 * (i & 1) + 1] = (int)(ow[1] ^ 0x80808080u);
+  }
+}
+
 // out[b] of the blocks 32 group .. 32 group + 31 below count: block b's P at a + 64 b, its O at bsrc + 64 b, row-major
 __device__ __forceinline__ void dev_satd8_blocks_wave(const Tables *tb, const u8 *a, const u8 *bsrc, int count, u32 *out, int group, int lane)
 {

@@ -73,6 +73,10 @@ KVZ_DEV int row16_sum(int v)
 // Layout the entries of Tables::mref_tab address (kvz_ctu.hpp CtuShared): a row of the extended main references is kMrefStride bytes with ref_main[0] at kMrefOrg,
 // the top / left reference arrays of a plane are kMrefRefRow bytes apart, the filtered set lies kMrefFiltered bytes behind the unfiltered one.
 constexpr unsigned kMrefStride = 36, kMrefOrg = 16, kMrefRefRow = 68, kMrefFiltered = 408;
+// ... and of Tables::satd_rows, from the same origin (CtuShared::ref): the extended main references (CtuShared::mref) start kMrefExtended bytes behind it, the
+// transposed source block (org_t) kSatdSrcT, the edge bytes of modes 10 / 26 (edge_x: [0] a zero, [1 + w o + q] satd_edge_byte) kSatdEdge.  A row's window is read
+// kSatdWindow bytes wide (nine are used).
+constexpr unsigned kMrefExtended = 3488, kSatdSrcT = 2080, kSatdEdge = 4588, kSatdWindow = 12, kSatdSrcVertical = 0x8000;
 
 struct Tables {
   i16 dct[4][32 * 32];   // [log2n-2] row-major n*n (dct-generic.c:46-120)
@@ -108,7 +112,57 @@ struct Tables {
   // CTU pass, rough search on the matrix cores (kvz_mfma.hpp satd8_group_mfma): lane l's A operand, sixteen +-1 bytes of its row of the 64 x 64 Walsh matrix
   // ([l][0..3], satd_walsh_word) and their negatives ([l][4..7])
   alignas(16) u32 satd_walsh[64][8];
+  // CTU pass, rough search of modes 2..33 (kvz_mfma.hpp satd_rows_predict): what lane l of a group of 32 (mode, block) pairs reads for its four rows -- [0] the group
+  // of an 8x8 CU, [1 + g] group g of a 16x16 CU; row i of the lane (row 4 (l >> 5) + i of the block, across the main reference) is the word pair [2 i], [2 i + 1]:
+  //   [2 i]      bits 0..15  byte offset of the row's reference window from CtuShared::ref (array, block origin and whole-sample displacement included)
+  //              bits 16..31 byte offset of its edge byte (the first row / column of modes 26 / 10; every other row: the zero at kSatdEdge)
+  //   [2 i + 1]  bits 0..15  8 x the fraction (the weight of a sample's right neighbour; the sample's own is 256 minus it)
+  //              bits 16..31 the source row: kSatdSrcVertical | offset from the CU's origin in the quadrant buffer (vertical modes), or the offset of the
+  //                          transposed block's row from CtuShared::ref (horizontal modes)
+  alignas(16) u32 satd_rows[5][64][8];
 };
+
+// A row of Tables::satd_rows taken apart, and the scalar statement of what the row generator makes of it (intra-generic.c:125-148 on the window, the edge byte
+// applied to sample 0): `ref0` = CtuShared::ref of a CU whose references, extended references and edge bytes are built
+struct SatdRow { unsigned window, edge, src; int df; bool vertical; };
+KVZ_HD SatdRow satd_row_of(u32 w0, u32 w1)
+{
+  SatdRow r;
+  r.window = w0 & 0xffff; r.edge = w0 >> 16; r.df = (int)(w1 & 0xffff) >> 3; r.vertical = (w1 >> 16 & kSatdSrcVertical) != 0; r.src = w1 >> 16 & (kSatdSrcVertical - 1);
+  return r;
+}
+KVZ_HD void satd_row_walk(const u8 *ref0, u32 w0, u32 w1, u8 out[8])
+{
+  const SatdRow r = satd_row_of(w0, w1);
+  const u8 *m = ref0 + r.window;
+  for (int k = 0; k < 8; k++) out[k] = (u8)(((32 - r.df) * m[k] + r.df * m[k + 1] + 16) >> 5);
+  out[0] ^= ref0[r.edge];
+}
+// intra.c:207-219 intra_post_process_angular as a byte to xor into the unpatched sample: entry i = w o + q of a 2^log2w CU is row q of mode 26 (o = 0: main
+// reference top, side reference left) / column q of mode 10 (o = 1).  The unpatched sample of such a row is ref_main[1] (displacement 0, block origin 0).
+KVZ_HD u8 satd_edge_byte(const u8 *ref0, int log2w, int i)
+{
+  const int o = i >> log2w, q = i & ((1 << log2w) - 1);
+  const u8 *side = ref0 + kMrefRefRow * (1 - o);
+  const int main1 = ref0[kMrefRefRow * o + 1];
+  return (u8)(iclip(0, 255, main1 + (((int)side[q + 1] - (int)side[0]) >> 1)) ^ main1);
+}
+// N entries of Tables::mref_tab carried out: all reads first, then all writes, so the LDS round trips of different entries overlap
+template <int N> KVZ_DEV void mref_copy(u8 *ref0, const u32 e[N])
+{
+  u8 vals[N];
+  for (int k = 0; k < N; k++) vals[k] = ref0[e[k] & 0xffff];
+  for (int k = 0; k < N; k++) ref0[kMrefExtended + (e[k] >> 16)] = vals[k];
+}
+// intra.c:176-204 intra_filter_reference for entry i of the 2 n luma reference samples (n = 2 w + 1; top first, then left) of the unfiltered set at ref0
+KVZ_HD u8 luma_filtered_ref(const u8 *ref0, int n, int i)
+{
+  const int side = i >= n, k = side ? i - n : i;
+  const u8 *r = ref0 + kMrefRefRow * side;
+  if (k == 0) return (u8)((ref0[kMrefRefRow + 1] + 2 * ref0[kMrefRefRow] + ref0[1] + 2) / 4);
+  if (k == n - 1) return r[k];
+  return (u8)((r[k - 1] + 2 * r[k] + r[k + 1] + 2) / 4);
+}
 
 // Register q (0..3) of lane `lane`'s fragment of the Walsh matrix of satd8_group_mfma: byte b is the entry of row i = lane & 31 (of either tile) for the sample in
 // row q >> 1 of a step, column 4 (q & 1) + b, as the lane half h = lane >> 5 brings it.  The bits pair up: i bit 4 <-> h, bit 3 <-> the row, bits 2..0 <-> the column

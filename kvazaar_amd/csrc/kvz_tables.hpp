@@ -6,6 +6,7 @@
 // up-right-diagonal / raster / column-major patterns applied to 4x4 coefficient groups (tables.c:9-67).
 // tests/test_hostsim.py checks the generated tables against the reference's through the oracle.
 #pragma once
+#include <assert.h>
 #include <string.h>
 
 #include "kvz_recon.hpp"
@@ -134,6 +135,25 @@ inline void build_tables(Tables *t)
     }
     for (int i = 15 * nq; i < 512; i++) t->mref_tab[l2 - 3][i] = t->mref_tab[l2 - 3][15 * nq - 1];  // the lanes past the end repeat the last entry: no bounds test in the kernel
   }
+  for (int l2 = 3; l2 <= 4; l2++)  // Tables::satd_rows (kvz_mfma.hpp satd_rows_predict; the layout constants are asserted against the kernel's in kvz_ctu.hpp)
+    for (int g = 0; g < (l2 == 3 ? 1 : 4); g++)
+      for (int lane = 0; lane < 64; lane++)
+        for (int i = 0; i < 4; i++) {
+          static const int disp_tab[9] = { 0, 2, 5, 9, 13, 17, 21, 26, 32 };
+          const int w = 1 << l2, lb = 2 * (l2 - 3), p = 32 * g + (lane & 31), mode = 2 + (p >> lb), b = p & ((1 << lb) - 1);
+          const int bx = (b & ((w >> 3) - 1)) * 8, by = (b >> (l2 - 3)) * 8, r = 4 * (lane >> 5) + i;  // the pair's block, the lane's row of it (across the main reference)
+          const int vertical = mode >= 18, md = vertical ? mode - 26 : 10 - mode, disp = md < 0 ? -disp_tab[-md] : disp_tab[md];
+          const int p0 = vertical ? bx : by, q0 = vertical ? by : bx, qa = q0 + r + 1, delta = qa * disp, df = delta & 31, di = (delta - df) / 32;
+          // the row of the array the mode reads (a negative displacement: its extended main reference) and how long that row is
+          const unsigned row = disp < 0 ? kMrefExtended + kMrefStride * (mode - 11) : (luma_reads_filtered(l2, mode) ? kMrefFiltered : 0u) + kMrefRefRow * (vertical ? 0 : 1);
+          const int at = (disp < 0 ? (int)kMrefOrg : 0) + p0 + 1 + di;
+          assert(at >= 0 && at + (int)kSatdWindow <= (int)(disp < 0 ? kMrefStride : kMrefRefRow));  // the wide read stays inside the row
+          const unsigned edge = disp == 0 && p0 == 0 ? kSatdEdge + 1 + (vertical ? 0 : w) + qa - 1 : kSatdEdge;
+          const unsigned src = vertical ? kSatdSrcVertical | (unsigned)((by + r) * 32 + bx) : kSatdSrcT + (unsigned)((bx + r) * w + by);
+          u32 *e = t->satd_rows[l2 == 3 ? 0 : 1 + g][lane] + 2 * i;
+          e[0] = (row + (unsigned)at) | edge << 16;
+          e[1] = (unsigned)(8 * df) | src << 16;
+        }
   for (int lane = 0; lane < 64; lane++)
     for (int q = 0; q < 4; q++) { t->satd_walsh[lane][q] = satd_walsh_word(lane, q); t->satd_walsh[lane][4 + q] = satd_walsh_word(lane, q) ^ 0xfefefefeu; }
   static const i16 dst4[16] = { 29, 55, 74, 84, 74, 74, 0, -74, 84, -29, -74, 55, 55, -84, 74, -29 };
