@@ -6,12 +6,13 @@ import numpy as np
 import flatapi
 
 
-def random_params(rng, n_ctus, chroma):
+def random_params(rng, n_ctus, chroma, band_positions=29):
+    """band_positions: positions are drawn from 0 .. band_positions - 1 (an encoder codes 0 .. 27; up to 31 fit the syntax)"""
     arr = (flatapi.SaoParams * n_ctus)()
     for p in arr:
         p.type = int(rng.choice([0, 1, 2, 2]))          # none / band / edge
         p.eo_class = int(rng.integers(0, 4))
-        p.band_position[0], p.band_position[1] = int(rng.integers(0, 29)), int(rng.integers(0, 29))
+        p.band_position[0], p.band_position[1] = int(rng.integers(0, band_positions)), int(rng.integers(0, band_positions))
         for i in range(10):
             p.offsets[i] = int(rng.integers(-7, 8))
         p.offsets[0] = 0                                  # category 0 of the edge classes carries no offset (sao.h:51)
