@@ -74,6 +74,13 @@ int  kvz_hip_dev_satd8_blocks(const uint8_t *a, const uint8_t *b, int count, uin
  * matrix cores in registers.  -1: a size it does not take, or a negative count. */
 int  kvz_hip_dev_rough_rows(int log2w, const uint8_t *top, const uint8_t *left, int count, uint8_t *out);
 
+/* The luma prediction of a 16x16 CU's reconstruction in the CTU pass (stage 1 of its recon_cu16), on `count` reference sets in device memory: top / left = count x 33
+ * unfiltered reference samples, [0] the corner; modes = count intra modes (0..34), one per set.  Runs the pass's own reference filter and extended references
+ * (modes 11..25 read their window from them, as behind the CU's rough search) and predicts in the pass's lane roles: 64 lanes, a row segment of four samples each.
+ * out = count x 256 bytes, the predicted block row-major -- what kvz_intra_predict gives for luma.  A developer entry point: the pass itself predicts into LDS.
+ * -1: a negative count. */
+int  kvz_hip_dev_cu16_predict(const uint8_t *top, const uint8_t *left, const uint8_t *modes, int count, uint8_t *out);
+
 /* Deblocking of all-intra, constant-QP pictures in place: kvz_filter_deblock_lcu (filter.c:783) over every LCU of every
  * frame.  frames = n_frames x [Y | U | V] tight planar 4:2:0 (the batch layout), cu_depth = n_frames x [H/8][W/8] CU depths
  * as the CTU pass returns them; beta / tc offsets are cfg.deblock_beta / cfg.deblock_tc (cfg.c: 0, 0).  Not a strategy in

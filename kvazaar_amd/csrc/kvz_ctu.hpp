@@ -390,6 +390,15 @@ static_assert(sizeof(((CtuSharedT<true> *)0)->edge_x) >= 1 + 2 * 16 && __builtin
               __builtin_offsetof(CtuSharedT<true>, org) == 0 && __builtin_offsetof(CtuSharedT<true>, ref) % 8 == 0 && __builtin_offsetof(CtuSharedT<true>, org_t) % 8 == 0,
               "the edge bytes of a 16x16 CU fit, behind satd_raw and inside the union; source rows (offsets that are multiples of 8 from org / org_t) are 8-byte aligned");
 static_assert(__builtin_offsetof(CtuSharedT<true>, lv2_coeff) - __builtin_offsetof(CtuSharedT<true>, tb_big) == 3072 + 1536, "the union is as large as its 32x32 regime: edge_x added nothing");
+// recon_cu16's stage 1 reads the extended references that the CU's rough_search left behind: what the reconstruction of a 16x16 CU writes in LDS -- the two
+// transform buffers, its candidate c2, its levels in lv2_coeff -- must lie outside them (and outside the edge bytes next to them)
+static_assert(__builtin_offsetof(CtuSharedT<true>, mref) >= __builtin_offsetof(CtuSharedT<true>, c2) + sizeof(((CtuSharedT<true> *)0)->c2) &&
+              __builtin_offsetof(CtuSharedT<true>, c2) >= __builtin_offsetof(CtuSharedT<true>, tb_small) + sizeof(((CtuSharedT<true> *)0)->tb_small) &&
+              __builtin_offsetof(CtuSharedT<true>, mref) + sizeof(((CtuSharedT<true> *)0)->mref) <= __builtin_offsetof(CtuSharedT<true>, edge_x) &&
+              __builtin_offsetof(CtuSharedT<true>, edge_x) + sizeof(((CtuSharedT<true> *)0)->edge_x) <= __builtin_offsetof(CtuSharedT<true>, lv2_coeff) &&
+              __builtin_offsetof(CtuSharedT<false>, mref) >= __builtin_offsetof(CtuSharedT<false>, c2) + sizeof(((CtuSharedT<false> *)0)->c2) &&
+              __builtin_offsetof(CtuSharedT<false>, edge_x) + sizeof(((CtuSharedT<false> *)0)->edge_x) <= __builtin_offsetof(CtuSharedT<false>, lv2_coeff),
+              "CtuShared::mref and edge_x lie behind the two transform buffers and the depth-2 candidate and in front of lv2_coeff: a 16x16 CU's reconstruction leaves them alone");
 #undef KVZ_FROM_REF
 static_assert(KVZ_CTU_THREADS == 128, "two wavefronts per CTU: thread 64 is 'the other wavefront' (recon_cu8, eval_pu, wide_task, rdoq_unit, prices_coeffs, kHookThread), a 16x16 CU's "
                                       "128 (mode, block) pairs are one round of rough_search, plane_sums routes DPP rows per wavefront, and mref_pre[4] covers Tables::mref_tab's 510 entries");
@@ -1719,8 +1728,8 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false, bool
   // lanes so that a DPP row of sixteen lanes never mixes planes: ONE row reduction (row16_sum + four v_readlane) serves all three planes of a stage, and the
   // decompositions differ only in which plane a row belongs to:
   //   ROWS_CU8    recon_cu8, eval_pu: the wavefront playing threads 0..63 is all luma; on the other one row 0 is U and row 1 V
-  //   ROWS_CU16   recon_cu16: one plane per wavefront and call -- luma on the wavefront playing threads 0..63 (rows 0-1; 2-3 idle), U, then V, on all rows of the
-  //               other one.  One writer per slot -- the wavefront that owns the plane -- so the sums are stored, not added; returns the plane's sum (packed: its count)
+  //   ROWS_CU16   recon_cu16: one plane per wavefront and call -- luma on the wavefront playing threads 0..63, U, then V, on the other one, each on all four rows of its
+  //               wavefront.  One writer per slot -- the wavefront that owns the plane -- so the sums are stored, not added; returns the plane's sum (packed: its count)
   //   ROWS_W16    a 16x16 CU (recon_tus: sign data hiding), one trip on the first wavefront: rows 0-1 luma, row 2 U, row 3 V
   //   ROWS_W32_Y  a 32x32 unit, trip 0: both wavefronts all luma
   //   ROWS_W32_C  ... trip 1: the first wavefront, rows 0-1 U, rows 2-3 V
@@ -1751,7 +1760,7 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false, bool
       }
       return tid < 64 ? luma : (tid < 80 ? r0 : r1);
     }
-    if (plan == ROWS_CU16) {  // c: lane 0's, which always has a task.  A row stays below 128 levels (luma: sixteen lanes of eight) and 2^23
+    if (plan == ROWS_CU16) {  // c: lane 0's, which always has a task.  A row stays below 128 levels (luma: sixteen lanes of four) and 2^23
       u32 a = r0 + r1 + r2 + r3, n = 0;
       if (packed) { a = (r0 & 0xffffffu) + (r1 & 0xffffffu) + (r2 & 0xffffffu) + (r3 & 0xffffffu); n = (r0 >> 24) + (r1 >> 24) + (r2 >> 24) + (r3 >> 24); }
       if ((tid & 63) == 0) {
@@ -2030,47 +2039,21 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false, bool
     return 1 + (tid >> 5);
   }
   // kvz_intra_predict (intra.c:252-301) for the eight samples (px0 .. px0 + 7, py) of plane c of a 2^l2 unit, l2 >= 3: predict_pixel() sample for sample, with
-  // what only depends on the mode and the row worked out once.  `mode` is uniform, so every branch on it is one for the wavefront.  Chroma: unfiltered
-  // references, no edge filters; 32-wide luma: no edge filters.
+  // what only depends on the mode and the row worked out once (kvz_ops.hpp predict_row_segment).  `mode` is uniform, so every branch on it is one for the
+  // wavefront.  Chroma: unfiltered references, no edge filters; 32-wide luma: no edge filters.
+  // The modes 11..25 project every sample below the corner from the side reference on the fly: merges and the 64x64 attempt have no rough search that would have
+  // left extended references (a 16x16 CU has one: recon_cu16, cu16_predict_lane).
   KVZ_DEV void predict_row8(int l2, int mode, int c, int px0, int py, u8 out[8]) const
   {
-    const int w = 1 << l2;
-    const bool edges = c == 0 && w < 32;  // intra.c:207-219 intra_post_process_angular, intra-generic.c:210-241
-    const u8 *top = s->ref[c][0], *left = s->ref[c][1];
-    if (c == 0 && luma_reads_filtered(l2, mode)) { top = s->fref[0]; left = s->fref[1]; }
-    if (mode == 0) {  // intra-generic.c:165-201: (w-1-x) L + (x+1) TR + (w-1-y) T[x] + (y+1) BL + w, the terms without x first
-      const int l = left[py + 1], tr = top[w + 1], bl = left[w + 1];
-      const int hb = (w - 1) * l + tr + (py + 1) * bl + w, dl = tr - l, wy = w - 1 - py;
-      for (int k = 0; k < 8; k++) out[k] = (u8)(((px0 + k) * dl + top[px0 + k + 1] * wy + hb) >> (l2 + 1));
-    } else if (mode == 1) {
-      const int dc = s->dcval[c];
-      for (int k = 0; k < 8; k++) out[k] = (u8)dc;
-      if (edges) {
-        if (py == 0) for (int k = 0; k < 8; k++) out[k] = (u8)((top[px0 + k + 1] + 3 * dc + 2) >> 2);
-        if (px0 == 0) out[0] = (u8)(py == 0 ? (left[1] + 2 * dc + top[1] + 2) >> 2 : (left[py + 1] + 3 * dc + 2) >> 2);
-      }
-    } else {  // intra-generic.c:49-155
-      const int disp = s->mode_disp[mode], inv = s->mode_inv[mode];
-      const bool vertical = mode >= 18;
-      const u8 *main_ref = vertical ? top : left, *side_ref = vertical ? left : top;
-      if (vertical) {  // one displacement for the row: nine samples of the (extended) main reference
-        const int delta = (py + 1) * disp, di = delta >> 5, df = delta & 31;
-        int r[9];
-        if (disp >= 0) for (int j = 0; j < 9; j++) r[j] = main_ref[px0 + di + j + 1];
-        else for (int j = 0; j < 9; j++) r[j] = angular_ref(main_ref, side_ref, px0 + di + j, inv);
-        for (int k = 0; k < 8; k++) out[k] = (u8)(((32 - df) * r[k] + df * r[k + 1] + 16) >> 5);  // df == 0 (mode 26 among them) leaves r[k]
-        if (edges && mode == 26 && px0 == 0) out[0] = (u8)iclip(0, 255, (int)out[0] + ((left[py + 1] - left[0]) >> 1));
-      } else {         // the displacement runs along the row
-        for (int k = 0; k < 8; k++) {
-          const int delta = (px0 + k + 1) * disp, di = delta >> 5, df = delta & 31;
-          const int r1 = disp >= 0 ? (int)main_ref[py + di + 1] : angular_ref(main_ref, side_ref, py + di, inv);
-          const int r2 = disp >= 0 ? (int)main_ref[py + di + 2] : angular_ref(main_ref, side_ref, py + di + 1, inv);
-          int v = ((32 - df) * r1 + df * r2 + 16) >> 5;
-          if (edges && mode == 10 && py == 0) v = iclip(0, 255, v + ((top[px0 + k + 1] - top[0]) >> 1));
-          out[k] = (u8)v;
-        }
-      }
-    }
+    RowRefs rr;
+    rr.top = s->ref[c][0]; rr.left = s->ref[c][1];
+    if (c == 0 && luma_reads_filtered(l2, mode)) { rr.top = s->fref[0]; rr.left = s->fref[1]; }
+    rr.edges = c == 0 && l2 < 5;  // intra.c:207-219 intra_post_process_angular, intra-generic.c:210-241
+    rr.dc = mode == 1 ? (int)s->dcval[c] : 0;
+    rr.disp = mode >= 2 ? (int)s->mode_disp[mode] : 0;
+    rr.inv = mode >= 2 ? (int)s->mode_inv[mode] : 0;
+    rr.ext = nullptr;
+    predict_row_segment<8, false>(l2, mode, rr, px0, py, out);
   }
 
   // kvz_intra_predict (intra.c:252-301) for sample (x, y) of BOTH chroma planes of a 2^l2 unit -- predict_pixel() for c = 1 and c = 2, which read the unfiltered
@@ -2097,7 +2080,8 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false, bool
   }
 
   // The 16x16 CU -- a 16x16 luma and two 8x8 chroma units -- with the stages of recon_tus() per wavefront ROLE, after the model of recon_cu8.  The wavefront playing
-  // threads 0..63 is all luma: 32 row tasks of eight samples (predict_row8, the wide quantise and reconstruct bodies of recon_tus) around the 16-point passes on the
+  // threads 0..63 is all luma: 64 row tasks of FOUR samples, lane = segment (kvz_recon.hpp cu16_luma_segment, cu16_predict_lane; the quantise and reconstruct
+  // bodies of recon_tus at half their length -- eight samples on half of the lanes made the wavefront's dependent chain twice as long) around the 16-point passes on the
   // matrix cores, in place.  The other one is all chroma: lane e takes sample e of U AND of V -- they share position, mode arithmetic and matrix rows -- through the
   // 8-point row passes of kvz_recon.hpp (cu8_fwd_first<3> .. cu8_inv_second<3>: the lane's eight inputs are one 16-byte LDS read against its row of the matrix as
   // int16 pairs), the two intermediates in front of the inverse passes stored transposed, and the coefficient a lane produces is the one it quantises.  In recon_tus
@@ -2126,17 +2110,20 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false, bool
     KVZ_FOR_THREADS(tid) {
       if (tid < 3) s->acc[3 * tid] = 0;
       if (tid >= 64 && tid < 70) s->acc[1 + (tid - 64) + ((tid - 64) >> 1)] = 0;  // 1, 2, 4, 5, 7, 8
-      if (tid < 32) {
-        // one b64 write of the row to the candidate, one b128 write of the residual (see recon_tus)
-        const int seg = mover_lane(tid), py = seg >> 1, px0 = (seg << 3) & 15;
-        u8 p[8], o[8];
-        i16 res[8];
-        predict_row8(4, umode, 0, px0, py, p);
-        __builtin_memcpy(o, KVZ_ALIGNED(org_at(0, xl + px0, yl + py), 8), 8);
-        for (int k = 0; k < 8; k++) res[k] = (i16)((int)o[k] - (int)p[k]);
-        __builtin_memcpy(KVZ_ALIGNED(&cv.at(0, xl + px0, yl + py), 8), p, 8);
-        __builtin_memcpy(KVZ_ALIGNED(tbuf(t, 0, 0) + (seg << 3), 16), res, 16);
-      } else if (tid >= 64) {
+      if (tid < 64) {
+        // one b32 write of the segment to the candidate, one b64 write of the residual (every buffer starts 16-aligned and a segment is 4 samples of a row whose
+        // origin is a multiple of 8 in its plane)
+        // (the modes 11..25 read their window from the extended references the CU's own rough_search has just left in CtuShared::mref: a 16x16 CU is only ever
+        // reconstructed behind it, eval_cu)
+        const int seg = mover_lane(tid), py = cu16_luma_segment(seg).py, px0 = cu16_luma_segment(seg).px0;
+        u8 p[4], o[4];
+        i16 res[4];
+        cu16_predict_lane(&s->ref[0][0][0], umode, umode == 1 ? (int)s->dcval[0] : 0, umode >= 2 ? (int)s->mode_disp[umode] : 0, umode >= 2 ? (int)s->mode_inv[umode] : 0, seg, p);
+        __builtin_memcpy(o, KVZ_ALIGNED(org_at(0, xl + px0, yl + py), 4), 4);
+        for (int k = 0; k < 4; k++) res[k] = (i16)((int)o[k] - (int)p[k]);
+        __builtin_memcpy(KVZ_ALIGNED(&cv.at(0, xl + px0, yl + py), 4), p, 4);
+        __builtin_memcpy(KVZ_ALIGNED(tbuf(t, 0, 0) + (seg << 2), 8), res, 8);
+      } else {
         const int e = tid - 64, px = e & 7, py = e >> 3;
         cu8_matrix_rows<3>(tb, e, KVZ_LANE(mat_f, tid), KVZ_LANE(mat_i, tid));
         u8 pu, pv;
@@ -2167,29 +2154,26 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false, bool
     KVZ_FOR_THREADS(tid) {
       const u32 cw_lo = (u32)uni((int)(u32)m->coeff_weights), cw_hi = (u32)uni((int)(u32)(m->coeff_weights >> 32));  // scalars for the call
       if (tid < 64) {
-        u32 packed = 0;
-        if (tid < 32) {
-          const int seg = mover_lane(tid);
-          const QuantScalars q = s->qs[2][0];
-          i16 cf[8], lvl[8], dq[8];
-          __builtin_memcpy(cf, KVZ_ALIGNED(tbuf(t, 0, 0) + (seg << 3), 16), 16);
-          u32 wsum = 0, nz = 0;
-          for (int k = 0; k < 8; k++) {
-            ListFactor f{ 0, 0 };
-            if constexpr (LISTS) f = factor_at(0, 4, (seg << 3) + k);
-            const int level = LISTS ? quant_level(cf[k], q, f.fwd) : quant_level(cf[k], q);
-            lvl[k] = (i16)level;
-            const LevelCost lc = level_cost(level, cw_lo, cw_hi);
-            wsum += lc.weight;
-            nz += lc.nonzero;
-            dq[k] = LISTS ? dequant_level(level, q, f.inv) : dequant_level(level, q);
-          }
-          packed = wsum | (nz << 24);
-          __builtin_memcpy(KVZ_ALIGNED(coeff_dst(lv, 0, xl, yl) + (seg << 3), 16), lvl, 16);
-          if (to_stage) __builtin_memcpy(KVZ_ALIGNED(levels_lds(lv, 0) + (seg << 3), 16), lvl, 16);
-          __builtin_memcpy(KVZ_ALIGNED(tbuf(t, 1, 0) + (seg << 3), 16), dq, 16);
+        const int seg = mover_lane(tid);
+        const QuantScalars q = s->qs[2][0];
+        i16 cf[4], lvl[4], dq[4];
+        __builtin_memcpy(cf, KVZ_ALIGNED(tbuf(t, 0, 0) + (seg << 2), 8), 8);
+        u32 wsum = 0, nz = 0;
+        for (int k = 0; k < 4; k++) {
+          ListFactor f{ 0, 0 };
+          if constexpr (LISTS) f = factor_at(0, 4, (seg << 2) + k);
+          const int level = LISTS ? quant_level(cf[k], q, f.fwd) : quant_level(cf[k], q);
+          lvl[k] = (i16)level;
+          const LevelCost lc = level_cost(level, cw_lo, cw_hi);
+          wsum += lc.weight;
+          nz += lc.nonzero;
+          dq[k] = LISTS ? dequant_level(level, q, f.inv) : dequant_level(level, q);
         }
-        KVZ_LANE(coded, tid) = plane_sums(ROWS_CU16, tid, tid < 32 ? 0 : -1, packed, true, 3) != 0;
+        const u32 packed = wsum | (nz << 24);
+        __builtin_memcpy(KVZ_ALIGNED(coeff_dst(lv, 0, xl, yl) + (seg << 2), 8), lvl, 8);
+        if (to_stage) __builtin_memcpy(KVZ_ALIGNED(levels_lds(lv, 0) + (seg << 2), 8), lvl, 8);
+        __builtin_memcpy(KVZ_ALIGNED(tbuf(t, 1, 0) + (seg << 2), 8), dq, 8);
+        KVZ_LANE(coded, tid) = plane_sums(ROWS_CU16, tid, 0, packed, true, 3) != 0;
       } else {
         const int e = tid - 64;
         const QuantScalars q = s->qs[1][1];  // U and V share the plane's scaled QP
@@ -2227,21 +2211,19 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false, bool
     KVZ_FOR_THREADS(tid) {
       if (tid < 64) {
         u32 ssd = 0;
-        if (tid < 32) {
-          const int seg = mover_lane(tid), py = seg >> 1, px0 = (seg << 3) & 15;
-          u8 *rp = &cv.at(0, xl + px0, yl + py);
-          u8 v[8], o[8];
-          __builtin_memcpy(v, KVZ_ALIGNED(rp, 8), 8);
-          __builtin_memcpy(o, KVZ_ALIGNED(org_at(0, xl + px0, yl + py), 8), 8);
-          if (KVZ_CU16_CODED(tid, 0)) {
-            i16 res[8];
-            __builtin_memcpy(res, KVZ_ALIGNED(tbuf(t, 1, 0) + (seg << 3), 16), 16);
-            for (int k = 0; k < 8; k++) v[k] = (u8)recon_sample(v[k], res[k]);
-            __builtin_memcpy(KVZ_ALIGNED(rp, 8), v, 8);
-          }
-          for (int k = 0; k < 8; k++) ssd += sq_err(o[k], v[k]);
+        const int seg = mover_lane(tid), py = cu16_luma_segment(seg).py, px0 = cu16_luma_segment(seg).px0;
+        u8 *rp = &cv.at(0, xl + px0, yl + py);
+        u8 v[4], o[4];
+        __builtin_memcpy(v, KVZ_ALIGNED(rp, 4), 4);
+        __builtin_memcpy(o, KVZ_ALIGNED(org_at(0, xl + px0, yl + py), 4), 4);
+        if (KVZ_CU16_CODED(tid, 0)) {
+          i16 res[4];
+          __builtin_memcpy(res, KVZ_ALIGNED(tbuf(t, 1, 0) + (seg << 2), 8), 8);
+          for (int k = 0; k < 4; k++) v[k] = (u8)recon_sample(v[k], res[k]);
+          __builtin_memcpy(KVZ_ALIGNED(rp, 4), v, 4);
         }
-        plane_sums(ROWS_CU16, tid, tid < 32 ? 0 : -1, ssd, false, 0);
+        for (int k = 0; k < 4; k++) ssd += sq_err(o[k], v[k]);
+        plane_sums(ROWS_CU16, tid, 0, ssd, false, 0);
       } else {
         const int e = tid - 64, px = e & 7, py = e >> 3;
         auto plane = [&](int c) {
@@ -2324,6 +2306,9 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false, bool
     KVZ_SYNC();
     KVZ_PROF(KVZ_P_RPRED);
     // stages 2-3: forward transform (dct-generic.c:559-568; 4x4 chroma uses the DCT, strategies-dct.c:82-86)
+    // (a unit whose three planes all have 16 or 32 points -- a 32x32 unit -- does both passes at pass 0: its second iteration is empty and ends in no barrier.
+    // Stated on the barrier, not on the loop bound: with one iteration the headline kernel kept two more registers in scratch memory)
+    const int passes = t.lc >= 4 ? 1 : 2;
     for (int pass = 0; pass < 2; pass++) {
       KVZ_FOR_THREADS(tid) {
         for (int c = 0; c < 3; c++) {
@@ -2340,7 +2325,7 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false, bool
           }
         }
       }
-      KVZ_SYNC();
+      if (pass < passes) KVZ_SYNC();
     }
     KVZ_PROF(KVZ_P_FDCT);
     // stage 4: quantise (quant-generic.c:57-81) -> coefficient store + cost sums; dequantise (:335-339) -> tb[1]
@@ -2474,7 +2459,7 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false, bool
           }
         }
       }
-      KVZ_SYNC();
+      if (pass < passes) KVZ_SYNC();
     }
     KVZ_PROF(KVZ_P_IDCT);
     // stage 7: reconstruction (quant-generic.c:266-277) + SSD against the source (search.c:500-505, 512-523)

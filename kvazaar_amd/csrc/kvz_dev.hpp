@@ -415,6 +415,38 @@ template <int L2> __global__ void __launch_bounds__(256) dev_rough_rows_kernel(c
   }
 }
 
+// kvz_hip_dev_cu16_predict: stage 1's luma prediction of a 16x16 CU's reconstruction (kvz_ctu.hpp recon_cu16) from unfiltered references in memory, a mode per CU:
+// the pass's reference filter and extended references as above, two wavefronts per CU, then the first one predicts in recon_cu16's lane roles -- lane = row segment
+// of four samples (kvz_recon.hpp cu16_predict_lane), one 4-byte store each.
+__global__ void __launch_bounds__(256) dev_cu16_predict_kernel(const Tables *tb, const u8 *top, const u8 *left, const u8 *modes, const int count, u8 *out)
+{
+  constexpr int W = 16, N = 2 * W + 1, NM = (15 * (2 * W + 2) + 127) / 128;
+  static_assert(2 * N <= 128 && NM * 128 <= 512, "a lane per reference sample; Tables::mref_tab rows");
+  __shared__ alignas(16) u8 lds[2][(kMrefExtended + 15 * kMrefStride + 15) & ~15u];  // two CUs per workgroup, each on its own pair of wavefronts
+  const int half = threadIdx.x >> 7, tid = threadIdx.x & 127;
+  const long cu = 2l * blockIdx.x + half;
+  const bool live = cu < count;  // (every thread stays for the barriers)
+  u8 *ref0 = lds[half];
+  const int side = tid >= N, k = side ? tid - N : tid;
+  if (live && tid < 2 * N) ref0[kMrefRefRow * side + k] = (side ? left : top)[cu * N + k];
+  __syncthreads();
+  if (live && tid < 2 * N) ref0[kMrefFiltered + kMrefRefRow * side + k] = luma_filtered_ref(ref0, N, tid);
+  __syncthreads();
+  if (live) {
+    u32 e[NM];
+    for (int j = 0; j < NM; j++) e[j] = tb->mref_tab[1][tid + j * 128];
+    mref_copy<NM>(ref0, e);
+  }
+  __syncthreads();
+  if (!live || tid >= 64) return;
+  const int mode = imin(modes[cu], 34);  // (a mode that does not exist reads nothing out of bounds)
+  int disp, inv;
+  angular_params(mode, &disp, &inv);
+  alignas(4) u8 p[4];
+  cu16_predict_lane(ref0, mode, dc_value(4, ref0, ref0 + kMrefRefRow), disp, inv, tid, p);
+  __builtin_memcpy(__builtin_assume_aligned(out + cu * (W * W) + 4 * tid, 4), p, 4);
+}
+
 template <int L2> __global__ void __launch_bounds__(256) dev_angular_kernel(const u8 *above, const u8 *left, const int count, const int mode, u8 *out)
 {
   constexpr int W = 1 << L2, NG = kAngularGroupsPerLane, GPB = W * W / 4, BLOCKS = 256 * NG / GPB, RS = 2 * W + 1, ES = (2 * W + 1 + 8 + 3) & ~3;
@@ -1398,6 +1430,13 @@ int kvz_hip_dev_rough_rows(int log2w, const uint8_t *top, const uint8_t *left, i
   if (count < 0 || (log2w != 3 && log2w != 4)) { fprintf(stderr, "kvz_hip_dev_rough_rows: log2w=%d count=%d\n", log2w, count); return -1; }
   if (log2w == 3) KVZ_DEV_LAUNCH(kvz::dev_rough_rows_kernel<3>, ((long)count + 1) / 2 * 256, kvz::device_tables(), top, left, count, out);
   else KVZ_DEV_LAUNCH(kvz::dev_rough_rows_kernel<4>, ((long)count + 1) / 2 * 256, kvz::device_tables(), top, left, count, out);
+  return 0;
+}
+
+int kvz_hip_dev_cu16_predict(const uint8_t *top, const uint8_t *left, const uint8_t *modes, int count, uint8_t *out)
+{
+  if (count < 0) { fprintf(stderr, "kvz_hip_dev_cu16_predict: count=%d\n", count); return -1; }
+  KVZ_DEV_LAUNCH(kvz::dev_cu16_predict_kernel, ((long)count + 1) / 2 * 256, kvz::device_tables(), top, left, modes, count, out);
   return 0;
 }
 

@@ -615,6 +615,16 @@ KVZ_DEV int angular_ref(const u8 *main_ref, const u8 *side_ref, int i, int inv)
   return *p;
 }
 
+// intra-generic.c:59-60, 70-76: the signed sample displacement and the inverse angle of angular mode `mode` (planar and DC: 0, 0)
+KVZ_DEV void angular_params(int mode, int *disp, int *inv)
+{
+  const int disp_tab[9] = { 0, 2, 5, 9, 13, 17, 21, 26, 32 };
+  const int inv_tab[9] = { 0, 4096, 1638, 910, 630, 482, 390, 315, 256 };
+  const int md = mode >= 18 ? mode - 26 : 10 - mode, ad = iabs(md);
+  *disp = mode < 2 ? 0 : (md < 0 ? -disp_tab[ad] : disp_tab[ad]);
+  *inv = mode < 2 ? 0 : inv_tab[ad];
+}
+
 // Value of angular mode `mode` at pixel (x, y) of a w x w block (intra-generic.c:49-155).
 KVZ_DEV u8 angular_pixel(int mode, int x, int y, const u8 *above, const u8 *left)
 {
@@ -660,6 +670,55 @@ KVZ_DEV u8 filtered_dc_pixel(int dc, int x, int y, const u8 *top, const u8 *left
   if (y == 0) return (u8)((top[x + 1] + 3 * dc + 2) / 4);
   if (x == 0) return (u8)((left[y + 1] + 3 * dc + 2) / 4);
   return (u8)dc;
+}
+
+// kvz_intra_predict (intra.c:252-301) for a ROW SEGMENT of N samples, (px0 .. px0 + N - 1, py), of a 2^l2 unit, l2 >= 3: the per-sample routines above sample for
+// sample, with what only depends on the mode and the row worked out once -- the planar constants, the DC edge rule, one displacement and fraction per row of a
+// vertical mode.  `mode` is uniform for the callers, so every branch on it is one for the wavefront.
+//   top / left   the references the mode reads (filtered or not: the caller's choice), [2w+1] with index 0 = corner
+//   ext          EXT, modes 11..25 (negative displacement): the extended main reference, ext[q] = ref_main[q] for q in [-w, w + 1] (CtuShared::mref); without EXT
+//                every sample below the corner is projected from the side reference on the fly (angular_ref)
+//   edges        the unit has the edge filters of intra.c:207-219 and intra-generic.c:210-241 (luma below 32 samples)
+struct RowRefs { const u8 *top, *left, *ext; int dc, disp, inv; bool edges; };
+template <int N, bool EXT> KVZ_DEV void predict_row_segment(int l2, int mode, const RowRefs &rr, int px0, int py, u8 *out)
+{
+  const int w = 1 << l2;
+  const u8 *top = rr.top, *left = rr.left;
+  if (mode == 0) {  // intra-generic.c:165-201: (w-1-x) L + (x+1) TR + (w-1-y) T[x] + (y+1) BL + w, the terms without x first
+    const int l = left[py + 1], tr = top[w + 1], bl = left[w + 1];
+    const int hb = (w - 1) * l + tr + (py + 1) * bl + w, dl = tr - l, wy = w - 1 - py;
+    for (int k = 0; k < N; k++) out[k] = (u8)(((px0 + k) * dl + top[px0 + k + 1] * wy + hb) >> (l2 + 1));
+  } else if (mode == 1) {
+    const int dc = rr.dc;
+    for (int k = 0; k < N; k++) out[k] = (u8)dc;
+    if (rr.edges) {
+      if (py == 0) for (int k = 0; k < N; k++) out[k] = (u8)((top[px0 + k + 1] + 3 * dc + 2) >> 2);
+      if (px0 == 0) out[0] = (u8)(py == 0 ? (left[1] + 2 * dc + top[1] + 2) >> 2 : (left[py + 1] + 3 * dc + 2) >> 2);
+    }
+  } else {  // intra-generic.c:49-155
+    const int disp = rr.disp, inv = rr.inv;
+    const bool vertical = mode >= 18;
+    const u8 *main_ref = vertical ? top : left, *side_ref = vertical ? left : top;
+    const u8 *ext = rr.ext;
+    if (vertical) {  // one displacement for the row: N + 1 samples of the (extended) main reference
+      const int delta = (py + 1) * disp, di = delta >> 5, df = delta & 31;
+      int r[N + 1];
+      if (disp >= 0) for (int j = 0; j <= N; j++) r[j] = main_ref[px0 + di + j + 1];
+      else if (EXT) for (int j = 0; j <= N; j++) r[j] = ext[px0 + di + j + 1];
+      else for (int j = 0; j <= N; j++) r[j] = angular_ref(main_ref, side_ref, px0 + di + j, inv);
+      for (int k = 0; k < N; k++) out[k] = (u8)(((32 - df) * r[k] + df * r[k + 1] + 16) >> 5);  // df == 0 (mode 26 among them) leaves r[k]
+      if (rr.edges && mode == 26 && px0 == 0) out[0] = (u8)iclip(0, 255, (int)out[0] + ((left[py + 1] - left[0]) >> 1));
+    } else {         // the displacement runs along the row
+      for (int k = 0; k < N; k++) {
+        const int delta = (px0 + k + 1) * disp, di = delta >> 5, df = delta & 31;
+        const int r1 = disp >= 0 ? (int)main_ref[py + di + 1] : (EXT ? (int)ext[py + di + 1] : angular_ref(main_ref, side_ref, py + di, inv));
+        const int r2 = disp >= 0 ? (int)main_ref[py + di + 2] : (EXT ? (int)ext[py + di + 2] : angular_ref(main_ref, side_ref, py + di + 1, inv));
+        int v = ((32 - df) * r1 + df * r2 + 16) >> 5;
+        if (rr.edges && mode == 10 && py == 0) v = iclip(0, 255, v + ((top[px0 + k + 1] - top[0]) >> 1));
+        out[k] = (u8)v;
+      }
+    }
+  }
 }
 
 // kind: 0 angular(mode), 1 planar, 2 filtered dc.  Blocks: refs at above + blk*ref_bstride, dst contiguous w*w.

@@ -16,6 +16,30 @@ KVZ_HD bool luma_reads_filtered(int log2w, int mode)
   return mode == 0 || imin(iabs(mode - 26), iabs(mode - 10)) > (log2w == 3 ? 7 : (log2w == 4 ? 1 : 0));
 }
 
+// What predict_row_segment (kvz_ops.hpp) reads for the LUMA block of a searched 2^log2w CU (log2w 3 or 4), on an image laid out like CtuShared from its `ref` on
+// (kMref*: kvz_ops.hpp): the mode's choice of the filtered or unfiltered references, and for the modes 11..25 the row of the extended main references the CU's
+// rough search built (Tables::mref_tab).  dc / disp / inv: the block's DC value and the mode's displacement and inverse angle (angular_params).
+KVZ_DEV RowRefs searched_luma_refs(const u8 *ref0, int log2w, int mode, int dc, int disp, int inv)
+{
+  RowRefs rr;
+  const unsigned set = luma_reads_filtered(log2w, mode) ? kMrefFiltered : 0u;
+  rr.top = ref0 + set; rr.left = ref0 + set + kMrefRefRow;
+  rr.ext = mode >= 11 && mode <= 25 ? ref0 + kMrefExtended + kMrefStride * (unsigned)(mode - 11) + kMrefOrg : nullptr;
+  rr.dc = dc; rr.disp = disp; rr.inv = inv;
+  rr.edges = true;  // intra.c:207-219 intra_post_process_angular, intra-generic.c:210-241: luma below 32 samples
+  return rr;
+}
+// The luma lane roles of a 16x16 CU's reconstruction (kvz_ctu.hpp recon_cu16, stages 1, 3 and 5): lane = row segment of FOUR samples, 64 of them -- row lane >> 2,
+// from sample 4 (lane & 3); the segment's elements of a row-major 16x16 buffer start at 4 lane.
+struct RowSegment { int py, px0; };
+KVZ_HD RowSegment cu16_luma_segment(int lane) { RowSegment g; g.py = lane >> 2; g.px0 = (lane & 3) << 2; return g; }
+// Stage 1's luma prediction of recon_cu16 for lane `lane` (0..63): the four samples of its segment
+KVZ_DEV void cu16_predict_lane(const u8 *ref0, int mode, int dc, int disp, int inv, int lane, u8 out[4])
+{
+  const RowSegment g = cu16_luma_segment(lane);
+  predict_row_segment<4, true>(4, mode, searched_luma_refs(ref0, 4, mode, dc, disp, inv), g.px0, g.py, out);
+}
+
 // One output point of a pass of the N-point transforms (dct-generic.c:559-579).  m(i): the matrix entry that multiplies input i, which is in[at + i] for the
 // forward passes (a row) and in[at + i * stride] for the inverse ones (a column).  Forward: the rounded sum wraps to int16 (as the reference's int16 store does);
 // inverse: it clips.

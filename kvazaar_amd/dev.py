@@ -27,6 +27,8 @@ class Dev:
         l.kvz_hip_dev_satd8_blocks.restype = ci; l.kvz_hip_dev_satd8_blocks.argtypes = [vp, vp, ci, vp]
         if hasattr(l, "kvz_hip_dev_rough_rows"):  # (an earlier build's library, given through KVZ_HIP_LIB for a comparison run, does not have it)
             l.kvz_hip_dev_rough_rows.restype = ci; l.kvz_hip_dev_rough_rows.argtypes = [ci, vp, vp, ci, vp]
+        if hasattr(l, "kvz_hip_dev_cu16_predict"):
+            l.kvz_hip_dev_cu16_predict.restype = ci; l.kvz_hip_dev_cu16_predict.argtypes = [vp, vp, vp, ci, vp]
 
     def put(self, a):
         a = np.ascontiguousarray(a)
