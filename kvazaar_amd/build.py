@@ -2,7 +2,8 @@
 
 The library's translation units are compiled in parallel: kvz_hip.hip (C ABI, per-call ops, streaming kernels, host side of the batch; with
 -DKVZ_CTU_SEPARATE_TUS it only declares the CTU kernels), kvz_ctu_tu.hip once per unit of the list in csrc/kvz_ctu_builds.hpp, one CTU kernel instantiation each
-(-DKVZ_CTU_KERNEL_TU=<unit>), and kvz_inter_tu.hip twelve times (the inter CTU pass with and without the residual coder's contexts: plain, with scaling lists, for joint launches, with a chosen integer motion search, for P pictures, for P pictures with reference lists).  Objects are rebuilt when one of the files they include (hipcc -MD) is newer."""
+(-DKVZ_CTU_KERNEL_TU=<unit>), and kvz_inter_tu.hip once per row of the list in csrc/kvz_inter_builds.hpp, one build of the inter CTU pass's kernel each (the row's
+-DKVZ_ICTU_<switch>=1, then -DKVZ_ICTU_CABAC=<0|1>).  Objects are rebuilt when one of the files they include (hipcc -MD) is newer."""
 import os
 import re
 import subprocess
@@ -18,21 +19,14 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off"]
 # the units of the CTU pass: every unit csrc/kvz_ctu_builds.hpp's two lists name.  The header is handed them as a bit mask and refuses to compile where this pattern and its own macros read the lists differently
 CTU_UNITS = sorted({int(k) for k in re.findall(r"\bX\((\d+),", open(os.path.join(CSRC, "kvz_ctu_builds.hpp")).read())})
+# the builds of the inter CTU pass: (unit, kernel name's suffix, (CABAC, LISTS, JOINT, ME, P, REFS)) of every row of csrc/kvz_inter_builds.hpp's list, which says what the switches mean.  The library's
+# main unit is handed the units as a bit mask, and the header refuses to compile where this pattern and its own macro read the list differently
+INTER_BUILDS = [(int(m[0]), m[1], tuple(int(v) for v in m[2:])) for m in re.findall(r"\bX\((\d+), (\w+)" + ", ([01])" * 6 + r"\)", open(os.path.join(CSRC, "kvz_inter_builds.hpp")).read())]
 # (object name, source, extra defines)
 MFMA_VGPR_FORM = ["-mllvm", "-amdgpu-mfma-vgpr-form"]  # an internal LLVM option, only a tuning of the streaming transform kernels: dropped where hipcc does not know it (_probe_flags)
-UNITS = ([("kvz_hip", "kvz_hip.hip", ["-DKVZ_CTU_SEPARATE_TUS"] + MFMA_VGPR_FORM)]  # (the streaming transform kernels: accumulators in VGPRs, no v_accvgpr moves around the bias pass)
+UNITS = ([("kvz_hip", "kvz_hip.hip", ["-DKVZ_CTU_SEPARATE_TUS", f"-DKVZ_ICTU_UNITS_BUILT={sum(1 << k for k, _, _ in INTER_BUILDS)}ull"] + MFMA_VGPR_FORM)]  # (the streaming transform kernels: accumulators in VGPRs, no v_accvgpr moves around the bias pass)
          + [(f"kvz_ctu_tu{k}", "kvz_ctu_tu.hip", [f"-DKVZ_CTU_KERNEL_TU={k}", f"-DKVZ_CTU_UNITS_BUILT={sum(1 << k for k in CTU_UNITS)}ull"]) for k in CTU_UNITS]
-         + [("kvz_inter_tu0", "kvz_inter_tu.hip", ["-DKVZ_ICTU_CABAC=0"]), ("kvz_inter_tu1", "kvz_inter_tu.hip", ["-DKVZ_ICTU_CABAC=1"])]  # the inter CTU pass's two builds (csrc/kvz_inter_kernels.hpp)
-         + [("kvz_inter_tu2", "kvz_inter_tu.hip", ["-DKVZ_ICTU_LISTS=1", "-DKVZ_ICTU_CABAC=0"]),  # ... and the two for launches with scaling lists
-            ("kvz_inter_tu3", "kvz_inter_tu.hip", ["-DKVZ_ICTU_LISTS=1", "-DKVZ_ICTU_CABAC=1"])]
-         + [("kvz_inter_tu4", "kvz_inter_tu.hip", ["-DKVZ_ICTU_JOINT=1", "-DKVZ_ICTU_CABAC=0"]),  # ... and the two for joint launches of pictures of different sizes
-            ("kvz_inter_tu5", "kvz_inter_tu.hip", ["-DKVZ_ICTU_JOINT=1", "-DKVZ_ICTU_CABAC=1"])]
-         + [("kvz_inter_tu6", "kvz_inter_tu.hip", ["-DKVZ_ICTU_ME=1", "-DKVZ_ICTU_CABAC=0"]),  # ... and the two for launches that choose the integer motion search (--me, --me-steps, --me-early-termination)
-            ("kvz_inter_tu7", "kvz_inter_tu.hip", ["-DKVZ_ICTU_ME=1", "-DKVZ_ICTU_CABAC=1"])]
-         + [("kvz_inter_tu8", "kvz_inter_tu.hip", ["-DKVZ_ICTU_P=1", "-DKVZ_ICTU_CABAC=0"]),  # ... and the two for launches of P pictures (--no-bipred: the program without its L1 half)
-            ("kvz_inter_tu9", "kvz_inter_tu.hip", ["-DKVZ_ICTU_P=1", "-DKVZ_ICTU_CABAC=1"])]
-         + [("kvz_inter_tu10", "kvz_inter_tu.hip", ["-DKVZ_ICTU_P=1", "-DKVZ_ICTU_REFS=1", "-DKVZ_ICTU_CABAC=0"]),  # ... and the two for launches of P pictures with reference lists of 1 .. 4 pictures (--ref N)
-            ("kvz_inter_tu11", "kvz_inter_tu.hip", ["-DKVZ_ICTU_P=1", "-DKVZ_ICTU_REFS=1", "-DKVZ_ICTU_CABAC=1"])])
+         + [(f"kvz_inter_tu{k}", "kvz_inter_tu.hip", [f"-DKVZ_ICTU_{n}=1" for n, v in zip(("LISTS", "JOINT", "ME", "P", "REFS"), sw[1:]) if v] + [f"-DKVZ_ICTU_CABAC={sw[0]}"]) for k, _, sw in INTER_BUILDS])
 
 
 def _deps(dfile):

@@ -1680,6 +1680,74 @@ int kvz_hip_dev_inter_ctu_pass_pictures(const uint8_t *src, const uint8_t *ref, 
 {
   return kvz_hip_dev_inter_ctu_pass_lists(src, ref, ref_cu, rec, cu, coeff, width, height, n_pictures, p, tile_xy, n_references, pictures, nullptr, 0, nullptr);
 }
+// ---- what the launches of the inter CTU pass share (kvz_inter_ctu_pass_run, kvz_hip_dev_inter_ctu_pass_groups): the scratch, the grid, and the launch itself ----
+namespace kvz {
+// the scratch per CTU of a launch of `total` CTUs (context output, `done` flags, ticket list) and the ticket / error words: grow-only
+static void inter_scratch_reserve(InterScratch &sc, long total)
+{
+  if (total > sc.n_ctus) {
+    if (sc.ctx) { KVZ_HIP_CHECK(hipFree(sc.ctx)); KVZ_HIP_CHECK(hipFree(sc.done)); KVZ_HIP_CHECK(hipFree(sc.items)); }
+    KVZ_HIP_CHECK(hipMalloc((void **)&sc.ctx, (size_t)total * sizeof(ICtx)));
+    KVZ_HIP_CHECK(hipMalloc((void **)&sc.done, (size_t)total * sizeof(unsigned)));
+    KVZ_HIP_CHECK(hipMalloc((void **)&sc.items, (size_t)total * sizeof(uint32_t)));
+    sc.n_ctus = total;
+  }
+  if (!sc.ticket) KVZ_HIP_CHECK(hipMalloc((void **)&sc.ticket, 2 * sizeof(unsigned)));
+}
+// The persistent grid of a launch of `total` CTUs under the build of `unit` (kvz_inter_builds.hpp), one workgroup per slot, with a slab for each: resident workgroups
+// (= wavefronts) per CU times the CUs, clamped to the work.  What THIS build's registers and LDS allow is the ceiling: a share (kvz_hip_dev_inter_set_share, per
+// calling thread) divides it, the developer's environment value is clamped to it.  n_groups: of a joint launch, for the KVZ_HIP_INTER_VERBOSE line
+static int inter_grid(InterScratch &sc, int unit, long total, int n_groups = 0)
+{
+  int dev_id = 0, n_cu = 256, fit = 0;
+  KVZ_HIP_CHECK(hipGetDevice(&dev_id));
+  KVZ_HIP_CHECK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev_id));
+  KVZ_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&fit, inter_build_kernel(unit), KVZ_ICTU_THREADS, 0));
+  if (fit <= 0) fit = 8;
+  const char *env = getenv("KVZ_HIP_INTER_WG_PER_CU");
+  int per_cu = fit / inter_share();
+  if (env && atoi(env) > 0) per_cu = atoi(env) < fit ? atoi(env) : fit;
+  if (per_cu < 1) per_cu = 1;
+  int n_wg = n_cu * per_cu;
+  if (getenv("KVZ_HIP_INTER_VERBOSE")) {  // the build by its words: the suffix of the kernel's name, spaced
+    char words[32], groups[32] = "";
+    snprintf(words, sizeof words, "%s", inter_build_suffix(unit));
+    for (char *c = words; *c; c++) if (*c == '_') *c = ' ';
+    if (n_groups) snprintf(groups, sizeof groups, "%d groups, ", n_groups);
+    fprintf(stderr, "kvz_hip inter pass: %s build, %s%d workgroups per CU x %d CUs\n", words, groups, per_cu, n_cu);
+  }
+  if ((long)n_wg > total) n_wg = (int)total;
+  if (n_wg > sc.n_slabs) {
+    if (sc.slabs) KVZ_HIP_CHECK(hipFree(sc.slabs));
+    KVZ_HIP_CHECK(hipMalloc((void **)&sc.slabs, (size_t)n_wg * sizeof(InterSlab)));
+    sc.n_slabs = n_wg;
+  }
+  return n_wg;
+}
+// The launch, timed by the events of inter_kernel_ms(): F.ctx_out / F.slabs and the schedule are the scratch's, whose ticket list the caller has uploaded and whose
+// `done` flags and ticket / error words it has zeroed.  Returns when the kernel has ended: 0, or -2 when it raised its error word
+static int inter_launch(InterScratch &sc, int unit, int n_wg, InterFrames F, const InterModel *d_model, long total, int no_wpp, hipStream_t st)
+{
+  F.ctx_out = sc.ctx; F.slabs = sc.slabs;
+  InterSched sched;
+  sched.items = sc.items; sched.ticket = sc.ticket; sched.done = sc.done; sched.error = sc.ticket + 1; sched.total = (unsigned)total; sched.no_wpp = no_wpp;
+  sched.wait_ticks = 3000000000ull;  // 30 s of the 100 MHz clock
+  const Tables *tb = device_tables();
+  void *args[] = { &F, &d_model, &tb, &sched };  // (the kernels' parameters: kvz_inter_kernels.hpp KVZ_ICTU_KERNEL)
+  DevTimer &tm = inter_timer();
+  if (!tm.e0) { KVZ_HIP_CHECK(hipEventCreate(&tm.e0)); KVZ_HIP_CHECK(hipEventCreate(&tm.e1)); }
+  KVZ_HIP_CHECK(hipEventRecord(tm.e0, st));
+  KVZ_HIP_CHECK(hipLaunchKernel(inter_build_kernel(unit), dim3((unsigned)n_wg), dim3(KVZ_ICTU_THREADS), args, 0, st));
+  KVZ_HIP_CHECK(hipGetLastError());
+  KVZ_HIP_CHECK(hipEventRecord(tm.e1, st));
+  unsigned flags[2] = { 0, 0 };
+  KVZ_HIP_CHECK(hipMemcpyAsync(flags, sc.ticket, sizeof flags, hipMemcpyDeviceToHost, st));
+  KVZ_HIP_CHECK(hipStreamSynchronize(st));
+  KVZ_HIP_CHECK(hipEventElapsedTime(&inter_kernel_ms(), tm.e0, tm.e1));
+  return flags[1] ? -2 : 0;
+}
+}  // namespace kvz
+
 static int kvz_inter_ctu_pass_run(const uint8_t *src, const uint8_t *ref, const kvz_hip_cu_info *ref_cu, uint8_t *rec, kvz_hip_cu_info *cu, int16_t *coeff, int width,
                                   int height, int n_pictures, const kvz_hip_inter_params *p, const int32_t *tile_xy, int n_references,
                                   const kvz_hip_inter_pictures *pictures, const kvz_hip_scaling_lists *sets, int n_sets, const uint16_t *set_of_picture, int slice_type, const kvz_hip_inter_refs *refs = nullptr);
@@ -1732,10 +1800,6 @@ static int kvz_inter_ctu_pass_run(const uint8_t *src, const uint8_t *ref, const 
   const int wc = (width + 63) / 64, hc = (height + 63) / 64, ctus = wc * hc;
   const long total = (long)ctus * n_pictures;
   kvz::InterScratch &sc = kvz::inter_scratch();
-  int dev_id = 0, n_cu = 256;
-  KVZ_HIP_CHECK(hipGetDevice(&dev_id));
-  KVZ_HIP_CHECK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev_id));
-  const char *env = getenv("KVZ_HIP_INTER_WG_PER_CU");
   // the kernel's build: with the residual coder's contexts in the LDS context sets only where the picture's coefficients are priced with them (kvz_inter_ctu.hpp)
   // (pictures with QPs of their own: when any of them is; the others run that build with coeff_cabac == 0)
   float fbits[128];
@@ -1752,36 +1816,10 @@ static int kvz_inter_ctu_pass_run(const uint8_t *src, const uint8_t *ref, const 
     table = kvz::inter_picture_table_lists(pictures ? pictures->qp : qp_all.data(), pictures ? pictures->poc : poc_all.data(), n_pictures, model_at_qp, sets, n_sets, set_of_picture);
   } else if (refs) table = kvz::inter_picture_table_refs(pictures->qp, pictures->poc, n_pictures, model_at_qp, refs);  // (P, and `pictures` is there: inter_refs_launch_known)
   else if (pictures) table = kvz::inter_picture_table(pictures->qp, pictures->poc, n_pictures, model_at_qp);
-  const bool cabac_build = (pictures || lists) ? table.any_cabac : kvz::inter_qp_prices_with_cabac(p->qp, p->fast_residual_cost);
-  const void *kernel = refs ? (cabac_build ? (const void *)kvz::inter_ctu_ticket_kernel_refs_cabac : (const void *)kvz::inter_ctu_ticket_kernel_refs_fast)
-                     : p_slice ? (cabac_build ? (const void *)kvz::inter_ctu_ticket_kernel_p_cabac : (const void *)kvz::inter_ctu_ticket_kernel_p_fast)
-                     : me ? (cabac_build ? (const void *)kvz::inter_ctu_ticket_kernel_me_cabac : (const void *)kvz::inter_ctu_ticket_kernel_me_fast)
-                     : lists ? (cabac_build ? (const void *)kvz::inter_ctu_ticket_kernel_lists_cabac : (const void *)kvz::inter_ctu_ticket_kernel_lists_fast)
-                             : (cabac_build ? (const void *)kvz::inter_ctu_ticket_kernel_cabac : (const void *)kvz::inter_ctu_ticket_kernel_fast);
-  // resident workgroups (= wavefronts) per CU: what the kernel's registers and LDS allow -- a persistent grid, one workgroup per slot
-  int fit = 0;
-  KVZ_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&fit, kernel, KVZ_ICTU_THREADS, 0));
-  // what THIS kernel build fits is the ceiling: a share (kvz_hip_dev_inter_set_share, per calling thread) divides it, the developer's environment value is clamped to it
-  if (fit <= 0) fit = 8;
-  int per_cu = fit / kvz::inter_share();
-  if (env && atoi(env) > 0) per_cu = atoi(env) < fit ? atoi(env) : fit;
-  if (per_cu < 1) per_cu = 1;
-  int n_wg = n_cu * per_cu;
-  if (getenv("KVZ_HIP_INTER_VERBOSE")) fprintf(stderr, "kvz_hip inter pass: %s%s build, %d workgroups per CU x %d CUs\n", refs ? "refs " : p_slice ? "p " : me ? "me " : lists ? "lists " : "", cabac_build ? "cabac" : "fast", per_cu, n_cu);
-  if ((long)n_wg > total) n_wg = (int)total;
-  if (n_wg > sc.n_slabs) {
-    if (sc.slabs) KVZ_HIP_CHECK(hipFree(sc.slabs));
-    KVZ_HIP_CHECK(hipMalloc((void **)&sc.slabs, (size_t)n_wg * sizeof(kvz::InterSlab)));
-    sc.n_slabs = n_wg;
-  }
-  if (total > sc.n_ctus) {
-    if (sc.ctx) { KVZ_HIP_CHECK(hipFree(sc.ctx)); KVZ_HIP_CHECK(hipFree(sc.done)); KVZ_HIP_CHECK(hipFree(sc.items)); }
-    KVZ_HIP_CHECK(hipMalloc((void **)&sc.ctx, (size_t)total * sizeof(kvz::ICtx)));
-    KVZ_HIP_CHECK(hipMalloc((void **)&sc.done, (size_t)total * sizeof(unsigned)));
-    KVZ_HIP_CHECK(hipMalloc((void **)&sc.items, (size_t)total * sizeof(uint32_t)));
-    sc.n_ctus = total;
-  }
-  if (!sc.ticket) KVZ_HIP_CHECK(hipMalloc((void **)&sc.ticket, 2 * sizeof(unsigned)));
+  const int build = kvz::inter_build_choose({ (pictures || lists) ? table.any_cabac : kvz::inter_qp_prices_with_cabac(p->qp, p->fast_residual_cost), lists, false, me, p_slice, refs != nullptr });
+  if (build == kvz::KVZ_ICTU_BUILD_NONE) { fprintf(stderr, "kvz_hip_dev_inter_ctu_pass: no kernel build for this launch\n"); return -1; }  // (the checks above have refused these, with the reason)
+  const int n_wg = kvz::inter_grid(sc, build, total);
+  kvz::inter_scratch_reserve(sc, total);
   // the model of the launch, or the table of a launch whose pictures have their own (records, then a row per distinct QP: kvz_inter_host.hpp inter_picture_table)
   kvz::InterModel m;
   if (!pictures && !lists) model_at_qp(&m, p->qp);
@@ -1816,7 +1854,7 @@ static int kvz_inter_ctu_pass_run(const uint8_t *src, const uint8_t *ref, const 
   KVZ_HIP_CHECK(hipStreamSynchronize(st));  // `items`, `m` and `table` are stack / heap objects of this call
   kvz::InterFrames F;
   F.W = width; F.H = height; F.wc = wc; F.hc = hc; F.frame_px = (long)width * height * 3 / 2; F.cells = (long)(width / 4) * (height / 4);
-  F.src = src; F.ref = ref; F.ref_cu = ref_cu; F.rec = rec; F.cu = cu; F.coeff = coeff; F.ctx_out = sc.ctx; F.slabs = sc.slabs;
+  F.src = src; F.ref = ref; F.ref_cu = ref_cu; F.rec = rec; F.cu = cu; F.coeff = coeff;
   F.prof = nullptr;
   F.tile_xy = (p->ref_width || p->ref_height) ? tile_xy : nullptr;
   F.ref_count = n_references > 0 ? n_references : 0;
@@ -1829,28 +1867,7 @@ static int kvz_inter_ctu_pass_run(const uint8_t *src, const uint8_t *ref, const 
   KVZ_HIP_CHECK(hipMemsetAsync(d_prof, 0, kvz::IP_COUNT * sizeof(unsigned long long), st));
   F.prof = d_prof;
 #endif
-  kvz::InterSched sched;
-  sched.items = sc.items; sched.ticket = sc.ticket; sched.done = sc.done; sched.error = sc.ticket + 1; sched.total = (unsigned)total; sched.no_wpp = p->no_wpp;
-  sched.wait_ticks = 3000000000ull;  // 30 s of the 100 MHz clock
-  kvz::DevTimer &tm = kvz::inter_timer();
-  if (!tm.e0) { KVZ_HIP_CHECK(hipEventCreate(&tm.e0)); KVZ_HIP_CHECK(hipEventCreate(&tm.e1)); }
-  KVZ_HIP_CHECK(hipEventRecord(tm.e0, st));
-  if (refs && cabac_build) hipLaunchKernelGGL(kvz::inter_ctu_ticket_kernel_refs_cabac, dim3((unsigned)n_wg), dim3(KVZ_ICTU_THREADS), 0, st, F, d_model, kvz::device_tables(), sched);
-  else if (refs) hipLaunchKernelGGL(kvz::inter_ctu_ticket_kernel_refs_fast, dim3((unsigned)n_wg), dim3(KVZ_ICTU_THREADS), 0, st, F, d_model, kvz::device_tables(), sched);
-  else if (p_slice && cabac_build) hipLaunchKernelGGL(kvz::inter_ctu_ticket_kernel_p_cabac, dim3((unsigned)n_wg), dim3(KVZ_ICTU_THREADS), 0, st, F, d_model, kvz::device_tables(), sched);
-  else if (p_slice) hipLaunchKernelGGL(kvz::inter_ctu_ticket_kernel_p_fast, dim3((unsigned)n_wg), dim3(KVZ_ICTU_THREADS), 0, st, F, d_model, kvz::device_tables(), sched);
-  else if (me && cabac_build) hipLaunchKernelGGL(kvz::inter_ctu_ticket_kernel_me_cabac, dim3((unsigned)n_wg), dim3(KVZ_ICTU_THREADS), 0, st, F, d_model, kvz::device_tables(), sched);
-  else if (me) hipLaunchKernelGGL(kvz::inter_ctu_ticket_kernel_me_fast, dim3((unsigned)n_wg), dim3(KVZ_ICTU_THREADS), 0, st, F, d_model, kvz::device_tables(), sched);
-  else if (lists && cabac_build) hipLaunchKernelGGL(kvz::inter_ctu_ticket_kernel_lists_cabac, dim3((unsigned)n_wg), dim3(KVZ_ICTU_THREADS), 0, st, F, d_model, kvz::device_tables(), sched);
-  else if (lists) hipLaunchKernelGGL(kvz::inter_ctu_ticket_kernel_lists_fast, dim3((unsigned)n_wg), dim3(KVZ_ICTU_THREADS), 0, st, F, d_model, kvz::device_tables(), sched);
-  else if (cabac_build) hipLaunchKernelGGL(kvz::inter_ctu_ticket_kernel_cabac, dim3((unsigned)n_wg), dim3(KVZ_ICTU_THREADS), 0, st, F, d_model, kvz::device_tables(), sched);
-  else hipLaunchKernelGGL(kvz::inter_ctu_ticket_kernel_fast, dim3((unsigned)n_wg), dim3(KVZ_ICTU_THREADS), 0, st, F, d_model, kvz::device_tables(), sched);
-  KVZ_HIP_CHECK(hipGetLastError());
-  KVZ_HIP_CHECK(hipEventRecord(tm.e1, st));
-  unsigned flags[2] = { 0, 0 };
-  KVZ_HIP_CHECK(hipMemcpyAsync(flags, sc.ticket, sizeof flags, hipMemcpyDeviceToHost, st));
-  KVZ_HIP_CHECK(hipStreamSynchronize(st));
-  KVZ_HIP_CHECK(hipEventElapsedTime(&kvz::inter_kernel_ms(), tm.e0, tm.e1));
+  const int rc = kvz::inter_launch(sc, build, n_wg, F, d_model, total, p->no_wpp, st);
 #ifdef KVZ_ICTU_PROFILE
   {
     unsigned long long hp[kvz::IP_COUNT];
@@ -1859,11 +1876,11 @@ static int kvz_inter_ctu_pass_run(const uint8_t *src, const uint8_t *ref, const 
     for (int i = 0; i < kvz::IP_COUNT; i++) fprintf(stderr, "ictu-profile %-18s %10.3f ms (sum over workgroups) %5.1f %%\n", names[i], hp[i] / 1e5, 100.0 * hp[i] / (double)hp[kvz::IP_TOTAL]);
   }
 #endif
-  return flags[1] ? -2 : 0;
+  return rc;
 }
 
-// Pictures of different sizes in one launch (kvz_inter_joint.hpp): the checks, the ticket list and the table are that header's; the scratch, the choice of the build
-// and the resident workgroups are those of kvz_hip_dev_inter_ctu_pass_lists above
+// Pictures of different sizes in one launch (kvz_inter_joint.hpp): the checks, the ticket list and the table are that header's; the scratch, the grid and the launch
+// are what every launch of the pass shares (above)
 int kvz_hip_dev_inter_ctu_pass_groups(const kvz_hip_inter_group *groups, int n_groups, const kvz_hip_inter_params *p)
 {
   if (!kvz::inter_joint_known(groups, n_groups, p, "kvz_hip_dev_inter_ctu_pass_groups")) return -1;
@@ -1872,19 +1889,9 @@ int kvz_hip_dev_inter_ctu_pass_groups(const kvz_hip_inter_group *groups, int n_g
   p = &full;
   hipStream_t st = be().stream;
   kvz::InterScratch &sc = kvz::inter_scratch();
-  int dev_id = 0, n_cu = 256;
-  KVZ_HIP_CHECK(hipGetDevice(&dev_id));
-  KVZ_HIP_CHECK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev_id));
-  const char *env = getenv("KVZ_HIP_INTER_WG_PER_CU");
   long total = 0;
   for (int i = 0; i < n_groups; i++) total += (long)((groups[i].width + 63) / 64) * ((groups[i].height + 63) / 64) * groups[i].n_pictures;
-  if (total > sc.n_ctus) {  // (before the table: the table holds the context scratch's address)
-    if (sc.ctx) { KVZ_HIP_CHECK(hipFree(sc.ctx)); KVZ_HIP_CHECK(hipFree(sc.done)); KVZ_HIP_CHECK(hipFree(sc.items)); }
-    KVZ_HIP_CHECK(hipMalloc((void **)&sc.ctx, (size_t)total * sizeof(kvz::ICtx)));
-    KVZ_HIP_CHECK(hipMalloc((void **)&sc.done, (size_t)total * sizeof(unsigned)));
-    KVZ_HIP_CHECK(hipMalloc((void **)&sc.items, (size_t)total * sizeof(uint32_t)));
-    sc.n_ctus = total;
-  }
+  kvz::inter_scratch_reserve(sc, total);  // (before the table: the table holds the context scratch's address)
   float fbits[128];
   for (int i = 0; i < 128; i++) fbits[i] = (float)kvz::kEntropyBits[i] / 32768.0f;
   const kvz::InterJointTable table = kvz::inter_joint_table(groups, n_groups, p, sc.ctx, [&](kvz::InterModel *row, int qp) {
@@ -1892,23 +1899,9 @@ int kvz_hip_dev_inter_ctu_pass_groups(const kvz_hip_inter_group *groups, int n_g
     kvz::inter_model_init(row, qp, p->poc, kvz_hip_default_coeff_weights(qp), fbits, p->mv_constraint, p->sao, p->deblock, p->fme_level, p->pu_depth_inter_max, p->no_wpp, p->fast_residual_cost,
                           0, 0, 0, 0, 0, 0, p->no_tmvp, 0);
   });
-  const bool cabac_build = table.any_cabac;
-  const void *kernel = cabac_build ? (const void *)kvz::inter_ctu_ticket_kernel_joint_cabac : (const void *)kvz::inter_ctu_ticket_kernel_joint_fast;
-  int fit = 0;
-  KVZ_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&fit, kernel, KVZ_ICTU_THREADS, 0));
-  if (fit <= 0) fit = 8;
-  int per_cu = fit / kvz::inter_share();
-  if (env && atoi(env) > 0) per_cu = atoi(env) < fit ? atoi(env) : fit;
-  if (per_cu < 1) per_cu = 1;
-  int n_wg = n_cu * per_cu;
-  if (getenv("KVZ_HIP_INTER_VERBOSE")) fprintf(stderr, "kvz_hip inter pass: joint %s build, %d groups, %d workgroups per CU x %d CUs\n", cabac_build ? "cabac" : "fast", n_groups, per_cu, n_cu);
-  if ((long)n_wg > total) n_wg = (int)total;
-  if (n_wg > sc.n_slabs) {
-    if (sc.slabs) KVZ_HIP_CHECK(hipFree(sc.slabs));
-    KVZ_HIP_CHECK(hipMalloc((void **)&sc.slabs, (size_t)n_wg * sizeof(kvz::InterSlab)));
-    sc.n_slabs = n_wg;
-  }
-  if (!sc.ticket) KVZ_HIP_CHECK(hipMalloc((void **)&sc.ticket, 2 * sizeof(unsigned)));
+  const int build = kvz::inter_build_choose({ table.any_cabac, false, true, false, false, false });
+  if (build == kvz::KVZ_ICTU_BUILD_NONE) { fprintf(stderr, "kvz_hip_dev_inter_ctu_pass_groups: no kernel build for this launch\n"); return -1; }  // (inter_joint_known has refused these, with the reason)
+  const int n_wg = kvz::inter_grid(sc, build, total, n_groups);
   bool fresh = false;
   if (table.bytes() > sc.joint_bytes) {
     if (sc.joint) KVZ_HIP_CHECK(hipFree(sc.joint));  // (the calling thread's stream is idle: every call ends synchronised)
@@ -1931,24 +1924,8 @@ int kvz_hip_dev_inter_ctu_pass_groups(const kvz_hip_inter_group *groups, int n_g
   KVZ_HIP_CHECK(hipStreamSynchronize(st));  // `items` is a heap object of this call
   kvz::InterFrames F;
   memset(&F, 0, sizeof F);  // no geometry and no picture buffers: begin_ctu takes them from the drawn picture's group record
-  F.ctx_out = sc.ctx; F.slabs = sc.slabs;
   F.pictures = (const kvz::InterPicture *)sc.joint;
-  const kvz::InterModel *d_model = table.model_of_picture(sc.joint, 0);
-  kvz::InterSched sched;
-  sched.items = sc.items; sched.ticket = sc.ticket; sched.done = sc.done; sched.error = sc.ticket + 1; sched.total = (unsigned)total; sched.no_wpp = p->no_wpp;
-  sched.wait_ticks = 3000000000ull;  // 30 s of the 100 MHz clock
-  kvz::DevTimer &tm = kvz::inter_timer();
-  if (!tm.e0) { KVZ_HIP_CHECK(hipEventCreate(&tm.e0)); KVZ_HIP_CHECK(hipEventCreate(&tm.e1)); }
-  KVZ_HIP_CHECK(hipEventRecord(tm.e0, st));
-  if (cabac_build) hipLaunchKernelGGL(kvz::inter_ctu_ticket_kernel_joint_cabac, dim3((unsigned)n_wg), dim3(KVZ_ICTU_THREADS), 0, st, F, d_model, kvz::device_tables(), sched);
-  else hipLaunchKernelGGL(kvz::inter_ctu_ticket_kernel_joint_fast, dim3((unsigned)n_wg), dim3(KVZ_ICTU_THREADS), 0, st, F, d_model, kvz::device_tables(), sched);
-  KVZ_HIP_CHECK(hipGetLastError());
-  KVZ_HIP_CHECK(hipEventRecord(tm.e1, st));
-  unsigned flags[2] = { 0, 0 };
-  KVZ_HIP_CHECK(hipMemcpyAsync(flags, sc.ticket, sizeof flags, hipMemcpyDeviceToHost, st));
-  KVZ_HIP_CHECK(hipStreamSynchronize(st));
-  KVZ_HIP_CHECK(hipEventElapsedTime(&kvz::inter_kernel_ms(), tm.e0, tm.e1));
-  return flags[1] ? -2 : 0;
+  return kvz::inter_launch(sc, build, n_wg, F, table.model_of_picture(sc.joint, 0), total, p->no_wpp, st);
 }
 
 float kvz_hip_dev_inter_kernel_ms(void) { return kvz::inter_kernel_ms(); }
@@ -1957,7 +1934,7 @@ int kvz_hip_dev_inter_slots_per_cu(void)
 {
   kvz::runtime_init(-1);
   int fit = 0;
-  KVZ_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&fit, (const void *)kvz::inter_ctu_ticket_kernel_fast, KVZ_ICTU_THREADS, 0));
+  KVZ_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&fit, kvz::inter_build_kernel(0), KVZ_ICTU_THREADS, 0));
   return fit > 0 ? fit : 8;
 }
 

@@ -5,6 +5,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "kvz_inter_builds.hpp"
 #include "kvz_inter_ctu.hpp"
 
 namespace kvz {
@@ -19,31 +20,20 @@ struct InterSched {
   unsigned long long wait_ticks;
 };
 
-// two builds of the kernel (kvz_inter_ctu.hpp KVZ_ICTU_CABAC): `_fast` for pictures whose coefficients are priced by kvz_fast_coeff_cost (small context sets: 20 KB of LDS,
-// eight workgroups per CU), `_cabac` for those priced with the residual coder's contexts; and the same two for launches with scaling lists
-// (-DKVZ_ICTU_LISTS=1, kvz_inter_ctu.hpp: kvz_hip_dev_inter_ctu_pass_lists), `_lists_fast` / `_lists_cabac`; and the same two for joint launches of pictures of
-// different sizes (-DKVZ_ICTU_JOINT=1: kvz_hip_dev_inter_ctu_pass_groups), `_joint_fast` / `_joint_cabac`.  In a joint launch the item's picture numbers the pictures
-// across the groups; F holds no geometry, F.pictures the launch's table (kvz_inter_ctu.hpp InterJointPicture / InterJointGroup), and sched.done is indexed by the
-// group's first CTU + the picture's index in the group x the group's CTUs + the CTU; and the same two for launches that choose the integer motion search
-// (-DKVZ_ICTU_ME=1: kvz_hip_inter_params me_algorithm / me_max_steps / me_early_termination), `_me_fast` / `_me_cabac`, which raise the launch's error word when a
-// search loop reached its bound (kvz_inter_ctu_pix.inc IC_ME_LOOP_BOUND); and the same two for launches of P pictures (-DKVZ_ICTU_P=1:
-// kvz_hip_dev_inter_ctu_pass_slices with KVZ_HIP_SLICE_P), `_p_fast` / `_p_cabac`, the program without its L1 half (kvz_inter_ctu.hpp KVZ_ICTU_P); and the same two for launches of P pictures with
-// reference lists (-DKVZ_ICTU_P=1 -DKVZ_ICTU_REFS=1: kvz_hip_dev_inter_ctu_pass_refs), `_refs_fast` / `_refs_cabac`: F.ref / F.ref_cu are a pool of frames and
-// F.pictures holds InterPictureRefs records (kvz_inter_ctu.hpp KVZ_ICTU_REFS)
+// the kernel's builds: kvz_inter_builds.hpp lists them -- unit, name and switches -- and says what each switch means
 #define KVZ_ICTU_KERNEL(name) __global__ void __launch_bounds__(KVZ_ICTU_THREADS) __attribute__((amdgpu_waves_per_eu(KVZ_ICTU_WAVES_PER_EU, KVZ_ICTU_WAVES_PER_EU))) name(const InterFrames F, const InterModel *model, const Tables *tb, const InterSched sched)
 #ifndef KVZ_INTER_KERNEL_BODY
-KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_fast);
-KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_cabac);
-KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_lists_fast);
-KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_lists_cabac);
-KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_joint_fast);
-KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_joint_cabac);
-KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_me_fast);
-KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_me_cabac);
-KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_p_fast);
-KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_p_cabac);
-KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_refs_fast);
-KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_refs_cabac);
+#define KVZ_ICTU_X(unit, suffix, ...) KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_##suffix);
+KVZ_ICTU_BUILDS(KVZ_ICTU_X)
+#undef KVZ_ICTU_X
+// the kernel of a unit of the list, for the occupancy query and the launch; nullptr where the list has no such unit
+inline const void *inter_build_kernel(int unit)
+{
+#define KVZ_ICTU_X(u, suffix, ...) if (unit == u) return (const void *)inter_ctu_ticket_kernel_##suffix;
+  KVZ_ICTU_BUILDS(KVZ_ICTU_X)
+#undef KVZ_ICTU_X
+  return nullptr;
+}
 #else
 #if KVZ_ICTU_JOINT && KVZ_ICTU_LISTS
 #error "scaling lists are not part of joint launches"
@@ -57,32 +47,33 @@ KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_refs_cabac);
 #if KVZ_ICTU_REFS && !KVZ_ICTU_P
 #error "reference lists are built for P pictures only"
 #endif
-#if KVZ_ICTU_REFS && KVZ_ICTU_CABAC
-KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_refs_cabac)
-#elif KVZ_ICTU_REFS
-KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_refs_fast)
-#elif KVZ_ICTU_P && KVZ_ICTU_CABAC
-KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_p_cabac)
+// the name this unit defines, from its switches: the kind, then how coefficients are priced.  The body holds the name and the switches against the list
+#if KVZ_ICTU_REFS
+#define KVZ_ICTU_KIND refs_
 #elif KVZ_ICTU_P
-KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_p_fast)
-#elif KVZ_ICTU_ME && KVZ_ICTU_CABAC
-KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_me_cabac)
+#define KVZ_ICTU_KIND p_
 #elif KVZ_ICTU_ME
-KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_me_fast)
-#elif KVZ_ICTU_JOINT && KVZ_ICTU_CABAC
-KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_joint_cabac)
+#define KVZ_ICTU_KIND me_
 #elif KVZ_ICTU_JOINT
-KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_joint_fast)
-#elif KVZ_ICTU_LISTS && KVZ_ICTU_CABAC
-KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_lists_cabac)
+#define KVZ_ICTU_KIND joint_
 #elif KVZ_ICTU_LISTS
-KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_lists_fast)
-#elif KVZ_ICTU_CABAC
-KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_cabac)
+#define KVZ_ICTU_KIND lists_
 #else
-KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_fast)
+#define KVZ_ICTU_KIND
 #endif
+#if KVZ_ICTU_CABAC
+#define KVZ_ICTU_THIS KVZ_ICTU_PASTE(KVZ_ICTU_KIND, cabac)
+#else
+#define KVZ_ICTU_THIS KVZ_ICTU_PASTE(KVZ_ICTU_KIND, fast)
+#endif
+#define KVZ_ICTU_PASTE_(a, b) a##b
+#define KVZ_ICTU_PASTE(a, b) KVZ_ICTU_PASTE_(a, b)
+#define KVZ_ICTU_STR_(x) #x
+#define KVZ_ICTU_STR(x) KVZ_ICTU_STR_(x)
+KVZ_ICTU_KERNEL(KVZ_ICTU_PASTE(inter_ctu_ticket_kernel_, KVZ_ICTU_THIS))
 {
+  static_assert(inter_build_named(inter_build_choose({ KVZ_ICTU_CABAC != 0, KVZ_ICTU_LISTS != 0, KVZ_ICTU_JOINT != 0, KVZ_ICTU_ME != 0, KVZ_ICTU_P != 0, KVZ_ICTU_REFS != 0 }), KVZ_ICTU_STR(KVZ_ICTU_THIS)),
+                "this unit's switches are no row of KVZ_ICTU_BUILDS (kvz_inter_builds.hpp), or the kernel it defines does not carry that row's name");
   __shared__ int s_ticket;
 #if KVZ_ICTU_JOINT
   __shared__ unsigned s_done_at;  // the drawn CTU's own `done` flag: lane 0 finds it in the records once per CTU, before the wait

@@ -6,6 +6,24 @@
 // (kvz_inter_host.hpp inter_picture_table) and found by the kernel's own begin_ctu.  tests/test_inter_mixed_qp_sim.py builds and uses it.
 #include "hostsim.cpp"
 #include "../../kvazaar_amd/csrc/kvz_inter_pictures.hpp"
+#include "../../kvazaar_amd/csrc/kvz_inter_builds.hpp"
+
+// The build list and the choice (kvz_inter_builds.hpp), for tests/test_inter_builds_sim.py.  rows [n][7]: unit, CABAC, LISTS, JOINT, ME, P, REFS of every build of the
+// list; returns n.  *unit_mask: the translation units, a bit each.  kvz_hostsim_inter_build_suffix: the suffix of a unit's kernel name
+extern "C" int kvz_hostsim_inter_builds(int *rows, unsigned long long *unit_mask)
+{
+#define KVZ_ICTU_X(unit, suffix, ...) unit, __VA_ARGS__,
+  const int list[] = { KVZ_ICTU_BUILDS(KVZ_ICTU_X) };
+#undef KVZ_ICTU_X
+  memcpy(rows, list, sizeof list);
+  *unit_mask = kvz::KVZ_ICTU_UNIT_MASK;
+  return (int)(sizeof list / sizeof list[0] / 7);
+}
+extern "C" const char *kvz_hostsim_inter_build_suffix(int unit) { return kvz::inter_build_suffix(unit); }
+extern "C" int kvz_hostsim_inter_build_choose(int any_cabac, int lists, int joint, int me, int p_slice, int refs)
+{
+  return kvz::inter_build_choose({ any_cabac != 0, lists != 0, joint != 0, me != 0, p_slice != 0, refs != 0 });
+}
 
 // 0 when a launch of n_pictures accepts the table / the bare QP array (the loop filters), -1 when the library refuses it
 extern "C" int kvz_hostsim_inter_pictures_check(const kvz_hip_inter_pictures *ip, int n_pictures)

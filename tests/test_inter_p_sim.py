@@ -219,7 +219,8 @@ def test_header_library_binding_and_build_list_agree(hiplib):
     units = {name: defs for name, _, defs in build.UNITS}
     assert units["kvz_inter_tu8"] == ["-DKVZ_ICTU_P=1", "-DKVZ_ICTU_CABAC=0"] and units["kvz_inter_tu9"] == ["-DKVZ_ICTU_P=1", "-DKVZ_ICTU_CABAC=1"]
     kernels = open(os.path.join(flatapi.ROOT, "kvazaar_amd", "csrc", "kvz_inter_kernels.hpp")).read()
-    assert "inter_ctu_ticket_kernel_p_fast" in kernels and "inter_ctu_ticket_kernel_p_cabac" in kernels
+    builds = open(os.path.join(flatapi.ROOT, "kvazaar_amd", "csrc", "kvz_inter_builds.hpp")).read()  # the kernels' names: inter_ctu_ticket_kernel_ and the suffix of a row of the list
+    assert "KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_##suffix);" in kernels and re.search(r"\bX\(8, p_fast, ", builds) and re.search(r"\bX\(9, p_cabac, ", builds)
     assert re.search(r"#if KVZ_ICTU_P && \(KVZ_ICTU_LISTS \|\| KVZ_ICTU_JOINT \|\| KVZ_ICTU_ME\)\n#error", kernels)
 
 

@@ -341,5 +341,6 @@ def test_header_library_binding_and_build_list_agree(hiplib):
     assert units[units.index("kvz_inter_tu9") + 1:units.index("kvz_inter_tu9") + 3] == ["kvz_inter_tu10", "kvz_inter_tu11"]
     assert defs["kvz_inter_tu10"] == ["-DKVZ_ICTU_P=1", "-DKVZ_ICTU_REFS=1", "-DKVZ_ICTU_CABAC=0"] and defs["kvz_inter_tu11"] == ["-DKVZ_ICTU_P=1", "-DKVZ_ICTU_REFS=1", "-DKVZ_ICTU_CABAC=1"]
     kernels = open(os.path.join(flatapi.ROOT, "kvazaar_amd", "csrc", "kvz_inter_kernels.hpp")).read()
-    assert "inter_ctu_ticket_kernel_refs_fast" in kernels and "inter_ctu_ticket_kernel_refs_cabac" in kernels
+    builds = open(os.path.join(flatapi.ROOT, "kvazaar_amd", "csrc", "kvz_inter_builds.hpp")).read()  # the kernels' names: inter_ctu_ticket_kernel_ and the suffix of a row of the list
+    assert "KVZ_ICTU_KERNEL(inter_ctu_ticket_kernel_##suffix);" in kernels and re.search(r"\bX\(10, refs_fast, ", builds) and re.search(r"\bX\(11, refs_cabac, ", builds)
     assert re.search(r"#if KVZ_ICTU_REFS && !KVZ_ICTU_P\n#error", kernels)
