@@ -209,6 +209,41 @@ long kvz_hip_batch_entropy_code_models(kvz_hip_batch *b, const kvz_hip_picture_m
 long kvz_hip_batch_entropy_code_then_models(kvz_hip_batch *b, const kvz_hip_picture_models *models, int sao, const uint8_t *not_last, uint8_t *out, size_t capacity,
                                             uint32_t *substream_bytes, kvz_hip_batch *next, const kvz_hip_picture_models *next_models);
 
+/* ---- A cost model per CTU: cu_qp_delta (kvz_hip_ctu_models, kvz_hip_types.h) ----
+ * kvz_hip_intra_frames_models with a model per CTU instead of a model per picture: every CTU is searched, quantised, priced and reconstructed under the qp, lambda,
+ * lambda_sqrt, coeff_weights and coeff_cabac of the row model_of_ctu names; its picture's slice model supplies ctx_init and the switches.  A map that repeats each
+ * picture's own model gives what kvz_hip_intra_frames_models gives, byte for byte.  Behind the pass, on the batch's stream, the call derives the QP every CU ends up
+ * with (encoderstate.c:574-633 set_cu_qps with max_qp_delta_depth 0, one quantisation group per CTU).  A substream's predictor `last` starts at the slice QP at the
+ * start of every CTU row (no_wpp: once per picture, running through the rows in raster order); for each CTU pred = last, the CUs in coding order before the first CU
+ * with any coded block flag take QP pred, that CU and all after it the CTU's QP Q, and afterwards last = Q if the CTU has a coefficient anywhere, else pred.  Q - pred is
+ * the cu_qp_delta the first transform unit with a coded block flag carries.
+ * Returns 1, or -1 with a message on stderr, NOTHING queued and the batch usable as before for: a struct_size this library does not know, a NULL member, a map index
+ * >= n_models; everything kvz_hip_intra_frames_models refuses; any model with rdoq, search_nxn or signhide; a batch that has scaling lists; KVZ_HIP_SCHED=wave; a picture
+ * whose QPs (slice QP and every CTU QP) span more than 25 -- which CTU predicts which depends on results, so the pairwise bound is what keeps every delta codable.
+ * Not built: tiles, batch groups, the inter path, preset `medium`; computing --vaq offsets or a rate controller's lambdas is the caller's business (it brings the map). */
+int  kvz_hip_intra_frames_ctu_models(kvz_hip_batch *b, const kvz_hip_ctu_models *cm);
+/* What the last kvz_hip_intra_frames_ctu_models derived for picture `frame` (after the stream has drained; any pointer may be NULL): cu_qp [(H/8)*(W/8)] the QP of
+ * every 8x8 unit, raster like cu_depth; ctu_qp [CTUs, raster] per CTU pred | Q << 8 | coded << 16 | first << 24 -- coded: the CTU has a coefficient, so a delta
+ * (0 included) is coded; first: the z-order index of the first 8x8 unit of the first CU with a coded block flag (64: none).  -1: no such pass has run on the batch, or
+ * the batch's last pass was invalid. */
+int  kvz_hip_batch_download_cu_qps(kvz_hip_batch *b, int frame, uint8_t *cu_qp, uint32_t *ctu_qp);
+/* device time of the CU-QP step behind the last kvz_hip_intra_frames_ctu_models (milliseconds; kvz_hip_batch_last_kernel_ms is the pass alone); call after a sync */
+float kvz_hip_batch_last_cu_qp_ms(kvz_hip_batch *b);
+/* kvz_hip_batch_loop_filters_models after kvz_hip_intra_frames_ctu_models with the same `cm`: every edge part is filtered at (QpP + QpQ + 1) >> 1 of the two CU QPs
+ * the pass left (filter.c:275-295); that value gives beta and tc, and the chroma tc through the chroma QP table.  The SAO decision of a CTU uses that CTU's lambda;
+ * its two contexts start from the slice QP.  -1 with a message and nothing queued for what kvz_hip_intra_frames_ctu_models refuses, when the batch's last pass
+ * was no such pass (the CU QPs come from it), and when `cm` is not that pass's map (another lambda, row or QP for any CTU: the lambdas and the CU QPs belong together).
+ */
+int  kvz_hip_batch_loop_filters_ctu_models(kvz_hip_batch *b, const kvz_hip_ctu_models *cm, int deblock, int beta_offset_div2, int tc_offset_div2, int sao);
+
+/* kvz_hip_batch_entropy_code_models after kvz_hip_intra_frames_ctu_models with the same `cm` (not_last must be NULL: no tiles): Q - pred of a CTU is coded in the first
+ * transform unit of the CTU that has a coded block flag (encode_coding_tree.c:282-305) -- cu_qp_delta_abs with a truncated-unary prefix, cMax 5, the first bin on
+ * context 0 and the others on context 1, and an EG0 suffix of |d| - 5 in bypass bins; cu_qp_delta_sign_flag as one bypass bin when d != 0.  The two contexts start
+ * from init value 154 at the slice QP; the library derives them, kvz_hip_intra_cost_model keeps its size.  Slice header, PPS (cu_qp_delta_enabled_flag,
+ * diff_cu_qp_delta_depth 0) and NAL framing stay with the host.  -1 with a message and nothing queued for what kvz_hip_intra_frames_ctu_models refuses, for
+ * not_last != NULL, when the batch's last pass was no such pass and when `cm` is not that pass's map. */
+long kvz_hip_batch_entropy_code_ctu_models(kvz_hip_batch *b, const kvz_hip_ctu_models *cm, int sao, const uint8_t *not_last, uint8_t *out, size_t capacity, uint32_t *substream_bytes);
+
 /* ---- Per-coefficient scaling lists (kvz_hip_scaling_lists, kvz_hip_types.h) ----
  * kvazaar's --scaling-list default: H.265 tables 7-5 and 7-6 (scalinglist.c:266-282), every DC term 16. */
 void kvz_hip_scaling_lists_default(kvz_hip_scaling_lists *lists);

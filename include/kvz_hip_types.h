@@ -158,6 +158,18 @@ typedef struct kvz_hip_picture_models {
   const uint16_t *model_of_picture;         /* [n_frames of the batch]: each < n_models */
 } kvz_hip_picture_models;
 
+/* A cost model per CTU of ONE batched launch (kvz_hip_batch.h, the kvz_hip_*_ctu_models entry points): HEVC's QP per quantisation group with one group per CTU
+ * (cu_qp_delta_enabled_flag, diff_cu_qp_delta_depth 0) -- what kvazaar's --roi, --vaq and rate control set per LCU.  `pictures` is the table of the launch;
+ * its model_of_picture names every picture's SLICE model: the slice QP, the initial context states and the switches.  model_of_ctu names, for every CTU in raster
+ * order, the row whose qp, lambda, lambda_sqrt, coeff_weights and coeff_cabac the CTU is searched, quantised, priced and reconstructed under (for --roi the model
+ * of a uniform picture at the CTU's QP; a rate controller's lambda is just another row).  The slice QP and the CTU QPs of one picture may span at most 25, which
+ * keeps every delta the coder can meet inside HEVC's -26 .. 25.  HOST arrays.  struct_size: sizeof of the caller's headers; an unknown size is refused with -1. */
+typedef struct kvz_hip_ctu_models {
+  uint32_t struct_size;
+  const kvz_hip_picture_models *pictures;   /* the table; model_of_picture: each picture's slice model */
+  const uint16_t *model_of_ctu;             /* [n_frames][CTU rows][CTU columns], raster; each < pictures->n_models */
+} kvz_hip_ctu_models;
+
 /* Per-coefficient scaling lists (kvazaar's --scaling-list / --cqmfile; scaling_list_enabled_flag of the SPS): state of a batch of the all-intra CTU pass
  * (kvz_hip_batch_set_scaling_lists, kvz_hip_batch.h), an argument of the inter CTU pass (kvz_hip_dev_inter_ctu_pass_lists, kvz_hip_dev.h); not part of a cost model.  The arrays are what kvazaar's scaling_list_t holds after kvz_scalinglist_parse or
  * kvz_scalinglist_get_default: per size (0: 4x4 .. 3: 32x32) and list (0-2 intra Y, U, V; 3-5 inter; two lists, intra and inter, at 32x32) the 16 entries of a 4x4

@@ -49,7 +49,8 @@ class PictureModels:
     the table then holds a model per distinct (QP, signhide).  HipBatch.launch / run / loop_filters / entropy_code take it wherever they take a CostModel.  The object owns the ctypes
     arrays the struct points into: keep it alive while a call uses it."""
 
-    def __init__(self, lib, qps, weights=None, **switches):
+    def __init__(self, lib, qps, weights=None, extra_qps=(), **switches):
+        """extra_qps: QPs the table also gets a row for although no picture runs at them (CtuModels: the QPs of CTUs)"""
         qps = [int(q) for q in qps]
         if not qps:
             raise ValueError("PictureModels: no pictures")
@@ -59,8 +60,8 @@ class PictureModels:
         if len(hide) != len(qps):
             raise ValueError("PictureModels: signhide per picture needs a value for every picture")
         self.signhide = hide
-        distinct = sorted(set(zip(qps, hide)))
-        row = {k: i for i, k in enumerate(distinct)}
+        distinct = sorted(set(zip(qps, hide)) | {(int(q), 0) for q in extra_qps})
+        row = self.row = {k: i for i, k in enumerate(distinct)}
         self.models = (CostModel * len(distinct))()
         for i, (q, sh) in enumerate(distinct):
             w = weights(q) if callable(weights) else (weights[q] if isinstance(weights, dict) else weights)
@@ -85,6 +86,39 @@ class PictureModels:
 
     def __len__(self):
         return len(self.qps)
+
+
+class CtuModelsStruct(C.Structure):
+    """kvz_hip_ctu_models (include/kvz_hip_types.h)"""
+    _fields_ = [("struct_size", C.c_uint32), ("pictures", C.POINTER(PictureModelsStruct)), ("model_of_ctu", C.POINTER(C.c_uint16))]
+
+
+class CtuModels:
+    """A cost model per CTU of a batch (kvz_hip_ctu_models): a QP per CTU inside a picture, HEVC's cu_qp_delta with one quantisation group per CTU -- what kvazaar's
+    --roi / --vaq / rate control set per LCU.  picture_qps: the slice QP of every picture of the batch; ctu_qps: per picture the QP of every CTU in raster order (CTU
+    rows x CTU columns).  The table (`pictures`, a PictureModels) holds one model per distinct QP; weights and switches as PictureModels takes them, without signhide,
+    rdoq and search_nxn.  The slice QP and the CTU QPs of one picture may span at most 25.  HipBatch.launch / run / loop_filters / entropy_code take it wherever they take a
+    PictureModels.  The object owns the ctypes arrays the struct points into: keep it alive while a call uses it."""
+
+    def __init__(self, lib, picture_qps, ctu_qps, weights=None, **switches):
+        for k in ("signhide", "rdoq", "search_nxn"):
+            if switches.get(k):
+                raise TypeError(f"CtuModels: {k} is not supported with a model per CTU")
+        ctu_qps = [[int(q) for q in np.asarray(p).reshape(-1)] for p in ctu_qps]
+        if len(ctu_qps) != len(picture_qps) or len({len(p) for p in ctu_qps}) > 1:
+            raise ValueError("CtuModels: ctu_qps needs the QP of every CTU of every picture")
+        self.ctu_qps = ctu_qps
+        self.pictures = PictureModels(lib, picture_qps, weights, extra_qps={q for p in ctu_qps for q in p}, **switches)
+        flat = [self.pictures.row[(q, 0)] for p in ctu_qps for q in p]
+        self.index = (C.c_uint16 * max(len(flat), 1))(*flat)
+        self.struct = CtuModelsStruct(C.sizeof(CtuModelsStruct), C.pointer(self.pictures.struct), self.index)
+
+    @property
+    def no_wpp(self):
+        return self.pictures.no_wpp
+
+    def __len__(self):
+        return len(self.pictures)
 
 
 class ScalingListsStruct(C.Structure):
@@ -116,6 +150,10 @@ class ScalingLists:
 
 def _is_table(model):
     return isinstance(model, PictureModels)
+
+
+def _is_ctu_map(model):
+    return isinstance(model, CtuModels)
 
 
 def outputs(width, height):
@@ -183,7 +221,13 @@ class HipBatch:
 
     def launch(self, model):
         """asynchronous on the batch's stream; returns the number of kernel launches.  model: a CostModel for every picture, or a PictureModels table
-        (kvz_hip_intra_frames_models)"""
+        (kvz_hip_intra_frames_models), or a CtuModels map (kvz_hip_intra_frames_ctu_models: the pass, and behind it the QP of every CU)"""
+        if _is_ctu_map(model):
+            self._check_table(model)
+            f = self.lib.kvz_hip_intra_frames_ctu_models
+            f.argtypes = [C.c_void_p, C.POINTER(CtuModelsStruct)]
+            f.restype = C.c_int
+            return f(self.handle, C.byref(model.struct))
         if _is_table(model):
             self._check_table(model)
             f = self.lib.kvz_hip_intra_frames_models
@@ -249,7 +293,18 @@ class HipBatch:
 
     def loop_filters(self, model, deblock=True, sao=True, beta_offset_div2=0, tc_offset_div2=0, wait=True):
         """kvz_hip_batch_loop_filters: deblocking + SAO decision + SAO reconstruction on the batch's stream (a PictureModels table: kvz_hip_batch_loop_filters_models,
-        every picture with its own QP, lambda and SAO contexts; with sao=False that is the deblocking of a mixed batch)"""
+        every picture with its own QP, lambda and SAO contexts; with sao=False that is the deblocking of a mixed batch; a CtuModels map, after a launch with it:
+        kvz_hip_batch_loop_filters_ctu_models, every edge at the QPs of the CUs on its two sides and every CTU's SAO decision under its own lambda)"""
+        if _is_ctu_map(model):
+            self._check_table(model)
+            f = self.lib.kvz_hip_batch_loop_filters_ctu_models
+            f.argtypes = [C.c_void_p, C.POINTER(CtuModelsStruct), C.c_int, C.c_int, C.c_int, C.c_int]
+            f.restype = C.c_int
+            if f(self.handle, C.byref(model.struct), int(deblock), beta_offset_div2, tc_offset_div2, int(sao)) != 0:
+                raise BatchError("kvz_hip_batch_loop_filters_ctu_models: the batch cannot run this map (see stderr)")
+            if wait:
+                self.sync()
+            return
         if _is_table(model):
             self._check_table(model)
             f = self.lib.kvz_hip_batch_loop_filters_models
@@ -272,6 +327,22 @@ class HipBatch:
         last loop_filters(sao=True)).  -> (bytes of all substreams back to back, sizes as an array [frame][substream]).  then = (batch, model): that batch's pass is
         started once this coder's first stage is through (kvz_hip_batch_entropy_code_then).  With a PictureModels table as `model` every picture's substreams start
         from its own initial contexts (kvz_hip_batch_entropy_code_then_models); `then` then names a batch with a table of its own"""
+        if _is_ctu_map(model):  # kvz_hip_batch_entropy_code_ctu_models: after a launch with the same map; every CTU with a coefficient codes its cu_qp_delta
+            self._check_table(model)
+            if then or not_last is not None:
+                raise TypeError("entropy_code with a CtuModels map: no `then`, no tiles")
+            f = self.lib.kvz_hip_batch_entropy_code_ctu_models
+            f.argtypes = [C.c_void_p, C.POINTER(CtuModelsStruct), C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+            f.restype = C.c_long
+            capacity = capacity or entropy_capacity(self.n, self.w, self.h)
+            if getattr(self, "_entropy_out", None) is None or self._entropy_out.nbytes < capacity:
+                pinned_free(self.lib, getattr(self, "_entropy_ptr", None))
+                self._entropy_ptr, self._entropy_out = pinned_bytes(self.lib, capacity)
+            sizes = np.zeros((self.n, 1 if model.no_wpp else (self.h + 63) // 64), np.uint32)
+            total = f(self.handle, C.byref(model.struct), int(sao), None, self._entropy_out.ctypes.data, capacity, sizes.ctypes.data)
+            if total < 0:
+                raise BatchError(f"kvz_hip_batch_entropy_code_ctu_models failed ({total}; see stderr)")
+            return self._entropy_out[:total], sizes
         table = _is_table(model)
         if table:
             self._check_table(model)
@@ -364,6 +435,16 @@ class HipBatch:
         if rc != 0:
             raise BatchError("kvz_hip_batch_download: the batch's last pass was invalid")
         return o
+
+    def download_cu_qps(self, frame):
+        """after a launch with a CtuModels map (kvz_hip_batch_download_cu_qps): (the QP of every 8x8 unit, per CTU pred | Q << 8 | coded << 16 | first << 24)"""
+        cu_qp, ctu_qp = np.zeros((self.h // 8) * (self.w // 8), np.uint8), np.zeros(self.ctus_per_frame, np.uint32)
+        f = self.lib.kvz_hip_batch_download_cu_qps
+        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        f.restype = C.c_int
+        if f(self.handle, frame, cu_qp.ctypes.data, ctu_qp.ctypes.data) != 0:
+            raise BatchError("kvz_hip_batch_download_cu_qps: invalid pass, or the batch's last pass had no CtuModels map")
+        return cu_qp, ctu_qp
 
     def download_partitions(self, frame):
         """after a pass with model.search_nxn: (NxN flag per 8x8 CU, luma mode per 4x4 unit)"""

@@ -2,7 +2,8 @@
 
 The library's translation units are compiled in parallel: kvz_hip.hip (C ABI, per-call ops, streaming kernels, host side of the batch; with
 -DKVZ_CTU_SEPARATE_TUS it only declares the CTU kernels), kvz_ctu_tu.hip once per unit of the list in csrc/kvz_ctu_builds.hpp, one CTU kernel instantiation each
-(-DKVZ_CTU_KERNEL_TU=<unit>), and kvz_inter_tu.hip once per row of the list in csrc/kvz_inter_builds.hpp, one build of the inter CTU pass's kernel each (the row's
+(-DKVZ_CTU_KERNEL_TU=<unit>), kvz_ctu_qp_tu.hip likewise per unit of csrc/kvz_ctu_qp_builds.hpp (-DKVZ_CTU_QP_KERNEL_TU=<unit>: the kernels that fetch a cost model per
+CTU), and kvz_inter_tu.hip once per row of the list in csrc/kvz_inter_builds.hpp, one build of the inter CTU pass's kernel each (the row's
 -DKVZ_ICTU_<switch>=1, then -DKVZ_ICTU_CABAC=<0|1>).  Objects are rebuilt when one of the files they include (hipcc -MD) is newer."""
 import os
 import re
@@ -19,6 +20,8 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off"]
 # the units of the CTU pass: every unit csrc/kvz_ctu_builds.hpp's two lists name.  The header is handed them as a bit mask and refuses to compile where this pattern and its own macros read the lists differently
 CTU_UNITS = sorted({int(k) for k in re.findall(r"\bX\((\d+),", open(os.path.join(CSRC, "kvz_ctu_builds.hpp")).read())})
+# ... and of the builds that fetch a cost model per CTU: every unit csrc/kvz_ctu_qp_builds.hpp's list names, checked by that header the same way
+CTU_QP_UNITS = sorted({int(k) for k in re.findall(r"\bX\((\d+),", open(os.path.join(CSRC, "kvz_ctu_qp_builds.hpp")).read())})
 # the builds of the inter CTU pass: (unit, kernel name's suffix, (CABAC, LISTS, JOINT, ME, P, REFS)) of every row of csrc/kvz_inter_builds.hpp's list, which says what the switches mean.  The library's
 # main unit is handed the units as a bit mask, and the header refuses to compile where this pattern and its own macro read the list differently
 INTER_BUILDS = [(int(m[0]), m[1], tuple(int(v) for v in m[2:])) for m in re.findall(r"\bX\((\d+), (\w+)" + ", ([01])" * 6 + r"\)", open(os.path.join(CSRC, "kvz_inter_builds.hpp")).read())]
@@ -26,6 +29,7 @@ INTER_BUILDS = [(int(m[0]), m[1], tuple(int(v) for v in m[2:])) for m in re.find
 MFMA_VGPR_FORM = ["-mllvm", "-amdgpu-mfma-vgpr-form"]  # an internal LLVM option, only a tuning of the streaming transform kernels: dropped where hipcc does not know it (_probe_flags)
 UNITS = ([("kvz_hip", "kvz_hip.hip", ["-DKVZ_CTU_SEPARATE_TUS", f"-DKVZ_ICTU_UNITS_BUILT={sum(1 << k for k, _, _ in INTER_BUILDS)}ull"] + MFMA_VGPR_FORM)]  # (the streaming transform kernels: accumulators in VGPRs, no v_accvgpr moves around the bias pass)
          + [(f"kvz_ctu_tu{k}", "kvz_ctu_tu.hip", [f"-DKVZ_CTU_KERNEL_TU={k}", f"-DKVZ_CTU_UNITS_BUILT={sum(1 << k for k in CTU_UNITS)}ull"]) for k in CTU_UNITS]
+         + [(f"kvz_ctuqp_tu{k}", "kvz_ctu_qp_tu.hip", [f"-DKVZ_CTU_QP_KERNEL_TU={k}", f"-DKVZ_CTU_QP_UNITS_BUILT={sum(1 << k for k in CTU_QP_UNITS)}ull"]) for k in CTU_QP_UNITS]
          + [(f"kvz_inter_tu{k}", "kvz_inter_tu.hip", [f"-DKVZ_ICTU_{n}=1" for n, v in zip(("LISTS", "JOINT", "ME", "P", "REFS"), sw[1:]) if v] + [f"-DKVZ_ICTU_CABAC={sw[0]}"]) for k, _, sw in INTER_BUILDS])
 
 

@@ -15,6 +15,7 @@
 #include "kvz_scaling_lists.hpp"
 
 #include "kvz_ctu_kernels.hpp"
+#include "kvz_cu_qp.hpp"
 
 namespace kvz {
 struct DevBuf { void *p = nullptr; size_t bytes = 0; };  // a grow-only device buffer (kvz_dev.hpp EntropyScratch::need)
@@ -92,7 +93,16 @@ struct kvz_hip_batch {
   std::vector<uint16_t> list_set_of_picture;
   kvz::DevBuf d_lists;
   std::vector<uint32_t> h_lists;
-  int device;   // the batch's buffers and stream live here; every entry point binds the calling thread to it
+  // a model per CTU (kvz_hip_intra_frames_ctu_models; allocated on first use).  Staged per launch like the model table (ctu_models_stage): every CTU's lambda | its row
+  // of the table (also behind the ticket words, for the pass) | its QP.  What the step behind the pass leaves (kvz_cu_qp.hpp): the QP of every 8x8 unit and a word per
+  // CTU, and the pass they belong to (0: none)
+  kvz::DevBuf d_ctu_map;
+  std::vector<uint8_t> h_ctu_map;
+  uint8_t *d_cu_qp = nullptr;
+  uint32_t *d_ctu_qp = nullptr;
+  unsigned cu_qp_epoch = 0;
+  hipEvent_t ev_cu_qp0 = nullptr, ev_cu_qp1 = nullptr;  // around that step (kvz_hip_batch_last_cu_qp_ms)
+  int device;  // the batch's buffers and stream live here; every entry point binds the calling thread to it
   int failed;   // sticky: a CTU hand-off wait of some run timed out, the results of that run are invalid
   unsigned long long wait_ticks;
   kvz_hip_batch_group *joint = nullptr;  // the group whose joint pass was the last one queued on this batch (kvz_hip_batch_group_intra_frames): batch_check also reads ITS error word; cleared by kvz_hip_batch_reset
@@ -243,6 +253,10 @@ inline ModelTableView picture_models_stage(kvz_hip_batch *b, const kvz_hip_pictu
     memcpy(image.data() + at_ctx + i * ctx_bytes, pm->models[i].ctx_init, sizeof pm->models[i].ctx_init);
     static_assert(sizeof pm->models[i].ctx_init <= KVZ_ENTROPY_ROW_SIGNHIDE && KVZ_ENTROPY_CTXS <= KVZ_ENTROPY_ROW_SIGNHIDE, "the switch sits behind the states");
     image[at_ctx + i * ctx_bytes + KVZ_ENTROPY_ROW_SIGNHIDE] = pm->models[i].signhide != 0;  // what the entropy coder reads of the model besides its states (entropy_signhide)
+    // cu_qp_delta_abs[2] (context.c: init value 154 for every slice type) at the row's QP, where an I picture has no other context: read only by the coder of
+    // kvz_hip_batch_entropy_code_ctu_models, for the pictures whose slice model the row is.  kvz_hip_intra_cost_model keeps its size.
+    static_assert(KVZ_EB_CX_QP_DELTA >= KVZ_HIP_CX_SAO_TYPE + 1 && KVZ_EB_CX_QP_DELTA + 2 <= (int)sizeof(((kvz_hip_intra_cost_model *)0)->ctx_init), "two bytes of a row that no I-picture syntax uses");
+    image[at_ctx + i * ctx_bytes + KVZ_EB_CX_QP_DELTA] = image[at_ctx + i * ctx_bytes + KVZ_EB_CX_QP_DELTA + 1] = (uint8_t)ctx_state(pm->models[i].qp, 154);
   }
   for (size_t f = 0; f < nf; f++) {
     const int32_t qp = pm->models[pm->model_of_picture[f]].qp;
@@ -309,6 +323,56 @@ inline void scaling_lists_stage(kvz_hip_batch *b, const kvz_hip_picture_models *
     KVZ_HIP_CHECK(hipStreamSynchronize(b->stream));
     b->h_lists.swap(image);
   }
+}
+
+// The map of a launch with a model per CTU (checked by ctu_models_known; its table is staged by picture_models_stage) on the device: what the kernels are handed
+struct CtuMapView {
+  const double *lambda_of_ctu;    // the SAO decision: [n_frames][ctu]
+  const uint16_t *model_of_ctu;   // the pass (the pointer also goes behind the ticket words: kvz_ctu_kernels.hpp KVZ_SCHED_CTU_MAP_AT)
+  const uint8_t *qp_of_ctu;       // the CU-QP step
+};
+// same_as_staged (the loop filters: the CU QPs they read come from the pass): nothing is staged and *same_as_staged says whether this is the map the device holds
+inline CtuMapView ctu_models_stage(kvz_hip_batch *b, const kvz_hip_ctu_models *cm, bool *same_as_staged = nullptr)
+{
+  const size_t nctu = (size_t)b->F.wc * b->F.hc * b->n_frames, at_map = nctu * sizeof(double), at_qp = at_map + nctu * sizeof(uint16_t), bytes = at_qp + nctu;
+  if (same_as_staged && bytes > b->d_ctu_map.bytes) { *same_as_staged = false; return CtuMapView{}; }
+  bool fresh = false;
+  if (bytes > b->d_ctu_map.bytes) {
+    KVZ_HIP_CHECK(hipStreamSynchronize(b->stream));  // a launch in flight may still read the old one
+    if (b->d_ctu_map.p) KVZ_HIP_CHECK(hipFree(b->d_ctu_map.p));
+    b->d_ctu_map.bytes = bytes;
+    KVZ_HIP_CHECK(hipMalloc(&b->d_ctu_map.p, b->d_ctu_map.bytes));
+    fresh = true;
+  }
+  if (!b->d_cu_qp) {
+    KVZ_HIP_CHECK(hipMalloc((void **)&b->d_cu_qp, (size_t)(b->F.W / 8) * (b->F.H / 8) * b->n_frames));
+    KVZ_HIP_CHECK(hipMalloc((void **)&b->d_ctu_qp, nctu * sizeof(uint32_t)));
+  }
+  std::vector<uint8_t> image(bytes, 0);
+  for (size_t i = 0; i < nctu; i++) {
+    const kvz_hip_intra_cost_model &m = cm->pictures->models[cm->model_of_ctu[i]];
+    memcpy(image.data() + i * sizeof(double), &m.lambda, sizeof(double));
+    image[at_qp + i] = (uint8_t)m.qp;
+  }
+  memcpy(image.data() + at_map, cm->model_of_ctu, nctu * sizeof(uint16_t));
+  uint8_t *d = (uint8_t *)b->d_ctu_map.p;
+  CtuMapView v{ (const double *)d, (const uint16_t *)(d + at_map), d + at_qp };
+  if (same_as_staged) { *same_as_staged = image == b->h_ctu_map; return v; }
+  if (fresh || image != b->h_ctu_map) {
+    CtuMapTable mt;
+    mt.model_of_ctu = v.model_of_ctu;
+    static_assert(sizeof(CtuMapTable) <= (KVZ_SCHED_TICKET_WORDS - KVZ_SCHED_CTU_MAP_AT) * sizeof(unsigned) && KVZ_SCHED_CTU_MAP_AT * sizeof(unsigned) % alignof(CtuMapTable) == 0, "d_ticket");
+    KVZ_HIP_CHECK(hipMemcpyAsync(d, image.data(), bytes, hipMemcpyHostToDevice, b->stream));
+    KVZ_HIP_CHECK(hipMemcpyAsync(b->tw.d_ticket + KVZ_SCHED_CTU_MAP_AT, &mt, sizeof mt, hipMemcpyHostToDevice, b->stream));
+    KVZ_HIP_CHECK(hipStreamSynchronize(b->stream));
+    b->h_ctu_map.swap(image);
+  }
+  return v;
+}
+// the job of the CU-QP step of a batch whose pass ran under (cm, its staged views)
+inline CuQpJob cu_qp_job(const kvz_hip_batch *b, const ModelTableView &t, const CtuMapView &v, int no_wpp)
+{
+  return CuQpJob{ b->F.W, b->F.H, b->F.wc, b->F.hc, b->n_frames, no_wpp, b->d_coeff, b->d_depth, v.qp_of_ctu, t.qp_of_picture, b->d_cu_qp, b->d_ctu_qp };
 }
 
 }  // namespace kvz
@@ -426,6 +490,8 @@ void kvz_hip_batch_destroy(kvz_hip_batch *b)
   if (b->ev_up) { (void)hipEventSynchronize(b->ev_up); (void)hipEventDestroy(b->ev_up); }
   if (b->ev_src_read) (void)hipEventDestroy(b->ev_src_read);
   (void)hipFree(b->d_sse); (void)hipFree(b->d_models.p); (void)hipFree(b->d_lists.p);
+  (void)hipFree(b->d_ctu_map.p); (void)hipFree(b->d_cu_qp); (void)hipFree(b->d_ctu_qp);
+  if (b->ev_cu_qp0) { (void)hipEventDestroy(b->ev_cu_qp0); (void)hipEventDestroy(b->ev_cu_qp1); }
   (void)hipStreamDestroy(b->stream);
   delete b;
 }
@@ -545,10 +611,12 @@ void kvz_hip_batch_order_after(kvz_hip_batch *b, kvz_hip_batch *other)
 // the price table every model shares; any_cabac: some model prices coefficients with the CABAC model -- that instantiation then prices the others' through its run-time switch;
 // any_signhide: some model hides sign bits -- the launch takes a sign-hiding instantiation, which reads the switch of the drawn picture's model; pm: the table, or nullptr).
 // A batch that has scaling lists takes the instantiations that quantise under a factor per position (the entry points have refused rdoq, search_nxn and signhide).
-static int kvz_intra_frames_queue(kvz_hip_batch *b, const kvz_hip_intra_cost_model *model, const kvz_hip_picture_models *pm, bool any_cabac, bool any_signhide)
+// ctu_map: the pass of kvz_hip_intra_frames_ctu_models (ctu_models_stage has put the map on the device) -- a build of kvz_ctu_qp_builds.hpp, which fetches the drawn CTU's row.
+static int kvz_intra_frames_queue(kvz_hip_batch *b, const kvz_hip_intra_cost_model *model, const kvz_hip_picture_models *pm, bool any_cabac, bool any_signhide, bool ctu_map = false)
 {
   const bool table = pm != nullptr, lists = b->n_list_sets > 0;
-  const int build = kvz::ctu_build_choose({ model->search_32x32 != 0, model->rdoq != 0, model->search_nxn != 0, any_cabac, any_signhide, lists, false });  // (of the ticket schedule)
+  const int build = ctu_map ? kvz::ctu_qp_build_choose(model->search_32x32 != 0, any_cabac)
+                            : kvz::ctu_build_choose({ model->search_32x32 != 0, model->rdoq != 0, model->search_nxn != 0, any_cabac, any_signhide, lists, false });  // (of the ticket schedule)
   if (b->sched_ticket && build == kvz::KVZ_CTU_BUILD_NONE) { fprintf(stderr, "kvz_hip_intra_frames: no kernel build for this launch\n"); return -1; }  // (before anything is staged; the entry points refuse these with the reason)
   kvz::batch_enter(b);
   const kvz::CtuFrames &F = b->F;
@@ -569,6 +637,12 @@ static int kvz_intra_frames_queue(kvz_hip_batch *b, const kvz_hip_intra_cost_mod
     b->epoch++;
     kvz::CtuSched sc{ cm.no_wpp ? b->d_items_raster : b->d_items, b->tw.d_ticket, b->d_done, b->tw.d_error, b->total_items, b->epoch, cm.no_wpp | (table ? kvz::KVZ_SCHED_MODEL_TABLE : 0), b->wait_ticks };
     b->tw.pass(b->stream, b->ev0, b->ev1, [&] {
+      if (ctu_map) {
+        kvz::ctu_qp_build_dispatch(build, [&](auto bt) {
+          hipLaunchKernelGGL((kvz::intra_ctu_ticket_kernel_ctuqp<decltype(bt)::cabac != 0, decltype(bt)::s32 != 0>), dim3(b->grid_ticket), dim3(KVZ_CTU_THREADS), 0, b->stream, F, cm, kvz::device_tables(), sc);
+        });
+        return;
+      }
       kvz::ctu_build_dispatch(build, [&](auto bt) {
         kvz::CtuFrames Fr = F;
         if constexpr (bt.rdoq) {  // the build that writes NxN flags and 4x4 modes
@@ -619,6 +693,46 @@ int kvz_hip_intra_frames_models(kvz_hip_batch *b, const kvz_hip_picture_models *
   kvz::batch_enter(b);
   kvz::picture_models_stage(b, pm);
   return kvz_intra_frames_queue(b, &pm->models[0], pm, kvz::picture_models_any_cabac(pm), kvz::picture_models_any_signhide(pm));
+}
+
+int kvz_hip_intra_frames_ctu_models(kvz_hip_batch *b, const kvz_hip_ctu_models *cm)
+{
+  if (!b || !kvz::ctu_models_known(cm, b->n_frames, b->F.wc * b->F.hc, b->sched_ticket != 0, b->n_list_sets > 0, "kvz_hip_intra_frames_ctu_models")) return -1;
+  kvz::batch_enter(b);
+  const kvz_hip_picture_models *pm = cm->pictures;
+  const kvz::ModelTableView table = kvz::picture_models_stage(b, pm);
+  const kvz::CtuMapView map = kvz::ctu_models_stage(b, cm);
+  const int rc = kvz_intra_frames_queue(b, &pm->models[0], pm, kvz::picture_models_any_cabac(pm), false, true);
+  if (rc < 0) return rc;
+  if (!b->ev_cu_qp0) { KVZ_HIP_CHECK(hipEventCreate(&b->ev_cu_qp0)); KVZ_HIP_CHECK(hipEventCreate(&b->ev_cu_qp1)); }
+  KVZ_HIP_CHECK(hipEventRecord(b->ev_cu_qp0, b->stream));
+  kvz::cu_qp_frames_on(b->stream, kvz::cu_qp_job(b, table, map, pm->models[0].no_wpp != 0));  // behind the pass: the QP of every CU, for the loop filters
+  KVZ_HIP_CHECK(hipGetLastError());
+  KVZ_HIP_CHECK(hipEventRecord(b->ev_cu_qp1, b->stream));
+  b->cu_qp_epoch = b->epoch;
+  return rc;
+}
+
+float kvz_hip_batch_last_cu_qp_ms(kvz_hip_batch *b)
+{
+  float ms = 0;
+  kvz::batch_enter(b);
+  if (!b->ev_cu_qp0) return 0;
+  KVZ_HIP_CHECK(hipEventSynchronize(b->ev_cu_qp1));
+  KVZ_HIP_CHECK(hipEventElapsedTime(&ms, b->ev_cu_qp0, b->ev_cu_qp1));
+  return ms;
+}
+
+int kvz_hip_batch_download_cu_qps(kvz_hip_batch *b, int frame, uint8_t *cu_qp, uint32_t *ctu_qp)
+{
+  if (!b || frame < 0 || frame >= b->n_frames) { fprintf(stderr, "kvz_hip_batch_download_cu_qps: bad argument\n"); return -1; }
+  kvz::batch_enter(b);
+  KVZ_HIP_CHECK(hipStreamSynchronize(b->stream));
+  if (!b->cu_qp_epoch || b->cu_qp_epoch != b->epoch) { fprintf(stderr, "kvz_hip_batch_download_cu_qps: the batch's last pass was no kvz_hip_intra_frames_ctu_models\n"); return -1; }
+  const size_t ncu = (size_t)(b->F.W / 8) * (b->F.H / 8), nctu = (size_t)b->F.wc * b->F.hc;
+  if (cu_qp) KVZ_HIP_CHECK(hipMemcpy(cu_qp, b->d_cu_qp + frame * ncu, ncu, hipMemcpyDeviceToHost));
+  if (ctu_qp) KVZ_HIP_CHECK(hipMemcpy(ctu_qp, b->d_ctu_qp + frame * nctu, nctu * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return kvz::batch_check(b);
 }
 
 int kvz_hip_batch_sync(kvz_hip_batch *b)

@@ -436,7 +436,11 @@ struct RdoqLds {
 // its chroma one; a picture without lists has the rows of a flat list and comes out as from the other instantiations.  The table stays in memory (a few hundred
 // bytes per picture that the caches keep; the workgroup's LDS block has no room for it).  Not with RDOQ (its error scales per coefficient are not built) and not
 // with SH (the hiding rule prices a change with ONE factor): kvz_picture_models.hpp scaling_lists_known.
-template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false, bool LISTS = false> struct CtuProgramT {
+// CTUQP: the instantiation of the launches whose CTUs have models of their own (kvz_hip_ctu_models).  The reference's real coder moves the residual contexts of a
+// substream with every CTU's levels, however that CTU's coefficients were priced; a picture under one model needs them only when it prices with them, but here a CTU
+// priced by the fast estimate may precede one priced with the CABAC model in the same row.  So the CABAC instantiations carry the residual contexts through EVERY CTU
+// (contexts_on()): loaded, replayed over the final levels and handed on, priced with only where the CTU's own model says so.  The others are what they were.
+template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false, bool LISTS = false, bool CTUQP = false> struct CtuProgramT {
   static_assert(!(SH && RDOQ), "kvz_rdoq's own sign hiding is not built");
   static_assert(!(LISTS && (RDOQ || SH)), "scaling lists with kvz_rdoq or sign data hiding are not built");
   using CtxSet = CtxSetT<CABAC>;
@@ -451,7 +455,8 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false, bool
   static constexpr bool NXN = RDOQ;
   KVZ_DEV bool nxn_on() const { return NXN && m->search_nxn; }
   KVZ_DEV bool cabac_on() const { return CABAC && m->coeff_cabac; }  // coefficients priced with the CABAC model (rdo.c:311-340)
-  KVZ_DEV bool hide_on() const { return SH && m->signhide; }         // the picture's levels go through sign data hiding (uniform: the model is the picture's)
+  KVZ_DEV bool contexts_on() const { return CTUQP ? CABAC : cabac_on(); }  // the residual contexts of the row are carried through this CTU
+  KVZ_DEV bool hide_on() const { return SH && m->signhide; }        // the picture's levels go through sign data hiding (uniform: the model is the picture's)
   int frame, cx, cy;  // CTU origin (luma px)
   int a1x, a1y, a2x, a2y;  // CTU-local luma origin of the depth-1 / depth-2 CU whose candidates are live (uniform)
   // The thread that runs a CU's scalar bookkeeping inside the first phase of its reference build (cu_header, price_modes: a serial chain of LDS lookups and
@@ -3216,7 +3221,7 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false, bool
         // one-CTU-wide picture and the first row start from the slice-start state, encoderstate.c:1218) -- or, without WPP, from
         // the last CTU of the row above (one coder runs through the picture in raster order).  Four per lane (the record's and the model's are 4-aligned);
         // the residual contexts are only looked at with the CABAC coefficient cost, and without it the ten syntax contexts come as two dwords and a half one.
-        const int n = cabac_on() ? KVZ_CX_COUNT : KVZ_CX_SYNTAX_COUNT, v = 4 * tid;
+        const int n = contexts_on() ? KVZ_CX_COUNT : KVZ_CX_SYNTAX_COUNT, v = 4 * tid;
         if (v < n) {
           const int ctx = cx >> 6, cty = cy >> 6;
           const u8 *base = F.border + (long)frame * F.wc * F.hc * KVZ_BORDER_BYTES;
@@ -3444,10 +3449,10 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false, bool
         static_assert(KVZ_CX_SYNTAX_COUNT == 10, "8 + 2 of 4");
         wide_move<8>(r + 288, s->pre[0].s);
         WideBytes<4> t = wide_load<4>(s->pre[0].s + 8);
-        if (!cabac_on()) t.w[0] &= 0xffffu;
+        if (!contexts_on()) t.w[0] &= 0xffffu;
         wide_store<4>(r + 296, t);
       }
-      if (cabac_on() && ml >= 3 && ml < KVZ_CX_COUNT / 4) wide_move<4>(r + 288 + 4 * ml, s->pre[0].s + 4 * ml);  // the other residual contexts, a dword per lane
+      if (contexts_on() && ml >= 3 && ml < KVZ_CX_COUNT / 4) wide_move<4>(r + 288 + 4 * ml, s->pre[0].s + 4 * ml);  // the other residual contexts, a dword per lane
       if (ml >= 64 && ml < 72) {  // record [256..287], a dword per lane: depth, mode of the bottom 8x8 row, then of the right 8x8 column (read back by init())
         const int k = ml - 64, i0 = (k & 1) * 4;
         u32 v = 0;
@@ -3732,7 +3737,7 @@ template <bool CABAC, bool S32 = false, bool RDOQ = false, bool SH = false, bool
       write_rec();
     }
     KVZ_PROF(KVZ_P_MISC);
-    if (m->adaptive && cabac_on()) { code_ctu_residual(); KVZ_PROF_SYNC(KVZ_P_PRED35); }  // category reused: the residual replay
+    if (m->adaptive && contexts_on()) { code_ctu_residual(); KVZ_PROF_SYNC(KVZ_P_PRED35); }  // category reused: the residual replay
     finish_info();
     KVZ_PROF(KVZ_P_FINISH);
 #if defined(KVZ_CTU_PROFILE) && !defined(KVZ_HOSTSIM)

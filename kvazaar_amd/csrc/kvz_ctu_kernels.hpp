@@ -8,9 +8,10 @@
 
 #include "kvz_ctu.hpp"
 #include "kvz_ctu_builds.hpp"
+#include "kvz_ctu_qp_builds.hpp"
 #include "kvz_joint.hpp"
 
-#if defined(KVZ_CTU_SEPARATE_TUS) && !defined(KVZ_CTU_KERNEL_TU)
+#if defined(KVZ_CTU_SEPARATE_TUS) && !defined(KVZ_CTU_KERNEL_TU) && !defined(KVZ_CTU_QP_KERNEL_TU)
 #define KVZ_CTU_KERNEL_BODIES 0
 #else
 #define KVZ_CTU_KERNEL_BODIES 1
@@ -57,7 +58,12 @@ template <bool CABAC> __global__ void __launch_bounds__(KVZ_CTU_THREADS) __attri
 // drains its stores, one lane releases at agent scope and stores the flag; consumer polls relaxed, one lane acquires,
 // then the workgroup barrier.  Compared with one launch per diagonal this removes the per-launch tail (a diagonal of
 // n CTUs x F frames rarely is a multiple of the resident workgroup count) and 61 of 62 launches.
-enum { KVZ_SCHED_MODEL_TABLE = 2 /* bit of CtuSched::no_wpp */, KVZ_SCHED_TABLE_AT = 4 /* words behind CtuSched::ticket */, KVZ_SCHED_LISTS_AT = 8 /* likewise */, KVZ_SCHED_TICKET_WORDS = 12 };
+enum { KVZ_SCHED_MODEL_TABLE = 2 /* bit of CtuSched::no_wpp */, KVZ_SCHED_TABLE_AT = 4 /* words behind CtuSched::ticket */, KVZ_SCHED_LISTS_AT = 8 /* likewise */, KVZ_SCHED_CTU_MAP_AT = 12 /* likewise */, KVZ_SCHED_TICKET_WORDS = 16 };
+// The map of a launch with a model per CTU (kvz_hip_intra_frames_ctu_models), read by the CTUQP instantiations alone, behind the ticket words beside the model table
+// it indexes: for every CTU of every picture, raster, its row of the table.
+struct CtuMapTable {
+  const uint16_t *model_of_ctu = nullptr;  // [frames][hc][wc]
+};
 // The scaling-list factors of a launch on a batch that has lists (kvz_batch.hpp scaling_lists_stage), read by the LISTS instantiations alone, behind the ticket
 // words like the model table: rows of KVZ_LIST_ROW words (kvz_recon.hpp), one per list set and qp % 6, and for every picture its luma row | its chroma row << 16.
 struct CtuListTable {
@@ -125,9 +131,13 @@ template <class T> __device__ __forceinline__ T uniform_fetch(const T *p)  // *p
   __builtin_memcpy(&v, w, sizeof(T));
   return v;
 }
-template <bool CABAC, bool S32, bool RDOQ, bool SH = false, bool LISTS = false, bool JOINT = false> __device__ __forceinline__ void ticket_loop(const CtuFrames &F_arg, const CtuModel &model, const Tables *tb, const CtuSched &sched)
+//
+// CTUQP (kvz_hip_intra_frames_ctu_models): `m` is the row the map behind the ticket words names for the drawn CTU -- its qp, lambda, lambda_sqrt, coeff_weights and
+// coeff_cabac -- with the initial context states of the picture's own (slice) row; the switches are the same in every row of a table.
+template <bool CABAC, bool S32, bool RDOQ, bool SH = false, bool LISTS = false, bool JOINT = false, bool CTUQP = false> __device__ __forceinline__ void ticket_loop(const CtuFrames &F_arg, const CtuModel &model, const Tables *tb, const CtuSched &sched)
 {
   static_assert(!(JOINT && (RDOQ || LISTS)), "joint launches: the ultrafast / fast builds");
+  static_assert(!(CTUQP && (RDOQ || SH || LISTS || JOINT)), "a model per CTU: the ultrafast / fast builds of a batch on its own");
   CtuFrames F_joint;  // JOINT: the frames of the drawn picture's batch
   const CtuFrames &F = JOINT ? F_joint : F_arg;
   __shared__ CtuSharedT<CABAC> shared;
@@ -137,7 +147,7 @@ template <bool CABAC, bool S32, bool RDOQ, bool SH = false, bool LISTS = false, 
 #ifndef KVZ_CTU_PROFILE
   static_assert(sizeof(CtuSharedT<CABAC>) + sizeof(CtuModel) <= 20480, "eight workgroups per CU");
 #endif
-  if constexpr (!JOINT) { if (threadIdx.x == 0 && !(sched.no_wpp & KVZ_SCHED_MODEL_TABLE)) m = model; }
+  if constexpr (!JOINT && !CTUQP) { if (threadIdx.x == 0 && !(sched.no_wpp & KVZ_SCHED_MODEL_TABLE)) m = model; }
   int ctus = 0;
   if constexpr (!JOINT) ctus = F.wc * F.hc;
   for (;;) {
@@ -167,7 +177,12 @@ template <bool CABAC, bool S32, bool RDOQ, bool SH = false, bool LISTS = false, 
     KVZ_TRACE(1);  // ticket drawn
     if (threadIdx.x == 0) {
       if constexpr (JOINT) m = *picture_model(models, frame);
-      else if (sched.no_wpp & KVZ_SCHED_MODEL_TABLE) m = *picture_model(*reinterpret_cast<const CtuModelTable *>(sched.ticket + KVZ_SCHED_TABLE_AT), frame);  // no lane reads m between the barrier above and the one below; the table is constant during the launch
+      else if constexpr (CTUQP) {
+        const CtuModelTable table = *reinterpret_cast<const CtuModelTable *>(sched.ticket + KVZ_SCHED_TABLE_AT);
+        const CtuMapTable map = *reinterpret_cast<const CtuMapTable *>(sched.ticket + KVZ_SCHED_CTU_MAP_AT);
+        m = table.models[map.model_of_ctu[(long)frame * ctus + y * F.wc + x]];
+        m.ctx_init = picture_model(table, frame)->ctx_init;
+      } else if (sched.no_wpp & KVZ_SCHED_MODEL_TABLE) m = *picture_model(*reinterpret_cast<const CtuModelTable *>(sched.ticket + KVZ_SCHED_TABLE_AT), frame);  // no lane reads m between the barrier above and the one below; the table is constant during the launch
       unsigned *done = done_flags + (long)frame * ctus;
       // a hand-off that timed out anywhere (this launch or an earlier one: the word is sticky until kvz_hip_batch_reset) poisons the pass: from then on
       // tickets are only drained -- no search on stale neighbour data, no further 30-second waits -- and every CTU still publishes its flag
@@ -182,7 +197,7 @@ template <bool CABAC, bool S32, bool RDOQ, bool SH = false, bool LISTS = false, 
     KVZ_TRACE(2);  // neighbours there
     const bool run_it = shared.best_mode != 0;  // uniform.  (run() first writes the field behind several barriers of its own: no lane can still be reading it here)
     if (run_it) {
-      CtuProgramT<CABAC, S32, RDOQ, SH, LISTS> p;
+      CtuProgramT<CABAC, S32, RDOQ, SH, LISTS, CTUQP> p;
       p.m = &m; p.tb = tb; p.F = F; p.s = &shared;
       if constexpr (LISTS) {  // the picture's two factor rows, as scalars (the table is constant during the launch)
         const CtuListTable lt = *reinterpret_cast<const CtuListTable *>(sched.ticket + KVZ_SCHED_LISTS_AT);
@@ -243,6 +258,18 @@ template <bool CABAC, bool S32> __global__ void __launch_bounds__(KVZ_CTU_THREAD
   ticket_loop<CABAC, S32, false, false, true>(F, model, tb, sched);
 }
 #endif
+// A cost model per CTU (kvz_hip_intra_frames_ctu_models, kvz_ctu_qp_builds.hpp): the first kernel above with the drawn CTU's row fetched through the map, for the two
+// coefficient cost models with and without the 32x32 search, and the program's CTUQP form (kvz_ctu.hpp: the residual contexts go through every CTU).  Instantiations of their own, in translation units of their own (kvz_ctu_qp_tu.hip): every other launch
+// takes the kernels it took.  `model` is not read.
+template <bool CABAC, bool S32> __global__ void __launch_bounds__(KVZ_CTU_THREADS) __attribute__((amdgpu_waves_per_eu(KVZ_CTU_WAVES_PER_EU))) KVZ_CTU_VGPR_ATTR intra_ctu_ticket_kernel_ctuqp(const CtuFrames F, const CtuModel model, const Tables *tb,
+                                                                        const CtuSched sched)
+#if !KVZ_CTU_KERNEL_BODIES
+;
+#else
+{
+  ticket_loop<CABAC, S32, false, false, false, false, true>(F, model, tb, sched);
+}
+#endif
 // Joint launches over the batches of a group (kvz_hip_batch_group_intra_frames): the builds above that a group may ask for -- fast estimate or CABAC coefficient model,
 // with and without the 32x32 search, and the two sign-hiding ones (SH: CABAC is implied) -- with the drawn picture's batch record fetched per ticket.  Instantiations of
 // their own: the kernels above are what they were.
@@ -265,7 +292,7 @@ template <bool CABAC, bool S32, bool SH> __global__ void __launch_bounds__(KVZ_C
 #endif
 #define KVZ_CTU_UNIT_HAS_RDOQ(unit, CABAC, S32, RDOQ, SH, LISTS, JOINT) || ((unit) == KVZ_CTU_KERNEL_TU && (RDOQ))
 __global__ void __launch_bounds__(KVZ_CTU_THREADS) __attribute__((amdgpu_waves_per_eu(KVZ_RDOQ_WAVES_PER_EU, KVZ_RDOQ_WAVES_PER_EU))) intra_ctu_ticket_kernel_rdoq(const CtuFrames F, const CtuModel model, const Tables *tb, const CtuSched sched)
-#if !KVZ_CTU_KERNEL_BODIES || (defined(KVZ_CTU_KERNEL_TU) && !(0 KVZ_CTU_BUILDS(KVZ_CTU_UNIT_HAS_RDOQ)))  // (not a template: its body goes where its build is)
+#if !KVZ_CTU_KERNEL_BODIES || defined(KVZ_CTU_QP_KERNEL_TU) || (defined(KVZ_CTU_KERNEL_TU) && !(0 KVZ_CTU_BUILDS(KVZ_CTU_UNIT_HAS_RDOQ)))  // (not a template: its body goes where its build is)
 ;
 #else
 {

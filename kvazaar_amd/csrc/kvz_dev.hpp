@@ -859,6 +859,15 @@ __device__ __forceinline__ void deblock_luma_lines_pk(dev_pk16 P[2][8], int beta
 }
 // Luma.  VERTICAL: part (x = 8 * x8, y = 4 * y4): 4 rows of the 8 samples x - 4 .. x + 3 (one 8-byte access per row, 4-byte
 // aligned); !VERTICAL: part (x = 4 * x4, y = 8 * y8): the 8 rows y - 4 .. y + 3 of 4 samples (one dword per row).
+// CUQP (kvz_hip_batch_loop_filters_ctu_models): cu_qp is the plane of CU QPs of the pictures (kvz_cu_qp.hpp), a byte per 8x8 unit, and an edge part is filtered at
+// (QpP + QpQ + 1) >> 1 of the units on its two sides (filter.c:275-295 get_qp_y_pred; (x, y): the part's first luma sample on the q side)
+__device__ __forceinline__ int deblock_edge_qp(const DeblockGeom &g, const u8 *cu_qp, long frame, int x, int y, bool vertical)
+{
+  const int w8 = g.W >> 3;
+  const u8 *plane = cu_qp + frame * (long)w8 * (g.H >> 3);
+  const int qp_q = plane[(long)(y >> 3) * w8 + (x >> 3)], qp_p = vertical ? plane[(long)(y >> 3) * w8 + ((x - 1) >> 3)] : plane[(long)((y - 1) >> 3) * w8 + (x >> 3)];
+  return (qp_p + qp_q + 1) >> 1;
+}
 template <bool VERTICAL> __global__ void __launch_bounds__(256) dev_deblock_luma_kernel(u8 *frames, const DeblockGeom g, const long parts)
 {
   const long p = (long)blockIdx.x * 256 + threadIdx.x;
@@ -914,6 +923,54 @@ template <bool VERTICAL> __global__ void __launch_bounds__(256) dev_deblock_luma
       *reinterpret_cast<u32 *>(Y + (long)(y - 4 + k) * g.W + x) = __builtin_amdgcn_perm(__builtin_bit_cast(u32, P[1][k]), __builtin_bit_cast(u32, P[0][k]), 0x06040200u);
   }
 }
+// ... of all-intra pictures with a QP per CU: the kernel above with the thresholds of the part's own edge QP, taken behind the edge test.  A kernel of its own with a
+// body of its own -- moving the body above into a function that both instantiate made the compiler schedule the existing kernels differently, and those stay what they were.
+template <bool VERTICAL> __global__ void __launch_bounds__(256) dev_deblock_luma_kernel_cuqp(u8 *frames, const DeblockGeom g, const long parts, const u8 *cu_qp)
+{
+  const long p = (long)blockIdx.x * 256 + threadIdx.x;
+  if (p >= parts) return;
+  const int nx = VERTICAL ? g.W >> 3 : g.W >> 2, ny = VERTICAL ? g.H >> 2 : g.H >> 3;
+  const long frame = p / ((long)nx * ny);
+  const int r = (int)(p % ((long)nx * ny)), ix = r % nx, iy = r / nx;
+  const int x = VERTICAL ? 8 * ix : 4 * ix, y = VERTICAL ? 4 * iy : 8 * iy;
+  if ((VERTICAL ? x : y) == 0) return;
+  if (!deblock_edge_on(g, frame, x, y, VERTICAL)) return;
+  const DeblockThresholds thr = deblock_thresholds(deblock_edge_qp(g, cu_qp, frame, x, y, VERTICAL), g.beta_off, g.tc_off);
+  u8 *Y = frames + frame * g.frame_bytes;
+  dev_pk16 P[2][8];
+  if (VERTICAL) {
+    u32 lo[4], hi[4];
+    for (int i = 0; i < 4; i++) {
+      const u32 *row = reinterpret_cast<const u32 *>(Y + (long)(y + i) * g.W + x - 4);
+      lo[i] = row[0]; hi[i] = row[1];
+    }
+    for (int p = 0; p < 2; p++)
+      for (int k = 0; k < 4; k++) {  // byte k of line 2 p -> low half, of line 2 p + 1 -> high half
+        const u32 sel = 0x0c000c00u | (u32)k | ((u32)(4 + k) << 16);
+        P[p][k] = __builtin_bit_cast(dev_pk16, __builtin_amdgcn_perm(lo[2 * p + 1], lo[2 * p], sel));
+        P[p][4 + k] = __builtin_bit_cast(dev_pk16, __builtin_amdgcn_perm(hi[2 * p + 1], hi[2 * p], sel));
+      }
+  } else {
+    for (int k = 0; k < 8; k++) {
+      const u32 v = *reinterpret_cast<const u32 *>(Y + (long)(y - 4 + k) * g.W + x);
+      P[0][k] = __builtin_bit_cast(dev_pk16, __builtin_amdgcn_perm(v, v, 0x0c010c00u));
+      P[1][k] = __builtin_bit_cast(dev_pk16, __builtin_amdgcn_perm(v, v, 0x0c030c02u));
+    }
+  }
+  deblock_luma_lines_pk(P, thr.beta, thr.tc);
+  if (VERTICAL) {
+    for (int p = 0; p < 2; p++) {
+      const u32 a01 = __builtin_bit_cast(u32, P[p][0]) | (__builtin_bit_cast(u32, P[p][1]) << 8), a23 = __builtin_bit_cast(u32, P[p][2]) | (__builtin_bit_cast(u32, P[p][3]) << 8);
+      const u32 a45 = __builtin_bit_cast(u32, P[p][4]) | (__builtin_bit_cast(u32, P[p][5]) << 8), a67 = __builtin_bit_cast(u32, P[p][6]) | (__builtin_bit_cast(u32, P[p][7]) << 8);
+      u32 *r0 = reinterpret_cast<u32 *>(Y + (long)(y + 2 * p) * g.W + x - 4), *r1 = reinterpret_cast<u32 *>(Y + (long)(y + 2 * p + 1) * g.W + x - 4);
+      r0[0] = __builtin_amdgcn_perm(a23, a01, 0x05040100u); r0[1] = __builtin_amdgcn_perm(a67, a45, 0x05040100u);
+      r1[0] = __builtin_amdgcn_perm(a23, a01, 0x07060302u); r1[1] = __builtin_amdgcn_perm(a67, a45, 0x07060302u);
+    }
+  } else {
+    for (int k = 1; k < 7; k++)
+      *reinterpret_cast<u32 *>(Y + (long)(y - 4 + k) * g.W + x) = __builtin_amdgcn_perm(__builtin_bit_cast(u32, P[1][k]), __builtin_bit_cast(u32, P[0][k]), 0x06040200u);
+  }
+}
 // Chroma (filter.c:567-632, 170-190): edges on the 8x8 chroma grid, 4 samples per part, both planes (part index carries the plane)
 template <bool VERTICAL> __global__ void __launch_bounds__(256) dev_deblock_chroma_kernel(u8 *frames, const DeblockGeom g, const long parts)
 {
@@ -940,10 +997,34 @@ template <bool VERTICAL> __global__ void __launch_bounds__(256) dev_deblock_chro
     s[0] = (u8)iclip(0, 255, m4 - delta);
   }
 }
+// ... of all-intra pictures with a QP per CU (a kernel of its own, as for luma): the chroma tc of the edge's luma QP through the chroma table (filter.c:588-592)
+template <bool VERTICAL> __global__ void __launch_bounds__(256) dev_deblock_chroma_kernel_cuqp(u8 *frames, const DeblockGeom g, const long parts, const u8 *cu_qp)
+{
+  const long p = (long)blockIdx.x * 256 + threadIdx.x;
+  if (p >= parts) return;
+  const int cw = g.W >> 1, ch = g.H >> 1;
+  const int nx = VERTICAL ? (cw + 7) >> 3 : cw >> 2, ny = VERTICAL ? ch >> 2 : (ch + 7) >> 3;  // same counts as deblock_frames_on
+  const long per_frame = 2L * nx * ny, frame = p / per_frame;
+  const int r = (int)(p % per_frame), plane = r / (nx * ny), q = r % (nx * ny), ix = q % nx, iy = q / nx;
+  const int xc = VERTICAL ? 8 * ix : 4 * ix, yc = VERTICAL ? 4 * iy : 8 * iy;
+  if ((VERTICAL ? xc : yc) == 0) return;
+  if (!deblock_edge_on(g, frame, 2 * xc, 2 * yc, VERTICAL)) return;
+  u8 *P = frames + frame * g.frame_bytes + (long)g.W * g.H + (long)plane * cw * ch;
+  const int across = VERTICAL ? 1 : cw, along = VERTICAL ? cw : 1;
+  const int tc_c = deblock_thresholds(deblock_edge_qp(g, cu_qp, frame, 2 * xc, 2 * yc, VERTICAL), g.beta_off, g.tc_off).tc_c;
+  for (int i = 0; i < 4; i++) {
+    u8 *s = P + (long)yc * cw + xc + i * along;
+    const int m2 = s[-2 * across], m3 = s[-across], m4 = s[0], m5 = s[across];
+    const int delta = iclip(-tc_c, tc_c, (((m4 - m3) * 4) + m2 - m5 + 4) >> 3);
+    s[-across] = (u8)iclip(0, 255, m3 + delta);
+    s[0] = (u8)iclip(0, 255, m4 - delta);
+  }
+}
 
 // passes: 1 = the vertical edges, 2 = the horizontal edges, 3 = both (in that order)
 inline void deblock_frames_on(hipStream_t stream, u8 *frames, int width, int height, int n_frames, const u8 *cu_depth, int qp, int beta_off, int tc_off, int passes = 3,
-                              const kvz_hip_cu_dbk *info = nullptr, int slice_b = 0, const int32_t *qp_of_picture = nullptr /* device: a QP per picture instead of `qp` */)
+                              const kvz_hip_cu_dbk *info = nullptr, int slice_b = 0, const int32_t *qp_of_picture = nullptr /* device: a QP per picture instead of `qp` */,
+                              const u8 *cu_qp = nullptr /* device: a QP per 8x8 unit instead of either (all-intra pictures: the CUQP kernels) */)
 {
   if (n_frames <= 0) return;
   DeblockGeom g;
@@ -956,6 +1037,14 @@ inline void deblock_frames_on(hipStream_t stream, u8 *frames, int width, int hei
   auto grid = [](long n) { return dim3((unsigned)((n + 255) / 256)); };
   const long lv = (long)n_frames * (width >> 3) * (height >> 2), lh = (long)n_frames * (width >> 2) * (height >> 3);
   const long cv = 2L * n_frames * ((cw + 7) >> 3) * (ch >> 2), chh = 2L * n_frames * (cw >> 2) * ((ch + 7) >> 3);
+  if (cu_qp) {
+    if (lv && (passes & 1)) hipLaunchKernelGGL(dev_deblock_luma_kernel_cuqp<true>, grid(lv), dim3(256), 0, stream, frames, g, lv, cu_qp);
+    if (cv && (passes & 1)) hipLaunchKernelGGL(dev_deblock_chroma_kernel_cuqp<true>, grid(cv), dim3(256), 0, stream, frames, g, cv, cu_qp);
+    if (lh && (passes & 2)) hipLaunchKernelGGL(dev_deblock_luma_kernel_cuqp<false>, grid(lh), dim3(256), 0, stream, frames, g, lh, cu_qp);
+    if (chh && (passes & 2)) hipLaunchKernelGGL(dev_deblock_chroma_kernel_cuqp<false>, grid(chh), dim3(256), 0, stream, frames, g, chh, cu_qp);
+    KVZ_HIP_CHECK(hipGetLastError());
+    return;
+  }
   if (lv && (passes & 1)) hipLaunchKernelGGL(dev_deblock_luma_kernel<true>, grid(lv), dim3(256), 0, stream, frames, g, lv);
   if (cv && (passes & 1)) hipLaunchKernelGGL(dev_deblock_chroma_kernel<true>, grid(cv), dim3(256), 0, stream, frames, g, cv);
   if (lh && (passes & 2)) hipLaunchKernelGGL(dev_deblock_luma_kernel<false>, grid(lh), dim3(256), 0, stream, frames, g, lh);
@@ -1155,6 +1244,17 @@ __global__ void __launch_bounds__(64) dev_sao_chain_kernel(const SaoStats *stats
   }
   sao_chain_picture(fbits, tb->ctx_next[0], tb->ctx_next[1], lambda, (u8)init_merge, (u8)init_type, no_wpp, g.wl, g.hl, stats + base * 3, cand + base * 3, recs + base * 3,
                     merge + base);
+}
+// ... with a cost model per CTU (kvz_hip_batch_loop_filters_ctu_models): every LCU under its own lambda, the two contexts from the picture's slice model
+__global__ void __launch_bounds__(64) dev_sao_chain_kernel_ctu(const SaoStats *stats, const SaoCand *cand, const SaoGeom g, const int n_frames, const float *fbits, const Tables *tb,
+                                                               const int no_wpp, SaoRec *recs, u8 *merge, const CtuModelTable pm, const double *lambda_of_ctu)
+{
+  const int f = blockIdx.x * 64 + threadIdx.x;
+  if (f >= n_frames) return;
+  const long base = (long)f * g.wl * g.hl;
+  const CtuModel *m = picture_model(pm, f);
+  sao_chain_picture(fbits, tb->ctx_next[0], tb->ctx_next[1], m->lambda, m->ctx_init[KVZ_HIP_CX_SAO_MERGE], m->ctx_init[KVZ_HIP_CX_SAO_TYPE], no_wpp, g.wl, g.hl, stats + base * 3, cand + base * 3,
+                    recs + base * 3, merge + base, lambda_of_ctu + base);
 }
 
 }  // namespace kvz
@@ -2008,13 +2108,16 @@ void kvz_hip_batch_deblock(kvz_hip_batch *b, int qp, int beta_offset_div2, int t
 }
 
 // kvz_hip_batch_loop_filters (v == nullptr: `model` for every picture) and kvz_hip_batch_loop_filters_models (`model` = the table's first: price table and no_wpp)
-static void kvz_batch_loop_filters_queue(kvz_hip_batch *b, const kvz_hip_intra_cost_model *model, const kvz::ModelTableView *v, int deblock, int beta_offset_div2, int tc_offset_div2, int sao)
+// map != nullptr (kvz_hip_batch_loop_filters_ctu_models, with v): deblocking at the QPs of the batch's plane of CU QPs, the SAO decision under every CTU's own lambda
+static void kvz_batch_loop_filters_queue(kvz_hip_batch *b, const kvz_hip_intra_cost_model *model, const kvz::ModelTableView *v, int deblock, int beta_offset_div2, int tc_offset_div2, int sao,
+                                         const kvz::CtuMapView *map = nullptr)
 {
+  const uint8_t *cu_qp = map ? b->d_cu_qp : nullptr;
   const kvz::CtuFrames &F = b->F;
   const int n = b->n_frames;
   const int32_t *qps = v ? v->qp_of_picture : nullptr;
   if (!sao) {
-    if (deblock) kvz::deblock_frames_on(b->stream, b->d_rec, F.W, F.H, n, b->d_depth, model->qp, beta_offset_div2, tc_offset_div2, 3, nullptr, 0, qps);
+    if (deblock) kvz::deblock_frames_on(b->stream, b->d_rec, F.W, F.H, n, b->d_depth, model->qp, beta_offset_div2, tc_offset_div2, 3, nullptr, 0, qps, cu_qp);
     return;
   }
   const size_t pic_bytes = (size_t)F.frame_px * n, lcus = (size_t)F.wc * F.hc * n;
@@ -2029,13 +2132,15 @@ static void kvz_batch_loop_filters_queue(kvz_hip_batch *b, const kvz_hip_intra_c
   }
   // R = d_rec (kept), V = d_ver, D = d_dbk
   KVZ_HIP_CHECK(hipMemcpyAsync(b->d_ver, b->d_rec, pic_bytes, hipMemcpyDeviceToDevice, b->stream));
-  if (deblock) kvz::deblock_frames_on(b->stream, b->d_ver, F.W, F.H, n, b->d_depth, model->qp, beta_offset_div2, tc_offset_div2, 1, nullptr, 0, qps);
+  if (deblock) kvz::deblock_frames_on(b->stream, b->d_ver, F.W, F.H, n, b->d_depth, model->qp, beta_offset_div2, tc_offset_div2, 1, nullptr, 0, qps, cu_qp);
   KVZ_HIP_CHECK(hipMemcpyAsync(b->d_dbk, b->d_ver, pic_bytes, hipMemcpyDeviceToDevice, b->stream));
-  if (deblock) kvz::deblock_frames_on(b->stream, b->d_dbk, F.W, F.H, n, b->d_depth, model->qp, beta_offset_div2, tc_offset_div2, 2, nullptr, 0, qps);
+  if (deblock) kvz::deblock_frames_on(b->stream, b->d_dbk, F.W, F.H, n, b->d_depth, model->qp, beta_offset_div2, tc_offset_div2, 2, nullptr, 0, qps, cu_qp);
   KVZ_HIP_CHECK(hipMemcpyAsync(b->d_sao_fbits, model->entropy_fbits, 128 * sizeof(float), hipMemcpyHostToDevice, b->stream));
   const kvz::SaoGeom g{ F.W, F.H, F.wc, F.hc, F.frame_px };
   hipLaunchKernelGGL(kvz::dev_sao_stats_kernel, dim3((unsigned)(lcus * 3)), dim3(256), 0, b->stream, b->d_src, b->d_rec, b->d_ver, b->d_dbk, g, (kvz::SaoStats *)b->d_sao_stats, (kvz::SaoCand *)b->d_sao_cand);
-  hipLaunchKernelGGL(kvz::dev_sao_chain_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, b->stream, (const kvz::SaoStats *)b->d_sao_stats, (const kvz::SaoCand *)b->d_sao_cand, g, n, b->d_sao_fbits, kvz::device_tables(),
+  if (map) hipLaunchKernelGGL(kvz::dev_sao_chain_kernel_ctu, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, b->stream, (const kvz::SaoStats *)b->d_sao_stats, (const kvz::SaoCand *)b->d_sao_cand, g, n, b->d_sao_fbits, kvz::device_tables(),
+                              model->no_wpp, b->d_sao_recs, b->d_sao_merge, v->ctu, map->lambda_of_ctu);
+  else hipLaunchKernelGGL(kvz::dev_sao_chain_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, b->stream, (const kvz::SaoStats *)b->d_sao_stats, (const kvz::SaoCand *)b->d_sao_cand, g, n, b->d_sao_fbits, kvz::device_tables(),
                      model->lambda, (int)model->ctx_init[KVZ_HIP_CX_SAO_MERGE], (int)model->ctx_init[KVZ_HIP_CX_SAO_TYPE], model->no_wpp, b->d_sao_recs, b->d_sao_merge, v ? v->ctu : kvz::CtuModelTable());
   // the SAO'd picture becomes the batch's reconstruction (R is not needed any more)
   kvz::launch_sao(b->stream, b->d_dbk, b->d_rec, F.W, F.H, n, b->d_sao_recs, nullptr, nullptr);
@@ -2055,6 +2160,19 @@ int kvz_hip_batch_loop_filters_models(kvz_hip_batch *b, const kvz_hip_picture_mo
   kvz::batch_enter(b);
   const kvz::ModelTableView v = kvz::picture_models_stage(b, pm);
   kvz_batch_loop_filters_queue(b, &pm->models[0], &v, deblock, beta_offset_div2, tc_offset_div2, sao);
+  return 0;
+}
+
+int kvz_hip_batch_loop_filters_ctu_models(kvz_hip_batch *b, const kvz_hip_ctu_models *cm, int deblock, int beta_offset_div2, int tc_offset_div2, int sao)
+{
+  if (!b || !kvz::ctu_models_known(cm, b->n_frames, b->F.wc * b->F.hc, b->sched_ticket != 0, b->n_list_sets > 0, "kvz_hip_batch_loop_filters_ctu_models")) return -1;
+  if (!b->cu_qp_epoch || b->cu_qp_epoch != b->epoch) { fprintf(stderr, "kvz_hip_batch_loop_filters_ctu_models: the batch's last pass was no kvz_hip_intra_frames_ctu_models (the CU QPs come from it)\n"); return -1; }
+  kvz::batch_enter(b);
+  bool same = false;
+  const kvz::CtuMapView map = kvz::ctu_models_stage(b, cm, &same);  // (compares: every CTU's lambda, row and QP)
+  if (!same) { fprintf(stderr, "kvz_hip_batch_loop_filters_ctu_models: this is not the map of the batch's last pass (the CU QPs and the lambdas must belong together)\n"); return -1; }
+  const kvz::ModelTableView v = kvz::picture_models_stage(b, cm->pictures);
+  kvz_batch_loop_filters_queue(b, &cm->pictures->models[0], &v, deblock, beta_offset_div2, tc_offset_div2, sao, &map);
   return 0;
 }
 
@@ -2113,8 +2231,9 @@ namespace kvz {
 // `stream` -- the caller synchronises the stream before it reads `out` -- which needs such a buffer: the next call, on another stream, compacts into the shared one at once.
 inline long entropy_code_pictures(hipStream_t stream, int device, int n, int wc, int hc, int no_wpp, const uint8_t *not_last, const std::function<EntropyJob(int, int)> &job,
                                   uint8_t *out, size_t capacity, uint32_t *substream_bytes, const std::function<void()> &chain_queued = nullptr,
-                                  EntropyScratch::Buf *own_out = nullptr, bool defer = false)
+                                  EntropyScratch::Buf *own_out = nullptr, bool defer = false, const uint32_t *ctu_qp = nullptr)
 {
+  // ctu_qp (device, [n][ctus]; kvz_hip_batch_entropy_code_ctu_models): the CTUs are quantisation groups -- stage 1 runs as the kernel that codes cu_qp_delta from these words
   EntropyScratch &S = entropy_scratch(device);
   std::lock_guard<std::mutex> guard(S.lock);
   if (S.ev_tail_set) KVZ_HIP_CHECK(hipStreamWaitEvent(stream, S.ev_tail, 0));  // the previous call's last kernels (on its own stream) read scratch this call writes
@@ -2149,17 +2268,22 @@ inline long entropy_code_pictures(hipStream_t stream, int device, int n, int wc,
     // WPP: the row contexts (stage 2: one lane per picture, a long chain) need the bins of the first two CTUs of every row only -- those and stage 2 run on a second
     // stream beside the bins of all the other CTUs
     const bool early_rows = !serial_bins && !no_wpp && wc > 2;
-    if (serial_bins) hipLaunchKernelGGL(dev_entropy_bins_kernel, dim3((unsigned)((items + 63) / 64)), dim3(64), 0, stream, J, device_tables(), items);
-    else if (!early_rows) hipLaunchKernelGGL(dev_entropy_bins_phased_kernel, dim3((unsigned)((items + 63) / 64)), dim3(64), 0, stream, J, device_tables(), items, 0);
+    const uint32_t *words = ctu_qp ? ctu_qp + (size_t)f0 * ctus : nullptr;
+    auto bins_part = [&](hipStream_t st, long lanes, int columns) {
+      if (words) hipLaunchKernelGGL(dev_entropy_bins_phased_kernel_cuqp, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, st, J, device_tables(), lanes, columns, words);
+      else hipLaunchKernelGGL(dev_entropy_bins_phased_kernel, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, st, J, device_tables(), lanes, columns);
+    };
+    if (serial_bins && !words) hipLaunchKernelGGL(dev_entropy_bins_kernel, dim3((unsigned)((items + 63) / 64)), dim3(64), 0, stream, J, device_tables(), items);
+    else if (!early_rows) bins_part(stream, items, 0);
     else {
       const long first = (long)nf * hc * 2, rest = items - first;
       if (!S.side) { KVZ_HIP_CHECK(hipStreamCreateWithFlags(&S.side, hipStreamNonBlocking)); KVZ_HIP_CHECK(hipEventCreateWithFlags(&S.ev_first, hipEventDisableTiming)); KVZ_HIP_CHECK(hipEventCreateWithFlags(&S.ev_rows, hipEventDisableTiming)); }
       KVZ_HIP_CHECK(hipEventRecord(S.ev_first, stream));  // (what the caller queued before -- the pass, the loop filters -- comes first on both streams)
       KVZ_HIP_CHECK(hipStreamWaitEvent(S.side, S.ev_first, 0));
-      hipLaunchKernelGGL(dev_entropy_bins_phased_kernel, dim3((unsigned)((first + 63) / 64)), dim3(64), 0, S.side, J, device_tables(), first, 1);
+      bins_part(S.side, first, 1);
       hipLaunchKernelGGL(dev_entropy_row_ctx_kernel<8>, dim3((unsigned)((nf + 7) / 8)), dim3(8), 0, S.side, J, device_tables());
       KVZ_HIP_CHECK(hipEventRecord(S.ev_rows, S.side));
-      hipLaunchKernelGGL(dev_entropy_bins_phased_kernel, dim3((unsigned)((rest + 63) / 64)), dim3(64), 0, stream, J, device_tables(), rest, 2);
+      bins_part(stream, rest, 2);
       KVZ_HIP_CHECK(hipStreamWaitEvent(stream, S.ev_rows, 0));  // the counts of every CTU are read next
     }
     counts.resize((size_t)items); bound_bits.resize((size_t)items);
@@ -2261,8 +2385,9 @@ long kvz_hip_batch_entropy_code_tiles(kvz_hip_batch *b, const kvz_hip_intra_cost
 // The coder of kvz_hip_batch_entropy_code_then (v == nullptr: `model`'s initial states for every picture) and of kvz_hip_batch_entropy_code_then_models (`model` = the
 // table's first: no_wpp, search_nxn).  start_next queues `next`'s pass, once; null when there is none.
 static long kvz_batch_entropy_code_queue(kvz_hip_batch *b, const kvz_hip_intra_cost_model *model, const kvz::ModelTableView *v, int sao, const uint8_t *not_last, uint8_t *out,
-                                         size_t capacity, uint32_t *substream_bytes, const std::function<void()> &start_next)
+                                         size_t capacity, uint32_t *substream_bytes, const std::function<void()> &start_next, const uint32_t *ctu_qp = nullptr)
 {
+  // ctu_qp (kvz_hip_batch_entropy_code_ctu_models, with v): the batch's CTU words -- every CTU codes its cu_qp_delta
   const kvz::CtuFrames &F = b->F;
   const int ctus = F.wc * F.hc;
   if (sao && !b->d_sao_recs) { fprintf(stderr, "kvz_hip_batch_entropy_code: kvz_hip_batch_loop_filters(..., sao = 1) has not run on this batch\n"); return -1; }
@@ -2284,7 +2409,20 @@ static long kvz_batch_entropy_code_queue(kvz_hip_batch *b, const kvz_hip_intra_c
     return J;
   };
   return kvz::entropy_code_pictures(b->stream, b->device, b->n_frames, F.wc, F.hc, model->no_wpp, not_last, job, out, capacity, substream_bytes,
-                                    start_next ? start_next : std::function<void()>(), b->entropy_deferred ? &b->entropy_out : nullptr, b->entropy_deferred != 0);
+                                    start_next ? start_next : std::function<void()>(), b->entropy_deferred ? &b->entropy_out : nullptr, b->entropy_deferred != 0, ctu_qp);
+}
+
+long kvz_hip_batch_entropy_code_ctu_models(kvz_hip_batch *b, const kvz_hip_ctu_models *cm, int sao, const uint8_t *not_last, uint8_t *out, size_t capacity, uint32_t *substream_bytes)
+{
+  if (!b || !kvz::ctu_models_known(cm, b->n_frames, b->F.wc * b->F.hc, b->sched_ticket != 0, b->n_list_sets > 0, "kvz_hip_batch_entropy_code_ctu_models")) return -1;
+  if (!b->cu_qp_epoch || b->cu_qp_epoch != b->epoch) { fprintf(stderr, "kvz_hip_batch_entropy_code_ctu_models: the batch's last pass was no kvz_hip_intra_frames_ctu_models (the coded deltas come from it)\n"); return -1; }
+  if (not_last) { fprintf(stderr, "kvz_hip_batch_entropy_code_ctu_models: tiles are not supported with a model per CTU\n"); return -1; }
+  kvz::batch_enter(b);
+  bool same = false;
+  (void)kvz::ctu_models_stage(b, cm, &same);
+  if (!same) { fprintf(stderr, "kvz_hip_batch_entropy_code_ctu_models: this is not the map of the batch's last pass\n"); return -1; }
+  const kvz::ModelTableView v = kvz::picture_models_stage(b, cm->pictures);
+  return kvz_batch_entropy_code_queue(b, &cm->pictures->models[0], &v, sao, nullptr, out, capacity, substream_bytes, std::function<void()>(), b->d_ctu_qp);
 }
 
 long kvz_hip_batch_entropy_code_then(kvz_hip_batch *b, const kvz_hip_intra_cost_model *model, int sao, const uint8_t *not_last, uint8_t *out, size_t capacity,

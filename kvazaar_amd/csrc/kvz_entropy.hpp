@@ -34,6 +34,9 @@ namespace kvz {
 // cu_mvd_model[2], mvp_idx_model[2], inter_dir[5], cu_qt_root_cbf_model)
 enum { KVZ_EB_CX_SKIP = 150, KVZ_EB_CX_MERGE_FLAG = 153, KVZ_EB_CX_MERGE_IDX = 154, KVZ_EB_CX_PRED_MODE = 155, KVZ_EB_CX_MVD = 156, KVZ_EB_CX_MVP_IDX = 158,
        KVZ_EB_CX_INTER_DIR = 160, KVZ_EB_CX_ROOT_CBF = 165, KVZ_EB_CX_REF_IDX = 166 /* 2: ref_idx_l0 of P pictures with reference lists */ };
+// I pictures under a cost model per CTU (kvz_hip_batch_entropy_code_ctu_models): cu_qp_delta_abs[2] (cabac.h), where an I picture has no inter syntax.  Their initial
+// states are not part of kvz_hip_intra_cost_model: the coder's host side derives them from init value 154 at the slice QP into these two bytes of every row
+enum { KVZ_EB_CX_QP_DELTA = 150 };
 
 struct EntropyJob {
   int W, H, wc, hc, n_frames, no_wpp;
@@ -164,12 +167,35 @@ struct CoeffBinsOp {
   }
 };
 
-struct EntropyCtu {  // one CTU of one picture
+// CUQP (kvz_hip_batch_entropy_code_ctu_models): the CTU is a quantisation group with a QP of its own -- qp_word is its word of the CU-QP step (kvz_cu_qp.hpp: pred | Q << 8
+// | ...), and the first transform unit with a coded block flag carries cu_qp_delta = Q - pred (qp_delta below).  The other instantiation has none of it.
+template <bool CUQP> struct EntropyCtuT {  // one CTU of one picture
   const EntropyJob &J;
   const Tables *tb;
   const u8 *depth, *mode, *part, *mode4;
   const i16 *ctu;
   int w8, w4;
+  u32 qp_word = 0;
+  mutable bool qp_delta_coded = false;  // must_code_qp_delta, the other way round (encode_coding_tree.c:282-305)
+  // cu_qp_delta_abs -- prefix: truncated unary, cMax 5, the first bin on context 0 and the others on context 1 (kvz_cabac_write_unary_max_symbol with offset 1); suffix:
+  // EG0 of |d| - 5 in bypass bins (kvz_cabac_write_ep_ex_golomb) -- and cu_qp_delta_sign_flag when d != 0
+  template <class S> KVZ_DEV void qp_delta(S &s) const
+  {
+    if (qp_delta_coded) return;
+    qp_delta_coded = true;
+    const int d = (int)((qp_word >> 8) & 0xff) - (int)(qp_word & 0xff), a = iabs(d), prefix = a < 5 ? a : 5;
+    s.ctx(KVZ_EB_CX_QP_DELTA, prefix != 0);
+    for (int k = 1; k < prefix; k++) s.ctx(KVZ_EB_CX_QP_DELTA + 1, 1);
+    if (prefix != 0 && prefix < 5) s.ctx(KVZ_EB_CX_QP_DELTA + 1, 0);
+    if (a >= 5) {
+      u32 symbol = (u32)(a - 5), count = 0, bins = 0;
+      int num_bins = 0;
+      while (symbol >= (1u << count)) { bins = 2 * bins + 1; ++num_bins; symbol -= 1u << count; ++count; }
+      bins = 2 * bins; ++num_bins;
+      s.ep((bins << count) | symbol, num_bins + (int)count);
+    }
+    if (d != 0) s.ep(d < 0 ? 1 : 0, 1);
+  }
   KVZ_DEV int mode_at(int x, int y) const
   {
     if (part && part[(y >> 3) * w8 + (x >> 3)]) return mode4[(y >> 2) * w4 + (x >> 2)];
@@ -203,7 +229,10 @@ struct EntropyCtu {  // one CTU of one picture
     if (depth > 0 && !nxn) {  // one transform block
       const bool cb_y = cbf(0, xl, yl, depth);
       s.ctx(KVZ_HIP_CX_CBF_LUMA + 1, cb_y);
-      if (cb_y | cu_u | cu_v) transform_unit(s, x, y, depth, cb_y, cu_u, cu_v);
+      if (cb_y | cu_u | cu_v) {
+        if constexpr (CUQP) qp_delta(s);
+        transform_unit(s, x, y, depth, cb_y, cu_u, cu_v);
+      }
       return;
     }
     const int o = 64 >> (depth + 1);
@@ -218,7 +247,10 @@ struct EntropyCtu {  // one CTU of one picture
       }
       const bool cb_y = cbf(0, qx & 63, qy & 63, d);
       s.ctx(KVZ_HIP_CX_CBF_LUMA, cb_y);
-      if (cb_y | cb_u | cb_v) transform_unit(s, qx, qy, d, cb_y, cb_u, cb_v);
+      if (cb_y | cb_u | cb_v) {
+        if constexpr (CUQP) qp_delta(s);
+        transform_unit(s, qx, qy, d, cb_y, cb_u, cb_v);
+      }
     }
   }
   // the leaf of kvz_encode_coding_tree: part_mode, encode_intra_coding_unit (encode_coding_tree.c:467-652), the transform tree
@@ -316,6 +348,7 @@ struct EntropyCtu {  // one CTU of one picture
     }
   }
 };
+using EntropyCtu = EntropyCtuT<false>;
 
 // ---- B pictures: kvz_encode_coding_tree with the inter syntax, from the frame-level CU records of the inter CTU pass (kvz_hip_dev_inter_ctu_pass) ----
 // One reference picture per list, 2Nx2N CUs, max_merge 5 (BASELINE config 4's presets).  What the records do not hold are the MV predictors the MVDs are coded against:
@@ -619,7 +652,8 @@ struct EntropyBinsLds {  // per workgroup of 64 lanes: the lanes' queues and tre
   u16 stack[16][64];
 };
 struct LaneStack { u16 *p; int stride; KVZ_DEV u16 &operator[](int i) { return p[i * stride]; } };
-KVZ_DEV void entropy_ctu_bins_phased(const EntropyJob &J, const Tables *tb, long item, bool live, u32 *queue, u16 *stack_mem, int stride)
+// CUQP: I pictures whose CTUs have QPs of their own; ctu_qp [frames * ctus]: the words of the CU-QP step (EntropyCtuT)
+template <bool CUQP = false> KVZ_DEV void entropy_ctu_bins_phased(const EntropyJob &J, const Tables *tb, long item, bool live, u32 *queue, u16 *stack_mem, int stride, const u32 *ctu_qp = nullptr)
 {
   const int ctus = J.wc * J.hc;
   if (!live) item = 0;  // (a lane past the end keeps the wavefront's votes company and writes nothing)
@@ -639,8 +673,10 @@ KVZ_DEV void entropy_ctu_bins_phased(const EntropyJob &J, const Tables *tb, long
   }
   const i16 *ctu = J.coeff + item * KVZ_HIP_CTU_COEFFS;
   const EntropyCtuB cb{ J, tb, J.cu ? J.cu + f * cells4 : nullptr, J.cu ? entropy_ref_cu(J, f, cells4) : nullptr, ctu, J.W >> 2, lx * 64, ly * 64, J.cu ? entropy_picture_poc(J, f) : 0, J.cu && J.refs ? J.refs + f : nullptr };
-  const EntropyCtu ci{ J, tb, J.cu ? nullptr : J.depth + f * cells8, J.cu ? nullptr : J.mode + f * cells8, J.part ? J.part + f * cells8 : nullptr,
-                       J.mode4 ? J.mode4 + f * cells4 : nullptr, ctu, J.W >> 3, J.W >> 2 };
+  u32 qp_word = 0;
+  if constexpr (CUQP) qp_word = ctu_qp[item];
+  const EntropyCtuT<CUQP> ci{ J, tb, J.cu ? nullptr : J.depth + f * cells8, J.cu ? nullptr : J.mode + f * cells8, J.part ? J.part + f * cells8 : nullptr,
+                              J.mode4 ? J.mode4 + f * cells4 : nullptr, ctu, J.W >> 3, J.W >> 2, qp_word };
   LaneStack stack{ stack_mem, stride };
   int sp = 0;
   if (live) stack[sp++] = 0;
@@ -965,6 +1001,20 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KVZ_ENT
     item = row * J.wc + (columns == 1 ? 0 : 2) + (item - row * per_row);
   }
   entropy_ctu_bins_phased(J, tb, item, live, &L.q[0][threadIdx.x], &L.stack[0][threadIdx.x], 64);
+}
+// ... of I pictures whose CTUs have QPs of their own (kvz_hip_batch_entropy_code_ctu_models): the kernel above with the cu_qp_delta syntax, a kernel of its own
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KVZ_ENTROPY_BINS_WAVES, KVZ_ENTROPY_BINS_WAVES))) dev_entropy_bins_phased_kernel_cuqp(const EntropyJob J, const Tables *tb, long total, int columns,
+                                                                                                                                                        const u32 *ctu_qp)
+{
+  __shared__ EntropyBinsLds L;
+  long item = (long)blockIdx.x * 64 + threadIdx.x;
+  const bool live = item < total;
+  if (columns != 0 && live) {
+    const int per_row = columns == 1 ? 2 : J.wc - 2;
+    const long row = item / per_row;  // picture-major: f * hc + ly
+    item = row * J.wc + (columns == 1 ? 0 : 2) + (item - row * per_row);
+  }
+  entropy_ctu_bins_phased<true>(J, tb, item, live, &L.q[0][threadIdx.x], &L.stack[0][threadIdx.x], 64, ctu_qp);
 }
 // Stage 2 is one long dependent chain per picture (its rows' first two CTUs, row after row): few lanes per workgroup spread the pictures over the chip
 template <int LANES> struct EntropyLds {

@@ -217,14 +217,16 @@ KVZ_DEV void sao_code_bin(const u8 *next_mps, const u8 *next_lps, u8 &st, int bi
 
 // One picture, raster order (the result does not depend on the order LCUs are visited in, only on the context hand-off rule).
 // recs: [lcu][3] packed records (out), merge: [lcu] 0 none / 1 left / 2 up (out).
+// lambda_of_lcu != nullptr (a cost model per CTU, kvz_hip_ctu_models): every LCU is decided under its own lambda (sao.c reads state->lambda of the LCU) instead of `lambda`.
 KVZ_DEV void sao_chain_picture(const float *fb, const u8 *next_mps, const u8 *next_lps, double lambda, u8 init_merge, u8 init_type, int no_wpp, int wl, int hl,
-                               const SaoStats *st /* [lcu][3] */, const SaoCand *cand /* [lcu][3] */, SaoRec *recs, u8 *merge)
+                               const SaoStats *st /* [lcu][3] */, const SaoCand *cand /* [lcu][3] */, SaoRec *recs, u8 *merge, const double *lambda_of_lcu = nullptr)
 {
   SaoCabac cab = { init_merge, init_type }, next_row = cab;
   for (int ly = 0; ly < hl; ly++) {
     if (!no_wpp) { if (ly == 0) { cab.merge = init_merge; cab.type = init_type; } else cab = next_row; }
     for (int lx = 0; lx < wl; lx++) {
       const int i = ly * wl + lx;
+      if (lambda_of_lcu) lambda = lambda_of_lcu[i];
       const SaoRec *top = ly ? &recs[(i - wl) * 3] : nullptr, *left = lx ? &recs[(i - 1) * 3] : nullptr;
       i32 mc_l[3] = { 0x7fffffff, 0, 0 }, mc_c[3] = { 0x7fffffff, 0, 0 };
       SaoRec out[3];
