@@ -237,6 +237,22 @@ int kvz_hip_dev_inter_slots_per_cu(void);
  * a thread that never filtered gets -1. */
 long kvz_hip_dev_entropy_code_inter(const kvz_hip_cu_info *cu, const kvz_hip_cu_info *ref_cu, const int16_t *coeff, int width, int height, int n_pictures,
                                     const kvz_hip_inter_params *params, uint8_t *out, size_t capacity, uint32_t *substream_bytes);
+/* Its twin for I pictures: kvz_hip_batch_entropy_code_tiles' coder (kvz_hip_batch.h; the same kernels) on results the CALLER holds on the device instead of a batch's own
+ * buffers -- a pass of the caller's own, or decisions constructed to reach a branch of the syntax (tests/entropy_atlas.py).
+ *   cu_depth, cu_mode   DEVICE [n_pictures][(height/8) * (width/8)]: CU depth and luma mode per 8x8 unit, every unit of a CU carrying the CU's
+ *   cu_part, cu_mode4   DEVICE [n_pictures][(height/8) * (width/8)] NxN flags and [n_pictures][(height/4) * (width/4)] PU modes; read only with model->search_nxn, else
+ *                       they may be NULL
+ *   coeff               DEVICE [n_pictures][CTU][KVZ_HIP_CTU_COEFFS]
+ *   model               HOST: ctx_init, no_wpp, search_nxn and signhide are read
+ *   not_last            HOST [n_pictures] or NULL, as kvz_hip_batch_entropy_code_tiles
+ *   luma, chroma, merge HOST [n_pictures][CTU] SAO decisions (merge 0 none / 1 left / 2 up), or all three NULL: no SAO syntax
+ *   out, capacity, substream_bytes   HOST, exactly as kvz_hip_batch_entropy_code_tiles returns them
+ * Runs on the calling thread's stream of the current device and returns when the bytes are in `out`.  Returns the total size; -1 with a message on stderr before anything
+ * is queued for a NULL required pointer, a width or height that is not a positive multiple of 8, a model whose struct_size is not this library's, search_nxn without
+ * the two partition maps, or SAO arrays of which some are NULL; -1 as well when `capacity` is too small. */
+long kvz_hip_dev_entropy_code_intra(const uint8_t *cu_depth, const uint8_t *cu_mode, const uint8_t *cu_part, const uint8_t *cu_mode4, const int16_t *coeff, int width, int height,
+                                    int n_pictures, const kvz_hip_intra_cost_model *model, const uint8_t *not_last, const kvz_hip_sao_params *luma,
+                                    const kvz_hip_sao_params *chroma, const uint8_t *merge, uint8_t *out, size_t capacity, uint32_t *substream_bytes);
 /* Pictures with a QP and a POC of their own in one launch (kvz_hip_inter_pictures, kvz_hip_types.h): sequences at different --qp, or at different positions of the
  * low-delay GOP (whose layer moves the picture QP on every picture), fill one launch instead of one small launch per (QP, POC).  The three entry points mirror
  * kvz_hip_dev_inter_ctu_pass_tiles, kvz_hip_dev_loop_filters_inter and kvz_hip_dev_entropy_code_inter, which stay what they are:

@@ -1559,6 +1559,30 @@ void kvz_hip_dev_deblock_frames_inter(uint8_t *frames, int width, int height, in
   kvz::deblock_frames_on(be().stream, frames, width, height, n_frames, nullptr, qp, beta_offset_div2, tc_offset_div2, 3, info, slice_is_b);
 }
 
+namespace kvz {
+// kvz_hip_sao_params <-> the packed records (kvz_sao.hpp SaoRec), stated once for every host-side conversion: plane 0 is the luma structure, planes 1 and 2 are the
+// chroma structure's slots 0 and 1 (band_position[slot], offsets[5 * slot ..]); type and eo_class are the structure's for both of its slots
+inline SaoRec sao_rec_pack(const kvz_hip_sao_params &p, int slot)
+{
+  SaoRec r = (SaoRec)(p.type & 0xff) | ((SaoRec)(p.eo_class & 0xff) << 8) | ((SaoRec)(p.band_position[slot] & 0xff) << 16);
+  for (int k = 0; k < 5; k++) r |= (SaoRec)(u8)(int8_t)p.offsets[5 * slot + k] << (24 + 8 * k);
+  return r;
+}
+inline void sao_rec_unpack(SaoRec r, kvz_hip_sao_params *o, int slot)
+{
+  if (slot == 0) { memset(o, 0, sizeof *o); o->bitdepth = 8; o->type = (int)(r & 0xff); o->eo_class = (int)((r >> 8) & 0xff); }
+  o->band_position[slot] = (int)((r >> 16) & 0xff);
+  for (int k = 0; k < 5; k++) o->offsets[5 * slot + k] = (int)(int8_t)(r >> (24 + 8 * k));
+}
+// ... of a picture's LCUs: recs [lcus][3]; luma / chroma may be null
+inline void sao_recs_unpack(const SaoRec *recs, size_t lcus, kvz_hip_sao_params *luma, kvz_hip_sao_params *chroma)
+{
+  for (size_t i = 0; i < lcus; i++) {
+    if (luma) sao_rec_unpack(recs[i * 3], &luma[i], 0);
+    if (chroma) { sao_rec_unpack(recs[i * 3 + 1], &chroma[i], 0); sao_rec_unpack(recs[i * 3 + 2], &chroma[i], 1); }
+  }
+}
+}  // namespace kvz
 // The loop filters between two pictures of a device-resident chain with inter prediction: kvz_hip_batch_loop_filters' pipeline (three pictures R / V / D, the
 // statistics kernel, the decision chain, the SAO kernel) with the deblocking edges and strengths taken from kvz_hip_cu_dbk records.
 namespace kvz {
@@ -1713,16 +1737,7 @@ static int kvz_loop_filters_inter_run(const uint8_t *src, uint8_t *rec, int widt
     KVZ_HIP_CHECK(hipMemcpyAsync(recs.data(), sc.recs, lcus * 3 * sizeof(kvz::SaoRec), hipMemcpyDeviceToHost, st));
     if (merge) KVZ_HIP_CHECK(hipMemcpyAsync(merge, sc.merge, lcus, hipMemcpyDeviceToHost, st));
     KVZ_HIP_CHECK(hipStreamSynchronize(st));
-    for (size_t i = 0; i < lcus; i++) {
-      auto unpack = [&](kvz_hip_sao_params *o, int plane, int slot) {
-        const kvz::SaoRec r = recs[i * 3 + plane];
-        if (slot == 0) { memset(o, 0, sizeof *o); o->bitdepth = 8; o->type = (int)(r & 0xff); o->eo_class = (int)((r >> 8) & 0xff); }
-        o->band_position[slot] = (int)((r >> 16) & 0xff);
-        for (int k = 0; k < 5; k++) o->offsets[5 * slot + k] = (int)(int8_t)(r >> (24 + 8 * k));
-      };
-      if (luma) unpack(&luma[i], 0, 0);
-      if (chroma) { unpack(&chroma[i], 1, 0); unpack(&chroma[i], 2, 1); }
-    }
+    kvz::sao_recs_unpack(recs.data(), lcus, luma, chroma);
   }
   return 0;
 }
@@ -2185,16 +2200,7 @@ int kvz_hip_batch_sao_params(kvz_hip_batch *b, int frame, kvz_hip_sao_params *lu
   KVZ_HIP_CHECK(hipStreamSynchronize(b->stream));
   KVZ_HIP_CHECK(hipMemcpy(recs.data(), b->d_sao_recs + (size_t)frame * lcus * 3, lcus * 3 * sizeof(kvz::SaoRec), hipMemcpyDeviceToHost));
   if (merge) KVZ_HIP_CHECK(hipMemcpy(merge, b->d_sao_merge + (size_t)frame * lcus, lcus, hipMemcpyDeviceToHost));
-  for (size_t i = 0; i < lcus; i++) {
-    auto unpack = [&](kvz_hip_sao_params *o, int plane, int slot) {
-      const kvz::SaoRec r = recs[i * 3 + plane];
-      if (slot == 0) { memset(o, 0, sizeof *o); o->bitdepth = 8; o->type = (int)(r & 0xff); o->eo_class = (int)((r >> 8) & 0xff); }
-      o->band_position[slot] = (int)((r >> 16) & 0xff);
-      for (int k = 0; k < 5; k++) o->offsets[5 * slot + k] = (int)(int8_t)(r >> (24 + 8 * k));
-    };
-    if (luma) unpack(&luma[i], 0, 0);
-    if (chroma) { unpack(&chroma[i], 1, 0); unpack(&chroma[i], 2, 1); }
-  }
+  kvz::sao_recs_unpack(recs.data(), lcus, luma, chroma);
   return kvz::batch_check(b);
 }
 
@@ -2574,6 +2580,51 @@ static long kvz_entropy_code_inter_run(const kvz_hip_cu_info *cu, const kvz_hip_
     return J;
   };
   return kvz::entropy_code_pictures(be().stream, device, n_pictures, wc, hc, params->no_wpp, nullptr, job, out, capacity, substream_bytes);
+}
+
+// ... of I pictures whose results the CALLER put on the device (kvz_hip_dev.h): the I-picture twin of kvz_hip_dev_entropy_code_inter -- kvz_hip_batch_entropy_code's
+// coder and kernels on device pointers instead of a batch's buffers, the SAO decisions from host structures
+long kvz_hip_dev_entropy_code_intra(const uint8_t *cu_depth, const uint8_t *cu_mode, const uint8_t *cu_part, const uint8_t *cu_mode4, const int16_t *coeff, int width, int height,
+                                    int n_pictures, const kvz_hip_intra_cost_model *model, const uint8_t *not_last, const kvz_hip_sao_params *luma,
+                                    const kvz_hip_sao_params *chroma, const uint8_t *merge, uint8_t *out, size_t capacity, uint32_t *substream_bytes)
+{
+  const char *who = "kvz_hip_dev_entropy_code_intra";
+  if (!kvz::cost_model_known(model, who)) return -1;
+  if (!cu_depth || !cu_mode || !coeff || !out || !substream_bytes) { fprintf(stderr, "%s: a required pointer is NULL\n", who); return -1; }
+  if (width <= 0 || height <= 0 || (width & 7) || (height & 7)) { fprintf(stderr, "%s: %d x %d is no picture of positive multiples of 8\n", who, width, height); return -1; }
+  if (model->search_nxn && (!cu_part || !cu_mode4)) { fprintf(stderr, "%s: search_nxn without the NxN partition maps\n", who); return -1; }
+  const bool sao = luma || chroma || merge;
+  if (sao && (!luma || !chroma || !merge)) { fprintf(stderr, "%s: SAO decisions are luma, chroma and merge together, or none of them\n", who); return -1; }
+  if (n_pictures <= 0) return 0;
+  const int wc = (width + 63) >> 6, hc = (height + 63) >> 6, ctus = wc * hc;
+  const long cells8 = (long)(height >> 3) * (width >> 3), cells4 = (long)(height >> 2) * (width >> 2);
+  int device = 0;
+  KVZ_HIP_CHECK(hipGetDevice(&device));
+  kvz::SaoRec *d_recs = nullptr; uint8_t *d_merge = nullptr;
+  if (sao) {
+    const size_t lcus = (size_t)ctus * n_pictures;
+    std::vector<kvz::SaoRec> recs(lcus * 3);
+    for (size_t i = 0; i < lcus; i++) { recs[i * 3] = kvz::sao_rec_pack(luma[i], 0); recs[i * 3 + 1] = kvz::sao_rec_pack(chroma[i], 0); recs[i * 3 + 2] = kvz::sao_rec_pack(chroma[i], 1); }
+    KVZ_HIP_CHECK(hipMalloc((void **)&d_recs, lcus * 3 * sizeof(kvz::SaoRec)));
+    KVZ_HIP_CHECK(hipMalloc((void **)&d_merge, lcus));
+    KVZ_HIP_CHECK(hipMemcpy(d_recs, recs.data(), lcus * 3 * sizeof(kvz::SaoRec), hipMemcpyHostToDevice));
+    KVZ_HIP_CHECK(hipMemcpy(d_merge, merge, lcus, hipMemcpyHostToDevice));
+  }
+  auto job = [&](int f0, int nf) {
+    kvz::EntropyJob J;
+    memset(&J, 0, sizeof J);
+    J.W = width; J.H = height; J.wc = wc; J.hc = hc; J.n_frames = nf; J.no_wpp = model->no_wpp;
+    J.depth = cu_depth + f0 * cells8; J.mode = cu_mode + f0 * cells8;
+    J.part = model->search_nxn ? cu_part + f0 * cells8 : nullptr; J.mode4 = model->search_nxn ? cu_mode4 + f0 * cells4 : nullptr;
+    J.coeff = coeff + (size_t)f0 * ctus * KVZ_HIP_CTU_COEFFS;
+    J.sao = sao ? d_recs + (size_t)f0 * ctus * 3 : nullptr; J.sao_merge = sao ? d_merge + (size_t)f0 * ctus : nullptr;
+    memcpy(J.ctx_init, model->ctx_init, sizeof model->ctx_init < sizeof J.ctx_init ? sizeof model->ctx_init : sizeof J.ctx_init);
+    J.signhide = model->signhide != 0;
+    return J;
+  };
+  const long total = kvz::entropy_code_pictures(be().stream, device, n_pictures, wc, hc, model->no_wpp, not_last, job, out, capacity, substream_bytes);  // (returns with its stream drained)
+  if (sao) { KVZ_HIP_CHECK(hipFree(d_recs)); KVZ_HIP_CHECK(hipFree(d_merge)); }
+  return total;
 }
 
 void kvz_hip_dev_picture_md5(const uint8_t *frames, int width, int height, int n_frames, uint8_t *out)

@@ -51,3 +51,26 @@ class Dev:
     def free(self, *ps):
         for p in ps:
             self.lib.kvz_hip_dev_free(p)
+
+    def entropy_code_intra(self, width, height, model, cu_depth, cu_mode, coeff, cu_part=None, cu_mode4=None, not_last=None, sao=None, capacity=None):
+        """kvz_hip_dev_entropy_code_intra on host arrays: the results of n I pictures back to back (cu_depth / cu_mode / cu_part per 8x8 unit, cu_mode4 per 4x4 unit,
+        coeff 6144 int16 per CTU; n from cu_depth), uploaded here and freed again.  model: a kvz_hip_intra_cost_model (batch.CostModel); not_last: a flag per
+        picture or None; sao: (luma, chroma, merge) -- kvz_hip_sao_params records of every CTU of every picture as bytes or int32 words, merge 0 / 1 / 2 -- or None.
+        -> (bytes of all substreams back to back, sizes as an array [picture][substream])"""
+        f = self.lib.kvz_hip_dev_entropy_code_intra
+        f.restype = C.c_long
+        f.argtypes = [C.c_void_p] * 5 + [C.c_int] * 3 + [C.c_void_p] * 6 + [C.c_size_t, C.c_void_p]
+        n = np.asarray(cu_depth).size // ((width // 8) * (height // 8))
+        host = [None if a is None else np.ascontiguousarray(a) for a in (not_last,) + (tuple(sao) if sao else (None, None, None))]
+        if host[0] is not None:
+            host[0] = host[0].astype(np.uint8)
+        capacity = capacity or n * width * height * 12 + 65536  # dense blocks of 16-bit levels cost 5 bytes per sample and more
+        out, sizes = np.zeros(capacity, np.uint8), np.zeros((n, 1 if model.no_wpp else (height + 63) // 64), np.uint32)
+        dev = [None if a is None else self.put(a) for a in (cu_depth, cu_mode, cu_part, cu_mode4, coeff)]
+        try:
+            total = f(*dev, width, height, n, C.addressof(model), *[None if a is None else a.ctypes.data for a in host], out.ctypes.data, capacity, sizes.ctypes.data)
+        finally:
+            self.free(*[p for p in dev if p is not None])
+        if total < 0:
+            raise RuntimeError(f"kvz_hip_dev_entropy_code_intra failed ({total}; see stderr)")
+        return out[:total].tobytes(), sizes

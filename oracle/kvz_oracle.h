@@ -217,6 +217,12 @@ size_t kvz_oracle_entropy_intra_tile(const kvz_hip_intra_cost_model *m, int widt
                                      const uint8_t *mode4, const int16_t *coeff, const kvz_hip_sao_params *sao_luma, const kvz_hip_sao_params *sao_chroma,
                                      const uint8_t *sao_merge, int not_last, uint8_t *out, size_t capacity, uint32_t *substream_bytes);
 
+/* ... and for a B picture of a low-delay sequence from its CU records (one per 4x4 unit), the reference picture's records (temporal MV predictors, from POC 2 on) and
+ * its levels: what kvz_hip_dev_entropy_code_inter reads, without a search in front.  sao_*: NULL (SAO off) or one record per LCU. */
+size_t kvz_oracle_entropy_b_picture(int qp, int poc, int no_wpp, int width, int height, const kvz_oracle_cu *cu, const kvz_oracle_cu *ref_cu, const int16_t *coeff,
+                                    const kvz_hip_sao_params *sao_luma, const kvz_hip_sao_params *sao_chroma, const uint8_t *sao_merge, uint8_t *out, size_t capacity,
+                                    uint32_t *substream_bytes);
+
 /* the per-call form (strategies-encode.h:49-65): one block's residual syntax as bin records (include/kvz_hip.h kvz_hip_coeff_nxn_bins), and records through the
  * arithmetic coder from given context states (KVZ_HIP_CX_* order; 150 of them) + flush + stop bit + alignment */
 int kvz_oracle_coeff_nxn_bins(const int16_t *coeff, int width, int type, int scan_mode, uint32_t *records, int capacity);

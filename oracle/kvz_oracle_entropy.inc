@@ -140,7 +140,8 @@ static void ec_finish(ecabac_t *c)  /* cabac.c:170-191 kvz_cabac_finish */
   eb_put(c->out, c->low >> 8, 24 - c->bits_left);
 }
 
-/* ---- the residual coder in real mode (encode_coding_tree-generic.c:40-283; sign hiding, transform skip and encryption off) ---- */
+/* ---- the residual coder in real mode (encode_coding_tree-generic.c:40-283; transform skip and encryption off; sign data hiding by `signhide`: a group whose first and
+ * last levels lie four scan positions or more apart leaves out the sign coded last, :199 and :240-247) ---- */
 static void e_last_xy(ecabac_t *c, int lastpos_x, int lastpos_y, int width, int type, int scan)  /* encode_coding_tree.c:63-115 */
 {
   static const uint8_t min_in_group[10] = { 0, 1, 2, 3, 4, 6, 8, 12, 16, 24 };  /* encoderstate.h:393 g_min_in_group */
@@ -173,7 +174,7 @@ static void e_coeff_remain(ecabac_t *c, uint32_t symbol, uint32_t r_param)  /* c
     ec_ep(c, (uint32_t)code_number, (int)length);
   }
 }
-static void e_coeff_nxn(ecabac_t *c, const int16_t *coeff, int width, int type, int scan_mode)
+static void e_coeff_nxn(ecabac_t *c, const int16_t *coeff, int width, int type, int scan_mode, int signhide)
 {
   int log2_size = 2;
   while ((1 << log2_size) < width) log2_size++;
@@ -203,7 +204,8 @@ static void e_coeff_nxn(ecabac_t *c, const int16_t *coeff, int width, int type, 
     const int sub_pos = i << 4, cg_blk_pos = (int)scan_cg[i], cg_pos_y = cg_blk_pos / num_blk_side, cg_pos_x = cg_blk_pos - cg_pos_y * num_blk_side;
     int abs_coeff[16], num_non_zero = 0;
     uint32_t coeff_signs = 0, go_rice = 0;
-    if (scan_pos_sig == scan_pos_last) { abs_coeff[0] = abs(coeff[pos_last]); coeff_signs = coeff[pos_last] < 0; num_non_zero = 1; scan_pos_sig--; }
+    int last_nz_pos_in_cg = -1, first_nz_pos_in_cg = 16;
+    if (scan_pos_sig == scan_pos_last) { abs_coeff[0] = abs(coeff[pos_last]); coeff_signs = coeff[pos_last] < 0; num_non_zero = 1; last_nz_pos_in_cg = first_nz_pos_in_cg = scan_pos_sig; scan_pos_sig--; }
     const int right = cg_pos_x < num_blk_side - 1 && sig_cg[cg_pos_y * num_blk_side + cg_pos_x + 1];
     const int lower = cg_pos_y < num_blk_side - 1 && sig_cg[(cg_pos_y + 1) * num_blk_side + cg_pos_x];
     if (i == scan_cg_last || i == 0) sig_cg[cg_blk_pos] = 1;
@@ -213,7 +215,11 @@ static void e_coeff_nxn(ecabac_t *c, const int16_t *coeff, int width, int type, 
       for (; scan_pos_sig >= sub_pos; scan_pos_sig--) {
         const int blk_pos = (int)scan[scan_pos_sig], pos_y = blk_pos >> log2_size, pos_x = blk_pos - (pos_y << log2_size), sig = coeff[blk_pos] != 0;
         if (scan_pos_sig > sub_pos || i == 0 || num_non_zero) ec_bin(c, base_sig + sig_ctx_inc(pattern, scan_mode, pos_x, pos_y, log2_size, type), sig);
-        if (sig) { abs_coeff[num_non_zero++] = abs(coeff[blk_pos]); coeff_signs = 2 * coeff_signs + (coeff[blk_pos] < 0); }
+        if (sig) {
+          abs_coeff[num_non_zero++] = abs(coeff[blk_pos]); coeff_signs = 2 * coeff_signs + (coeff[blk_pos] < 0);
+          if (last_nz_pos_in_cg == -1) last_nz_pos_in_cg = scan_pos_sig;
+          first_nz_pos_in_cg = scan_pos_sig;
+        }
       }
     } else scan_pos_sig = sub_pos - 1;
     if (num_non_zero > 0) {
@@ -229,7 +235,8 @@ static void e_coeff_nxn(ecabac_t *c, const int16_t *coeff, int width, int type, 
         else if (c1 < 3 && c1 > 0) c1++;
       }
       if (c1 == 0 && first_c2 != -1) ec_bin(c, (type == 0 ? CX_ABS_LUMA : CX_ABS_CHROMA) + ctx_set, abs_coeff[first_c2] > 2);
-      ec_ep(c, coeff_signs, num_non_zero);
+      if (signhide && last_nz_pos_in_cg - first_nz_pos_in_cg >= 4) ec_ep(c, coeff_signs >> 1, num_non_zero - 1);
+      else ec_ep(c, coeff_signs, num_non_zero);
       if (c1 == 0 || num_non_zero > 8) {
         int first_coeff2 = 1;
         for (int idx = 0; idx < num_non_zero; idx++) {
@@ -251,6 +258,7 @@ typedef struct {
   const uint8_t *depth, *mode, *part, *mode4;  /* per 8x8: CU depth, luma mode, NxN flag (or NULL); per 4x4: luma mode of NxN CUs (or NULL) */
   const int16_t *coeff;                          /* KVZ_HIP_CTU_COEFFS per CTU, raster CTU order; inside: Y | U | V, z-order */
   const int16_t *ctu;                            /* the current CTU's */
+  int signhide;                                  /* the picture is coded with sign data hiding (kvz_hip_intra_cost_model::signhide) */
 } epic_t;
 static int e_any(const int16_t *c, int n) { for (int i = 0; i < n; i++) if (c[i]) return 1; return 0; }
 static int e_mode_at(const epic_t *p, int x, int y)
@@ -292,11 +300,11 @@ static void e_transform_tree(ecabac_t *c, const epic_t *p, int x, int y, int dep
   if (!(cb_y | cu_u | cu_v)) return;
   /* encode_transform_unit (:117-190) */
   const int w = 64 >> depth, cw = depth == 4 ? w : w / 2;
-  if (cb_y) e_coeff_nxn(c, p->ctu + zorder(xl, yl), w, 0, scan_order(e_mode_at(p, x, y), depth));
+  if (cb_y) e_coeff_nxn(c, p->ctu + zorder(xl, yl), w, 0, scan_order(e_mode_at(p, x, y), depth), p->signhide);
   if (depth == 4 && (x % 8 == 0 || y % 8 == 0)) return;  /* the 4x4 chroma blocks follow the last luma block, under the first PU's mode */
   const int cscan = scan_order(e_mode_at(p, x & ~7, y & ~7), depth), cxl = (xl & ~7) / 2, cyl = (yl & ~7) / 2;
-  if (cu_u) e_coeff_nxn(c, p->ctu + 4096 + zorder(cxl, cyl), cw, 2, cscan);
-  if (cu_v) e_coeff_nxn(c, p->ctu + 5120 + zorder(cxl, cyl), cw, 2, cscan);
+  if (cu_u) e_coeff_nxn(c, p->ctu + 4096 + zorder(cxl, cyl), cw, 2, cscan, p->signhide);
+  if (cu_v) e_coeff_nxn(c, p->ctu + 5120 + zorder(cxl, cyl), cw, 2, cscan, p->signhide);
 }
 
 static void e_coding_tree(ecabac_t *c, const epic_t *p, int x, int y, int depth)  /* encode_coding_tree.c:745-900, I slice */
@@ -381,8 +389,8 @@ static void e_sao_color(ecabac_t *c, const kvz_hip_sao_params *sao, int color)  
 }
 
 /* (kvz_oracle.h declares both entry points) */
-/* The slice data of one I picture: one substream per CTU row with WPP, one for the picture without.  m: qp, ctx_init (the slice's initial context states) and no_wpp are
- * read.  cu_depth / cu_mode per 8x8, part / mode4 (or NULL) as kvz_hip_batch_download / _download_partitions return them; coeff as kvz_hip_batch_download returns it;
+/* The slice data of one I picture: one substream per CTU row with WPP, one for the picture without.  m: qp, ctx_init (the slice's initial context states), no_wpp and signhide
+ * are read.  cu_depth / cu_mode per 8x8, part / mode4 (or NULL) as kvz_hip_batch_download / _download_partitions return them; coeff as kvz_hip_batch_download returns it;
  * sao_luma / sao_chroma / sao_merge (or NULL when SAO is off): one record per LCU, merge 0 none / 1 left / 2 up.  out receives the substreams back to back,
  * substream_bytes their sizes; returns the total size (the caller checks it against capacity). */
 size_t kvz_oracle_entropy_intra_picture(const kvz_hip_intra_cost_model *m, int width, int height, const uint8_t *cu_depth, const uint8_t *cu_mode, const uint8_t *part,
@@ -398,7 +406,7 @@ size_t kvz_oracle_entropy_intra_tile(const kvz_hip_intra_cost_model *m, int widt
 {
   build_transitions();
   const int wc = (width + 63) / 64, hc = (height + 63) / 64;
-  epic_t p = { width, height, width >> 3, width >> 2, cu_depth, cu_mode, part, mode4, coeff, NULL };
+  epic_t p = { width, height, width >> 3, width >> 2, cu_depth, cu_mode, part, mode4, coeff, NULL, m->signhide != 0 };
   ebits_t bits = { out, capacity, 0, 0, 0, 0, 0 };
   ecabac_t c, next_row;
   memset(&c, 0, sizeof c);
@@ -443,7 +451,7 @@ int kvz_oracle_coeff_nxn_bins(const int16_t *coeff, int width, int type, int sca
   ecabac_t c;
   memset(&c, 0, sizeof c);
   c.rec = records; c.rec_cap = capacity;
-  e_coeff_nxn(&c, coeff, width, type, scan_mode);
+  e_coeff_nxn(&c, coeff, width, type, scan_mode, 0);
   return c.rec_n;
 }
 /* `n` records through the arithmetic coder, contexts starting from ctx_states (KVZ_HIP_CX_* order), then the coder's flush, a stop bit and the alignment: the bytes
@@ -571,9 +579,9 @@ static void eb_coding_tree(ecabac_t *c, ctu_t *t, int x, int y, int depth)
     ec_bin(c, CX_CBF_LUMA + 1, cb_y);
     scan = scan_order(cur->mode, depth);
   }
-  if (cb_y) e_coeff_nxn(c, &l0->coeff[0][zorder(xl, yl)], w, 0, scan);
-  if (cb_u) e_coeff_nxn(c, &l0->coeff[1][zorder(xl / 2, yl / 2)], cw, 2, scan);
-  if (cb_v) e_coeff_nxn(c, &l0->coeff[2][zorder(xl / 2, yl / 2)], cw, 2, scan);
+  if (cb_y) e_coeff_nxn(c, &l0->coeff[0][zorder(xl, yl)], w, 0, scan, 0);  /* (B pictures never hide signs: the inter pass has no hiding step) */
+  if (cb_u) e_coeff_nxn(c, &l0->coeff[1][zorder(xl / 2, yl / 2)], cw, 2, scan, 0);
+  if (cb_v) e_coeff_nxn(c, &l0->coeff[2][zorder(xl / 2, yl / 2)], cw, 2, scan, 0);
 }
 
 /* the slice data of one B picture after its search: t as b_picture left it (fcu, in); coeff: KVZ_HIP_CTU_COEFFS per CTU; init: the slice's initial context states (CX_ALL) */
@@ -622,4 +630,29 @@ static size_t e_b_picture(ctu_t *t, const uint8_t *init, int no_wpp, const int16
   }
   if (no_wpp) substream_bytes[0] = (uint32_t)bits.n;
   return bits.n;
+}
+
+/* The slice data of one B picture from its CU records alone (kvz_oracle.h): the ctu_t as b_picture leaves it -- the picture's records, the reference picture's for the
+ * temporal MV predictors (which exist from POC 2 on, inter.c:1290), the B slice's initial states -- handed to e_b_picture.  No search runs: records that a coder can
+ * walk are the caller's business (every 4x4 unit of a CU carries the CU's record, skipped implies merged, a coded block flag is set exactly when its block has a level). */
+size_t kvz_oracle_entropy_b_picture(int qp, int poc, int no_wpp, int width, int height, const kvz_oracle_cu *cu, const kvz_oracle_cu *ref_cu, const int16_t *coeff,
+                                    const kvz_hip_sao_params *sao_luma, const kvz_hip_sao_params *sao_chroma, const uint8_t *sao_merge, uint8_t *out, size_t capacity,
+                                    uint32_t *substream_bytes)
+{
+  build_transitions();
+  ctu_t *t = (ctu_t *)calloc(1, sizeof(ctu_t));
+  kvz_hip_intra_cost_model m;
+  struct inter_seq in;
+  uint8_t init[CX_ALL];
+  memset(&m, 0, sizeof m);
+  memset(&in, 0, sizeof in);
+  b_slice_contexts(qp, init);
+  m.qp = qp; m.no_wpp = no_wpp;
+  in.poc = poc; in.ref_cu = ref_cu;
+  in.ref[0] = (const uint8_t *)ref_cu;  /* mv_candidates only asks whether a reference picture exists; no sample is read */
+  t->m = &m; t->W = width; t->H = height; t->fcu = (cu_t *)cu; t->slice_b = 1; t->in = &in;
+  build_avail_tables(t);
+  const size_t n = e_b_picture(t, init, no_wpp, coeff, sao_luma, sao_chroma, sao_merge, out, capacity, substream_bytes);
+  free(t);
+  return n;
 }

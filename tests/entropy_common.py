@@ -200,3 +200,121 @@ def hostsim_slice_data(oracle, hostsim_cdll, case, cap=12288, retry=True):
         assert total >= 0, (total, most.value)
         out.append((buf[:total].tobytes(), [int(v) for v in sizes[:1 if model.no_wpp else hc]]))
     return out
+
+
+# ---- the constructed pictures of tests/entropy_atlas.py through the oracle and the host simulation ----
+def atlas_model(oracle, sw):
+    """the cost model of an atlas switch set: the coder reads ctx_init (by QP), no_wpp, search_nxn and signhide"""
+    from test_encoder_parity import oracle_model
+    model = oracle_model(oracle, sw["qp"])
+    model.no_wpp, model.search_nxn, model.signhide = int(sw["no_wpp"]), int(sw["nxn"]), int(sw["signhide"])
+    return model
+
+
+def atlas_oracle_group(oracle, group):
+    """[(slice data, substream sizes)] per picture of an intra or stage group"""
+    name, w, h, sw, pictures = group
+    model = atlas_model(oracle, sw)
+    return [oracle_entropy(oracle, model, w, h, p.outputs(sw["nxn"]), p.sao_bytes(), sw["not_last"][k] if sw["not_last"] else 0) for k, p in enumerate(pictures)]
+
+
+def atlas_hostsim_group(oracle, hostsim_cdll, group, cap=49152):
+    """the device sources in host simulation (kvz_hostsim_entropy_code_tiles), a picture at a time"""
+    name, w, h, sw, pictures = group
+    model = atlas_model(oracle, sw)
+    f = hostsim_cdll.kvz_hostsim_entropy_code_tiles
+    f.restype = C.c_long
+    f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 8 + [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+    wc, hc = (w + 63) // 64, (h + 63) // 64
+    out = []
+    for k, p in enumerate(pictures):
+        o, sao = p.outputs(sw["nxn"]), p.sao_bytes()
+        recs = pack_sao_records(sao[0], sao[1], wc * hc) if sao else None
+        not_last = np.array([sw["not_last"][k]], np.uint8) if sw["not_last"] else None
+        buf, sizes, most = np.zeros(w * h * 12 + 65536, np.uint8), np.zeros(hc, np.uint32), C.c_uint32(0)
+        total = f(C.addressof(model), w, h, 1, o["depth"].ctypes.data, o["mode"].ctypes.data, o["part"].ctypes.data if sw["nxn"] else None,
+                  o["mode4"].ctypes.data if sw["nxn"] else None, o["coeff"].ctypes.data, recs.ctypes.data if recs is not None else None, sao[2].ctypes.data if sao else None,
+                  not_last.ctypes.data if not_last is not None else None, cap, buf.ctypes.data, sizes.ctypes.data, C.byref(most))
+        assert total >= 0, (name, k, total, most.value)
+        out.append((buf[:total].tobytes(), [int(v) for v in sizes[:1 if sw["no_wpp"] else hc]]))
+    return out
+
+
+def oracle_entropy_b(oracle, sw, w, h, p):
+    """kvz_oracle_entropy_b_picture on a constructed B picture (entropy_atlas.BPicture) -> (slice data, substream sizes)"""
+    f = oracle.lib.kvz_oracle_entropy_b_picture
+    f.restype = C.c_size_t
+    f.argtypes = [C.c_int] * 5 + [C.c_void_p] * 7 + [C.c_size_t, C.c_void_p]
+    hc = (h + 63) // 64
+    cap = w * h * 12 + 65536
+    out, sizes = np.zeros(cap, np.uint8), np.zeros(hc, np.uint32)
+    cu, ref, coeff = np.ascontiguousarray(p.cu), np.ascontiguousarray(p.ref_cu), np.ascontiguousarray(p.coeff)
+    n = f(sw["qp"], sw["poc"], sw["no_wpp"], w, h, cu.ctypes.data, ref.ctypes.data, coeff.ctypes.data, None, None, None, out.ctypes.data, cap, sizes.ctypes.data)
+    assert n <= cap
+    return out[:n].tobytes(), [int(v) for v in sizes[:1 if sw["no_wpp"] else hc]]
+
+
+def hostsim_entropy_b(oracle, hostsim_cdll, sw, w, h, p, cap=49152):
+    """kvz_hostsim_entropy_code_inter on a constructed B picture"""
+    from inter_common import b_slice_context_states
+    f = hostsim_cdll.kvz_hostsim_entropy_code_inter
+    f.restype = C.c_long
+    f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_uint32, C.c_void_p, C.c_void_p]
+    hc = (h + 63) // 64
+    init = b_slice_context_states(oracle, sw["qp"])
+    out, sizes = np.zeros(w * h * 12 + 65536, np.uint8), np.zeros(hc, np.uint32)
+    cu, ref, coeff = np.ascontiguousarray(p.cu), np.ascontiguousarray(p.ref_cu), np.ascontiguousarray(p.coeff)
+    total = f(init.ctypes.data, w, h, sw["poc"], sw["no_wpp"], cu.ctypes.data, ref.ctypes.data, coeff.ctypes.data, None, None, cap, out.ctypes.data, sizes.ctypes.data)
+    assert total >= 0
+    return out[:total].tobytes(), [int(v) for v in sizes[:1 if sw["no_wpp"] else hc]]
+
+
+# ---- ... and through the device (-m gpu) ----
+def device_intra_group(lib, group):
+    """kvz_hip_dev_entropy_code_intra on all pictures of an intra or stage group in ONE call -> [(slice data, substream sizes)] per picture, as atlas_oracle_group"""
+    from kvazaar_amd.batch import cost_model
+    from kvazaar_amd.dev import Dev
+    name, w, h, sw, pictures = group
+    model = cost_model(lib, sw["qp"])
+    model.no_wpp, model.search_nxn, model.signhide = int(sw["no_wpp"]), int(sw["nxn"]), int(sw["signhide"])
+    outs = [p.outputs(sw["nxn"]) for p in pictures]
+    cat = lambda key: np.concatenate([o[key] for o in outs])  # noqa: E731
+    sao = None
+    if sw["sao"]:
+        sao = tuple(np.concatenate([p.sao_bytes()[i] for p in pictures]) for i in range(3))
+    data, sizes = Dev(lib).entropy_code_intra(w, h, model, cat("depth"), cat("mode"), cat("coeff"), cat("part") if sw["nxn"] else None, cat("mode4") if sw["nxn"] else None,
+                                              np.array(sw["not_last"], np.uint8) if sw["not_last"] else None, sao)
+    out, at = [], 0
+    for k in range(len(pictures)):
+        n = int(sizes[k].sum())
+        out.append((data[at:at + n], [int(v) for v in sizes[k]]))
+        at += n
+    assert at == len(data)
+    return out
+
+
+def device_b_group(lib, group):
+    """kvz_hip_dev_entropy_code_inter on all pictures of a B group in one call -> [(slice data, substream sizes)] per picture"""
+    from kvazaar_amd import inter
+    from kvazaar_amd.dev import Dev
+    name, w, h, sw, pictures = group
+    dev, n = Dev(lib), len(pictures)
+    lib.kvz_hip_dev_entropy_code_inter.restype = C.c_long
+    lib.kvz_hip_dev_entropy_code_inter.argtypes = [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    prm = inter.veryfast_params(sw["qp"], sw["poc"])
+    prm.sao, prm.no_wpp = 0, int(sw["no_wpp"])
+    d = [dev.put(np.concatenate([np.ascontiguousarray(getattr(p, key)).reshape(-1) for p in pictures])) for key in ("cu", "ref_cu", "coeff")]
+    cap = n * w * h * 12 + 65536
+    buf, sizes = np.zeros(cap, np.uint8), np.zeros((n, 1 if sw["no_wpp"] else (h + 63) // 64), np.uint32)
+    try:
+        total = lib.kvz_hip_dev_entropy_code_inter(d[0], d[1], d[2], w, h, n, C.addressof(prm), buf.ctypes.data, cap, sizes.ctypes.data)
+    finally:
+        dev.free(*d)
+    assert total >= 0
+    out, at = [], 0
+    for k in range(n):
+        m = int(sizes[k].sum())
+        out.append((buf[at:at + m].tobytes(), [int(v) for v in sizes[k]]))
+        at += m
+    assert at == total
+    return out

@@ -271,9 +271,19 @@ extern "C" long kvz_hostsim_escape(const uint8_t *raw, uint32_t n, uint8_t *out)
   return before == by_position ? (long)n + before : -1;
 }
 
+extern "C" long kvz_hostsim_entropy_code_tiles(const kvz_hip_intra_cost_model *m, int width, int height, int n_frames, const uint8_t *cu_depth, const uint8_t *cu_mode, const uint8_t *part,
+                                               const uint8_t *mode4, const int16_t *coeff, const unsigned long long *sao_recs, const uint8_t *sao_merge, const uint8_t *not_last,
+                                               uint32_t cap, uint8_t *out, uint32_t *substream_bytes, uint32_t *most_records);
 extern "C" long kvz_hostsim_entropy_code(const kvz_hip_intra_cost_model *m, int width, int height, int n_frames, const uint8_t *cu_depth, const uint8_t *cu_mode, const uint8_t *part,
                                          const uint8_t *mode4, const int16_t *coeff, const unsigned long long *sao_recs, const uint8_t *sao_merge, uint32_t cap, uint8_t *out,
                                          uint32_t *substream_bytes, uint32_t *most_records)
+{
+  return kvz_hostsim_entropy_code_tiles(m, width, height, n_frames, cu_depth, cu_mode, part, mode4, coeff, sao_recs, sao_merge, nullptr, cap, out, substream_bytes, most_records);
+}
+// ... with what kvz_hip_dev_entropy_code_intra hands the job besides: not_last ([n_frames] or null: tiles that are not their slice's last) and the model's signhide
+extern "C" long kvz_hostsim_entropy_code_tiles(const kvz_hip_intra_cost_model *m, int width, int height, int n_frames, const uint8_t *cu_depth, const uint8_t *cu_mode, const uint8_t *part,
+                                               const uint8_t *mode4, const int16_t *coeff, const unsigned long long *sao_recs, const uint8_t *sao_merge, const uint8_t *not_last,
+                                               uint32_t cap, uint8_t *out, uint32_t *substream_bytes, uint32_t *most_records)
 {
   static kvz::Tables tb;
   kvz::build_tables(&tb);
@@ -281,6 +291,7 @@ extern "C" long kvz_hostsim_entropy_code(const kvz_hip_intra_cost_model *m, int 
   memset(&J, 0, sizeof J);
   J.W = width; J.H = height; J.wc = (width + 63) / 64; J.hc = (height + 63) / 64; J.n_frames = n_frames; J.no_wpp = m->no_wpp;
   J.depth = cu_depth; J.mode = cu_mode; J.part = part; J.mode4 = mode4; J.coeff = coeff; J.sao = sao_recs; J.sao_merge = sao_merge;
+  J.not_last = not_last; J.signhide = m->signhide != 0;
   const long items = (long)n_frames * J.wc * J.hc, streams = (long)n_frames * (m->no_wpp ? 1 : J.hc);
   cap = (cap + 15u) & ~15u;
   J.bins = (uint32_t *)aligned_alloc(64, (size_t)items * cap * sizeof(uint32_t)); J.nbins = (uint32_t *)malloc((size_t)items * sizeof(uint32_t)); J.nbits = (uint32_t *)malloc((size_t)items * sizeof(uint32_t)); J.cap = cap;

@@ -9,13 +9,15 @@ import numpy as np
 import pytest
 
 import ctu_common as cc
+import entropy_common as ec
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
 
 
 @pytest.mark.gpu
 def test_hip_ctu_pass_fuzz_equals_oracle(oracle):
-    """50 random cases through the kernels of `ultrafast` .. `faster` (fast and CABAC coefficient cost, WPP on / off, adaptive / frozen contexts)"""
+    """50 random cases through the kernels of `ultrafast` .. `faster` (fast and CABAC coefficient cost, WPP on / off, adaptive / frozen contexts); every batch is then
+    coded on the device (kvz_hip_batch_entropy_code) and its slice data held against the oracle's coder on the same results"""
     import kvazaar_amd
     import fuzz_ctu
     lib = kvazaar_amd.load_library()
@@ -33,10 +35,21 @@ def test_hip_ctu_pass_fuzz_equals_oracle(oracle):
             for k, f in enumerate(frames):
                 b.upload(k, f)
             b.run(model)
+            got = [b.download(k) for k in range(len(frames))]
             for k, f in enumerate(frames):
-                diff = cc.compare(b.download(k), cc.run_oracle(oracle, model, w, h, f))
+                diff = cc.compare(got[k], cc.run_oracle(oracle, model, w, h, f))
                 if diff:
                     bad.append((i, k, w, h, qp, int(model.no_wpp), int(model.adaptive), diff))
+            # ... and coded: the slice data of what the pass searched, against the oracle's coder on the downloaded results
+            data, sizes = b.entropy_code(model)
+            data, at = bytes(data), 0
+            for k in range(len(frames)):
+                want, want_sizes = ec.oracle_entropy(oracle, model, w, h, got[k])
+                if [int(v) for v in sizes[k]] != want_sizes or data[at:at + len(want)] != want:
+                    bad.append((i, k, w, h, qp, int(model.no_wpp), int(model.adaptive), "slice data", [int(v) for v in sizes[k]], want_sizes))
+                at += int(sizes[k].sum())
+            if at != len(data):
+                bad.append((i, w, h, qp, "slice data length", at, len(data)))
         finally:
             b.close()
     assert not bad, bad[:6]
